@@ -1,9 +1,12 @@
 """bench.py -- simplex pivots/sec on Netlib 25FV47 (BASELINE.json configs[1]) on MI355X, and every other BASELINE config beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 25fv47]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 25fv47] [--dump-outputs DIR]
 
 One "step" = one complete ``solve_relaxation`` of the workload, LP resident in HBM when the timed region starts
-(MPS parsing, standardisation and the H2D upload happen before it).  ``value`` = pivots of all ranks / wall time.
+(MPS parsing, standardisation and the H2D upload happen before it).  ``value`` = pivots of all ranks / wall time,
+``ms_per_step`` = wall time of the K timed steps / K.  ``--dump-outputs DIR`` writes what the last timed step returned to its
+caller (objective, pivot counts, solution, basis; the exact optimum as float64 when certified; per LP for the Netlib batch) as
+``DIR/<name>.npy``: the inputs are fixed files or seeded generators, so two builds can be compared output for output.
 N > 1 (launched by torch.distributed.run, one rank per GPU): every rank solves its own copy -- independent LPs shard
 one per GPU with no data-path collective (weak scaling); the barrier + max-over-ranks timing is the only exchange.
 
@@ -570,6 +573,19 @@ def single_lp(args, ctx):
     barrier()
     elapsed = time.perf_counter() - start
     final_basis = solver.basis() if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from its last step (--dump-outputs), before the roofline pivots below move the solver on
+        outputs = {"objective": [last.objective], "pivots": [last.pivots_phase_one, last.pivots_phase_two],
+                   "solution": solver.solution(), "basis": final_basis}
+        if not dense and not graph and not args.no_certify and last.certified:
+            import numpy as np
+            num, den = solver.objective_exact().split("/")
+            outputs["objective_exact"] = [int(num) / int(den)]
+            exact_x = np.zeros(solver.n_structural)
+            for j, value in solver.solution_exact().items():
+                exact_x[j] = float(value)
+            outputs["solution_exact"] = exact_x
+        ctx["outputs"] = outputs
     # one record per rank (what each GPU did); the makespan is the max over ranks of the barrier-to-barrier time
     per_rank = batch.gather_records({"rank": rank, "solves": args.steps, "pivots": int(pivots), "busy_seconds": loop_seconds + certify_seconds,
                                      "elapsed_seconds": elapsed})
@@ -896,6 +912,15 @@ def netlib_batch(args, ctx):
     pool.close()
     if rank != 0:
         return None
+    if args.dump_outputs:
+        # per LP of the suite (netlib_names order): objective and pivots of its last ticket in the timed queue, over all ranks
+        last_result = {}
+        for rank_record in gathered:
+            for name, objective, lp_pivots, _ in rank_record["results"]:
+                last_result[name] = (objective, lp_pivots)
+        missing = (float("nan"), float("nan"))
+        ctx["outputs"] = {"objective": [last_result.get(name, missing)[0] for name in names],
+                          "pivots": [last_result.get(name, missing)[1] for name in names]}
     wrong = []
     longest = {}
     for rank_record in gathered:
@@ -1057,6 +1082,7 @@ def all_configs(args, ctx, legs):
     def variant(**overrides):
         v = copy.copy(args)
         v.no_concurrency_probe = True
+        v.dump_outputs = None  # --dump-outputs is the headline's
         for k, val in overrides.items():
             setattr(v, k, val)
         return v
@@ -1128,6 +1154,30 @@ def all_configs(args, ctx, legs):
             if "error" not in out[key]:
                 out[key]["cpu_baseline"] = netlib_cpu
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x5EED0D0
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: each array as DIR/<name>.npy in float64, 64 MB at most in all.  Over the limit, the largest array is replaced by
+    a fixed, seeded sample of its entries (DIR/<name>.npy) and the sampled positions (DIR/<name>_index.npy), until the rest fits."""
+    import numpy as np
+    arrays = {name: np.asarray(value, dtype=np.float64).ravel() for name, value in outputs.items()}
+    header = 4096  # allowance for each file's .npy header
+    while sum(a.nbytes + header for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        whole = [n for n in arrays if not n.endswith("_index") and n + "_index" not in arrays]
+        if not whole:
+            break
+        name = max(whole, key=lambda n: arrays[n].nbytes)
+        others = sum(a.nbytes + header for n, a in arrays.items() if n != name)
+        keep = max(1, (DUMP_LIMIT_BYTES - others - 2 * header) // 16)  # the sample and its index
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(arrays[name].size, size=keep, replace=False))
+        arrays[name], arrays[name + "_index"] = arrays[name][index], index.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
 
 
 def free_port():
@@ -1246,6 +1296,8 @@ def main():
     parser.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)
     parser.add_argument("--launch-check", action="store_true",
                         help="no solve: the ranks rendezvous, reduce their ranks and rank 0 prints {n_gpus, ranks} (runs without a GPU over gloo)")
+    parser.add_argument("--dump-outputs", default=None, metavar="DIR",
+                        help="after the timed steps, write what the workload's last timed step computed as DIR/<name>.npy (float64, 64 MB at most)")
     args = parser.parse_args()
 
     if args.cpu_leg:  # child process: one CPU baseline, no GPU
@@ -1254,6 +1306,8 @@ def main():
 
     if args.gpus < 1:
         parser.error("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        parser.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher -- it has not imported torch or touched HIP -- and the N
         # ranks are its children (one per GPU, rendezvous on 127.0.0.1); rank 0's line is relayed as the last line of stdout
@@ -1300,6 +1354,8 @@ def main():
     want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
 
     line = netlib_batch(args, ctx) if batch_workload else single_lp(args, ctx)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx.pop("outputs"))
 
     if want_cpu and not batch_workload and not graph and not dense:
         legs.start("exact_faithful", "exact_faithful", args.cpu_seconds)

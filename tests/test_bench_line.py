@@ -93,3 +93,24 @@ def test_compact_line_is_bounded_whatever_the_record_holds():
     line = json.loads(text)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert key in line, key
+
+
+def test_dump_outputs_writes_float64_arrays_and_samples_past_the_limit(tmp_path):
+    """`--dump-outputs DIR`: one DIR/<name>.npy per output in float64; past 64 MB in all, the largest array becomes a fixed, seeded sample
+    with its positions beside it, the same from run to run."""
+    import numpy as np
+    bench = load_bench()
+    bench.dump_outputs(str(tmp_path / "small"), {"objective": [1.5], "basis": np.arange(7, dtype=np.int32)})
+    objective, basis = np.load(tmp_path / "small" / "objective.npy"), np.load(tmp_path / "small" / "basis.npy")
+    assert objective.dtype == np.float64 and objective.tolist() == [1.5]
+    assert basis.dtype == np.float64 and basis.tolist() == list(range(7))
+    big = np.arange(9 << 20, dtype=np.float64)  # 72 MB
+    for run in ("first", "second"):
+        bench.dump_outputs(str(tmp_path / run), {"solution": big, "objective": [2.0]})
+    files = sorted(p.name for p in (tmp_path / "first").iterdir())
+    assert files == ["objective.npy", "solution.npy", "solution_index.npy"]
+    assert sum((tmp_path / "first" / name).stat().st_size for name in files) <= 64 << 20
+    sample, index = np.load(tmp_path / "first" / "solution.npy"), np.load(tmp_path / "first" / "solution_index.npy")
+    assert sample.dtype == index.dtype == np.float64 and np.array_equal(sample, big[index.astype(np.int64)])
+    assert np.array_equal(sample, np.load(tmp_path / "second" / "solution.npy"))
+    assert np.load(tmp_path / "first" / "objective.npy").tolist() == [2.0]

@@ -114,3 +114,20 @@ def test_default_bench_compact_line_and_detail_file_with_every_baseline_config()
     assert abs(configs["maxflow_reference_start"]["config"]["objective"] + 778.0) < 1e-9
     assert abs(configs["maxflow_crash"]["config"]["objective"] + 778.0) < 1e-9
     assert configs["maxflow_crash"]["cpu_baseline"]["scipy_max_flow"]["flow_value"] == 778
+
+
+def test_dump_outputs_holds_the_last_timed_solve(tmp_path):
+    """`--dump-outputs DIR` on the default workload: the objective, pivot counts, solution, basis and exact optimum of the last timed step,
+    in float64, consistent with the bench line; `--steps` is the number of timed steps."""
+    import numpy as np
+    dump = tmp_path / "outputs"
+    short, line, _ = run_bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-configs", "--no-concurrency-probe",
+                                "--dump-outputs", str(dump)])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and short["ms_per_step"] > 0
+    arrays = {p.stem: np.load(p) for p in dump.iterdir()}
+    assert set(arrays) == {"objective", "pivots", "solution", "basis", "objective_exact", "solution_exact"}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert arrays["objective"][0] == line["config"]["objective"] and abs(arrays["objective_exact"][0] - 5501.8458883) < 1e-6
+    assert int(arrays["pivots"].sum()) == line["config"]["pivots_per_solve"]
+    assert arrays["basis"].size == 821 and arrays["solution"].size == arrays["solution_exact"].size
+    assert np.max(np.abs(arrays["solution"] - arrays["solution_exact"])) < 1e-6

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import relp_amd
-from relp_oracle import FiniteOptimum, Infeasible, MatrixData, Unbounded, Variable, solve_relaxation
+from relp_oracle import BasisInverseRows, FiniteOptimum, Infeasible, MatrixData, Unbounded, Variable, solve_relaxation
 
 pytestmark = pytest.mark.gpu
 
@@ -43,8 +43,11 @@ def test_random_lp_matches_oracle_exactly(seed):
     try:
         expected = solve_relaxation(data)
     except AssertionError:
-        # the reference's LU needs m >= 2 (decomposition/mod.rs:32); removing redundant rows can leave a single row
-        pytest.skip("the reference's LU cannot factor a 1 x 1 basis")
+        # the reference's LU needs m >= 2 (decomposition/mod.rs:32); removing redundant rows can leave a single row (seed 19:
+        # two copies of one equality row).  The oracle's other exact carry, the explicit inverse, takes the 1 x 1 basis.
+        data = MatrixData(columns, b, ranges, counts[0], counts[1], counts[2], counts[3],
+                          [Variable(c, upper_bound=u) for c, u in zip(cost, upper)])
+        expected = solve_relaxation(data, BasisInverseRows)
 
     column_start = [0]
     rows, nums = [], []

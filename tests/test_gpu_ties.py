@@ -19,7 +19,7 @@ import relp_amd
 from relp_oracle import (BasisInverseRows, FiniteOptimum, LUDecomposition, MatrixData, SteepestDescentAlongObjective,
                          Tableau, Variable, solve_relaxation)
 from relp_oracle.mps import load_problem
-from relp_oracle.solve import Infeasible
+from relp_oracle.solve import Infeasible, Unbounded
 
 pytestmark = pytest.mark.gpu
 
@@ -75,6 +75,8 @@ def device_trace(solver):
         while True:
             done, reason = solver.iterate(1)
             if done == 0:
+                if phase == 2 and reason == relp_amd.STOP_UNBOUNDED:  # an entering column with no leaving row (phase_two.rs:36-58)
+                    return pivots, "unbounded"
                 assert reason == relp_amd.STOP_NO_ENTERING
                 break
             _, q, p, leaving = solver.last_pivot()
@@ -142,12 +144,14 @@ def test_identical_sequence_through_both_phases_without_redundant_rows(seed, car
         assert pivots == [t for t in trace.pivots if t[0] == 1]
         solver.close()
         return
-    if not isinstance(expected, FiniteOptimum):
-        pytest.skip("unbounded instance")
     n_art = solver.n_art
     oracle = [(ph, q + (n_art if ph == 2 else 0), p, leaving + (n_art if ph == 2 else 0)) for ph, q, p, leaving in trace.pivots]
     pivots, status = device_trace(solver)
-    assert status == "optimal"
+    if isinstance(expected, Unbounded):  # (seed 1) the same pivots, then phase two finds the same program unbounded
+        assert status == "unbounded"
+    else:
+        assert isinstance(expected, FiniteOptimum)
+        assert status == "optimal"
     assert pivots == oracle, (pivots, oracle)
     solver.close()
 
