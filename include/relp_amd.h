@@ -54,13 +54,21 @@ typedef enum relp_carry {
     RELP_CARRY_EXPLICIT = 0,   /* `BasisInverseRows` (carry/basis_inverse_rows.rs:21-229): explicit inverse, product-form update */
     RELP_CARRY_LU = 1,         /* `LUDecomposition` (carry/lower_upper/mod.rs:36-272): P B Q = L U, Forrest-Tomlin updates,
                                   refactorisation every `refactor_period` updates */
-    RELP_CARRY_LU_INVERSE = 2  /* the same factorisation (`LUDecomposition::invert`, lower_upper/mod.rs:78-92, at every
+    RELP_CARRY_LU_INVERSE = 2, /* the same factorisation (`LUDecomposition::invert`, lower_upper/mod.rs:78-92, at every
                                   refactorisation) applied through the sparse INVERSES of its two triangles: FTRAN / BTRAN
                                   (mod.rs:180-237) are two sparse matrix-vector products each instead of two level-by-level
                                   triangular solves, and the basis changes between refactorisations are kept in product form on
                                   top (the etas of `BasisInverseRows`, basis_inverse_rows.rs:96-135, as at most `refactor_period`
                                   columns) instead of Forrest-Tomlin row etas.  At most about 5800 rows (four vectors in LDS up to
                                   about 4300 rows, three beyond). */
+    RELP_CARRY_NETWORK = 3     /* network LPs only (the graph providers, examples/max_flow.rs and examples/shortest_path.rs):
+                                  the basis is kept as a spanning forest of the rows, O(m) memory, no m x m array.  FTRAN is
+                                  the tree path of the entering arc, row p of the inverse the subtree the leaving arc cuts off.
+                                  Accepts a device LP (after implicit bounds are taken out) whose every column has at most two
+                                  entries, each +-1, of opposite signs when there are two; anything else fails to load with
+                                  RELP_ERR_ARGUMENT naming the first such column (the max-flow provider needs implicit_bounds).
+                                  The certificate (certify) is proved from the tree for finite optima; INFEASIBLE and
+                                  UNBOUNDED results stay uncertified under this carry. */
 } relp_carry;
 
 /* `Tableau::select_primal_pivot_row` (tableau/mod.rs:287-313). */
@@ -69,11 +77,12 @@ typedef enum relp_ratio_rule {
                                   needs on real data), ties to the lowest leaving column */
     RELP_RATIO_TEXTBOOK = 1,   /* the reference's rule: the exact minimum ratio, ties to the lowest leaving column (Bland).  For
                                   data on which f64 is exact (small integers); rows <= 8192 (RELP_ERR_ARGUMENT at load beyond:
-                                  the multi-workgroup ratio test implements the two-pass rule only) */
+                                  the multi-workgroup ratio test implements the two-pass rule only), any number of rows
+                                  under RELP_CARRY_NETWORK */
     RELP_RATIO_AUTO = 2        /* the default since round 6 ("defaults reproduce the reference"): the
                                   reference's rule where the data are small integers -- every matrix entry an integer of at most
                                   64 in magnitude, every cost and right-hand side an integer below 2^20 -- and the LP has at most
-                                  8192 rows; the two-pass Harris test otherwise (decimal data: Netlib).  The per-LP record
+                                  8192 rows (any number under RELP_CARRY_NETWORK); the two-pass Harris test otherwise (decimal data: Netlib).  The per-LP record
                                   (relp_get_record_json) says which one ran */
 } relp_ratio_rule;
 
@@ -119,7 +128,9 @@ typedef enum relp_switch {
     RELP_SW_LUF_CLAIM_TARGETS = 1 << 11,    /* device refactorisation: target rows claimed from a counter */
     RELP_SW_LUF_NO_LDS_ARENA = 1 << 12,     /* ... the active sub-matrix in global memory throughout */
     RELP_SW_LUI_CLAIM_ROWS = 1 << 13,       /* ... inversion of the triangles: rows claimed from a counter */
-    RELP_SW_BI_FACTOR_HOST = 1 << 14        /* stand-alone BasisInverse: `invert` on a host core */
+    RELP_SW_BI_FACTOR_HOST = 1 << 14,       /* stand-alone BasisInverse: `invert` on a host core */
+    RELP_SW_NETWORK_STATS = 1 << 15         /* RELP_CARRY_NETWORK: count row depths, subtree and path sizes at every pivot (the record's
+                                               "network_tree"; a diagnostic, it costs atomics in the forest update) */
 } relp_switch;
 
 typedef struct relp_options {
@@ -371,8 +382,11 @@ int32_t relp_get_solution_exact(const relp_handle* handle, int32_t original, int
 int32_t relp_get_variable_name(const relp_handle* handle, int32_t j, char* buffer, int32_t capacity, int32_t* length);
 /* One JSON object describing the last relp_solve_relaxation of this handle (the per-LP record of SURVEY.md section 5; the
  * reference has no logging at all): name, m, n, nnz, result, pivots per phase, polishes / refactorisations, wall times,
- * pivots/s, algorithmic bytes per pivot, objective (f64) and objective_exact ("num/den" when certified).  *length receives
- * the full length; at most capacity - 1 bytes are written. */
+ * pivots/s, algorithmic bytes per pivot, objective (f64) and objective_exact ("num/den" when certified).  "device_bytes":
+ * the handle's own device arrays (the LP, its vectors and the carry's state: the explicit inverse, the forest); the factor sets of
+ * the LU carries, the certificate's scratch and transient buffers are not counted.  "network_tree" (RELP_SW_NETWORK_STATS):
+ * per-pivot means and maxima of the row depth, of the subtree the leaving arc cuts off and of the entering arc's path.
+ * *length receives the full length; at most capacity - 1 bytes are written. */
 int32_t relp_get_record_json(const relp_handle* handle, char* buffer, int32_t capacity, int32_t* length);
 /* ---- the loop in exact fixed-width integer arithmetic on the device ------------------------------------------------------
  * `solve_relaxation::<Carry<RationalBig, _>>` with the reference's arbitrary-precision rationals replaced by LIMBS x 64-bit

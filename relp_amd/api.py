@@ -17,7 +17,7 @@ OK, ERR_ARGUMENT, ERR_PARSE, ERR_DEVICE, ERR_OVERFLOW, ERR_STATE, ERR_NUMERICAL 
 FINITE_OPTIMUM, INFEASIBLE, UNBOUNDED, ITERATION_LIMIT = 1, 2, 3, 4
 STEEPEST_EDGE, DANTZIG, FIRST_PROFITABLE, FIRST_PROFITABLE_MEMORY = 0, 1, 2, 3
 STOP_NO_ENTERING, STOP_UNBOUNDED, STOP_BUDGET = 1, 2, 3
-CARRY_EXPLICIT, CARRY_LU, CARRY_LU_INVERSE = 0, 1, 2
+CARRY_EXPLICIT, CARRY_LU, CARRY_LU_INVERSE, CARRY_NETWORK = 0, 1, 2, 3
 RATIO_HARRIS, RATIO_TEXTBOOK, RATIO_AUTO = 0, 1, 2
 
 
@@ -44,7 +44,7 @@ class Options(C.Structure):
 
 # relp_switch bits of Options.switches (include/relp_amd.h)
 SW_NO_TOUCHED, SW_K2_SINGLE, SW_ELL_WIDE, SW_NO_GENERATED_COLUMNS, SW_NO_SLACK_IN_BTRAN, SW_NO_DENSE_LANE, SW_POLISH_ALWAYS, SW_NO_RHO_BITS, \
-    SW_PRICE_UNIT_PAIRS, SW_CERTIFY_NO_LEVELS, SW_GEMM_VECTOR, SW_LUF_CLAIM_TARGETS, SW_LUF_NO_LDS_ARENA, SW_LUI_CLAIM_ROWS, SW_BI_FACTOR_HOST = (1 << k for k in range(15))
+    SW_PRICE_UNIT_PAIRS, SW_CERTIFY_NO_LEVELS, SW_GEMM_VECTOR, SW_LUF_CLAIM_TARGETS, SW_LUF_NO_LDS_ARENA, SW_LUI_CLAIM_ROWS, SW_BI_FACTOR_HOST, SW_NETWORK_STATS = (1 << k for k in range(16))
 
 # The library reads no environment variable that changes a kernel or a result (round 5).  This BINDING -- test and bench plumbing --
 # still maps the old variable names onto option fields for the tools that A/B them; an option given by the caller always wins.

@@ -785,7 +785,7 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     static const char* presolve_states[] = {"off", "applied", "applied without the implied bounds beyond 126 bits", "dropped (did not fit the host model)"};
     out << "{\"name\": \"" << json_escaped(sv.form().name) << "\", \"presolve\": \"" << presolve_states[sv.form().presolve_state & 3] << "\", \"m\": " << md.nr_rows() << ", \"n\": " << md.nr_columns() << ", \"nnz\": " << nnz
         << ", \"device_rows\": " << d.m << ", \"artificials\": " << d.n_art << ", \"result\": \"" << kinds[r.kind >= 0 && r.kind <= 4 ? r.kind : 0]
-        << "\", \"carry\": \"" << (h->options.carry == RELP_CARRY_LU ? "lu" : h->options.carry == RELP_CARRY_LU_INVERSE ? "lu_inverse" : "explicit") << "\", \"pivots_phase_one\": " << r.pivots_phase_one
+        << "\", \"carry\": \"" << (h->options.carry == RELP_CARRY_LU ? "lu" : h->options.carry == RELP_CARRY_LU_INVERSE ? "lu_inverse" : sv.network_carry() ? "network" : "explicit") << "\", \"pivots_phase_one\": " << r.pivots_phase_one
         << ", \"pivots_phase_two\": " << r.pivots_phase_two << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
         << "\", \"device_refactor_fallbacks\": " << sv.device_refactor_fallbacks()
@@ -793,10 +793,18 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
         << ", \"solve_seconds\": " << r.solve_seconds << ", \"certify_seconds\": " << r.certify_seconds
         << ", \"pivots_per_second\": " << (r.solve_seconds > 0 ? (double)pivots / r.solve_seconds : 0.0)
         << ", \"pricing_bytes_per_pivot\": " << st.price_bytes << ", \"inverse_bytes_per_pivot_bound\": " << (h->options.carry != RELP_CARRY_EXPLICIT ? 0 : st.update_bytes)
-        << ", \"kernel_launches\": " << st.launches << ", \"certified\": " << (r.certified ? "true" : "false")
+        << ", \"kernel_launches\": " << st.launches << ", \"device_bytes\": " << sv.device_bytes() << ", \"certified\": " << (r.certified ? "true" : "false")
         << ", \"exact_repair_pivots\": " << r.exact_repair_pivots << ", \"objective\": ";
     if (r.kind == RELP_RESULT_FINITE_OPTIMUM) out << r.objective;
     else out << "null";
+    const std::vector<unsigned long long>& ns = sv.network_stats();
+    if (ns.size() == NS_WORDS && ns[NS_PIVOTS] > 0) {
+        const double pivots_seen = (double)ns[NS_PIVOTS];
+        out << ", \"network_tree\": {\"pivots\": " << ns[NS_PIVOTS] << ", \"depth_mean\": " << (double)ns[NS_DEPTH_SUM] / (pivots_seen * d.m)
+            << ", \"depth_max\": " << ns[NS_DEPTH_MAX] << ", \"subtree_mean\": " << (double)ns[NS_SUBTREE_SUM] / pivots_seen
+            << ", \"subtree_max\": " << ns[NS_SUBTREE_MAX] << ", \"path_mean\": " << (double)ns[NS_PATH_SUM] / pivots_seen
+            << ", \"path_max\": " << ns[NS_PATH_MAX] << "}";
+    }
     out << ", \"objective_exact\": ";
     if (r.certified && !sv.exact_objective.empty()) out << "\"" << sv.exact_objective << "\"";
     else out << "null";

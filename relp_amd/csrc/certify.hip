@@ -765,6 +765,22 @@ std::vector<std::pair<int, std::string>> exact_primal_values(const ExactPrimal& 
     return out;
 }
 
+// The exact primal values of a certificate made elsewhere (network_carry.hip: the forest's): provider column and value, over one
+// common denominator.
+std::shared_ptr<const ExactPrimal> make_exact_primal(const std::vector<int>& columns, const std::vector<Rat>& values) {
+    auto primal = std::make_shared<ExactPrimal>();
+    primal->basis = columns;
+    BigInt denom(1);
+    for (const Rat& v : values) {
+        const BigInt d = BigInt::from_i128(v.d);
+        const BigInt g = BigInt::gcd(denom, d);
+        denom = denom * (d / g);
+    }
+    primal->denom = denom;
+    for (const Rat& v : values) primal->numer.push_back(BigInt::from_i128(v.n) * (denom / BigInt::from_i128(v.d)));
+    return primal;
+}
+
 void certify_basis(const StandardForm& form, const std::vector<int>& basis_columns, int device, hipStream_t stream,
                    std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
                    std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch) {

@@ -2065,6 +2065,40 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_harris_kernel(DeviceLP lp, in
     }
 }
 
+// k2l_ftran_kernel for the spanning-forest carry (network_carry.hip): q and its reduced cost are in the control block and the column
+// B^-1 a_q in alpha_in, written by net_ftran_kernel; the rest -- signs, |alpha|^2 and Harris pass-1 partials -- as k2l_ftran_kernel.
+__global__ void __launch_bounds__(K2L_THREADS) k2l_preselected_kernel(DeviceLP lp, double tol_pivot, double harris_delta, int skip_artificial_rows) {
+    __shared__ double s_red[18];
+    Ctl* ctl = lp.ctl;
+    const int m = lp.m;
+    const bool bounded = lp.ub != nullptr;
+    const int i = blockIdx.x * K2L_THREADS + threadIdx.x;
+    const double xb = i < m ? lp.xB[i] : 0.0;
+    const int bas = i < m ? lp.basis[i] : 0;
+    const double up = (bounded && i < m) ? lp.xub[i] : INFINITY;
+    const double ain = i < m ? lp.alpha_in[i] : 0.0;
+    const int status = ctl->status, q = ctl->q;
+    if (status != ST_RUNNING || q < 0) return;
+    const double sgn_q = (bounded && lp.flipped[q]) ? -1.0 : 1.0;
+    const double a = ain * sgn_q;
+    double sumsq = 0.0, theta = INFINITY;
+    if (i < m) {
+        lp.alpha[i] = a;
+        sumsq = a * a;
+        if (!(skip_artificial_rows && bas < lp.n_art)) {
+            if (a > tol_pivot) theta = (fmax(xb, 0.0) + harris_delta) / a;
+            else if (bounded && a < -tol_pivot && up < INFINITY) theta = (fmax(up - xb, 0.0) + harris_delta) / -a;
+        }
+    }
+    sumsq = block_reduce<0>(sumsq, s_red);
+    __syncthreads();
+    theta = block_reduce<1>(theta, s_red);
+    if (threadIdx.x == 0) {
+        lp.k2_partd[K2L_PD * blockIdx.x] = sumsq;
+        lp.k2_partd[K2L_PD * blockIdx.x + 1] = theta;
+    }
+}
+
 // Every workgroup takes the same decision from the per-workgroup candidates (no row data is read again, so the x_B
 // writes of one workgroup cannot be seen by another's decision); workgroup 0 alone does the bookkeeping.
 __global__ void __launch_bounds__(K2L_THREADS) k2l_apply_kernel(DeviceLP lp, int n_blocks) {
@@ -3945,6 +3979,13 @@ void launch_pi(const DeviceLP& d, hipStream_t s) {
     hipLaunchKernelGGL(cb_kernel, dim3(1), dim3(CB_THREADS), 0, s, d);
     hipLaunchKernelGGL(pi_kernel, dim3((d.m + 3) / 4), dim3(256), 0, s, d);       // (one of the two returns at once:
     hipLaunchKernelGGL(pi_sparse_kernel, dim3((d.m + 255) / 256), dim3(256), 0, s, d);  //  decided on the device by nnz(c_B))
+}
+void launch_cb(const DeviceLP& d, hipStream_t s) { hipLaunchKernelGGL(cb_kernel, dim3(1), dim3(CB_THREADS), 0, s, d); }
+void launch_k2l_preselected(const DeviceLP& d, double tol_pivot, double harris_delta, int skip_artificial_rows, hipStream_t s) {
+    const int blocks = (d.m + K2L_THREADS - 1) / K2L_THREADS;
+    hipLaunchKernelGGL(k2l_preselected_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, tol_pivot, harris_delta, skip_artificial_rows);
+    hipLaunchKernelGGL(k2l_harris_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks, tol_pivot, skip_artificial_rows);
+    hipLaunchKernelGGL(k2l_apply_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks);
 }
 void launch_xb(const DeviceLP& d, hipStream_t s) {
     hipLaunchKernelGGL(xb_kernel, dim3((d.m + WAVE - 1) / WAVE), dim3(256), 0, s, d);

@@ -87,6 +87,16 @@ void upload_vec(T* dst, const std::vector<T>& src, hipStream_t s) {
 }
 }  // namespace
 
+template <class T>
+T* Solver::device_alloc(size_t count) {
+    T* p = dmalloc<T>(count);
+    device_bytes_ += std::max<size_t>(count, 1) * sizeof(T);
+    return p;
+}
+
+// network_carry.hip
+void launch_net_row(const DeviceLP& d, const NetTree& t, int r, double* out, hipStream_t s);
+
 Solver::Solver(const relp_options& options) : opt_(options) {
     int count = 0;
     hipError_t err = hipGetDeviceCount(&count);
@@ -121,7 +131,12 @@ void Solver::free_device() {
                     d_.alpha, d_.rho, d_.nz_index, d_.nz_alpha, d_.w, d_.cand_key, d_.cand_j, d_.cand_cbar, d_.cand_rows, d_.cand_vals, d_.cand_len, d_.ell_rows, d_.ell_vals, d_.scratch, d_.ctl, d_.dbg, d_.dense_val, d_.dense_val32, d_.dense_val8, d_.alpha_part, d_.alpha_in, d_.eta_cols, d_.eta_rows, d_.eta_slot, d_.eta_gather, d_.eta_dot_part, d_.touched, d_.tlist, d_.ub, d_.xub, d_.flipped, d_.rhs0, d_.k2_partd, d_.k2_parti, d_.prw, d_.rho_nz, d_.rho_bits, d_.cost8, d_.cost8_2, d_.cb, d_.cb_idx, d_.slack_of_row, d_.state[0].ctl, d_.state[0].xB, d_.state[0].basis, d_.state[1].ctl, d_.state[1].xB, d_.state[1].basis};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    void* tree[] = {net_.parent, net_.slot, net_.sign, net_.child, net_.mark, net_.chain, net_.path, net_.state, net_.stats};
+    for (void* p : tree)
+        if (p) (void)hipFree(p);
     d_ = DeviceLP{};
+    net_ = NetTree{};
+    device_bytes_ = 0;
 }
 
 void Solver::reset_stats() { stats_ = relp_stats{}; }
@@ -198,6 +213,22 @@ void Solver::upload() {
         col_start[n_art + j + 1] = (int)row_index.size();
     }
     tick("columns -> CSC");
+    network_ = opt_.carry == RELP_CARRY_NETWORK;
+    if (network_) {  // a network LP: at most two entries per column, each +-1, of opposite signs when there are two
+        for (int j = n_art; j < n; ++j) {
+            const int a = col_start[j], len = col_start[j + 1] - a;
+            bool fits = len <= 2;
+            for (int e = a; fits && e < a + len; ++e) fits = value[e] == 1.0 || value[e] == -1.0;
+            if (fits && len == 2) fits = value[a] == -value[a + 1];
+            if (fits) continue;
+            const int c = j - n_art;
+            const std::string name = c < (int)form_.column_names.size() ? form_.column_names[c] : "slack";
+            std::string hint;
+            if (!bounded_ && md.nr_variable_bounds() > 0) hint = "; its upper bound is a row of the device LP: set implicit_bounds = 1";
+            throw std::invalid_argument("RELP_CARRY_NETWORK: column " + std::to_string(c) + " (" + name + ") is not a network column (" + std::to_string(len) +
+                                        " entries; at most two, each +-1, of opposite signs)" + hint);
+        }
+    }
     const size_t nnz = row_index.size();
     std::vector<int> row_start(m + 1, 0), col_index(nnz);
     std::vector<double> row_value(nnz);
@@ -248,7 +279,7 @@ void Solver::upload() {
     int n_dense = 0;
     if (opt_.pivot_rule == RELP_PIVOT_STEEPEST_EDGE && m >= 64)
         while (n_dense < n_p && (col_start[n_art + n_dense + 1] - col_start[n_art + n_dense]) * 2 > m) ++n_dense;
-    if (n_dense < 64 || bounded_ || lu_mode_) n_dense = 0;  // (the dense pipeline belongs to the explicit inverse)
+    if (n_dense < 64 || bounded_ || lu_mode_ || network_) n_dense = 0;  // (the dense pipeline belongs to the explicit inverse)
     d_.n_dense = n_dense;
     d_.dense_first = n_art;
     d_.dense_ld = (m + 3) & ~3;
@@ -321,43 +352,43 @@ void Solver::upload() {
     const int ftran_min_nnz = ftran_min_nnz_opt;
     if (max_nnz > ftran_min_nnz && fast_k2_available(d_, price_blocks_ + dense_blocks_)) ftran_slices_ = opt_.ftran_slices > 0 ? opt_.ftran_slices : std::min(64, (max_nnz + 255) / 256);  // (4096 x 8192: 8 / 16 / 32 / 64 slices = 20.8k / 21.2k / 20.8k / 19.7k pivots/s)
 
-    d_.col_start = dmalloc<int>(n + 1);
-    d_.row_index = dmalloc<int>(nnz);
-    d_.value = dmalloc<double>(nnz);
-    d_.row_start = dmalloc<int>(m + 1);
-    d_.col_index = dmalloc<int>(nnz);
-    d_.row_value = dmalloc<double>(nnz);
-    d_.cost = dmalloc<double>(n);
-    d_.cost1 = dmalloc<double>(n);
-    d_.cost2 = dmalloc<double>(n);
-    d_.rhs = dmalloc<double>(m);
-    d_.xB = dmalloc<double>(m);
-    d_.minus_pi = dmalloc<double>(vector_len);
+    d_.col_start = device_alloc<int>(n + 1);
+    d_.row_index = device_alloc<int>(nnz);
+    d_.value = device_alloc<double>(nnz);
+    d_.row_start = device_alloc<int>(m + 1);
+    d_.col_index = device_alloc<int>(nnz);
+    d_.row_value = device_alloc<double>(nnz);
+    d_.cost = device_alloc<double>(n);
+    d_.cost1 = device_alloc<double>(n);
+    d_.cost2 = device_alloc<double>(n);
+    d_.rhs = device_alloc<double>(m);
+    d_.xB = device_alloc<double>(m);
+    d_.minus_pi = device_alloc<double>(vector_len);
     RELP_HIP(hipMemsetAsync(d_.minus_pi, 0, (size_t)vector_len * sizeof(double), stream_));
-    d_.basis = dmalloc<int>(m);
-    d_.pos = dmalloc<int>(n);
-    d_.gamma = dmalloc<double>(n);
-    d_.cb = dmalloc<double>(m);
-    d_.cb_idx = dmalloc<int>(m + 1);
+    d_.basis = device_alloc<int>(m);
+    d_.pos = device_alloc<int>(n);
+    d_.gamma = device_alloc<double>(n);
+    d_.cb = device_alloc<double>(m);
+    d_.cb_idx = device_alloc<int>(m + 1);
     tick("sparse arrays");
-    if (!lu_mode_) d_.Binv = dmalloc<double>((size_t)m * d_.ld);  // the LU carry has no m x m array at all
+    if (!lu_mode_ && !network_) d_.Binv = device_alloc<double>((size_t)m * d_.ld);  // the LU and the forest carries have no m x m array at all
     // The second copy of the inverse and the residual matrix are only needed once a polish finds something to correct
     // (Solver::ensure_polish_buffers): at m = 65 534 each is 34 GB and about a second of hipMalloc, and the max-flow LP of
     // config 5, whose bases are unimodular, never needs them.
     tick("inverse buffers (hipMalloc)");
-    d_.alpha = dmalloc<double>(m);
-    d_.rho = dmalloc<double>(vector_len);
+    d_.alpha = device_alloc<double>(m);
+    d_.rho = device_alloc<double>(vector_len);
     RELP_HIP(hipMemsetAsync(d_.rho, 0, (size_t)vector_len * sizeof(double), stream_));
-    d_.nz_index = dmalloc<int>(m);
-    d_.nz_alpha = dmalloc<double>(m);
-    d_.w = dmalloc<double>(vector_len);
+    d_.nz_index = device_alloc<int>(m);
+    d_.nz_alpha = device_alloc<double>(m);
+    d_.w = device_alloc<double>(vector_len);
     RELP_HIP(hipMemsetAsync(d_.w, 0, (size_t)vector_len * sizeof(double), stream_));
-    d_.cand_key = dmalloc<double>(price_blocks_ + dense_blocks_);
-    d_.cand_j = dmalloc<int>(price_blocks_ + dense_blocks_);
-    d_.cand_cbar = dmalloc<double>(price_blocks_ + dense_blocks_);
-    d_.cand_rows = dmalloc<int>((size_t)(price_blocks_ + dense_blocks_) * ELL_W);
-    d_.cand_vals = dmalloc<double>((size_t)(price_blocks_ + dense_blocks_) * ELL_W);
-    d_.cand_len = dmalloc<int>(price_blocks_ + dense_blocks_);
+    d_.cand_key = device_alloc<double>(price_blocks_ + dense_blocks_);
+    d_.cand_j = device_alloc<int>(price_blocks_ + dense_blocks_);
+    d_.cand_cbar = device_alloc<double>(price_blocks_ + dense_blocks_);
+    d_.cand_rows = device_alloc<int>((size_t)(price_blocks_ + dense_blocks_) * ELL_W);
+    d_.cand_vals = device_alloc<double>((size_t)(price_blocks_ + dense_blocks_) * ELL_W);
+    d_.cand_len = device_alloc<int>(price_blocks_ + dense_blocks_);
     RELP_HIP(hipMemsetAsync(d_.cand_rows, 0, (size_t)(price_blocks_ + dense_blocks_) * ELL_W * sizeof(int), stream_));  // width-2 pricing writes two of the ELL_W slots
     RELP_HIP(hipMemsetAsync(d_.cand_vals, 0, (size_t)(price_blocks_ + dense_blocks_) * ELL_W * sizeof(double), stream_));
     {
@@ -378,41 +409,41 @@ void Solver::upload() {
                 }
             std::vector<signed char> c8(n);
             for (int j = 0; j < n; ++j) c8[j] = (signed char)cost2[j];
-            d_.cost8 = dmalloc<signed char>(n);
-            d_.cost8_2 = dmalloc<signed char>(n);
+            d_.cost8 = device_alloc<signed char>(n);
+            d_.cost8_2 = device_alloc<signed char>(n);
             upload_vec(d_.cost8_2, c8, stream_);
         } else {
-            d_.ell_vals = dmalloc<double>(ev.size());
+            d_.ell_vals = device_alloc<double>(ev.size());
             upload_vec(d_.ell_vals, ev, stream_);
         }
-        d_.ell_rows = dmalloc<int>(er.size());
+        d_.ell_rows = device_alloc<int>(er.size());
         upload_vec(d_.ell_rows, er, stream_);
         RELP_HIP(hipStreamSynchronize(stream_));
     }
-    d_.alpha_part = dmalloc<double>((size_t)std::max(1, ftran_slices_) * m);
-    d_.alpha_in = dmalloc<double>(m);
+    d_.alpha_part = device_alloc<double>((size_t)std::max(1, ftran_slices_) * m);
+    d_.alpha_in = device_alloc<double>(m);
     // deferred product form of the inverse: the dense pipeline (multi-block FTRAN), m even and <= 4096 (alpha_reduce_kernel, btran_pass_kernel)
     // (relp_options.product_form = 1 / RELP_ETA=0 keeps the per-pivot rank-one update: A/B measurements)
     eta_mode_ = n_dense > 0 && ftran_slices_ > 0 && m % 2 == 0 && m <= 4096 && !product_form_off;
     d_.eta_cap = eta_mode_ ? eta_max() : 0;
     slack_in_btran_ = eta_mode_ && !slack_of_row.empty();
     if (slack_in_btran_) {
-        d_.slack_of_row = dmalloc<int>(m);
+        d_.slack_of_row = device_alloc<int>(m);
         upload_vec(d_.slack_of_row, slack_of_row, stream_);
         RELP_HIP(hipStreamSynchronize(stream_));
     }
     // unit columns of the inverse are tracked where skipping them pays: the dense pipeline and the larger sparse LPs
     // (below that the update kernel is latency bound and the extra indirection would cost a round trip)
-    d_.track_touched = (eta_mode_ || m > 2048) && !lu_mode_ && !sw(RELP_SW_NO_TOUCHED) ? 1 : 0;
-    d_.touched = dmalloc<int>(m);
-    d_.tlist = dmalloc<int>(m);
+    d_.track_touched = (eta_mode_ || m > 2048) && !lu_mode_ && !network_ && !sw(RELP_SW_NO_TOUCHED) ? 1 : 0;
+    d_.touched = device_alloc<int>(m);
+    d_.tlist = device_alloc<int>(m);
     RELP_HIP(hipMemsetAsync(d_.touched, 0, m * sizeof(int), stream_));
     if (eta_mode_) {
-        d_.eta_cols = dmalloc<double>((size_t)2 * d_.eta_cap * d_.ld);
-        d_.eta_dot_part = dmalloc<double>((size_t)d_.eta_cap * ((m + 63) / 64));
-        d_.eta_rows = dmalloc<int>(d_.eta_cap);
-        d_.eta_slot = dmalloc<int>(m);
-        d_.eta_gather = dmalloc<double>((size_t)d_.eta_cap * m);
+        d_.eta_cols = device_alloc<double>((size_t)2 * d_.eta_cap * d_.ld);
+        d_.eta_dot_part = device_alloc<double>((size_t)d_.eta_cap * ((m + 63) / 64));
+        d_.eta_rows = device_alloc<int>(d_.eta_cap);
+        d_.eta_slot = device_alloc<int>(m);
+        d_.eta_gather = device_alloc<double>((size_t)d_.eta_cap * m);
         RELP_HIP(hipMemsetAsync(d_.eta_slot, 0xff, m * sizeof(int), stream_));
         configure_btran_lds((size_t)2 * ((m + 1) & ~1) * sizeof(double));
     }
@@ -424,7 +455,7 @@ void Solver::upload() {
                 const int row = row_index[e], within = row % 64;  // tile (group, row / 64): 64 lanes x 16 bytes; see price_dense_lane_kernel
                 bytes[(((size_t)(jd / 16) * tiles_per_group + row / 64) * 64 + 16 * (within / 16) + jd % 16) * 16 + within % 16] = (signed char)value[e];
             }
-        d_.dense_val8 = dmalloc<signed char>(bytes.size());
+        d_.dense_val8 = device_alloc<signed char>(bytes.size());
         upload_vec(d_.dense_val8, bytes, stream_);
         dense_entry_bytes_ = 1;
         RELP_HIP(hipStreamSynchronize(stream_));
@@ -440,7 +471,7 @@ void Solver::upload() {
                 const int row = row_index[e], within = row % 64, t = within % 16;
                 floats[((((size_t)(jd / 16) * tiles_per_group + row / 64) * 4 + t / 4) * 64 + 16 * (within / 16) + jd % 16) * 4 + t % 4] = (float)value[e];
             }
-        d_.dense_val32 = dmalloc<float>(floats.size());
+        d_.dense_val32 = device_alloc<float>(floats.size());
         upload_vec(d_.dense_val32, floats, stream_);
         dense_entry_bytes_ = 4;
         RELP_HIP(hipStreamSynchronize(stream_));
@@ -454,7 +485,7 @@ void Solver::upload() {
                 const int row = row_index[e], within = row % 64, t = within % 16;
                 doubles[((((size_t)(jd / 16) * tiles_per_group + row / 64) * 8 + t / 2) * 64 + 16 * (within / 16) + jd % 16) * 2 + t % 2] = value[e];
             }
-        d_.dense_val = dmalloc<double>(doubles.size());
+        d_.dense_val = device_alloc<double>(doubles.size());
         upload_vec(d_.dense_val, doubles, stream_);
         dense_entry_bytes_ = 8;
         RELP_HIP(hipStreamSynchronize(stream_));
@@ -467,7 +498,7 @@ void Solver::upload() {
                 const int pair = within / 128, lane = (within % 128) / 2, t = 2 * pair + (within & 1);  // see price_dense_kernel
                 bytes[(size_t)jd * d_.dense_ld + (size_t)chunk * 1024 + lane * 16 + t] = (signed char)value[e];
             }
-        d_.dense_val8 = dmalloc<signed char>(bytes.size());
+        d_.dense_val8 = device_alloc<signed char>(bytes.size());
         upload_vec(d_.dense_val8, bytes, stream_);
         dense_entry_bytes_ = 1;
         RELP_HIP(hipStreamSynchronize(stream_));
@@ -480,17 +511,17 @@ void Solver::upload() {
         for (size_t k = 0; exact_in_float && k < dense.size(); ++k) exact_in_float = (double)(float)dense[k] == dense[k];
         if (exact_in_float) {
             std::vector<float> dense32(dense.begin(), dense.end());
-            d_.dense_val32 = dmalloc<float>(dense32.size());
+            d_.dense_val32 = device_alloc<float>(dense32.size());
             upload_vec(d_.dense_val32, dense32, stream_);
         } else {
-            d_.dense_val = dmalloc<double>(dense.size());
+            d_.dense_val = device_alloc<double>(dense.size());
             upload_vec(d_.dense_val, dense, stream_);
         }
         dense_entry_bytes_ = exact_in_float ? 4 : 8;
         RELP_HIP(hipStreamSynchronize(stream_));
         configure_dense_lds((size_t)3 * d_.dense_ld * sizeof(double));
     }
-    d_.rhs0 = dmalloc<double>(m);
+    d_.rhs0 = device_alloc<double>(m);
     if (bounded_) {
         std::vector<double> ub(n, std::numeric_limits<double>::infinity());
         for (int j = 0; j < md.nr_normal_variables(); ++j)
@@ -498,22 +529,23 @@ void Solver::upload() {
         for (int k = 0; k < md.nr_range; ++k) ub[n_art + md.col_end[0] + k] = md.ranges[k].to_double();
         zero_width_.assign(n, 0);
         for (int j = 0; j < n; ++j) zero_width_[j] = ub[j] == 0.0 ? 1 : 0;
-        d_.ub = dmalloc<double>(n);
-        d_.xub = dmalloc<double>(m);
-        d_.flipped = dmalloc<int>(n);
+        d_.ub = device_alloc<double>(n);
+        d_.xub = device_alloc<double>(m);
+        d_.flipped = device_alloc<int>(n);
         upload_vec(d_.ub, ub, stream_);
         RELP_HIP(hipStreamSynchronize(stream_));
     }
-    if (!fast_k2_available(d_, price_blocks_ + dense_blocks_) && !sw(RELP_SW_K2_SINGLE)) {  // m > 8192: multi-workgroup ratio test
-        d_.k2_partd = dmalloc<double>((size_t)8 * ((m + 1023) / 1024));
-        d_.k2_parti = dmalloc<int>((size_t)4 * ((m + 1023) / 1024));
+    if (!fast_k2_available(d_, price_blocks_ + dense_blocks_) && (!sw(RELP_SW_K2_SINGLE) || network_)) {  // m > 8192: multi-workgroup ratio test
+        d_.k2_partd = device_alloc<double>((size_t)8 * ((m + 1023) / 1024));
+        d_.k2_parti = device_alloc<int>((size_t)4 * ((m + 1023) / 1024));
     }
     // `Tableau::select_primal_pivot_row` (tableau/mod.rs:287-313): which ratio test runs.  The reference's rule is implemented by the
     // register-resident ratio test (m <= 8192), the fused pivot kernel and the LU pivot kernel; the multi-workgroup test beyond 8192 rows
     // and the one-workgroup fallback implement the two-pass rule only.  AUTO (the default): the reference's rule where the data are
     // small integers, Harris on decimal data.
     {
-        const bool kernels_have_it = lu_mode_ || fast_k2_available(d_, price_blocks_ + dense_blocks_);
+        // (the forest carry has the reference's rule at every size: alpha is +-1 on its path, see net_enqueue_pivot)
+        const bool kernels_have_it = lu_mode_ || network_ || fast_k2_available(d_, price_blocks_ + dense_blocks_);
         bool small_integers = true;
         for (size_t e = 0; e < nnz && small_integers; ++e) small_integers = value[e] == std::nearbyint(value[e]) && std::fabs(value[e]) <= 64.0;
         for (int j = 0; j < n && small_integers; ++j) small_integers = cost2[j] == std::nearbyint(cost2[j]) && std::fabs(cost2[j]) < 1048576.0;
@@ -523,19 +555,19 @@ void Solver::upload() {
         ratio_textbook_ = opt_.ratio_rule == RELP_RATIO_TEXTBOOK || (opt_.ratio_rule == RELP_RATIO_AUTO && small_integers && kernels_have_it);
     }
     // small LPs: ratio test and inverse update in one launch (pivot_fused_kernel; RELP_NO_FUSED=1 keeps the three-kernel pivot)
-    fused_ = !lu_mode_ && !bounded_ && !eta_mode_ && n_dense == 0 && ftran_slices_ == 0 && !d_.track_touched && d_.ell_w == ELL_W &&
+    fused_ = !lu_mode_ && !network_ && !bounded_ && !eta_mode_ && n_dense == 0 && ftran_slices_ == 0 && !d_.track_touched && d_.ell_w == ELL_W &&
              fused_pivot_available(d_, price_blocks_) && opt_.pivot_kernels != 1;
     if (fused_) {
         for (int k = 0; k < 2; ++k) {
-            d_.state[k].ctl = dmalloc<Ctl>(1);
-            d_.state[k].xB = dmalloc<double>(m);
-            d_.state[k].basis = dmalloc<int>(m);
+            d_.state[k].ctl = device_alloc<Ctl>(1);
+            d_.state[k].xB = device_alloc<double>(m);
+            d_.state[k].basis = device_alloc<int>(m);
         }
         ensure_polish_buffers();  // the second buffer of the out-of-place update
     }
-    d_.scratch = dmalloc<double>((size_t)std::max(m, n) * 3 + 16);  // fine-grained ops carve m ints + 2 m doubles out of it
-    d_.ctl = dmalloc<Ctl>(1);
-    d_.dbg = dmalloc<unsigned long long>(64);
+    d_.scratch = device_alloc<double>((size_t)std::max(m, n) * 3 + 16);  // fine-grained ops carve m ints + 2 m doubles out of it
+    d_.ctl = device_alloc<Ctl>(1);
+    d_.dbg = device_alloc<unsigned long long>(64);
     RELP_HIP(hipMemsetAsync(d_.dbg, 0, 64 * sizeof(unsigned long long), stream_));
 
     upload_vec(d_.col_start, col_start, stream_);
@@ -549,17 +581,17 @@ void Solver::upload() {
     upload_vec(d_.rhs, rhs, stream_);
     upload_vec(d_.rhs0, rhs, stream_);
     if (d_.ell_w == 2 && !d_.cost8) {  // columns with values: the packed records of price_kernel<.., 2>
-        d_.prw = dmalloc<double>((size_t)4 * m);
+        d_.prw = device_alloc<double>((size_t)4 * m);
         RELP_HIP(hipMemsetAsync(d_.prw, 0, (size_t)4 * m * sizeof(double), stream_));
     } else if (d_.ell_w == 2) {  // generated columns: -pi from its own vector, rho_p's non-zero rows as bits (bytes beyond LDS)
         d_.price_unit_pairs = sw(RELP_SW_PRICE_UNIT_PAIRS);
         d_.rho_words = ((m + 127) / 128) * 4;
         if ((size_t)d_.rho_words * 4 > 64 * 1024 || sw(RELP_SW_NO_RHO_BITS) || d_.price_unit_pairs) d_.rho_words = 0;
         if (d_.rho_words) {
-            d_.rho_bits = dmalloc<unsigned>((size_t)2 * d_.rho_words);
+            d_.rho_bits = device_alloc<unsigned>((size_t)2 * d_.rho_words);
             RELP_HIP(hipMemsetAsync(d_.rho_bits, 0, (size_t)2 * d_.rho_words * sizeof(unsigned), stream_));
         } else {
-            d_.rho_nz = dmalloc<unsigned char>(m);
+            d_.rho_nz = device_alloc<unsigned char>(m);
             RELP_HIP(hipMemsetAsync(d_.rho_nz, 0, m, stream_));
         }
     }
@@ -574,10 +606,11 @@ void Solver::upload() {
     stats_.price_bytes = (long long)(col_start[n] - col_start[sparse_first_]) * 12 + (long long)(n - n_art) * 24 +
                          (long long)n_dense * m * dense_entry_bytes_;  // upper bound: every dense column non-basic
     if (d_.cost8) stats_.price_bytes = (long long)(n - n_art) * (8 + 1 + 4);  // endpoints, cost byte, pos (+ the weight of the few columns that need it)
-    stats_.update_bytes = (long long)2 * m * m * 8;
+    stats_.update_bytes = network_ ? 0 : (long long)2 * m * m * 8;
+    if (network_) net_allocate();
     h_basis_.assign(m, -1);
     h_solution_.assign(md.nr_columns(), 0.0);
-    if (lu_mode_ || opt_.crash) {
+    if (lu_mode_ || network_ || opt_.crash) {
         h_col_start_ = col_start;
         h_row_index_ = row_index;
         h_value_ = value;
@@ -651,6 +684,10 @@ void Solver::begin_phase_one() {
     }
     RELP_HIP(hipMemcpyAsync(d_.xB, d_.rhs, m * sizeof(double), hipMemcpyDeviceToDevice, stream_));
     if (lu_mode_) lu_identity();
+    else if (network_) {
+        net_upload(net_build(basis, std::vector<int>()));  // every row its own root (unit columns)
+        if (net_.stats) RELP_HIP(hipMemsetAsync(net_.stats, 0, NS_WORDS * sizeof(unsigned long long), stream_));
+    }
     else launch_identity(d_.Binv, m, d_.ld, stream_);
     RELP_HIP(hipMemsetAsync(d_.touched, 0, m * sizeof(int), stream_));  // every column is a unit vector
     binv_identity_ = true;
@@ -741,6 +778,12 @@ bool Solver::crash_basis() {
     const int covered = (int)crash_rows.size();
     tick("rows by columns, BFS");
     if (covered == 0) return false;
+    if (network_) {  // the forest carry takes the crash columns as they are: no inverse on the host
+        if (!net_crash(basis)) return false;
+        crash_rows_covered_ = covered;
+        tick("forest, x_B, weights");
+        return true;
+    }
     // Inverse by back-substitution: B (rows x positions, position of a crash column = its row) is upper triangular in the
     // order [rows that kept a unit column | crash rows in covering order].  Column r of B^-1 (r a crash row) solves B v = e_r.
     const size_t entry_cap = (size_t)64 * m + (1u << 22);
@@ -904,6 +947,7 @@ void Solver::set_phase(int phase) {
         else RELP_HIP(hipMemcpyAsync(d_.cost8, d_.cost8_2, d_.n, hipMemcpyDeviceToDevice, stream_));
     }
     if (lu_mode_) launch_lu_pi(d_, lu().device(), stream_);
+    else if (network_) net_refresh(false, true);
     else launch_pi(d_, stream_);
     // Steepest-edge weights gamma_j = 1 + |B^-1 a_j|^2 do not depend on the costs, and the recurrences that maintain them
     // are exact: what phase one leaves is what `SteepestDescentAlongObjective::new` (pivot_rule.rs:202-219) would recompute
@@ -927,6 +971,8 @@ void Solver::set_phase(int phase) {
             gamma_ready_ = false;  // the crash computed them on the host from its sparse inverse
         } else if (lu_mode_ && !binv_identity_) {
             launch_lu_gamma(d_, lu().device(), stream_);
+        } else if (network_ && !binv_identity_) {
+            net_set_gamma();
         } else {
             launch_gamma_init(d_, binv_identity_ ? 1 : 0, stream_);
         }
@@ -959,6 +1005,15 @@ void Solver::launch_pivots(int count, bool forced) {
         return;
     }
     launch_budget(d_, count, stream_);
+    if (network_) {  // pricing, entering column + tree path, ratio test, forest update: a linear chain of launches
+        for (int it = 0; it < count; ++it) {
+            enqueue_price(0);
+            net_enqueue_pivot(0);
+        }
+        stats_.launches += 1 + (long long)net_launches_per_pivot() * count;
+        stats_.price_launches += count;
+        return;
+    }
     if (lu_mode_) {  // two kernels per pivot: the pricing pass and the single-workgroup LU kernel
         for (int it = 0; it < count; ++it) {
             enqueue_price(0);
@@ -1023,6 +1078,10 @@ void Solver::enqueue_consolidate() {
 void Solver::enqueue_ftran_ratio(int mode) {
     const int skip_art = phase_ == 2 ? 1 : 0;
     const int slots = price_blocks_ + dense_blocks_;
+    if (network_) {
+        net_enqueue_pivot(mode);
+        return;
+    }
     if (lu_mode_) {
         hipEvent_t start = nullptr, stop = nullptr;
         take_launch_timer(1, &start, &stop);
@@ -1063,6 +1122,14 @@ void Solver::build_graph(int count) {
 void Solver::polish(bool refresh_vectors, bool force) {
     if (lu_mode_) {  // the LU carry's refresh is a refactorisation
         refactor_lu(refresh_vectors);
+        return;
+    }
+    if (network_) {  // the forest is exact: x_B, -pi and the objective recomputed from it
+        if (since_polish_ == 0 && !force && !(opt_.switches & RELP_SW_POLISH_ALWAYS)) return;
+        if (refresh_vectors) net_refresh(true, true);
+        polish_scale_ = std::min(256, polish_scale_ * 4);
+        polishes_++;
+        since_polish_ = 0;
         return;
     }
     // nothing has changed since the inverse was last made exact (identity, crash basis, set_basis, the previous polish): at
@@ -1121,13 +1188,17 @@ void Solver::polish(bool refresh_vectors, bool force) {
 // From-scratch inverse by Newton-Schulz from X0 = B' / (|B|_1 |B|_inf) (converges for every nonsingular B).
 // Plays the role of `BasisInverse::invert` (lower_upper/mod.rs:78-92) for `from_basis` / warm starts.
 void Solver::ensure_polish_buffers() {
-    if (d_.Binv2 == nullptr) d_.Binv2 = dmalloc<double>((size_t)d_.m * d_.ld);
-    if (d_.R == nullptr) d_.R = dmalloc<double>((size_t)d_.m * d_.ld);
+    if (d_.Binv2 == nullptr) d_.Binv2 = device_alloc<double>((size_t)d_.m * d_.ld);
+    if (d_.R == nullptr) d_.R = device_alloc<double>((size_t)d_.m * d_.ld);
 }
 
 void Solver::invert_from_scratch() {
     if (lu_mode_) {
         refactor_lu(false);
+        return;
+    }
+    if (network_) {  // the forest of the basis on the device, built on the host in O(m)
+        net_upload(net_download());
         return;
     }
     const int m = d_.m;
@@ -1261,6 +1332,7 @@ void Solver::set_basis(const int* basis_columns) {
     write_ctl(c);
     invert_from_scratch();
     if (lu_mode_) launch_lu_xb(d_, lu().device(), stream_);
+    else if (network_) net_refresh(true, false);
     else launch_xb(d_, stream_);
     binv_identity_ = false;
     refactors_ = 0;
@@ -1291,7 +1363,7 @@ long long Solver::iterate(long long count, int* stop_reason) {
         if (opt_.use_graph && batch == full_batch) {
             build_graph(batch);
             RELP_HIP(hipGraphLaunch(graph_exec_[graph_index()], stream_));
-            stats_.launches += 1 + (lu_mode_ ? 2LL : 3LL) * batch;
+            stats_.launches += 1 + (network_ ? (long long)net_launches_per_pivot() : lu_mode_ ? 2LL : 3LL) * batch;
             stats_.price_launches += batch;
         } else {
             launch_pivots(batch);
@@ -1342,6 +1414,10 @@ int Solver::drive_out_artificials() {
             RELP_HIP(hipMemcpyAsync(d_slot, &r, sizeof(int), hipMemcpyHostToDevice, stream_));
             RELP_HIP(hipMemcpyAsync(d_one, &one, sizeof(double), hipMemcpyHostToDevice, stream_));
             launch_lu_btran(lu().device(), d_slot, d_one, 1, rowvec, stream_);
+            launch_lu_row_scan(d_, rowvec, 1e-7, stream_);
+        } else if (network_) {  // row r of the inverse from the forest, then the same scan
+            double* rowvec = d_.scratch + (d_.m + 1) / 2 + 1 + d_.m;
+            launch_net_row(d_, net_, r, rowvec, stream_);
             launch_lu_row_scan(d_, rowvec, 1e-7, stream_);
         } else {
             launch_row_scan(d_, r, 1e-7, stream_);
@@ -1473,6 +1549,11 @@ void Solver::solve(relp_result* result) {
             if (pos[d_.n_art + j] != -2) h_solution_[md.col_end[4] + k2] = ub[d_.n_art + j] - h_solution_[j];
         }
     }
+    if (net_.stats) {
+        net_stats_.assign(NS_WORDS, 0);
+        RELP_HIP(hipMemcpyAsync(net_stats_.data(), net_.stats, NS_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+        RELP_HIP(hipStreamSynchronize(stream_));
+    }
     res.kind = kind;
     res.pivots_phase_one = pivots_[0];
     res.pivots_phase_two = pivots_[1];
@@ -1526,6 +1607,11 @@ std::vector<int> Solver::explicit_basis(const std::vector<int>& basis, const std
 }
 
 void Solver::certify(relp_result* result) {
+    if (network_) {  // from the forest, O(m + n) (certify_basis needs m^2 words); the other verdicts stay uncertified here
+        if (result->kind == RELP_RESULT_FINITE_OPTIMUM) net_certify(result);
+        else last_error = "RELP_CARRY_NETWORK certifies finite optima only";
+        return;
+    }
     const double t0 = now_seconds();
     bool ok = false;
     long long repairs = 0;
@@ -1756,6 +1842,13 @@ void Solver::ftran(int nnz, const int* rows, const double* values, double* out) 
     double* d_out = d_vals + d_.m;
     check_sparse(nnz, rows, values, d_.m);
     RELP_HIP(hipSetDevice(opt_.device));
+    if (network_) {
+        std::vector<double> v(d_.m, 0.0);
+        for (int e = 0; e < nnz; ++e) v[rows[e]] += values[e];
+        const std::vector<double> x = net_host_solve(net_download(), false, v);
+        std::copy(x.begin(), x.end(), out);
+        return;
+    }
     RELP_HIP(hipMemcpyAsync(d_rows, rows, nnz * sizeof(int), hipMemcpyHostToDevice, stream_));
     RELP_HIP(hipMemcpyAsync(d_vals, values, nnz * sizeof(double), hipMemcpyHostToDevice, stream_));
     if (lu_mode_) launch_lu_ftran(lu().device(), d_rows, d_vals, nnz, d_out, 0, stream_);
@@ -1769,6 +1862,13 @@ void Solver::btran(int nnz, const int* rows, const double* values, double* out) 
     double* d_out = d_vals + d_.m;
     check_sparse(nnz, rows, values, d_.m);
     RELP_HIP(hipSetDevice(opt_.device));
+    if (network_) {
+        std::vector<double> v(d_.m, 0.0);
+        for (int e = 0; e < nnz; ++e) v[rows[e]] += values[e];
+        const std::vector<double> x = net_host_solve(net_download(), true, v);
+        std::copy(x.begin(), x.end(), out);
+        return;
+    }
     RELP_HIP(hipMemcpyAsync(d_rows, rows, nnz * sizeof(int), hipMemcpyHostToDevice, stream_));
     RELP_HIP(hipMemcpyAsync(d_vals, values, nnz * sizeof(double), hipMemcpyHostToDevice, stream_));
     if (lu_mode_) launch_lu_btran(lu().device(), d_rows, d_vals, nnz, d_out, stream_);
@@ -1951,7 +2051,20 @@ double Solver::profile_kernel(int which, int repetitions) {
         RELP_HIP(hipEventCreate(&stops[k]));
     }
     Ctl before = read_ctl();
-    if (fused_) {
+    if (network_) {  // (the forest's kernels are bracketed by events of their own: 0 pricing, 1 path + ratio test, 2 forest update)
+        launch_budget(d_, repetitions, stream_);
+        for (int k = 0; k < repetitions; ++k) {
+            if (which == 0) RELP_HIP(hipEventRecord(starts[k], stream_));
+            enqueue_price(0);
+            if (which == 0) RELP_HIP(hipEventRecord(stops[k], stream_));
+            if (which == 1) RELP_HIP(hipEventRecord(starts[k], stream_));
+            net_enqueue_pivot(0, 1);
+            if (which == 1) RELP_HIP(hipEventRecord(stops[k], stream_));
+            if (which == 2) RELP_HIP(hipEventRecord(starts[k], stream_));
+            net_enqueue_pivot(0, 2);
+            if (which == 2) RELP_HIP(hipEventRecord(stops[k], stream_));
+        }
+    } else if (fused_) {
         launch_begin_batch(d_, repetitions, stream_);
         for (int k = 0; k < repetitions; ++k) {
             if (which == 0) arm_launch_timer(0, starts[k], stops[k]);
@@ -2028,3 +2141,4 @@ void Solver::get_solution(double* x) const {
 }
 
 }  // namespace relp
+

@@ -192,6 +192,27 @@ __device__ __forceinline__ void mark_rho_row(const DeviceLP& lp, int rho_buf, in
 }
 #endif
 
+// Spanning-forest carry (relp_options.carry == RELP_CARRY_NETWORK, network_carry.hip).  Every basis of a network LP is a spanning
+// forest of the rows: a basic incidence column joins two rows, a basic single-entry column (artificial, arc at a removed vertex) is
+// the root arc of its row's tree.  B^-1 (slot i, row j) = sign[child[i]] when row j lies below the arc of slot i, else 0.
+struct NetTree {
+    int* parent = nullptr;        // [m] row above this row in its tree (-1: a root)
+    int* slot = nullptr;          // [m] basis slot of the arc to the parent (a root: its root arc)
+    signed char* sign = nullptr;  // [m] entry of that basic column (negated when it is held complemented) at this row
+    int* child = nullptr;         // [m] slot -> the row below its arc
+    int* mark = nullptr;          // [m] walk stamps of the entering column's path search
+    int* chain = nullptr;         // [m] rows of one endpoint's root path (scratch of that search)
+    int* path = nullptr;          // [m] slots where alpha_in is non-zero (cleared by the next search)
+    int* state = nullptr;         // [2] stamp, path length
+    unsigned long long* stats = nullptr;  // [NS_WORDS] RELP_SW_NETWORK_STATS only: counters over the pivots since phase one began
+};
+enum : int { NS_PIVOTS = 0, NS_SUBTREE_SUM, NS_SUBTREE_MAX, NS_DEPTH_SUM, NS_DEPTH_MAX, NS_SUBTREE_NOW, NS_PATH_SUM, NS_PATH_MAX, NS_WORDS };
+// Host copy of the forest (set_basis, crash, the fine-grained operations, the certificate): `order` lists every row after its parent.
+struct HostTree {
+    std::vector<int> parent, slot, child, order, depth;
+    std::vector<signed char> sign;
+};
+
 // The calling thread's A/B switches and sizes (relp_options.switches and the fields beside it): set by the C ABI from the handle's
 // options for the duration of a call (capi.cpp `guarded`), read by the launch helpers that have no handle in reach (lu_factor.hip,
 // lu_device_tasks.hip, certify.hip).  Round 5: these were getenv calls; nothing that changes a kernel or a result reads the
@@ -282,6 +303,9 @@ public:
     void solve_exact(int first_limbs, int max_limbs, long long max_pivots, int trace_capacity, int* status, int* limbs, long long* p1,
                      long long* p2, std::vector<int>* trace, std::string* objective, std::vector<int>* basis,
                      std::vector<std::pair<int, long long>>* survived, int* redundant_rows = nullptr);
+    size_t device_bytes() const { return device_bytes_; }  // bytes this handle has allocated on the device
+    bool network_carry() const { return network_; }
+    const std::vector<unsigned long long>& network_stats() const { return net_stats_; }  // RELP_SW_NETWORK_STATS: NS_* of the last solve
     const std::vector<ExactWidthRecord>& exact_records() const { return exact_records_; }  // of the last solve_exact, one per width tried
     void last_pivot(int* phase, int* column, int* row, int* leaving);
     double refactor();
@@ -333,7 +357,26 @@ private:
     void write_ctl(const Ctl& c);
     int drive_out_artificials();
     void certify(relp_result* result);
+    std::vector<double> net_host_solve(const HostTree& t, bool transposed, const std::vector<double>& v) const;  // B^-1 v or v' B^-1
     CertifyScratch certify_scratch_;
+    // spanning-forest carry (network_carry.hip)
+    bool network_ = false;
+    NetTree net_;
+    void net_allocate();
+    HostTree net_build(const std::vector<int>& basis, const std::vector<int>& flipped) const;  // throws unless the basis is a forest
+    void net_upload(const HostTree& tree);
+    HostTree net_download();
+    void net_refresh(bool xb, bool pi);       // x_B and / or -pi (and the objective) recomputed from the forest on the device
+    void net_gamma(const HostTree& tree, const std::vector<int>& pos, std::vector<double>* gamma) const;  // 1 + path length
+    void net_set_gamma();                     // ... of every non-basic column, uploaded
+    bool net_crash(const std::vector<int>& basis);
+    void net_certify(relp_result* result);
+    int net_launches_per_pivot() const;      // pricing, path, ratio test (one kernel, or three across workgroups), update, re-hang
+    void net_enqueue_pivot(int mode, int parts = 3);  // entering column + tree path, ratio test (+ forest update in mode 0)
+    size_t device_bytes_ = 0;
+    std::vector<unsigned long long> net_stats_;
+    template <class T>
+    T* device_alloc(size_t count);
     // LU carry (relp_options.carry == RELP_CARRY_LU)
     void refactor_lu(bool refresh_vectors, bool settle = true);  // BasisInverse::invert of the current basis: kernels on the device (lu_factor.hip), or ...
     void refactor_lu_host(bool refresh_vectors);  // ... host Markowitz + upload (relp_options.lu_refactor; the LU + Forrest-Tomlin carry; the fallback)
