@@ -129,8 +129,9 @@ typedef enum relp_switch {
     RELP_SW_LUF_NO_LDS_ARENA = 1 << 12,     /* ... the active sub-matrix in global memory throughout */
     RELP_SW_LUI_CLAIM_ROWS = 1 << 13,       /* ... inversion of the triangles: rows claimed from a counter */
     RELP_SW_BI_FACTOR_HOST = 1 << 14,       /* stand-alone BasisInverse: `invert` on a host core */
-    RELP_SW_NETWORK_STATS = 1 << 15         /* RELP_CARRY_NETWORK: count row depths, subtree and path sizes at every pivot (the record's
+    RELP_SW_NETWORK_STATS = 1 << 15,        /* RELP_CARRY_NETWORK: count row depths, subtree and path sizes at every pivot (the record's
                                                "network_tree"; a diagnostic, it costs atomics in the forest update) */
+    RELP_SW_MANY_GLOBAL_TIER = 1 << 16      /* relp_many: every LP keeps its inverse in global memory, also where it fits LDS (test hook) */
 } relp_switch;
 
 typedef struct relp_options {
@@ -695,6 +696,51 @@ int32_t relp_batch_run(relp_batch* batch, const int32_t* schedule, int64_t n_tic
 int32_t relp_batch_get_objective_exact(const relp_batch* batch, int64_t ticket, char* buffer, int32_t capacity, int32_t* length);
 /* the resident handle of (worker, model), e.g. for relp_get_record_json / relp_get_solution_exact after a run */
 int32_t relp_batch_handle(const relp_batch* batch, int32_t worker, int32_t model, relp_handle** out);
+
+/* ---- many small LPs in one launch, one workgroup per LP (relp_amd/csrc/many.hip) ----------------------------
+ * `solve_relaxation` (two_phase/mod.rs:25-109) for each of `n_models` independent LPs of at most 512 standard-form rows.  Each LP is
+ * solved by ONE workgroup for its whole two-phase solve inside one ordinary kernel launch (no grid barrier, no cooperative launch):
+ * the same provider, index spaces and starting basis as a handle's (artificials first, the reference's initial slack pivots), the
+ * pricing and steepest-edge update of price_kernel (pivot_rule.rs:190-296), the two-pass ratio test of the fused pivot kernel or the
+ * textbook rule (tableau/mod.rs:287-313; RELP_RATIO_AUTO resolved per LP as relp_load_model does), the product-form update of the
+ * explicit inverse (basis_inverse_rows.rs:36-70) and zero-level pivots for the artificials left at the end of phase one
+ * (phase_one.rs:232-278; rows without one keep their artificial, as the single-LP path does).  Every `polish_period` pivots and before
+ * every verdict B^-1 is re-inverted from the basis columns by Gauss-Jordan with partial pivoting (`BasisInverse::invert`,
+ * lower_upper/mod.rs:78-92); a fresh inverse whose residual max |B B^-1 - I| exceeds 1e-6, or a singular basis, ends THAT LP with
+ * RELP_ERR_NUMERICAL.  B^-1 lives in the workgroup's LDS up to 139 rows (the LDS tier), in a per-LP slab of global memory from 140 to
+ * 512 rows (the global tier).  Results do not depend on which other LPs share the launch, nor on their order.
+ * relp_options is read as relp_create reads it; refused with RELP_ERR_ARGUMENT: a carry other than RELP_CARRY_EXPLICIT,
+ * implicit_bounds, crash, a pivot rule other than steepest edge and Dantzig, and the switches of the generated graph columns.
+ * relp_many_create checks every model before it touches the device (RELP_ERR_ARGUMENT naming the model's index, e.g. more than 512
+ * rows), then RELP_ERR_DEVICE without a usable device.  With options.certify, every FINITE_OPTIMUM, INFEASIBLE and UNBOUNDED result
+ * is proved after the launch by the exact certificate of relp_solve_relaxation; its time is `certify_seconds`, outside
+ * `*kernel_seconds` (the launch alone, HIP events). */
+typedef struct relp_many relp_many;
+typedef struct relp_many_result {
+    int32_t status;            /* relp_status of this LP: 0, or RELP_ERR_NUMERICAL */
+    int32_t kind;              /* relp_result_kind */
+    int32_t certified;         /* options.certify and the exact certificate holds */
+    int32_t inverse_in_lds;    /* 1: the LDS tier, 0: the global tier */
+    int64_t pivots_phase_one;  /* zero-level pivots included, as relp_result's */
+    int64_t pivots_phase_two;
+    int64_t reinversions;      /* Gauss-Jordan re-inversions of B */
+    double objective;          /* f64 objective incl. fixed cost (NaN unless FINITE_OPTIMUM) */
+    double max_residual;       /* largest max |B B^-1 - I| found before a re-inversion */
+    double certify_seconds;    /* host wall time of this LP's certificate */
+} relp_many_result;
+int32_t relp_many_create(const relp_model* const* models, int32_t n_models, const relp_options* options, relp_many** out, char* error,
+                         int32_t error_capacity);
+/* Solves every LP (again, from the start).  results[k]: model k, in the caller's order; *kernel_seconds: the launch. */
+int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kernel_seconds);
+/* As relp_get_basis (provider columns, -1-k for artificial k), relp_get_solution and relp_get_objective_exact, for model `model`. */
+int32_t relp_many_get_basis(const relp_many* many, int32_t model, int32_t* basis);
+int32_t relp_many_get_solution(const relp_many* many, int32_t model, double* x_structural);
+int32_t relp_many_get_objective_exact(const relp_many* many, int32_t model, char* buffer, int32_t capacity, int32_t* length);
+/* Standard-form rows and structural columns of model `model` (the lengths of the two arrays above). */
+int32_t relp_many_dimensions(const relp_many* many, int32_t model, int32_t* nr_rows, int32_t* nr_structural);
+/* Why the last relp_many_solve failed, or why a certificate was not obtained. */
+const char* relp_many_last_error(const relp_many* many);
+int32_t relp_many_free(relp_many* many);
 
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);

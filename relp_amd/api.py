@@ -44,7 +44,8 @@ class Options(C.Structure):
 
 # relp_switch bits of Options.switches (include/relp_amd.h)
 SW_NO_TOUCHED, SW_K2_SINGLE, SW_ELL_WIDE, SW_NO_GENERATED_COLUMNS, SW_NO_SLACK_IN_BTRAN, SW_NO_DENSE_LANE, SW_POLISH_ALWAYS, SW_NO_RHO_BITS, \
-    SW_PRICE_UNIT_PAIRS, SW_CERTIFY_NO_LEVELS, SW_GEMM_VECTOR, SW_LUF_CLAIM_TARGETS, SW_LUF_NO_LDS_ARENA, SW_LUI_CLAIM_ROWS, SW_BI_FACTOR_HOST, SW_NETWORK_STATS = (1 << k for k in range(16))
+    SW_PRICE_UNIT_PAIRS, SW_CERTIFY_NO_LEVELS, SW_GEMM_VECTOR, SW_LUF_CLAIM_TARGETS, SW_LUF_NO_LDS_ARENA, SW_LUI_CLAIM_ROWS, SW_BI_FACTOR_HOST, SW_NETWORK_STATS, SW_MANY_GLOBAL_TIER = \
+    (1 << k for k in range(17))
 
 # The library reads no environment variable that changes a kernel or a result (round 5).  This BINDING -- test and bench plumbing --
 # still maps the old variable names onto option fields for the tools that A/B them; an option given by the caller always wins.
@@ -124,6 +125,12 @@ class BatchWorker(C.Structure):
                 ("queue_seconds", C.c_double), ("idle_seconds", C.c_double), ("finish_seconds", C.c_double)]
 
 
+class ManyResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("kind", C.c_int32), ("certified", C.c_int32), ("inverse_in_lds", C.c_int32),
+                ("pivots_phase_one", C.c_int64), ("pivots_phase_two", C.c_int64), ("reinversions", C.c_int64),
+                ("objective", C.c_double), ("max_residual", C.c_double), ("certify_seconds", C.c_double)]
+
+
 class Stats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("price_launches", C.c_int64), ("price_seconds", C.c_double),
                 ("update_seconds", C.c_double), ("ftran_seconds", C.c_double), ("price_bytes", C.c_int64),
@@ -154,6 +161,9 @@ SYMBOLS = [
     # exact solution vector, variable names, batches of independent LPs
     "relp_get_solution_exact", "relp_get_variable_name",
     "relp_batch_create", "relp_batch_destroy", "relp_batch_workers", "relp_batch_run", "relp_batch_get_objective_exact", "relp_batch_handle",
+    # many small LPs in one launch, one workgroup each (relp_amd/csrc/many.hip)
+    "relp_many_create", "relp_many_solve", "relp_many_get_basis", "relp_many_get_solution", "relp_many_get_objective_exact",
+    "relp_many_dimensions", "relp_many_last_error", "relp_many_free",
 ]
 
 
@@ -167,6 +177,8 @@ def lib():
         _lib.relp_version.restype = C.c_char_p
         _lib.relp_last_error.restype = C.c_char_p
         _lib.relp_last_error.argtypes = [C.c_void_p]
+        _lib.relp_many_last_error.restype = C.c_char_p
+        _lib.relp_many_last_error.argtypes = [C.c_void_p]
     return _lib
 
 
@@ -755,4 +767,66 @@ class Batch:
             return None
         buf = C.create_string_buffer(length.value + 1)
         lib().relp_batch_get_objective_exact(self._h, C.c_int64(ticket), buf, length.value + 1, C.byref(length))
+        return buf.value.decode()
+
+
+class Many:
+    """``relp_many_*``: independent LPs of at most 512 rows solved in ONE launch, one workgroup per LP.
+    ``models``: ``Model`` objects (kept alive here).  Options as for ``Solver``; ``.solve()`` returns one ``ManyResult`` per model, in
+    the given order, and leaves the launch time in ``.kernel_seconds``."""
+
+    def __init__(self, models, options=None, **overrides):
+        self.models = list(models)
+        self.options = options or default_options(**overrides)
+        self._h = C.c_void_p()
+        handles = (C.c_void_p * len(self.models))(*[m._h for m in self.models])
+        error = C.create_string_buffer(512)
+        status = lib().relp_many_create(handles, len(self.models), C.byref(self.options), C.byref(self._h), error, 512)
+        if status != OK:
+            self._h = None
+            raise RelpError(status, error.value.decode() or "relp_many_create failed")
+        self.kernel_seconds = 0.0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().relp_many_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _check(self, status):
+        if status != OK:
+            raise RelpError(status, lib().relp_many_last_error(self._h).decode())
+
+    def last_error(self):
+        return lib().relp_many_last_error(self._h).decode()
+
+    def solve(self):
+        results = (ManyResult * len(self.models))()
+        seconds = C.c_double()
+        self._check(lib().relp_many_solve(self._h, results, C.byref(seconds)))
+        self.kernel_seconds = seconds.value
+        return list(results)
+
+    def _dimensions(self, i):
+        rows, structural = C.c_int32(), C.c_int32()
+        self._check(lib().relp_many_dimensions(self._h, int(i), C.byref(rows), C.byref(structural)))
+        return rows.value, structural.value
+
+    def basis(self, i):
+        """As ``Solver.basis``: provider column per row, ``-1 - k`` for artificial k."""
+        out = np.zeros(self._dimensions(i)[0], dtype=np.int32)
+        self._check(lib().relp_many_get_basis(self._h, int(i), _ptr(out, C.c_int32)))
+        return out
+
+    def solution(self, i):
+        out = np.zeros(max(1, self._dimensions(i)[1]))
+        self._check(lib().relp_many_get_solution(self._h, int(i), _ptr(out, C.c_double)))
+        return out[:self._dimensions(i)[1]]
+
+    def objective_exact(self, i):
+        length = C.c_int32()
+        lib().relp_many_get_objective_exact(self._h, int(i), None, 0, C.byref(length))
+        buf = C.create_string_buffer(length.value + 1)
+        self._check(lib().relp_many_get_objective_exact(self._h, int(i), buf, length.value + 1, C.byref(length)))
         return buf.value.decode()
