@@ -1,6 +1,6 @@
-"""bench.py -- simplex pivots/sec on Netlib 25FV47 (BASELINE.json configs[1]) on MI355X, and every other BASELINE config beside it.
+"""bench.py -- simplex pivots/sec on Netlib 25FV47 (BASELINE.json configs[1]) on MI355X; with --full, every other BASELINE config beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 25fv47] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 25fv47] [--dump-outputs DIR] [--full]
 
 One "step" = one complete ``solve_relaxation`` of the workload, LP resident in HBM when the timed region starts
 (MPS parsing, standardisation and the H2D upload happen before it).  ``value`` = pivots of all ranks / wall time,
@@ -10,19 +10,20 @@ caller (objective, pivot counts, solution, basis; the exact optimum as float64 w
 N > 1 (launched by torch.distributed.run, one rank per GPU): every rank solves its own copy -- independent LPs shard
 one per GPU with no data-path collective (weak scaling); the barrier + max-over-ranks timing is the only exchange.
 
-The JSON line carries ``roofline`` (the dominant kernel by measured time: SURVEY.md section 8(d)'s algorithmic bytes of that
-kernel / its HIP-event time per launch vs 8 TB/s HBM; the kernel's own byte count beside it) and ``cpu_baseline`` (the
-exact-rational restatement of relp's own algorithm on one host core, bounded sample).  The default run (N = 1) also measures
-the other BASELINE configs in the same process and reports them under ``configs``: the LU carry on 25FV47, the dense LP of
-config 3 with the block stored as double and in the narrowest exact type, the Netlib batch of config 4 without and with the
-reference's presolve, and the max-flow LP of config 5 from the reference's artificial start and from the crash basis --
-each with its own ``value``, ``ms_per_step``, ``roofline`` and ``cpu_baseline``.  CPU legs run as child processes, started after
-the headline's timed region (one core each; the all-cores Netlib leg runs alone at the end).
+A plain run sets up, warms up, times the K steps, writes its outputs and prints its line: nothing else.  ``--full`` adds what takes
+runs of its own: ``roofline`` (the dominant kernel by measured time: SURVEY.md section 8(d)'s algorithmic bytes of that kernel / its
+HIP-event time per launch vs 8 TB/s HBM; the kernel's own byte count beside it), the same LP with 4 copies in flight, and
+``cpu_baseline`` (the exact-rational restatement of relp's own algorithm on one host core, bounded sample).  At N = 1 on the default
+workload it also measures the other BASELINE configs in the same process and reports them under ``configs``: the LU carry on
+25FV47, the dense LP of config 3 with the block stored as double and in the narrowest exact type, the Netlib batch of config 4
+without and with the reference's presolve, and the max-flow LP of config 5 from the reference's artificial start and from the crash
+basis -- each with its own ``value``, ``ms_per_step``, ``roofline`` and ``cpu_baseline``.  CPU legs run as child processes, started
+after the headline's timed region (one core each; the all-cores Netlib leg runs alone at the end).
 
-Output: the LAST stdout line is ONE COMPACT JSON object (< 4 KB: the driver's capture is bounded) with every contract field, the
-roofline of the dominant kernel, the CPU baselines, ``value_lu_carry`` / ``value_lu_inverse_carry`` (the same LP and step under the
-LU carries: BASELINE configs[1] as written) and ``configs_summary`` {name: [value, ms_per_step, roofline.frac]}; the full record --
-per-kernel tables, every config object, CPU samples, per-rank records -- is written to ``bench_configs.json`` (``--detail``).
+Output: the LAST stdout line is ONE COMPACT JSON object (< 4 KB: the driver's capture is bounded) with every contract field and, with
+--full, the roofline of the dominant kernel, the CPU baselines, ``value_lu_carry`` / ``value_lu_inverse_carry`` (the same LP and step
+under the LU carries: BASELINE configs[1] as written) and ``configs_summary`` {name: [value, ms_per_step, roofline.frac]}; the full
+record -- per-kernel tables, every config object, CPU samples, per-rank records -- is written to ``bench_configs.json`` (``--detail``).
 """
 import argparse
 import copy
@@ -515,8 +516,8 @@ def contract_bytes(price_bytes, nnz_f, m):
 # one LP resident on the GPU: 25FV47, the dense LPs, the max-flow LPs
 # =====================================================================================================================
 def single_lp(args, ctx):
-    """Times `steps` solves of one workload (barrier + synchronize on both sides, max over ranks) and measures the kernels of a
-    pivot with HIP events inside the real pivot sequence.  Returns the line (rank 0) or None."""
+    """Times `steps` solves of one workload (barrier + synchronize on both sides, max over ranks); with --full, also 4 copies in flight
+    and the kernels of a pivot with HIP events inside the real pivot sequence.  Returns the line (rank 0) or None."""
     import torch
     import relp_amd
     from relp_amd import batch
@@ -592,7 +593,7 @@ def single_lp(args, ctx):
     elapsed, pivots = batch.aggregate(elapsed, pivots, device=ctx["reduce_device"])
 
     in_flight = None
-    if rank == 0 and world == 1 and not dense and not graph and not args.no_concurrency_probe:
+    if args.full and rank == 0 and world == 1 and not dense and not graph and not args.no_concurrency_probe:
         # headroom: the same LP, 4 independent copies in flight on this GPU (one host thread and stream each); a single
         # latency-bound solve uses a fraction of the chip.  Reported beside `value`, never as `value`.
         import threading
@@ -633,6 +634,70 @@ def single_lp(args, ctx):
                      "solution_exact_nonzeros": len(solver.solution_exact())}
         else:
             exact = {"certified": False}
+    if graph:
+        workload = ("max-flow LP (examples/max_flow.rs provider) on a random graph V=%d E=%d (splitmix64 seed 0x5EED0005): "
+                    "%d conservation rows on the device, the %d capacity rows as implicit bounds, %s" % (
+                        path[1], path[2], path[1] - 2, path[2],
+                        "phase one from the spanning-forest crash basis" if args.crash else "artificial start as in the reference"))
+        data = "synthetic"
+    elif dense:
+        workload = "synthetic dense random LP m=%d n=%d f64 (splitmix64 seed 0x5EED0001), steepest-edge pricing, dense block stored as %s" % (
+            path + ({"narrowest": "signed bytes (narrowest exact type)", "f32": "float", "f64": "double"}[args.dense_storage],))
+        data = "synthetic"
+    else:
+        workload = ("Netlib 25FV47 %dx%d, steepest-edge pricing, %s carry, exact certificate %s the timed step, %s" % (
+            solver.m, solver.n_provider, {1: "LU + Forrest-Tomlin", 2: "LU inverse factors + product-form updates"}.get(args.carry, "explicit-inverse"),
+            "outside" if args.no_certify else "inside",
+            "after the reference's presolve" if args.presolve else "no presolve (+520 virtual artificials)"))
+        data = "Netlib 25FV47.SIF (shipped problem file), one copy per GPU"
+    options = solver.options
+    lu_carry = args.carry in (1, 2) and not dense and not graph
+    line = {
+        "metric": "simplex pivots/sec + wall-clock to optimal, Netlib 25fv47 @1 GPU",
+        "value": pivots / elapsed, "unit": "pivots/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": data,
+        "config": {"workload": workload,
+                   "pivots_per_solve": int(last.pivots_phase_one + last.pivots_phase_two),
+                   "objective": last.objective,
+                   "wall_clock_to_exact_optimum_s": (loop_seconds + certify_seconds) / args.steps,
+                   "wall_clock_f64_loop_s": loop_seconds / args.steps,
+                   "pivots_per_s_f64_loop_only": pivots / world / loop_seconds if loop_seconds > 0 else None,
+                   "carry": {1: "lu", 2: "lu_inverse"}.get(args.carry, "explicit"), "refactors": int(last.refactors),
+                   "lu_refactor": ("device kernels (lu_factor.hip, lu_device_tasks.hip)" if args.lu_refactor == 1 else "host core") if lu_carry else None,
+                   "refactor_seconds_per_solve": float(last.refactor_seconds),
+                   "polishes": int(last.polishes), "max_residual_before_polish": last.max_residual,
+                   # the reference is exact and has neither tolerances nor a Harris test: what f64 adds, and what it changes
+                   # (relp_options.ratio_rule = AUTO resolves against the data at load: the per-LP record says which test ran)
+                   "ratio_rule": "harris two-pass (what AUTO -- the default -- resolves to on decimal data; the reference's textbook rule with Bland ties "
+                                 "runs on small-integer data and under relp_options.ratio_rule = 1)"
+                                 if solver.record().get("ratio_rule") == "harris" else "textbook minimum ratio, Bland ties (the reference's)",
+                   "tolerances": {"tol_dual": options.tol_dual, "tol_pivot": options.tol_pivot, "harris_delta": options.harris_delta,
+                                  "tol_feasible": options.tol_feasible},
+                   "pivot_sequence": "f64 + Harris: 2383 pivots on 25FV47 where the exact reference rule makes 2392 (tests/golden/25FV47.json); "
+                                     "the certified optimum is the same rational" if not dense and not graph else None,
+                   "parallelism": "1 LP per GPU x%d" % world,
+                   "makespan_s": elapsed, "per_rank": sorted(per_rank, key=lambda r: r["rank"]), "exact": exact,
+                   "aggregate_with_copies_in_flight": in_flight},
+    }
+    if graph:
+        line["metric"] = "simplex pivots/sec + wall-clock to optimal, max-flow LP @1 GPU"
+    elif dense:
+        line["metric"] = "simplex pivots/sec + wall-clock to optimal, dense LP @1 GPU"
+    if args.full:
+        line["roofline"] = kernel_roofline(args, solver, model, final_basis, loop_seconds / max(1, pivots // max(1, world)))
+    solver.close()
+    return line
+
+
+def kernel_roofline(args, solver, model, final_basis, seconds_per_pivot):
+    """--full: the roofline of the dominant kernel of a single-LP workload.  Runs further real pivots on `solver` after the timed steps,
+    each profiled kernel bracketed by HIP events, and prices them on the contract's bytes and on each kernel's own."""
+    import relp_amd
+    path = WORKLOADS[args.workload]
+    graph = isinstance(path, tuple) and path[0] == "maxflow"
+    dense = not isinstance(path, str) and not graph
+    lu_carry = args.carry in (1, 2) and not dense and not graph
     # ---- roofline of the dominant kernel, measured live with HIP events on the solver's stream -------------------------------
     solver.begin_phase_one()
     # (phase one of the flow LP has only a few hundred ordinary pivots before the zero-level ones: short samples there)
@@ -642,7 +707,6 @@ def single_lp(args, ctx):
         solver.iterate(20)
     reps = 40 if graph else (100 if dense else 200)  # further real pivots, the profiled kernel of each bracketed by its own event pair
     solver.profile_kernel(0, 10 if graph else 50)   # discarded: brings clocks and caches to the state of a running solve
-    lu_carry = args.carry in (1, 2) and not dense and not graph
     kernels = ["price", "lu_pivot"] if lu_carry else ["price", "ftran_ratio", "update"]
     try:
         seconds = {name: solver.profile_kernel(which, reps) for which, name in enumerate(kernels)}
@@ -722,93 +786,44 @@ def single_lp(args, ctx):
                 if pmc_names[dominant] in name:
                     traffic = entry["hbm_bytes_corrected"]
                     break
+    roofline = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "seconds_per_launch": seconds,
+                "algorithmic_bytes_per_launch": per_kernel[dominant]["contract_bytes_per_launch"],
+                "kernel_bytes_per_launch": per_kernel[dominant]["kernel_bytes_per_launch"],
+                "kernel_bytes_frac": per_kernel[dominant]["kernel_bytes_frac"],
+                "contract_bytes_per_pivot": contract, "factor_nonzeros": int(nnz_f),
+                "per_pivot": {"seconds": seconds_per_pivot, "contract_gb_s": contract["per_pivot"] / seconds_per_pivot / 1e9 if seconds_per_pivot > 0 else None,
+                              "contract_frac": contract["per_pivot"] / seconds_per_pivot / 1e9 / HBM_PEAK_GBS if seconds_per_pivot > 0 else None},
+                "kernels": per_kernel}
     if graph:
-        workload = ("max-flow LP (examples/max_flow.rs provider) on a random graph V=%d E=%d (splitmix64 seed 0x5EED0005): "
-                    "%d conservation rows on the device, the %d capacity rows as implicit bounds, %s" % (
-                        path[1], path[2], path[1] - 2, path[2],
-                        "phase one from the spanning-forest crash basis" if args.crash else "artificial start as in the reference"))
-        data = "synthetic"
+        roofline["note"] = ("the dominant kernel by measured time is listed first; 'price' generates each incidence column from the 8 bytes of "
+                            "its arc's endpoints (+ 1 B cost, 4 B basis position: 13 B per arc; a steepest-edge weight is read/written only by candidates "
+                            "and by columns with an entry in the pivot row) and gathers one packed 32-byte (-pi, rho, w) record per entry from "
+                            "L2; 'update' walks the non-zero rows of alpha in every column of the inverse that is not a unit vector (8-byte "
+                            "gathers, one cache line each: PMC traffic is line-granular)")
     elif dense:
-        workload = "synthetic dense random LP m=%d n=%d f64 (splitmix64 seed 0x5EED0001), steepest-edge pricing, dense block stored as %s" % (
-            path + ({"narrowest": "signed bytes (narrowest exact type)", "f32": "float", "f64": "double"}[args.dense_storage],))
-        data = "synthetic"
-    else:
-        workload = ("Netlib 25FV47 %dx%d, steepest-edge pricing, %s carry, exact certificate %s the timed step, %s" % (
-            solver.m, solver.n_provider, {1: "LU + Forrest-Tomlin", 2: "LU inverse factors + product-form updates"}.get(args.carry, "explicit-inverse"),
-            "outside" if args.no_certify else "inside",
-            "after the reference's presolve" if args.presolve else "no presolve (+520 virtual artificials)"))
-        data = "Netlib 25FV47.SIF (shipped problem file), one copy per GPU"
-    options = solver.options
-    seconds_per_pivot = loop_seconds / max(1, pivots // max(1, world))
-    line = {
-        "metric": "simplex pivots/sec + wall-clock to optimal, Netlib 25fv47 @1 GPU",
-        "value": pivots / elapsed, "unit": "pivots/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": data,
-        "config": {"workload": workload,
-                   "pivots_per_solve": int(last.pivots_phase_one + last.pivots_phase_two),
-                   "objective": last.objective,
-                   "wall_clock_to_exact_optimum_s": (loop_seconds + certify_seconds) / args.steps,
-                   "wall_clock_f64_loop_s": loop_seconds / args.steps,
-                   "pivots_per_s_f64_loop_only": pivots / world / loop_seconds if loop_seconds > 0 else None,
-                   "carry": {1: "lu", 2: "lu_inverse"}.get(args.carry, "explicit"), "refactors": int(last.refactors),
-                   "lu_refactor": ("device kernels (lu_factor.hip, lu_device_tasks.hip)" if args.lu_refactor == 1 else "host core") if lu_carry else None,
-                   "refactor_seconds_per_solve": float(last.refactor_seconds),
-                   "polishes": int(last.polishes), "max_residual_before_polish": last.max_residual,
-                   # the reference is exact and has neither tolerances nor a Harris test: what f64 adds, and what it changes
-                   # (relp_options.ratio_rule = AUTO resolves against the data at load: the per-LP record says which test ran)
-                   "ratio_rule": "harris two-pass (what AUTO -- the default -- resolves to on decimal data; the reference's textbook rule with Bland ties "
-                                 "runs on small-integer data and under relp_options.ratio_rule = 1)"
-                                 if solver.record().get("ratio_rule") == "harris" else "textbook minimum ratio, Bland ties (the reference's)",
-                   "tolerances": {"tol_dual": options.tol_dual, "tol_pivot": options.tol_pivot, "harris_delta": options.harris_delta,
-                                  "tol_feasible": options.tol_feasible},
-                   "pivot_sequence": "f64 + Harris: 2383 pivots on 25FV47 where the exact reference rule makes 2392 (tests/golden/25FV47.json); "
-                                     "the certified optimum is the same rational" if not dense and not graph else None,
-                   "parallelism": "1 LP per GPU x%d" % world,
-                   "makespan_s": elapsed, "per_rank": sorted(per_rank, key=lambda r: r["rank"]), "exact": exact,
-                   "aggregate_with_copies_in_flight": in_flight},
-        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "seconds_per_launch": seconds,
-                     "algorithmic_bytes_per_launch": per_kernel[dominant]["contract_bytes_per_launch"],
-                     "kernel_bytes_per_launch": per_kernel[dominant]["kernel_bytes_per_launch"],
-                     "kernel_bytes_frac": per_kernel[dominant]["kernel_bytes_frac"],
-                     "contract_bytes_per_pivot": contract, "factor_nonzeros": int(nnz_f),
-                     "per_pivot": {"seconds": seconds_per_pivot, "contract_gb_s": contract["per_pivot"] / seconds_per_pivot / 1e9 if seconds_per_pivot > 0 else None,
-                                   "contract_frac": contract["per_pivot"] / seconds_per_pivot / 1e9 / HBM_PEAK_GBS if seconds_per_pivot > 0 else None},
-                     "kernels": per_kernel},
-    }
-    if graph:
-        line["metric"] = "simplex pivots/sec + wall-clock to optimal, max-flow LP @1 GPU"
-        line["roofline"]["note"] = ("the dominant kernel by measured time is listed first; 'price' generates each incidence column from the 8 bytes of "
-                                    "its arc's endpoints (+ 1 B cost, 4 B basis position: 13 B per arc; a steepest-edge weight is read/written only by candidates "
-                                    "and by columns with an entry in the pivot row) and gathers one packed 32-byte (-pi, rho, w) record per entry from "
-                                    "L2; 'update' walks the non-zero rows of alpha in every column of the inverse that is not a unit vector (8-byte "
-                                    "gathers, one cache line each: PMC traffic is line-granular)")
-    elif dense:
-        line["metric"] = "simplex pivots/sec + wall-clock to optimal, dense LP @1 GPU"
         if args.dense_storage == "narrowest":
-            line["roofline"]["note"] = ("dense block held in the narrowest exact type (this workload: signed bytes, 1 B per entry -- data specific; the "
-                                        "generic figure is the f64-storage config): one column per lane, -pi / rho / w "
-                                        "broadcast through DPP inside the f64 FMA (no LDS traffic); 5 VALU instructions per entry = %.1f us "
-                                        "of issue time on 1024 SIMDs (tools/micro/valu_rates.hip: 1.9 ns each), the rest of the launch is "
-                                        "the first load's latency and the per-workgroup tail" % (stats.price_bytes * 5 * 1.9e-3 / 64 / 1024))
+            roofline["note"] = ("dense block held in the narrowest exact type (this workload: signed bytes, 1 B per entry -- data specific; the "
+                                "generic figure is the f64-storage config): one column per lane, -pi / rho / w "
+                                "broadcast through DPP inside the f64 FMA (no LDS traffic); 5 VALU instructions per entry = %.1f us "
+                                "of issue time on 1024 SIMDs (tools/micro/valu_rates.hip: 1.9 ns each), the rest of the launch is "
+                                "the first load's latency and the per-workgroup tail" % (stats.price_bytes * 5 * 1.9e-3 / 64 / 1024))
         else:
-            line["roofline"]["note"] = {
+            roofline["note"] = {
                 "f32": "dense block streamed as float (exact for this data; all arithmetic f64): one column per lane, 16-byte "
                        "non-temporal loads, -pi / rho / w broadcast through DPP inside the f64 FMA (no LDS traffic); bound by HBM",
                 "f64": "dense block streamed as double (SURVEY.md section 8(d)'s bytes: 8 B per entry): one column per lane, 16-byte non-temporal "
                        "loads, -pi / rho / w broadcast through DPP inside the f64 FMA (no LDS traffic); bound by HBM"}[args.dense_storage]
     else:
-        line["roofline"]["note"] = ("latency bound by construction: the dominant kernel BY MEASURED TIME is '%s'; `frac` prices it on the contract's "
-                                    "bytes (SURVEY.md section 8(d): the factor entries twice + twelve m-vectors, %d KB per pivot outside pricing), "
-                                    "`kernel_bytes_frac` on what the kernel itself streams (%d KB per launch, resident in L2 / Infinity Cache); every kernel of "
-                                    "the pivot is listed under 'kernels' with its share of the pivot time; traffic = 2 x FETCH_SIZE + "
-                                    "WRITE_SIZE of the committed PMC passes for that kernel; the HBM-roofline configuration is BASELINE "
-                                    "configs[2], under configs.dense4096_f64") % (dominant, contract["ftran_btran_vectors"] // 1024,
-                                                                                  per_kernel[dominant]["kernel_bytes_per_launch"] // 1024)
-    solver.close()
-    return line
+        roofline["note"] = ("latency bound by construction: the dominant kernel BY MEASURED TIME is '%s'; `frac` prices it on the contract's "
+                            "bytes (SURVEY.md section 8(d): the factor entries twice + twelve m-vectors, %d KB per pivot outside pricing), "
+                            "`kernel_bytes_frac` on what the kernel itself streams (%d KB per launch, resident in L2 / Infinity Cache); every kernel of "
+                            "the pivot is listed under 'kernels' with its share of the pivot time; traffic = 2 x FETCH_SIZE + "
+                            "WRITE_SIZE of the committed PMC passes for that kernel; the HBM-roofline configuration is BASELINE "
+                            "configs[2], under configs.dense4096_f64") % (dominant, contract["ftran_btran_vectors"] // 1024,
+                                                                          per_kernel[dominant]["kernel_bytes_per_launch"] // 1024)
+    return roofline
 
 
 # =====================================================================================================================
@@ -1274,6 +1289,9 @@ def main():
     parser.add_argument("--crash", type=int, default=1, help="graph workloads: start phase one from the spanning-forest crash basis")
     parser.add_argument("--dense-storage", choices=["narrowest", "f32", "f64"], default="narrowest",
                         help="dense workloads: storage type of the dense block (narrowest exact type: signed bytes for this generator)")
+    parser.add_argument("--full", action="store_true",
+                        help="measure everything besides the headline as well: the roofline of the dominant kernel, 4 copies in flight, the CPU "
+                             "baselines and (N = 1, default workload) every other BASELINE config; a plain run times the headline alone")
     parser.add_argument("--cpu-seconds", type=float, default=15.0)
     parser.add_argument("--exact-cpu-seconds", type=float, default=150.0,
                         help="budget of the exact CPU port on 25FV47 (same_work_exact_25fv47: the device is timed on the pivots it reached; "
@@ -1346,12 +1364,12 @@ def main():
     batch_workload = path == "batch"
     graph = isinstance(path, tuple) and path[0] == "maxflow"
     dense = not isinstance(path, str) and not graph
-    full = rank == 0 and world == 1 and args.workload == "25fv47" and not args.no_configs and not args.presolve and args.carry == 0
+    configs = args.full and rank == 0 and world == 1 and args.workload == "25fv47" and not args.no_configs and not args.presolve and args.carry == 0
 
-    # CPU legs (reported at N = 1 only) start AFTER the headline's timed region -- nothing competes with the host thread that feeds the
-    # GPU while `value` is measured -- and run beside the other configs
+    # CPU legs (--full, reported at N = 1 only) start AFTER the headline's timed region -- nothing competes with the host thread that feeds
+    # the GPU while `value` is measured -- and run beside the other configs
     legs = CpuLegs()
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
 
     line = netlib_batch(args, ctx) if batch_workload else single_lp(args, ctx)
     if rank == 0 and args.dump_outputs:
@@ -1361,13 +1379,13 @@ def main():
         legs.start("exact_faithful", "exact_faithful", args.cpu_seconds)
         legs.start("exact_tuned", "exact_tuned", args.cpu_seconds)
         legs.start("f64", "f64", args.cpu_seconds)
-    if want_cpu and (dense or full):
+    if want_cpu and (dense or configs):
         dims = path if dense else WORKLOADS["dense4096"]
         legs.start("dense", "dense:%dx%d" % dims, args.cpu_seconds)
-    if want_cpu and (graph or full):
+    if want_cpu and (graph or configs):
         legs.start("maxflow", "maxflow", args.cpu_seconds)
     if rank == 0:
-        if full:
+        if configs:
             line["configs"] = all_configs(args, ctx, legs)
             # BASELINE configs[1] as written ("LU carry BasisInverse"): the same LP, same step, under the two LU carries
             for key, name in (("value_lu_carry", "lu_carry_25fv47"), ("value_lu_inverse_carry", "lu_inverse_carry_25fv47"),

@@ -1,6 +1,7 @@
-"""The driver's contract for ``bench.py`` (``-m gpu``): one JSON line as the LAST line of stdout with the named fields, the
-roofline object of the dominant kernel and the CPU baseline -- the default workload, end to end as a child process."""
+"""The driver's contract for ``bench.py`` (``-m gpu``): one JSON line as the LAST line of stdout with the named fields -- and with
+``--full``, the roofline object of the dominant kernel and the CPU baseline -- the default workload, end to end as a child process."""
 import os
+import time
 
 import pytest
 
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_bench_line_contract():
-    short, line, _ = run_bench(["--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--no-configs", "--no-concurrency-probe"])
+    short, line, _ = run_bench(["--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--no-configs", "--no-concurrency-probe"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in line, key
@@ -52,6 +53,23 @@ def test_default_bench_line_contract():
     assert line["config"]["exact"]["solution_exact_nonzeros"] > 0
 
 
+def test_plain_bench_line_is_the_headline_alone():
+    """A plain run (no --full): set-up, warm-up, the timed steps and the line -- the contract's fields and the certified optimum of the last
+    timed step, with no roofline, CPU baseline, copies in flight or other configs, and little time spent outside the steps."""
+    start = time.perf_counter()
+    short, line, _ = run_bench(["--steps", "2", "--warmup", "1"])
+    outside = time.perf_counter() - start - (line["steps"] + line["warmup"]) * line["ms_per_step"] * 1e-3
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in short and key in line, key
+    for key in ("roofline", "cpu_baseline", "cpu_baseline_tuned", "cpu_baseline_f64", "configs", "value_lu_carry", "same_work_exact"):
+        assert key not in line and key not in short, key
+    assert "configs_summary" not in short and line["config"]["aggregate_with_copies_in_flight"] is None
+    assert short["config"]["certified"] is True and short["config"]["objective_bits"] == 1791
+    assert abs(short["config"]["objective"] - 5501.8458883) < 1e-6 and line["config"]["exact"]["certified"] is True
+    assert abs(line["value"] - line["config"]["pivots_per_solve"] / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert outside < 90.0, outside  # (the whole run with --full spends minutes outside its steps)
+
+
 def test_netlib_batch_line_through_the_library_batch_entry():
     """`bench.py --workload netlib --steps 1`: the batch runner (relp_batch_run, four LPs in flight) on one GPU."""
     short, line, _ = run_bench(["--workload", "netlib", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
@@ -66,10 +84,10 @@ def test_netlib_batch_line_through_the_library_batch_entry():
 
 
 def test_default_bench_compact_line_and_detail_file_with_every_baseline_config():
-    """The driver's default invocation: the LAST stdout line is compact (parses from the final 4096 bytes: checked by run_bench) and
+    """The driver's invocation with --full: the LAST stdout line is compact (parses from the final 4096 bytes: checked by run_bench) and
     carries the headline, its roofline and CPU baseline, the LU carries' figures on the same LP at top level and a summary of every
     other BASELINE config; the detail file carries every config with its own value, roofline and CPU baseline (short CPU legs here)."""
-    short, line, _ = run_bench(["--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--exact-cpu-seconds", "20"], timeout=1500)
+    short, line, _ = run_bench(["--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--exact-cpu-seconds", "20"], timeout=1500)
     configs = line["configs"]
     assert set(short["configs_summary"]) == set(configs)
     for name, triple in short["configs_summary"].items():

@@ -516,14 +516,14 @@ def test_bench_more_ranks_than_devices_fails_loudly():
 @pytest.mark.gpu
 @pytest.mark.parametrize("crash", [1, 0], ids=["crash-basis", "reference-start"])
 def test_bench_max_flow_workload_line(crash):
-    """`bench.py --workload maxflow64k` (the 64 k-arc twin of BASELINE config 5) end to end as a child process: one JSON line with the
+    """`bench.py --workload maxflow64k --full` (the 64 k-arc twin of BASELINE config 5) end to end as a child process: one JSON line with the
     roofline of every kernel of the pivot, with and without the crash basis (the roofline leg profiles phase two when phase one has
     nothing to do)."""
     import json
     import subprocess
     import sys
     from bench_support import run_bench
-    short, line, _ = run_bench(["--workload", "maxflow64k", "--steps", "1", "--warmup", "1", "--crash", str(crash), "--no-cpu-baseline"], timeout=600)
+    short, line, _ = run_bench(["--workload", "maxflow64k", "--full", "--steps", "1", "--warmup", "1", "--crash", str(crash), "--no-cpu-baseline"], timeout=600)
     assert abs(short["config"]["objective"] + 421.0) < 1e-9 and short["roofline"]["frac"] > 0
     assert line["unit"] == "pivots/s" and line["n_gpus"] == 1 and line["value"] > 0
     assert abs(line["config"]["objective"] + 421.0) < 1e-9            # scipy's max-flow value on this graph
@@ -550,12 +550,12 @@ def test_bench_two_ranks_sharing_one_device(workload):
     from bench_support import run_bench
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", "29537"]
-    short, line, out = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload], env=env, launcher=launcher)
+    short, line, out = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload, "--full"], env=env, launcher=launcher)
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]  # rank 0 prints the one line
     assert short["n_gpus"] == 2 and short["value"] > 0 and "configs_summary" not in short and "cpu_baseline" not in short
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["value"] > 0
-    assert "configs" not in line and "cpu_baseline" not in line  # N = 1 only
+    assert "configs" not in line and "cpu_baseline" not in line  # N = 1 only, even with --full
     config = line["config"]
     if workload == "netlib":
         assert line["scaling"] == "strong"

@@ -20,6 +20,6 @@ python3 $R/tools/pmc_traffic.py $OUT/fetch $OUT/write $OUT/pmc_traffic_crash1.js
 rm -rf $OUT/fetch $OUT/write
 cd $R
 unset RELP_GRAPH RELP_CRASH RELP_IMPLICIT_BOUNDS
-python3 bench.py --workload maxflow --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_maxflow_crash.json 2> $OUT/bench_crash.log
-python3 bench.py --workload maxflow --steps 1 --warmup 0 --crash 0 --no-cpu-baseline > $OUT/bench_maxflow_reference_start.json 2> $OUT/bench_nocrash.log
+python3 bench.py --full --workload maxflow --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_maxflow_crash.json 2> $OUT/bench_crash.log
+python3 bench.py --full --workload maxflow --steps 1 --warmup 0 --crash 0 --no-cpu-baseline > $OUT/bench_maxflow_reference_start.json 2> $OUT/bench_nocrash.log
 ls -la $OUT

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/prof_r5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 COMMON="--no-cpu-baseline --no-configs --no-concurrency-probe"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_25fv47 -- python3 $R/bench.py --steps 3 --warmup 1 $COMMON > $OUT/bench_25fv47_under_rocprof.json 2> $OUT/stats_25fv47.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_25fv47 -- python3 $R/bench.py --full --steps 3 --warmup 1 $COMMON > $OUT/bench_25fv47_under_rocprof.json 2> $OUT/stats_25fv47.log
 find $OUT/stats_25fv47 -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_25fv47.csv \;
 rm -rf $OUT/stats_25fv47
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_exact -- python3 $R/tools/exact_roofline.py 25FV47 > $OUT/exact_roofline_under_rocprof.txt 2> $OUT/stats_exact.log
