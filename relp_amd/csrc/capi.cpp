@@ -10,18 +10,7 @@
 #include "presolve.hpp"
 #include "solver.hpp"
 
-namespace relp {
-void exact_finish_entries(int device, int limbs, int count, const unsigned long long* T, const int* carry, const int* words, int shift, int flip,
-                          unsigned long long* N_out, int* bits_out);
-void exact_words_test(int device, int limbs, int mode, int count, const unsigned long long* a, const unsigned long long* b, unsigned long long* out);
-void grid_barrier_test(int device, int grid, int rounds, int reads, int mode, long long limit_ticks, long long* out8);
-double exact_tile_bench(int device, int limbs, int tiles, int nb64, int terms, int shift);
-}
 using namespace relp;
-
-struct relp_model {
-    StandardForm form;
-};
 
 struct relp_handle {
     relp_options options;

@@ -736,7 +736,7 @@ struct CertifyStatic {
     std::vector<Rat> rhs;
     std::vector<i128> row_mult;
     i128 cost_mult = 1;
-    std::vector<int> artificial_rows;
+    DeviceColumns cols;
     std::vector<BigInt> rhs_big;
     BigInt rhs_den = BigInt(1);
 };
@@ -765,8 +765,6 @@ std::vector<std::pair<int, std::string>> exact_primal_values(const ExactPrimal& 
     return out;
 }
 
-// The exact primal values of a certificate made elsewhere (network_carry.hip: the forest's): provider column and value, over one
-// common denominator.
 std::shared_ptr<const ExactPrimal> make_exact_primal(const std::vector<int>& columns, const std::vector<Rat>& values) {
     auto primal = std::make_shared<ExactPrimal>();
     primal->basis = columns;
@@ -844,13 +842,7 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
             built->cost_mult = 0;  // (only the phase-one certificate, which has its own costs, can do without)
         }
         // basis columns: provider column c >= 0, or artificial -1-k (unit column on its row, cost 0; redundant rows)
-        {
-            auto pivots = md.pivot_element_indices();
-            std::vector<char> has(m, 0);
-            for (auto& [row, column] : pivots) has[row] = 1;
-            for (int i = 0; i < m; ++i)
-                if (!has[i]) built->artificial_rows.push_back(i);
-        }
+        built->cols = DeviceColumns(md);
         // b_i * row_mult_i = rhs_big[i] / rhs_den  (exact, arbitrary width)
         built->rhs_big.resize(m);
         {
@@ -875,7 +867,7 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         return;
     }
     const i128 cost_mult = mode == 1 ? (i128)1 : statics->cost_mult;
-    const std::vector<int>& artificial_rows = statics->artificial_rows;
+    const DeviceColumns& cols = statics->cols;
     const std::vector<BigInt>& rhs_big = statics->rhs_big;
     const BigInt& rhs_den = statics->rhs_den;
     auto scaled = [&](const Rat& v, i128 mult) { return mul_checked(v.n, mult / v.d); };
@@ -906,7 +898,7 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
                 if (!fits(cv)) { *message = "scaled cost does not fit 62 bits"; return; }
                 cost_basis[k] = (i64)cv;
             } else {
-                int row = artificial_rows.at(-1 - c);
+                int row = cols.artificial_rows.at(cols.to_device(c));
                 if (!fits(row_mult[row])) { *message = "row multiplier does not fit 62 bits"; return; }
                 B.row_index.push_back(row);
                 B.value.push_back((i64)row_mult[row]);

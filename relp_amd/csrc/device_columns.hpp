@@ -1,0 +1,90 @@
+// The index space of the device LP, in one place (host-only).
+//
+// Every solve path numbers its columns [one artificial per row without an initial pivot | provider columns]: the virtual identity
+// columns of `Partially::original_column` (kind/artificial/partially.rs:52-60) first, then the columns of `MatrixData::column`
+// (matrix_data.rs:308-327).  It starts from "artificial k on its row, the free slack pivot on the others"
+// (`Carry::create_for_partially_artificial`, carry/mod.rs:397-442) and reports a basis in provider columns, with a negative code
+// for artificial k.  `DeviceColumns` is that numbering; `DeviceMatrix` is the f64 data the f64 paths put behind it (the exact paths
+// scale their own integers and need the numbering only).
+#pragma once
+#include <cmath>
+#include <vector>
+
+#include "model.hpp"
+
+namespace relp {
+
+struct DeviceColumns {
+    int m = 0, n_p = 0, n_art = 0;
+    std::vector<int> artificial_rows;  // [n_art] row of artificial k
+    std::vector<int> basis0;           // [m] device column basic in row i at the start of phase one
+
+    DeviceColumns() = default;
+    // The first `rows` rows and `provider_columns` columns of `md`: all of them, or with implicit bounds the constraint rows and the
+    // first four column groups (the bound rows and their slack columns are not part of the device LP then).
+    DeviceColumns(const MatrixData& md, int rows, int provider_columns) : m(rows), n_p(provider_columns) {
+        std::vector<int> real_column_of_row(m, -1);
+        for (auto& [row, column] : md.pivot_element_indices())
+            if (row < m && column < n_p) real_column_of_row[row] = column;
+        for (int i = 0; i < m; ++i)
+            if (real_column_of_row[i] < 0) artificial_rows.push_back(i);
+        n_art = (int)artificial_rows.size();
+        basis0.resize(m);
+        for (int i = 0, k = 0; i < m; ++i) basis0[i] = real_column_of_row[i] < 0 ? k++ : n_art + real_column_of_row[i];
+    }
+    explicit DeviceColumns(const MatrixData& md) : DeviceColumns(md, md.nr_rows(), md.nr_columns()) {}
+
+    int n() const { return n_art + n_p; }
+    std::vector<int> pos0() const {  // device column -> its row in basis0, -1 for the others
+        std::vector<int> pos(n(), -1);
+        for (int i = 0; i < m; ++i) pos[basis0[i]] = i;
+        return pos;
+    }
+    // device column <-> provider code: the provider column, or -1 - k for artificial k
+    int to_provider(int device_column) const { return device_column >= n_art ? device_column - n_art : -1 - device_column; }
+    int to_device(int provider_code) const { return provider_code >= 0 ? n_art + provider_code : -1 - provider_code; }
+    std::vector<int> to_provider(const std::vector<int>& device_basis) const {
+        std::vector<int> out(device_basis.size());
+        for (size_t i = 0; i < out.size(); ++i) out[i] = to_provider(device_basis[i]);
+        return out;
+    }
+};
+
+// f64 CSC of [artificials | provider columns] (12 bytes per virtual column, so materialising them costs nothing and makes the
+// pricing pass one uniform CSC sweep), the costs of phase two and the right-hand side.
+struct DeviceMatrix {
+    std::vector<int> col_start, row_index;
+    std::vector<double> value, cost2, rhs;
+
+    DeviceMatrix() = default;
+    DeviceMatrix(const DeviceColumns& c, const MatrixData& md) : col_start(c.n() + 1, 0), cost2(c.n(), 0.0), rhs(c.m) {
+        for (int k = 0; k < c.n_art; ++k) {
+            row_index.push_back(c.artificial_rows[k]);
+            value.push_back(1.0);
+            col_start[k + 1] = (int)row_index.size();
+        }
+        for (int j = 0; j < c.n_p; ++j) {
+            const SparseColumn column = md.column(j);
+            for (size_t e = 0; e < column.nnz(); ++e) {
+                if (column.index[e] >= c.m) continue;  // the bound-row entry of a bounded column (implicit bounds)
+                row_index.push_back(column.index[e]);
+                value.push_back(column.value[e].to_double());
+            }
+            col_start[c.n_art + j + 1] = (int)row_index.size();
+            cost2[c.n_art + j] = md.cost_value(j).to_double();
+        }
+        const auto rhs_exact = md.right_hand_side();
+        for (int i = 0; i < c.m; ++i) rhs[i] = rhs_exact[i].to_double();
+    }
+    // RELP_RATIO_AUTO takes the reference's ratio test on such data: every entry an integer with |a| <= 64, costs and right-hand
+    // side integers below 2^20.
+    bool small_integer_data() const {
+        bool small_integers = true;
+        for (size_t e = 0; e < value.size() && small_integers; ++e) small_integers = value[e] == std::nearbyint(value[e]) && std::fabs(value[e]) <= 64.0;
+        for (size_t j = 0; j < cost2.size() && small_integers; ++j) small_integers = cost2[j] == std::nearbyint(cost2[j]) && std::fabs(cost2[j]) < 1048576.0;
+        for (size_t i = 0; i < rhs.size() && small_integers; ++i) small_integers = rhs[i] == std::nearbyint(rhs[i]) && std::fabs(rhs[i]) < 1048576.0;
+        return small_integers;
+    }
+};
+
+}  // namespace relp

@@ -3854,13 +3854,9 @@ void exact_simplex(const StandardForm& form, int device, hipStream_t stream, int
         return (i64)v;
     };
     // index space of the device loop: artificials first (one per row without an initial pivot), then the provider columns
-    auto pivots = md.pivot_element_indices();
-    std::vector<int> real_column_of_row(m, -1);
-    for (auto& [row, column] : pivots) real_column_of_row[row] = column;
-    std::vector<int> artificial_rows;
-    for (int i = 0; i < m; ++i)
-        if (real_column_of_row[i] < 0) artificial_rows.push_back(i);
-    const int n_art = (int)artificial_rows.size(), n = n_art + n_p;
+    const DeviceColumns cols(md);
+    const std::vector<int>& artificial_rows = cols.artificial_rows;
+    const int n_art = cols.n_art, n = cols.n();
     // lcm of the row multipliers (W = lcm^2 weights the squared norms) and of those of the artificial rows (phase-one costs)
     i128 lcm_all = 1, lcm_art = 1;
     for (int i = 0; i < m; ++i) lcm_all = lcm(lcm_all, row_mult[i]);
@@ -3897,14 +3893,8 @@ void exact_simplex(const StandardForm& form, int device, hipStream_t stream, int
         set_weight(n_art + j, ratio);
     }
     for (int i = 0; i < m; ++i) rhs_scaled[i] = small(mul_checked(rhs[i].n, row_mult[i] / rhs[i].d));
-    std::vector<int> basis0(m), pos0(n, -1);
-    {
-        int k = 0;
-        for (int i = 0; i < m; ++i) {
-            basis0[i] = real_column_of_row[i] < 0 ? k++ : n_art + real_column_of_row[i];
-            pos0[basis0[i]] = i;
-        }
-    }
+    const std::vector<int>& basis0 = cols.basis0;
+    const std::vector<int> pos0 = cols.pos0();
     // B_0 = diag(d_i) with d_i the unit entry of row i's initial basic column (1 after the scaling above): D_0 = prod d_i
     std::vector<i64> diag0(m);
     for (int i = 0; i < m; ++i) {
@@ -4198,10 +4188,7 @@ void exact_simplex(const StandardForm& form, int device, hipStream_t stream, int
         }
         std::vector<int> basis(m);
         RELP_HIP(hipMemcpy(basis.data(), d_basis, m * sizeof(int), hipMemcpyDeviceToHost));
-        if (final_basis) {
-            final_basis->resize(m);
-            for (int i = 0; i < m; ++i) (*final_basis)[i] = basis[i] >= n_art ? basis[i] - n_art : -1 - basis[i];
-        }
+        if (final_basis) *final_basis = cols.to_provider(basis);
         if (objective && out[0] == EX_OPTIMAL) {
             // objective = sum_i c_{B_i} x~_i / (D cost_mult) + fixed cost   (general_form/mod.rs:840-851)
             std::vector<u64> hx((size_t)m * big), hd(big);

@@ -1,0 +1,58 @@
+// Launch helpers that one file defines and another calls: the f64 pipeline of kernels.hip and the forest carry's row of the inverse
+// (network_carry.hip).  Included by the defining file too, so that a changed parameter list is a diagnostic and not a link error.
+#pragma once
+#include "solver.hpp"
+
+namespace relp {
+
+// kernels.hip
+void launch_price(const DeviceLP& d, int rule, int blocks, size_t lds, bool use_lds, int skip_weights, double tol,
+                  int first, int last, int cand_offset, hipStream_t s);
+void launch_price_dense(const DeviceLP& d, int blocks, int skip_weights, double tol, int cand_offset, hipStream_t s);
+void configure_dense_lds(size_t lds);
+int dense_lane_slots(int n_dense);
+int dense_lane_ld(int m);
+void launch_ftran_partial(const DeviceLP& d, int n_slices, int n_price_blocks, int rule, hipStream_t s);
+bool fast_k2_available(const DeviceLP& d, int n_price_blocks);
+void arm_launch_timer(int which, hipEvent_t start, hipEvent_t stop);
+void take_launch_timer(int which, hipEvent_t* start, hipEvent_t* stop);
+void configure_lds(size_t price_lds);
+int price_columns_per_block(int ell_w, bool generated);
+void launch_ftran_ratio(const DeviceLP& d, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
+                        int skip_artificial_rows, int mode, int n_alpha_slices, hipStream_t s);
+void launch_update(const DeviceLP& d, hipStream_t s);
+bool fused_pivot_available(const DeviceLP& d, int n_price_blocks);
+void launch_pivot_fused(const DeviceLP& d, int rule, int parity, int n_price_blocks, double tol_pivot, double harris_delta,
+                        int skip_artificial_rows, hipStream_t s);
+void launch_begin_batch(const DeviceLP& d, long long add, hipStream_t s);
+void launch_commit(const DeviceLP& d, int parity, hipStream_t s);
+void launch_budget(const DeviceLP& d, long long add, hipStream_t s);
+void launch_pi(const DeviceLP& d, hipStream_t s);
+void launch_cb(const DeviceLP& d, hipStream_t s);
+void launch_k2l_preselected(const DeviceLP& d, double tol_pivot, double harris_delta, int skip_artificial_rows, hipStream_t s);
+void launch_xb(const DeviceLP& d, hipStream_t s);
+void launch_gamma_init(const DeviceLP& d, int identity, hipStream_t s);
+void launch_identity(double* X, int m, int ld, hipStream_t s);
+void launch_scatter(double* X, const long long* index, const double* value, long long count, hipStream_t s);
+void launch_residual(const DeviceLP& d, const double* X, double* R, hipStream_t s);
+void launch_gemm_polish(const double* X, const double* R, double* C, int m, int ld, const int* row_list, int n_rows, hipStream_t s);
+void launch_residual_dense(const DeviceLP& d, double* Bd, const double* T, double* S, const int* row_list, int n_rows, hipStream_t s);
+void launch_copy_rows(const double* src, double* dst, int m, int ld, const int* row_list, int n_rows, hipStream_t s);
+bool gemm_row_lists_supported();
+void launch_alpha_reduce(const DeviceLP& d, int n_slices, hipStream_t s);
+int eta_max();
+void configure_btran_lds(size_t lds);
+void launch_eta_update(const DeviceLP& d, double tol_dual, hipStream_t s);
+int btran_pass_blocks();
+void launch_eta_consolidate(const DeviceLP& d, hipStream_t s);
+void launch_mark_all_touched(const DeviceLP& d, hipStream_t s);
+void launch_scaled_basis(const DeviceLP& d, double* T, double scale, hipStream_t s);
+void launch_row_scan(const DeviceLP& d, int r, double tol, hipStream_t s);
+void launch_ftran_vec(const DeviceLP& d, const int* rows, const double* vals, int nnz, double* out, hipStream_t s);
+void launch_btran_vec(const DeviceLP& d, const int* rows, const double* vals, int nnz, double* out, hipStream_t s);
+void launch_relative_cost(const DeviceLP& d, double* out, hipStream_t s);
+
+// network_carry.hip
+void launch_net_row(const DeviceLP& d, const NetTree& t, int r, double* out, hipStream_t s);
+
+}  // namespace relp

@@ -205,6 +205,7 @@ void launch_lu_xb(const DeviceLP& d, const DeviceLU& lu, hipStream_t s);
 void launch_lu_pi(const DeviceLP& d, const DeviceLU& lu, hipStream_t s);
 void launch_lu_gamma(const DeviceLP& d, const DeviceLU& lu, hipStream_t s);
 void launch_lu_row_scan(const DeviceLP& d, const double* rowvec, double tol, hipStream_t s);
+void launch_clear_refactor_status(const DeviceLP& d, hipStream_t s);
 
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -36,10 +36,6 @@
 
 namespace relp {
 
-void certify_basis(const StandardForm& form, const std::vector<int>& basis_provider_columns, int device, hipStream_t stream,
-                   std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
-                   std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch);
-
 constexpr int MANY_THREADS = 512;
 constexpr int MANY_WAVES = MANY_THREADS / WAVE;
 constexpr int MANY_MAX_ROWS = 512;
@@ -474,69 +470,33 @@ double many_now() {
 constexpr unsigned MANY_REFUSED_SWITCHES = RELP_SW_ELL_WIDE | RELP_SW_PRICE_UNIT_PAIRS | RELP_SW_NO_RHO_BITS | RELP_SW_NETWORK_STATS;
 }  // namespace
 
-// One LP as the device sees it: what Solver::upload builds for the explicit carry without implicit bounds.
+// One LP as the device sees it (the index space and the data a `Solver` with the explicit carry and no implicit bounds has), and
+// what is this path's own: the tier, the launch group and the work estimate.
 struct ManyHostLP {
     int m = 0, n = 0, n_art = 0, textbook = 0, lds = 0, bucket = 0;
-    std::vector<int> col_start, row_index, basis0;
-    std::vector<double> value, cost2, rhs;
+    DeviceColumns cols;
+    DeviceMatrix data;
     double work = 0.0;  // estimated solve time, for the launch order
 };
 
 ManyHostLP many_host_lp(const StandardForm& form, const relp_options& o) {
-    const MatrixData& md = form.data;
     ManyHostLP lp;
-    const int m = md.nr_rows(), n_p = md.nr_columns();
-    std::vector<int> real_column_of_row(m, -1);
-    for (auto& [row, column] : md.pivot_element_indices())
-        if (row < m && column < n_p) real_column_of_row[row] = column;
-    std::vector<int> artificial_rows;
-    for (int i = 0; i < m; ++i)
-        if (real_column_of_row[i] < 0) artificial_rows.push_back(i);
-    const int n_art = (int)artificial_rows.size(), n = n_art + n_p;
-    lp.m = m;
-    lp.n = n;
-    lp.n_art = n_art;
-    lp.col_start.assign(n + 1, 0);
-    for (int k = 0; k < n_art; ++k) {
-        lp.row_index.push_back(artificial_rows[k]);
-        lp.value.push_back(1.0);
-        lp.col_start[k + 1] = (int)lp.row_index.size();
-    }
-    for (int j = 0; j < n_p; ++j) {
-        const SparseColumn c = md.column(j);
-        for (size_t e = 0; e < c.nnz(); ++e) {
-            lp.row_index.push_back(c.index[e]);
-            lp.value.push_back(c.value[e].to_double());
-        }
-        lp.col_start[n_art + j + 1] = (int)lp.row_index.size();
-    }
-    lp.cost2.assign(n, 0.0);
-    for (int j = 0; j < n_p; ++j) lp.cost2[n_art + j] = md.cost_value(j).to_double();
-    const auto rhs = md.right_hand_side();
-    lp.rhs.resize(m);
-    for (int i = 0; i < m; ++i) lp.rhs[i] = rhs[i].to_double();
-    lp.basis0.resize(m);
-    for (int i = 0, k = 0; i < m; ++i) lp.basis0[i] = real_column_of_row[i] < 0 ? k++ : n_art + real_column_of_row[i];
+    lp.cols = DeviceColumns(form.data);
+    lp.data = DeviceMatrix(lp.cols, form.data);
+    const int m = lp.m = lp.cols.m, n = lp.n = lp.cols.n();
+    lp.n_art = lp.cols.n_art;
     // RELP_RATIO_AUTO as Solver::upload resolves it (every LP here has at most 512 rows: the kernels have the textbook rule)
-    bool small_integers = true;
-    for (double v : lp.value) small_integers = small_integers && v == std::nearbyint(v) && std::fabs(v) <= 64.0;
-    for (double v : lp.cost2) small_integers = small_integers && v == std::nearbyint(v) && std::fabs(v) < 1048576.0;
-    for (double v : lp.rhs) small_integers = small_integers && v == std::nearbyint(v) && std::fabs(v) < 1048576.0;
-    lp.textbook = o.ratio_rule == RELP_RATIO_TEXTBOOK || (o.ratio_rule == RELP_RATIO_AUTO && small_integers);
+    lp.textbook = o.ratio_rule == RELP_RATIO_TEXTBOOK || (o.ratio_rule == RELP_RATIO_AUTO && lp.data.small_integer_data());
     lp.lds = m <= many_lds_tier_rows() && !(o.switches & RELP_SW_MANY_GLOBAL_TIER);
     // launch groups: three LDS sizes (7, 2 and 1 workgroups per CU) and the global tier
     lp.bucket = !lp.lds ? 3 : m <= 48 ? 0 : m <= 96 ? 1 : 2;
-    lp.work = (double)(m + n) * m * ((double)m + (double)lp.row_index.size() / std::max(1, n));
+    lp.work = (double)(m + n) * m * ((double)m + (double)lp.data.row_index.size() / std::max(1, n));
     return lp;
 }
 
 }  // namespace relp
 
 using namespace relp;
-
-struct relp_model {  // (as capi.cpp defines it)
-    StandardForm form;
-};
 
 struct relp_many {
     relp_options options;
@@ -553,11 +513,12 @@ struct relp_many {
     int bucket_rows[4] = {0, 0, 0, 0};  // largest m of each bucket
     hipStream_t streams[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_done[4] = {nullptr, nullptr, nullptr, nullptr};
+    DeviceAllocations memory;  // every device array above
     CertifyScratch certify_scratch;
     // results of the last solve
     bool solved = false;
     std::vector<relp_many_result> results;
-    std::vector<std::vector<int>> bases;      // provider columns, -1 - k for artificial k
+    std::vector<std::vector<int>> bases;      // provider codes (DeviceColumns::to_provider)
     std::vector<std::vector<double>> solutions;  // every column of MatrixData
     std::vector<std::string> exact;
     std::string error;
@@ -565,9 +526,7 @@ struct relp_many {
     void release() {
         (void)hipSetDevice(device);
         certify_scratch.release();
-        for (void* p : {(void*)d_lps, (void*)d_order, (void*)d_col_start, (void*)d_row_index, (void*)d_basis0, (void*)d_pos, (void*)d_basis_out,
-                        (void*)d_value, (void*)d_cost2, (void*)d_rhs, (void*)d_gamma, (void*)d_inverse, (void*)d_xb_out, (void*)d_out})
-            if (p) (void)hipFree(p);
+        memory.free_all();
         for (hipStream_t& s : streams)
             if (s) (void)hipStreamDestroy(s);
         for (hipEvent_t e : {ev_start, ev_stop, ev_done[0], ev_done[1], ev_done[2], ev_done[3]})
@@ -583,16 +542,9 @@ void many_set_error(char* error, int32_t capacity, const std::string& text) {
     error[n] = 0;
 }
 template <class T>
-T* many_upload(const std::vector<T>& host) {
-    T* p = nullptr;
-    RELP_HIP(hipMalloc(&p, std::max<size_t>(1, host.size()) * sizeof(T)));
+T* many_upload(DeviceAllocations& memory, const std::vector<T>& host) {
+    T* p = memory.alloc<T>(host.size());
     if (!host.empty()) RELP_HIP(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return p;
-}
-template <class T>
-T* many_alloc(size_t count) {
-    T* p = nullptr;
-    RELP_HIP(hipMalloc(&p, std::max<size_t>(1, count) * sizeof(T)));
     return p;
 }
 // The options this path honours; the message names the first one it cannot.
@@ -674,12 +626,12 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
             d.inv_off = lp.lds ? 0 : inverse_words;
             if (!lp.lds) inverse_words += (long long)lp.m * lp.m;
             d.max_pivots = adopted.max_pivots > 0 ? adopted.max_pivots : 200LL * (lp.m + lp.n) + 100000;
-            col_start.insert(col_start.end(), lp.col_start.begin(), lp.col_start.end());
-            row_index.insert(row_index.end(), lp.row_index.begin(), lp.row_index.end());
-            value.insert(value.end(), lp.value.begin(), lp.value.end());
-            cost2.insert(cost2.end(), lp.cost2.begin(), lp.cost2.end());
-            rhs.insert(rhs.end(), lp.rhs.begin(), lp.rhs.end());
-            basis0.insert(basis0.end(), lp.basis0.begin(), lp.basis0.end());
+            col_start.insert(col_start.end(), lp.data.col_start.begin(), lp.data.col_start.end());
+            row_index.insert(row_index.end(), lp.data.row_index.begin(), lp.data.row_index.end());
+            value.insert(value.end(), lp.data.value.begin(), lp.data.value.end());
+            cost2.insert(cost2.end(), lp.data.cost2.begin(), lp.data.cost2.end());
+            rhs.insert(rhs.end(), lp.data.rhs.begin(), lp.data.rhs.end());
+            basis0.insert(basis0.end(), lp.cols.basis0.begin(), lp.cols.basis0.end());
         }
         // launch order: by bucket, then the longest estimated solve first (ties: the caller's order)
         std::vector<int> order(n);
@@ -698,20 +650,20 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
                     many->bucket_rows[b] = std::max(many->bucket_rows[b], many->lps[k].m);
                 }
         }
-        many->d_lps = many_upload(desc);
-        many->d_order = many_upload(order);
-        many->d_col_start = many_upload(col_start);
-        many->d_row_index = many_upload(row_index);
-        many->d_value = many_upload(value);
-        many->d_cost2 = many_upload(cost2);
-        many->d_rhs = many_upload(rhs);
-        many->d_basis0 = many_upload(basis0);
-        many->d_gamma = many_alloc<double>(cost2.size());
-        many->d_pos = many_alloc<int>(cost2.size());
-        many->d_inverse = many_alloc<double>((size_t)inverse_words);
-        many->d_basis_out = many_alloc<int>(rhs.size());
-        many->d_xb_out = many_alloc<double>(rhs.size());
-        many->d_out = many_alloc<ManyOut>((size_t)n);
+        many->d_lps = many_upload(many->memory, desc);
+        many->d_order = many_upload(many->memory, order);
+        many->d_col_start = many_upload(many->memory, col_start);
+        many->d_row_index = many_upload(many->memory, row_index);
+        many->d_value = many_upload(many->memory, value);
+        many->d_cost2 = many_upload(many->memory, cost2);
+        many->d_rhs = many_upload(many->memory, rhs);
+        many->d_basis0 = many_upload(many->memory, basis0);
+        many->d_gamma = many->memory.alloc<double>(cost2.size());
+        many->d_pos = many->memory.alloc<int>(cost2.size());
+        many->d_inverse = many->memory.alloc<double>((size_t)inverse_words);
+        many->d_basis_out = many->memory.alloc<int>(rhs.size());
+        many->d_xb_out = many->memory.alloc<double>(rhs.size());
+        many->d_out = many->memory.alloc<ManyOut>((size_t)n);
         for (hipStream_t& s : many->streams) RELP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         RELP_HIP(hipEventCreate(&many->ev_start));
         RELP_HIP(hipEventCreate(&many->ev_stop));
@@ -820,7 +772,7 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
             for (int i = 0; i < lp.m; ++i) {
                 const int dev = basis[r0 + i];
                 if (dev < 0 || dev >= lp.n) throw std::runtime_error("model " + std::to_string(k) + ": the device returned an invalid basis");
-                provider_basis[i] = dev >= lp.n_art ? dev - lp.n_art : -1 - dev;
+                provider_basis[i] = lp.cols.to_provider(dev);
                 if (dev >= lp.n_art) x[dev - lp.n_art] = xb[r0 + i];
             }
             r0 += lp.m;

@@ -219,3 +219,8 @@ struct StandardForm {
 StandardForm load_mps(const std::string& text, bool fixed_format, bool presolve = false);
 
 }  // namespace relp
+
+// The model handle of the C ABI (include/relp_amd.h).
+struct relp_model {
+    relp::StandardForm form;
+};

@@ -10,6 +10,7 @@
 // the ratio test of the explicit carry with alpha preselected (kernels.hip: register-resident up to 8192 rows, across workgroups
 // beyond -- the reference's rule at every size, see net_enqueue_pivot), net_update_kernel (rho_p, w = B^-T alpha, the -pi shift: one thread per row walks its root path in the OLD
 // forest) and net_rehang_kernel (the path from the entering endpoint to the leaving arc reversed, one thread).  No array is m x m.
+#include "kernels.hpp"
 #include "solver.hpp"
 
 #include <algorithm>
@@ -21,15 +22,6 @@
 #include "rat.hpp"
 
 namespace relp {
-
-// kernels.hip
-void launch_ftran_ratio(const DeviceLP& d, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
-                        int skip_artificial_rows, int mode, int n_alpha_slices, hipStream_t s);
-bool fast_k2_available(const DeviceLP& d, int n_price_blocks);
-void launch_k2l_preselected(const DeviceLP& d, double tol_pivot, double harris_delta, int skip_artificial_rows, hipStream_t s);
-void launch_cb(const DeviceLP& d, hipStream_t s);
-// certify.hip
-std::shared_ptr<const ExactPrimal> make_exact_primal(const std::vector<int>& columns, const std::vector<Rat>& values);
 
 namespace {
 double now_seconds_net() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -274,26 +266,18 @@ int net_grid(int m) { return (m + NET_THREADS - 1) / NET_THREADS; }
 // ---------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------
-template <class T>
-static T* net_alloc(size_t count, size_t* bytes) {
-    T* p = nullptr;
-    RELP_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
-    *bytes += std::max<size_t>(count, 1) * sizeof(T);
-    return p;
-}
-
 void Solver::net_allocate() {
     const int m = d_.m;
-    net_.parent = net_alloc<int>(m, &device_bytes_);
-    net_.slot = net_alloc<int>(m, &device_bytes_);
-    net_.sign = net_alloc<signed char>(m, &device_bytes_);
-    net_.child = net_alloc<int>(m, &device_bytes_);
-    net_.mark = net_alloc<int>(m, &device_bytes_);
-    net_.chain = net_alloc<int>(m, &device_bytes_);
-    net_.path = net_alloc<int>(m, &device_bytes_);
-    net_.state = net_alloc<int>(2, &device_bytes_);
+    net_.parent = device_alloc<int>(m);
+    net_.slot = device_alloc<int>(m);
+    net_.sign = device_alloc<signed char>(m);
+    net_.child = device_alloc<int>(m);
+    net_.mark = device_alloc<int>(m);
+    net_.chain = device_alloc<int>(m);
+    net_.path = device_alloc<int>(m);
+    net_.state = device_alloc<int>(2);
     if (opt_.switches & RELP_SW_NETWORK_STATS) {
-        net_.stats = net_alloc<unsigned long long>(NS_WORDS, &device_bytes_);
+        net_.stats = device_alloc<unsigned long long>(NS_WORDS);
         RELP_HIP(hipMemsetAsync(net_.stats, 0, NS_WORDS * sizeof(unsigned long long), stream_));
     }
     RELP_HIP(hipMemsetAsync(net_.mark, 0, (size_t)m * sizeof(int), stream_));
@@ -306,9 +290,9 @@ void Solver::net_allocate() {
 // otherwise): complemented columns sit in B negated.
 HostTree Solver::net_build(const std::vector<int>& basis, const std::vector<int>& flipped) const {
     const int m = d_.m;
-    const std::vector<int>& cs = h_col_start_;
-    const std::vector<int>& ri = h_row_index_;
-    const std::vector<double>& va = h_value_;
+    const std::vector<int>& cs = host_.col_start;
+    const std::vector<int>& ri = host_.row_index;
+    const std::vector<double>& va = host_.value;
     HostTree t;
     t.parent.assign(m, -1);
     t.slot.assign(m, -1);
@@ -417,8 +401,8 @@ void Solver::net_refresh(bool xb, bool pi) {
 void Solver::net_gamma(const HostTree& t, const std::vector<int>& pos, std::vector<double>* gamma) const {
     const int n = d_.n, n_art = d_.n_art;
     gamma->assign(n, 1.0);
-    const std::vector<int>& cs = h_col_start_;
-    const std::vector<int>& ri = h_row_index_;
+    const std::vector<int>& cs = host_.col_start;
+    const std::vector<int>& ri = host_.row_index;
     auto range = [&](int first, int last) {
         for (int j = first; j < last; ++j) {
             if (pos[j] >= 0) continue;
@@ -471,7 +455,7 @@ void Solver::net_set_gamma() {
 bool Solver::net_crash(const std::vector<int>& basis) {
     const int m = d_.m, n = d_.n;
     const HostTree t = net_build(basis, std::vector<int>());  // (nothing is complemented at the start of phase one)
-    std::vector<double> sub(h_rhs_.begin(), h_rhs_.end()), xb(m, 0.0);
+    std::vector<double> sub(host_.rhs.begin(), host_.rhs.end()), xb(m, 0.0);
     for (int k = m - 1; k >= 0; --k) {
         const int x = t.order[k];
         xb[t.slot[x]] = t.sign[x] * sub[x];
@@ -484,7 +468,7 @@ bool Solver::net_crash(const std::vector<int>& basis) {
         RELP_HIP(hipStreamSynchronize(stream_));
     }
     double scale = 1.0;
-    for (int i = 0; i < m; ++i) scale = std::max(scale, std::fabs(h_rhs_[i]));
+    for (int i = 0; i < m; ++i) scale = std::max(scale, std::fabs(host_.rhs[i]));
     for (int i = 0; i < m; ++i) {
         if (xb[i] < -1e-9 * scale) return false;
         if (bounded_ && xb[i] > ub[basis[i]] + 1e-9 * scale) return false;
@@ -579,7 +563,7 @@ void Solver::net_certify(relp_result* result) {
         // column keeps its complemented form when it enters the basis, and its basic value is then u_j - x_j)
         for (int j = n_art; j < n; ++j)
             if (bounded_ && flipped[j])
-                for (int e = h_col_start_[j]; e < h_col_start_[j + 1]; ++e) rhs[h_row_index_[e]] = rhs[h_row_index_[e]] - upper[j] * Rat((long long)h_value_[e]);
+                for (int e = host_.col_start[j]; e < host_.col_start[j + 1]; ++e) rhs[host_.row_index[e]] = rhs[host_.row_index[e]] - upper[j] * Rat((long long)host_.value[e]);
         // x_B in B's own (possibly complemented) orientation: x_B[slot] = sign * (sum of rhs below)
         std::vector<Rat> below(rhs), xb(m);
         for (int k = m - 1; k >= 0; --k) {
@@ -621,7 +605,7 @@ void Solver::net_certify(relp_result* result) {
         for (int j = n_art; j < n && feasible && optimal; ++j) {
             if (pos[j] >= 0) continue;
             Rat d = cost(j);
-            for (int e = h_col_start_[j]; e < h_col_start_[j + 1]; ++e) d = d - Rat((long long)h_value_[e]) * y[h_row_index_[e]];
+            for (int e = host_.col_start[j]; e < host_.col_start[j + 1]; ++e) d = d - Rat((long long)host_.value[e]) * y[host_.row_index[e]];
             const bool up = bounded_ && flipped[j];
             if (up) {
                 objective = objective + md.cost_value(j - n_art) * upper[j];

@@ -3,6 +3,7 @@
 //   phase_one.rs:123-278           phase-one loop + zero-level pivots
 //   phase_two.rs:22-59             phase-two loop
 //   kind/artificial/partially.rs   virtual artificial columns (index space: artificials first)
+#include "kernels.hpp"
 #include "solver.hpp"
 
 #include <thread>
@@ -14,66 +15,10 @@
 
 namespace relp {
 
-// kernels.hip
-void launch_price(const DeviceLP& d, int rule, int blocks, size_t lds, bool use_lds, int skip_weights, double tol,
-                  int first, int last, int cand_offset, hipStream_t s);
-void launch_price_dense(const DeviceLP& d, int blocks, int skip_weights, double tol, int cand_offset, hipStream_t s);
-void configure_dense_lds(size_t lds);
-int dense_lane_slots(int n_dense);
-int dense_lane_ld(int m);
-void launch_ftran_partial(const DeviceLP& d, int n_slices, int n_price_blocks, int rule, hipStream_t s);
-bool fast_k2_available(const DeviceLP& d, int n_price_blocks);
-void arm_launch_timer(int which, hipEvent_t start, hipEvent_t stop);
-void take_launch_timer(int which, hipEvent_t* start, hipEvent_t* stop);
-void configure_lds(size_t price_lds);
-int price_columns_per_block(int ell_w, bool generated);
-void launch_ftran_ratio(const DeviceLP& d, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
-                        int skip_artificial_rows, int mode, int n_alpha_slices, hipStream_t s);
-void launch_update(const DeviceLP& d, hipStream_t s);
-bool fused_pivot_available(const DeviceLP& d, int n_price_blocks);
-void launch_pivot_fused(const DeviceLP& d, int rule, int parity, int n_price_blocks, double tol_pivot, double harris_delta,
-                        int skip_artificial_rows, hipStream_t s);
-void launch_begin_batch(const DeviceLP& d, long long add, hipStream_t s);
-void launch_commit(const DeviceLP& d, int parity, hipStream_t s);
-void launch_budget(const DeviceLP& d, long long add, hipStream_t s);
-void launch_pi(const DeviceLP& d, hipStream_t s);
-void launch_xb(const DeviceLP& d, hipStream_t s);
-void launch_gamma_init(const DeviceLP& d, int identity, hipStream_t s);
-void launch_identity(double* X, int m, int ld, hipStream_t s);
-void launch_scatter(double* X, const long long* index, const double* value, long long count, hipStream_t s);
-void launch_residual(const DeviceLP& d, const double* X, double* R, hipStream_t s);
-void launch_gemm_polish(const double* X, const double* R, double* C, int m, int ld, const int* row_list, int n_rows, hipStream_t s);
-void launch_residual_dense(const DeviceLP& d, double* Bd, const double* T, double* S, const int* row_list, int n_rows, hipStream_t s);
-void launch_copy_rows(const double* src, double* dst, int m, int ld, const int* row_list, int n_rows, hipStream_t s);
-bool gemm_row_lists_supported();
-void launch_alpha_reduce(const DeviceLP& d, int n_slices, hipStream_t s);
-int eta_max();
-void configure_btran_lds(size_t lds);
-void launch_eta_update(const DeviceLP& d, double tol_dual, hipStream_t s);
-int btran_pass_blocks();
-void launch_eta_consolidate(const DeviceLP& d, hipStream_t s);
-void launch_mark_all_touched(const DeviceLP& d, hipStream_t s);
-void launch_clear_refactor_status(const DeviceLP& d, hipStream_t s);
-void launch_scaled_basis(const DeviceLP& d, double* T, double scale, hipStream_t s);
-void launch_row_scan(const DeviceLP& d, int r, double tol, hipStream_t s);
-void launch_ftran_vec(const DeviceLP& d, const int* rows, const double* vals, int nnz, double* out, hipStream_t s);
-void launch_btran_vec(const DeviceLP& d, const int* rows, const double* vals, int nnz, double* out, hipStream_t s);
-void launch_relative_cost(const DeviceLP& d, double* out, hipStream_t s);
-// certify.hip
-void certify_basis(const StandardForm& form, const std::vector<int>& basis_provider_columns, int device,
-                   hipStream_t stream, std::string* objective, bool* certified, long long* repair_pivots,
-                   std::string* message, int mode, int entering, std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch);
-
 namespace {
 double now_seconds() {
     using clock = std::chrono::steady_clock;
     return std::chrono::duration<double>(clock::now().time_since_epoch()).count();
-}
-template <class T>
-T* dmalloc(size_t count) {
-    T* p = nullptr;
-    RELP_HIP(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
-    return p;
 }
 void check_sparse(int nnz, const int* rows, const double* values, int m) {
     if (nnz < 0 || nnz > m) throw std::invalid_argument("nnz out of range");
@@ -85,17 +30,22 @@ template <class T>
 void upload_vec(T* dst, const std::vector<T>& src, hipStream_t s) {
     if (!src.empty()) RELP_HIP(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s));
 }
-}  // namespace
-
+// The dense block as the column-per-lane pricing reads it (price_dense_lane_kernel): tile (group of 16 columns, 64 rows) is
+// sizeof(T) pieces of 64 lanes x 16 bytes -- one piece of 16 bytes, four of 4 floats, eight of 2 doubles; lane 16 * (row % 64 / 16) +
+// column % 16 of piece (row % 16) / (entries per piece) holds the entry.  Zero where a column has no entry.
 template <class T>
-T* Solver::device_alloc(size_t count) {
-    T* p = dmalloc<T>(count);
-    device_bytes_ += std::max<size_t>(count, 1) * sizeof(T);
-    return p;
+std::vector<T> pack_dense_lanes(const DeviceMatrix& a, int first_column, int n_dense, int groups, int dense_ld) {
+    constexpr int per_piece = 16 / (int)sizeof(T), pieces = (int)sizeof(T);
+    const int tiles_per_group = dense_ld / 64;
+    std::vector<T> packed((size_t)groups * 16 * dense_ld, T(0));
+    for (int jd = 0; jd < n_dense; ++jd)
+        for (int e = a.col_start[first_column + jd]; e < a.col_start[first_column + jd + 1]; ++e) {
+            const int row = a.row_index[e], within = row % 64, t = within % 16;
+            packed[((((size_t)(jd / 16) * tiles_per_group + row / 64) * pieces + t / per_piece) * 64 + 16 * (within / 16) + jd % 16) * per_piece + t % per_piece] = (T)a.value[e];
+        }
+    return packed;
 }
-
-// network_carry.hip
-void launch_net_row(const DeviceLP& d, const NetTree& t, int r, double* out, hipStream_t s);
+}  // namespace
 
 Solver::Solver(const relp_options& options) : opt_(options) {
     int count = 0;
@@ -126,17 +76,9 @@ Solver::~Solver() {
 }
 
 void Solver::free_device() {
-    void* ptrs[] = {d_.col_start, d_.row_index, d_.value, d_.row_start, d_.col_index, d_.row_value, d_.cost, d_.cost1,
-                    d_.cost2, d_.rhs, d_.xB, d_.minus_pi, d_.basis, d_.pos, d_.gamma, d_.Binv, d_.Binv2, d_.R,
-                    d_.alpha, d_.rho, d_.nz_index, d_.nz_alpha, d_.w, d_.cand_key, d_.cand_j, d_.cand_cbar, d_.cand_rows, d_.cand_vals, d_.cand_len, d_.ell_rows, d_.ell_vals, d_.scratch, d_.ctl, d_.dbg, d_.dense_val, d_.dense_val32, d_.dense_val8, d_.alpha_part, d_.alpha_in, d_.eta_cols, d_.eta_rows, d_.eta_slot, d_.eta_gather, d_.eta_dot_part, d_.touched, d_.tlist, d_.ub, d_.xub, d_.flipped, d_.rhs0, d_.k2_partd, d_.k2_parti, d_.prw, d_.rho_nz, d_.rho_bits, d_.cost8, d_.cost8_2, d_.cb, d_.cb_idx, d_.slack_of_row, d_.state[0].ctl, d_.state[0].xB, d_.state[0].basis, d_.state[1].ctl, d_.state[1].xB, d_.state[1].basis};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    void* tree[] = {net_.parent, net_.slot, net_.sign, net_.child, net_.mark, net_.chain, net_.path, net_.state, net_.stats};
-    for (void* p : tree)
-        if (p) (void)hipFree(p);
+    device_memory_.free_all();
     d_ = DeviceLP{};
     net_ = NetTree{};
-    device_bytes_ = 0;
 }
 
 void Solver::reset_stats() { stats_ = relp_stats{}; }
@@ -186,32 +128,11 @@ void Solver::upload() {
     const int m = bounded_ ? md.nr_constraints() : md.nr_rows();
     const int n_p = bounded_ ? md.col_end[3] : md.nr_columns();
     if (m < 1) throw std::runtime_error("LP without rows");
-    auto pivots = md.pivot_element_indices();
-    std::vector<int> real_column_of_row(m, -1);
-    for (auto& [row, column] : pivots)
-        if (row < m && column < n_p) real_column_of_row[row] = column;
-    std::vector<int> artificial_rows;
-    for (int i = 0; i < m; ++i)
-        if (real_column_of_row[i] < 0) artificial_rows.push_back(i);
-    const int n_art = (int)artificial_rows.size();
-    const int n = n_art + n_p;
-
-    std::vector<int> col_start(n + 1, 0), row_index;
-    std::vector<double> value;
-    for (int k = 0; k < n_art; ++k) {
-        row_index.push_back(artificial_rows[k]);
-        value.push_back(1.0);
-        col_start[k + 1] = (int)row_index.size();
-    }
-    for (int j = 0; j < n_p; ++j) {
-        SparseColumn c = md.column(j);
-        for (size_t e = 0; e < c.nnz(); ++e) {
-            if (c.index[e] >= m) continue;  // the bound-row entry of a bounded column (implicit bounds)
-            row_index.push_back(c.index[e]);
-            value.push_back(c.value[e].to_double());
-        }
-        col_start[n_art + j + 1] = (int)row_index.size();
-    }
+    cols_ = DeviceColumns(md, m, n_p);
+    host_ = DeviceMatrix(cols_, md);
+    const int n_art = cols_.n_art, n = cols_.n();
+    const std::vector<int>&col_start = host_.col_start, &row_index = host_.row_index;
+    const std::vector<double>&value = host_.value, &cost2 = host_.cost2, &rhs = host_.rhs;
     tick("columns -> CSC");
     network_ = opt_.carry == RELP_CARRY_NETWORK;
     if (network_) {  // a network LP: at most two entries per column, each +-1, of opposite signs when there are two
@@ -243,11 +164,8 @@ void Solver::upload() {
                 row_value[dst] = value[e];
             }
     }
-    std::vector<double> cost1(n, 0.0), cost2(n, 0.0), rhs(m);
+    std::vector<double> cost1(n, 0.0);
     for (int k = 0; k < n_art; ++k) cost1[k] = 1.0;  // artificial::Cost::One (kind/artificial/partially.rs:42-50)
-    for (int j = 0; j < n_p; ++j) cost2[n_art + j] = md.cost_value(j).to_double();
-    auto rhs_exact = md.right_hand_side();
-    for (int i = 0; i < m; ++i) rhs[i] = rhs_exact[i].to_double();
 
     tick("CSR, costs, rhs");
     d_.m = m;
@@ -448,13 +366,7 @@ void Solver::upload() {
         configure_btran_lds((size_t)2 * ((m + 1) & ~1) * sizeof(double));
     }
     if (dense_bytes && d_.dense_lane) {
-        const int groups = dense_blocks_, tiles_per_group = d_.dense_ld / 64;
-        std::vector<signed char> bytes((size_t)groups * 16 * d_.dense_ld, 0);
-        for (int jd = 0; jd < n_dense; ++jd)
-            for (int e = col_start[n_art + jd]; e < col_start[n_art + jd + 1]; ++e) {
-                const int row = row_index[e], within = row % 64;  // tile (group, row / 64): 64 lanes x 16 bytes; see price_dense_lane_kernel
-                bytes[(((size_t)(jd / 16) * tiles_per_group + row / 64) * 64 + 16 * (within / 16) + jd % 16) * 16 + within % 16] = (signed char)value[e];
-            }
+        const std::vector<signed char> bytes = pack_dense_lanes<signed char>(host_, n_art, n_dense, dense_blocks_, d_.dense_ld);
         d_.dense_val8 = device_alloc<signed char>(bytes.size());
         upload_vec(d_.dense_val8, bytes, stream_);
         dense_entry_bytes_ = 1;
@@ -463,28 +375,14 @@ void Solver::upload() {
         dense_bytes = false;  // (the row-permuted form keeps the padded vectors in LDS)
     }
     if (dense_floats && d_.dense_lane) {
-        const int groups = dense_blocks_, tiles_per_group = d_.dense_ld / 64;
-        std::vector<float> floats((size_t)groups * 16 * d_.dense_ld, 0.f);
-        for (int jd = 0; jd < n_dense; ++jd)
-            for (int e = col_start[n_art + jd]; e < col_start[n_art + jd + 1]; ++e) {
-                // tile (group, row / 64): four pieces of 64 lanes x 4 floats; see price_dense_lane_kernel<true>
-                const int row = row_index[e], within = row % 64, t = within % 16;
-                floats[((((size_t)(jd / 16) * tiles_per_group + row / 64) * 4 + t / 4) * 64 + 16 * (within / 16) + jd % 16) * 4 + t % 4] = (float)value[e];
-            }
+        const std::vector<float> floats = pack_dense_lanes<float>(host_, n_art, n_dense, dense_blocks_, d_.dense_ld);
         d_.dense_val32 = device_alloc<float>(floats.size());
         upload_vec(d_.dense_val32, floats, stream_);
         dense_entry_bytes_ = 4;
         RELP_HIP(hipStreamSynchronize(stream_));
     } else if (dense_bytes && d_.dense_lane) {
     } else if (d_.dense_lane) {
-        const int groups = dense_blocks_, tiles_per_group = d_.dense_ld / 64;
-        std::vector<double> doubles((size_t)groups * 16 * d_.dense_ld, 0.0);
-        for (int jd = 0; jd < n_dense; ++jd)
-            for (int e = col_start[n_art + jd]; e < col_start[n_art + jd + 1]; ++e) {
-                // tile (group, row / 64): eight pieces of 64 lanes x 2 doubles; see price_dense_lane_kernel<8>
-                const int row = row_index[e], within = row % 64, t = within % 16;
-                doubles[((((size_t)(jd / 16) * tiles_per_group + row / 64) * 8 + t / 2) * 64 + 16 * (within / 16) + jd % 16) * 2 + t % 2] = value[e];
-            }
+        const std::vector<double> doubles = pack_dense_lanes<double>(host_, n_art, n_dense, dense_blocks_, d_.dense_ld);
         d_.dense_val = device_alloc<double>(doubles.size());
         upload_vec(d_.dense_val, doubles, stream_);
         dense_entry_bytes_ = 8;
@@ -546,13 +444,9 @@ void Solver::upload() {
     {
         // (the forest carry has the reference's rule at every size: alpha is +-1 on its path, see net_enqueue_pivot)
         const bool kernels_have_it = lu_mode_ || network_ || fast_k2_available(d_, price_blocks_ + dense_blocks_);
-        bool small_integers = true;
-        for (size_t e = 0; e < nnz && small_integers; ++e) small_integers = value[e] == std::nearbyint(value[e]) && std::fabs(value[e]) <= 64.0;
-        for (int j = 0; j < n && small_integers; ++j) small_integers = cost2[j] == std::nearbyint(cost2[j]) && std::fabs(cost2[j]) < 1048576.0;
-        for (int i = 0; i < m && small_integers; ++i) small_integers = rhs[i] == std::nearbyint(rhs[i]) && std::fabs(rhs[i]) < 1048576.0;
         if (opt_.ratio_rule == RELP_RATIO_TEXTBOOK && !kernels_have_it)
             throw std::invalid_argument("RELP_RATIO_TEXTBOOK: the reference's ratio test is implemented up to 8192 rows (the multi-workgroup ratio test has the two-pass rule only)");
-        ratio_textbook_ = opt_.ratio_rule == RELP_RATIO_TEXTBOOK || (opt_.ratio_rule == RELP_RATIO_AUTO && small_integers && kernels_have_it);
+        ratio_textbook_ = opt_.ratio_rule == RELP_RATIO_TEXTBOOK || (opt_.ratio_rule == RELP_RATIO_AUTO && host_.small_integer_data() && kernels_have_it);
     }
     // small LPs: ratio test and inverse update in one launch (pivot_fused_kernel; RELP_NO_FUSED=1 keeps the three-kernel pivot)
     fused_ = !lu_mode_ && !network_ && !bounded_ && !eta_mode_ && n_dense == 0 && ftran_slices_ == 0 && !d_.track_touched && d_.ell_w == ELL_W &&
@@ -610,16 +504,11 @@ void Solver::upload() {
     if (network_) net_allocate();
     h_basis_.assign(m, -1);
     h_solution_.assign(md.nr_columns(), 0.0);
-    if (lu_mode_ || network_ || opt_.crash) {
-        h_col_start_ = col_start;
-        h_row_index_ = row_index;
-        h_value_ = value;
-        h_rhs_ = rhs;
-        if (opt_.crash) {  // the rows by columns too (the crash walks them)
-            h_row_start_ = row_start;
-            h_col_index_ = col_index;
-        }
+    if (opt_.crash) {  // the rows by columns too (the crash walks them)
+        h_row_start_ = row_start;
+        h_col_index_ = col_index;
     }
+    if (!(lu_mode_ || network_ || opt_.crash)) host_ = DeviceMatrix{};  // (nothing on the host reads it after the upload)
 }
 
 Ctl Solver::read_ctl() {
@@ -658,21 +547,12 @@ void Solver::write_ctl(const Ctl& c) {
 void Solver::begin_phase_one() {
     if (!loaded_) throw std::runtime_error("no LP loaded");
     RELP_HIP(hipSetDevice(opt_.device));
-    const MatrixData& md = form_.data;
     const int m = d_.m, n = d_.n, n_art = d_.n_art;
-    std::vector<int> basis(m), pos(n, -1);
+    const std::vector<int>& basis = cols_.basis0;
+    std::vector<int> pos = cols_.pos0();
     if (bounded_)  // a variable whose two bounds coincide can never move: it is not priced (pos -3; see DeviceLP::pos)
         for (int j = n_art; j < n; ++j)
-            if (zero_width_[j]) pos[j] = -3;
-    auto pivots = md.pivot_element_indices();
-    std::vector<int> real_column_of_row(m, -1);
-    for (auto& [row, column] : pivots)
-        if (row < m && column < n - n_art) real_column_of_row[row] = column;
-    int k = 0;
-    for (int i = 0; i < m; ++i) {
-        basis[i] = real_column_of_row[i] < 0 ? k++ : n_art + real_column_of_row[i];
-        pos[basis[i]] = i;
-    }
+            if (zero_width_[j] && pos[j] < 0) pos[j] = -3;
     upload_vec(d_.basis, basis, stream_);
     upload_vec(d_.pos, pos, stream_);
     RELP_HIP(hipMemcpyAsync(d_.rhs, d_.rhs0, m * sizeof(double), hipMemcpyDeviceToDevice, stream_));
@@ -720,7 +600,7 @@ void Solver::begin_phase_one() {
 // gamma_j = 1 + |B^-1 a_j|^2 (pivot_rule.rs:202-219) are computed from the same sparse columns.  The crash is only kept when
 // it is primal feasible; phase one then starts from it (with zero artificials left it ends without a pivot).
 bool Solver::crash_basis() {
-    if (lu_mode_ || eta_mode_ || d_.n_dense > 0 || h_col_start_.empty() || h_row_start_.empty()) return false;
+    if (lu_mode_ || eta_mode_ || d_.n_dense > 0 || host_.col_start.empty() || h_row_start_.empty()) return false;
     const int m = d_.m, n = d_.n, n_art = d_.n_art;
     const bool timing = diagnostic("RELP_TIME_SOLVE");
     double t_last = now_seconds();
@@ -733,9 +613,9 @@ bool Solver::crash_basis() {
     std::vector<int> basis(m);
     RELP_HIP(hipMemcpyAsync(basis.data(), d_.basis, m * sizeof(int), hipMemcpyDeviceToHost, stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
-    const std::vector<int>& cs = h_col_start_;
-    const std::vector<int>& ri = h_row_index_;
-    const std::vector<double>& va = h_value_;
+    const std::vector<int>& cs = host_.col_start;
+    const std::vector<int>& ri = host_.row_index;
+    const std::vector<double>& va = host_.value;
     std::vector<char> uncovered(m, 0);
     for (int i = 0; i < m; ++i) uncovered[i] = basis[i] < n_art ? 1 : 0;
     // rows -> columns: the CSR of the device LP kept by upload() (artificial columns included: skipped below)
@@ -830,9 +710,9 @@ bool Solver::crash_basis() {
     // x_B = B^-1 b, must be a basic feasible solution of the phase-one problem
     std::vector<double> xb(m, 0.0);
     for (int i = 0; i < m; ++i)
-        if (order_of_row[i] < 0) xb[i] = h_rhs_[i];
+        if (order_of_row[i] < 0) xb[i] = host_.rhs[i];
     for (int k = 0; k < covered; ++k) {
-        const double b = h_rhs_[crash_rows[k]];
+        const double b = host_.rhs[crash_rows[k]];
         if (b == 0.0) continue;
         for (size_t e = inv_start[k]; e < inv_start[k + 1]; ++e) xb[inv_pos[e]] += inv_val[e] * b;
     }
@@ -843,7 +723,7 @@ bool Solver::crash_basis() {
         RELP_HIP(hipStreamSynchronize(stream_));
     }
     double scale = 1.0;
-    for (int i = 0; i < m; ++i) scale = std::max(scale, std::fabs(h_rhs_[i]));
+    for (int i = 0; i < m; ++i) scale = std::max(scale, std::fabs(host_.rhs[i]));
     for (int i = 0; i < m; ++i) {
         if (xb[i] < -1e-9 * scale) return false;
         if (bounded_ && xb[i] > ub[basis[i]] + 1e-9 * scale) return false;
@@ -1251,7 +1131,7 @@ void Solver::set_basis(const int* basis_columns) {
     if (!bounded_) {
         for (int i = 0; i < m; ++i) {
             int c = basis_columns[i];
-            int dev = c >= 0 ? d_.n_art + c : (-1 - c);
+            int dev = cols_.to_device(c);
             if (dev < 0 || dev >= n || pos[dev] >= 0) throw std::invalid_argument("bad basis");
             basis[i] = dev;
             pos[dev] = i;
@@ -1270,7 +1150,7 @@ void Solver::set_basis(const int* basis_columns) {
                 if (c >= cols_full || row_of[c] >= 0) throw std::invalid_argument("bad basis");
                 row_of[c] = i;
             } else {
-                const int k = -1 - c;
+                const int k = cols_.to_device(c);  // (an artificial's device column is its number)
                 if (k >= d_.n_art || artificial_row_of[k] >= 0) throw std::invalid_argument("bad basis");
                 artificial_row_of[k] = i;
             }
@@ -1517,7 +1397,7 @@ void Solver::solve(relp_result* result) {
     std::fill(h_solution_.begin(), h_solution_.end(), 0.0);
     if (!bounded_) {
         for (int i = 0; i < m; ++i) {
-            h_basis_[i] = basis[i] >= d_.n_art ? basis[i] - d_.n_art : -1 - basis[i];
+            h_basis_[i] = cols_.to_provider(basis[i]);
             if (basis[i] >= d_.n_art) h_solution_[basis[i] - d_.n_art] = xb[i];
         }
     } else {
@@ -1593,7 +1473,7 @@ void Solver::resolve_fixed_columns(std::vector<int>& pos) {
 std::vector<int> Solver::explicit_basis(const std::vector<int>& basis, const std::vector<int>& pos) const {
     const MatrixData& md = form_.data;
     std::vector<int> out(md.nr_rows(), -1);
-    for (int i = 0; i < d_.m; ++i) out[i] = basis[i] >= d_.n_art ? basis[i] - d_.n_art : -1 - basis[i];
+    for (int i = 0; i < d_.m; ++i) out[i] = cols_.to_provider(basis[i]);
     const int nb = (int)md.bound_to_variable.size();
     for (int k2 = 0; k2 < nb; ++k2) {
         const int j = md.bound_to_variable[k2];
@@ -1650,7 +1530,7 @@ void Solver::lu_identity() {
     f.u_start.assign(m + 1, 0);
     f.diag.assign(m, 1.0);
     // (device refactorisation: every array sized by bounds first, so that the layout -- and the captured graphs -- stay put)
-    if (device_refactor_ && lu().prepare_device(m, refactor_period_ + 1, true, (size_t)h_col_start_.back())) destroy_graphs();
+    if (device_refactor_ && lu().prepare_device(m, refactor_period_ + 1, true, (size_t)host_.col_start.back())) destroy_graphs();
     if (lu().upload(f, refactor_period_ + 1, stream_, lu_inverse_)) destroy_graphs();  // the captured batches hold the old addresses
 }
 // `BasisInverse::invert(basis columns)` (lower_upper/mod.rs:78-92; called by `Carry::change_basis` when `should_refactor`,
@@ -1706,7 +1586,7 @@ void Solver::start_async_refactor(long long iters_now) {
         launch_lu_probe_fill(d_probe_, m, stream_);
         if (bounded_) RELP_HIP(hipMalloc(&d_flipped_snapshot_, (size_t)d_.n * sizeof(*d_.flipped)));
     }
-    if (!next.device_prepared()) next.prepare_device(m, refactor_period_ + 1, true, (size_t)h_col_start_.back());
+    if (!next.device_prepared()) next.prepare_device(m, refactor_period_ + 1, true, (size_t)host_.col_start.back());
     RELP_HIP(hipMemcpyAsync(d_basis_snapshot_, d_.basis, (size_t)m * sizeof(int), hipMemcpyDeviceToDevice, stream_));
     if (bounded_) RELP_HIP(hipMemcpyAsync(d_flipped_snapshot_, d_.flipped, (size_t)d_.n * sizeof(*d_.flipped), hipMemcpyDeviceToDevice, stream_));
     lu().start_log(stream_);
@@ -1785,7 +1665,7 @@ void Solver::refactor_lu_host(bool refresh_vectors) {
     size_t total = 0;
     for (int k = 0; k < m; ++k) {
         if (basis[k] < 0 || basis[k] >= d_.n) throw std::runtime_error("the device returned an invalid basis");
-        total += (size_t)(h_col_start_[basis[k] + 1] - h_col_start_[basis[k]]);
+        total += (size_t)(host_.col_start[basis[k] + 1] - host_.col_start[basis[k]]);
         cs[k + 1] = (int)total;
     }
     std::vector<int> rows(total);
@@ -1797,9 +1677,9 @@ void Solver::refactor_lu_host(bool refresh_vectors) {
         RELP_HIP(hipStreamSynchronize(stream_));
     }
     for (int k = 0; k < m; ++k) {
-        const int a = h_col_start_[basis[k]], len = h_col_start_[basis[k] + 1] - a;
-        std::copy(h_row_index_.begin() + a, h_row_index_.begin() + a + len, rows.begin() + cs[k]);
-        std::copy(h_value_.begin() + a, h_value_.begin() + a + len, vals.begin() + cs[k]);
+        const int a = host_.col_start[basis[k]], len = host_.col_start[basis[k] + 1] - a;
+        std::copy(host_.row_index.begin() + a, host_.row_index.begin() + a + len, rows.begin() + cs[k]);
+        std::copy(host_.value.begin() + a, host_.value.begin() + a + len, vals.begin() + cs[k]);
         if (bounded_ && flipped[basis[k]])
             for (int e = cs[k]; e < cs[k] + len; ++e) vals[e] = -vals[e];
     }
@@ -1948,10 +1828,6 @@ void Solver::ratio(int column, int* row, double* alpha_out) {
     c.forced_q = c.forced_p = -1;
     write_ctl(c);
 }
-void exact_simplex(const StandardForm& form, int device, hipStream_t stream, int first_limbs, int max_limbs, long long max_pivots,
-                   int trace_capacity, int* status, int* limbs_used, long long* pivots_phase_one, long long* pivots_phase_two,
-                   std::vector<int>* trace, std::string* objective, std::vector<int>* final_basis,
-                   std::vector<std::pair<int, long long>>* pivots_survived, int* redundant_rows, std::vector<ExactWidthRecord>* counters, int update_mode, int forced_grid);
 void Solver::solve_exact(int first_limbs, int max_limbs, long long max_pivots, int trace_capacity, int* status, int* limbs, long long* p1,
                          long long* p2, std::vector<int>* trace, std::string* objective, std::vector<int>* basis,
                          std::vector<std::pair<int, long long>>* survived, int* redundant_rows) {
@@ -2133,7 +2009,7 @@ void Solver::get_basis(int* out) {
         std::copy(full.begin(), full.end(), out);
         return;
     }
-    for (int i = 0; i < d_.m; ++i) out[i] = basis[i] >= d_.n_art ? basis[i] - d_.n_art : -1 - basis[i];
+    for (int i = 0; i < d_.m; ++i) out[i] = cols_.to_provider(basis[i]);
 }
 void Solver::get_solution(double* x) const {
     const int n_struct = form_.data.nr_normal_variables();

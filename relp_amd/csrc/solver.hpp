@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "../../include/relp_amd.h"
+#include "device_columns.hpp"
+#include "device_memory.hpp"
 #include "model.hpp"
 #include "lu.hpp"
 
@@ -43,6 +45,13 @@ struct CertifyScratch {
 };
 // (provider column, "num/den" reduced) for every basic provider column with a non-zero exact value, ascending column
 std::vector<std::pair<int, std::string>> exact_primal_values(const ExactPrimal& primal);
+// The exact primal values of a certificate made elsewhere (network_carry.hip: the forest's): provider column and value, over one
+// common denominator.
+std::shared_ptr<const ExactPrimal> make_exact_primal(const std::vector<int>& columns, const std::vector<Rat>& values);
+// The exact certificate of a basis given in provider columns (certify.hip, where the modes are described).
+void certify_basis(const StandardForm& form, const std::vector<int>& basis_provider_columns, int device, hipStream_t stream,
+                   std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
+                   std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch);
 
 // Device control block, written by single-workgroup kernels, polled by the host.
 struct Ctl {
@@ -274,6 +283,17 @@ struct ExactWidthRecord {
     long long update_products_needed = 0;         // 64 x 64 -> 128-bit word products of the update of N: what the entries' bit bounds ask for ...
     long long update_products_issued = 0;         // ... and what the waves execute (every lane of a wave runs the longest count among its entries)
 };
+// exact.hip: the host driver of the exact simplex, and the entry points of its unit tests and of tools/tile_bench.py
+void exact_simplex(const StandardForm& form, int device, hipStream_t stream, int first_limbs, int max_limbs, long long max_pivots,
+                   int trace_capacity, int* status, int* limbs_used, long long* pivots_phase_one, long long* pivots_phase_two,
+                   std::vector<int>* trace, std::string* objective, std::vector<int>* final_basis,
+                   std::vector<std::pair<int, long long>>* pivots_survived, int* redundant_rows, std::vector<ExactWidthRecord>* counters, int update_mode, int forced_grid);
+void exact_finish_entries(int device, int limbs, int count, const unsigned long long* T, const int* carry, const int* words, int shift, int flip,
+                          unsigned long long* N_out, int* bits_out);
+void exact_words_test(int device, int limbs, int mode, int count, const unsigned long long* a, const unsigned long long* b, unsigned long long* out);
+double exact_tile_bench(int device, int limbs, int tiles, int nb64, int terms, int shift);
+// grid_barrier_test.hip
+void grid_barrier_test(int device, int grid, int rounds, int reads, int mode, long long limit_ticks, long long* out8);
 
 class Solver {
 public:
@@ -303,7 +323,7 @@ public:
     void solve_exact(int first_limbs, int max_limbs, long long max_pivots, int trace_capacity, int* status, int* limbs, long long* p1,
                      long long* p2, std::vector<int>* trace, std::string* objective, std::vector<int>* basis,
                      std::vector<std::pair<int, long long>>* survived, int* redundant_rows = nullptr);
-    size_t device_bytes() const { return device_bytes_; }  // bytes this handle has allocated on the device
+    size_t device_bytes() const { return device_memory_.bytes(); }  // bytes this handle has allocated on the device
     bool network_carry() const { return network_; }
     const std::vector<unsigned long long>& network_stats() const { return net_stats_; }  // RELP_SW_NETWORK_STATS: NS_* of the last solve
     const std::vector<ExactWidthRecord>& exact_records() const { return exact_records_; }  // of the last solve_exact, one per width tried
@@ -373,10 +393,10 @@ private:
     void net_certify(relp_result* result);
     int net_launches_per_pivot() const;      // pricing, path, ratio test (one kernel, or three across workgroups), update, re-hang
     void net_enqueue_pivot(int mode, int parts = 3);  // entering column + tree path, ratio test (+ forest update in mode 0)
-    size_t device_bytes_ = 0;
     std::vector<unsigned long long> net_stats_;
+    DeviceAllocations device_memory_;  // every buffer of the loaded LP: d_, net_ (free_device)
     template <class T>
-    T* device_alloc(size_t count);
+    T* device_alloc(size_t count) { return device_memory_.alloc<T>(count); }
     // LU carry (relp_options.carry == RELP_CARRY_LU)
     void refactor_lu(bool refresh_vectors, bool settle = true);  // BasisInverse::invert of the current basis: kernels on the device (lu_factor.hip), or ...
     void refactor_lu_host(bool refresh_vectors);  // ... host Markowitz + upload (relp_options.lu_refactor; the LU + Forrest-Tomlin carry; the fallback)
@@ -411,8 +431,8 @@ private:
     int unbounded_column_ = -1;  // provider column of the ray when the result is UNBOUNDED
     long long refactors_ = 0;
     double refactor_seconds_ = 0.0;
-    std::vector<int> h_col_start_, h_row_index_;  // host copy of the device CSC (basis columns for the refactorisation)
-    std::vector<double> h_value_, h_rhs_;
+    DeviceColumns cols_;  // index space of the loaded LP
+    DeviceMatrix host_;   // host copy of the device CSC and right-hand side, kept where the host reads them (the refactorisation's basis columns, the forest, the crash basis)
     std::vector<int> h_row_start_, h_col_index_;  // the same matrix by rows (kept for the crash basis)
     bool crash_basis();           // relp_options.crash: triangular crash basis as the start of phase one
     bool gamma_ready_ = false;    // the next set_phase keeps the uploaded steepest-edge weights
@@ -475,16 +495,5 @@ struct PerDeviceOnce {
         done.fetch_or(bit, std::memory_order_release);
     }
 };
-
-struct DeviceError : std::runtime_error {
-    explicit DeviceError(const std::string& what) : std::runtime_error(what) {}
-};
-
-#define RELP_HIP(call)                                                                                   \
-    do {                                                                                                 \
-        hipError_t err__ = (call);                                                                       \
-        if (err__ != hipSuccess)                                                                         \
-            throw ::relp::DeviceError(std::string(#call) + ": " + hipGetErrorString(err__));             \
-    } while (0)
 
 }  // namespace relp
