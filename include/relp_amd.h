@@ -462,6 +462,9 @@ int32_t relp_bring_into_basis(relp_handle* handle, int32_t column, int32_t row);
 /* The last basis change: `BasisChangeComputationInfo::{pivot_row_index, pivot_column_index, leaving_column_index}`
  * (tableau/mod.rs:205-234) in the index space of relp_price, and the phase it was made in.  -1 when none was made yet. */
 int32_t relp_get_last_pivot(relp_handle* handle, int32_t* phase, int32_t* column, int32_t* row, int32_t* leaving);
+/* relp_options.implicit_bounds: how many iterations since the last relp_begin_phase_one (a solve starts with one) moved the entering
+ * variable to its other bound without a basis change.  They are counted among the pivots of relp_result too.  0 without the mode. */
+int32_t relp_get_bound_flips(const relp_handle* handle, int64_t* bound_flips);
 /* `PivotRule::after_basis_update(info, tableau)` (strategy/pivot_rule.rs:23-54; `SteepestDescentAlongObjective` :243-296): the
  * Goldfarb-Reid update of the steepest-edge weights for the last relp_bring_into_basis / relp_iterate pivot.  Inside the
  * device loop the update rides on the next pricing pass; this entry applies it now (no-op when none is pending, or for the
@@ -709,6 +712,14 @@ int32_t relp_batch_handle(const relp_batch* batch, int32_t worker, int32_t model
  * lower_upper/mod.rs:78-92); a fresh inverse whose residual max |B B^-1 - I| exceeds 1e-6, or a singular basis, ends THAT LP with
  * RELP_ERR_NUMERICAL.  B^-1 lives in the workgroup's LDS up to 139 rows (the LDS tier), in a per-LP slab of global memory from 140 to
  * 512 rows (the global tier).  Results do not depend on which other LPs share the launch, nor on their order.
+ * relp_many_create_with and relp_many_config.implicit_bounds = 1: the upper bounds of the variables and the ranges are not rows of
+ * the device LP but kept by the bounded-variable ratio test, as a handle with relp_options.implicit_bounds does (complemented
+ * columns, bound flips, leaving at the upper bound; a bounded LP walks that handle's pivot sequence, a bound flip counting as an
+ * iteration of its phase).  The device LP then has the CONSTRAINT rows only: the 512-row limit applies to them, the LDS tier of an LP
+ * that has a bound ends at 138 rows, and an LP without any finite bound runs exactly as without the config.  relp_many_get_basis,
+ * relp_many_get_solution and relp_many_dimensions keep speaking the reference's formulation (every standard-form row, the bound
+ * rows and their slacks included), as relp_get_basis does on a handle in both modes.  With options.certify a FINITE_OPTIMUM is proved
+ * from that basis; INFEASIBLE and UNBOUNDED results of a bounded LP stay uncertified in this mode, as on the handle.
  * relp_options is read as relp_create reads it; refused with RELP_ERR_ARGUMENT: a carry other than RELP_CARRY_EXPLICIT,
  * implicit_bounds, crash, a pivot rule other than steepest edge and Dantzig, and the switches of the generated graph columns.
  * relp_many_create checks every model before it touches the device (RELP_ERR_ARGUMENT naming the model's index, e.g. more than 512
@@ -730,6 +741,15 @@ typedef struct relp_many_result {
 } relp_many_result;
 int32_t relp_many_create(const relp_model* const* models, int32_t n_models, const relp_options* options, relp_many** out, char* error,
                          int32_t error_capacity);
+/* What relp_options cannot say about this path.  `config` NULL: relp_many_create.  A struct_size other than
+ * sizeof(relp_many_config) of a header of this library is RELP_ERR_ARGUMENT.  relp_options.implicit_bounds stays refused: the mode
+ * is switched on here. */
+typedef struct relp_many_config {
+    int32_t struct_size;      /* sizeof(relp_many_config) of the caller's header */
+    int32_t implicit_bounds;  /* 1: bounds and ranges by the bounded-variable ratio test, not as rows */
+} relp_many_config;
+int32_t relp_many_create_with(const relp_model* const* models, int32_t n_models, const relp_options* options,
+                              const relp_many_config* config, relp_many** out, char* error, int32_t error_capacity);
 /* Solves every LP (again, from the start).  results[k]: model k, in the caller's order; *kernel_seconds: the launch. */
 int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kernel_seconds);
 /* As relp_get_basis (provider columns, -1-k for artificial k), relp_get_solution and relp_get_objective_exact, for model `model`. */
@@ -738,6 +758,8 @@ int32_t relp_many_get_solution(const relp_many* many, int32_t model, double* x_s
 int32_t relp_many_get_objective_exact(const relp_many* many, int32_t model, char* buffer, int32_t capacity, int32_t* length);
 /* Standard-form rows and structural columns of model `model` (the lengths of the two arrays above). */
 int32_t relp_many_dimensions(const relp_many* many, int32_t model, int32_t* nr_rows, int32_t* nr_structural);
+/* Bound flips among the iterations of model `model` in the last solve (0 without implicit bounds). */
+int32_t relp_many_get_bound_flips(const relp_many* many, int32_t model, int64_t* bound_flips);
 /* Why the last relp_many_solve failed, or why a certificate was not obtained. */
 const char* relp_many_last_error(const relp_many* many);
 int32_t relp_many_free(relp_many* many);

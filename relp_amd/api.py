@@ -131,6 +131,11 @@ class ManyResult(C.Structure):
                 ("objective", C.c_double), ("max_residual", C.c_double), ("certify_seconds", C.c_double)]
 
 
+class ManyConfig(C.Structure):
+    """``relp_many_config``: what ``relp_many_create_with`` takes beside the options."""
+    _fields_ = [("struct_size", C.c_int32), ("implicit_bounds", C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("price_launches", C.c_int64), ("price_seconds", C.c_double),
                 ("update_seconds", C.c_double), ("ftran_seconds", C.c_double), ("price_bytes", C.c_int64),
@@ -164,6 +169,8 @@ SYMBOLS = [
     # many small LPs in one launch, one workgroup each (relp_amd/csrc/many.hip)
     "relp_many_create", "relp_many_solve", "relp_many_get_basis", "relp_many_get_solution", "relp_many_get_objective_exact",
     "relp_many_dimensions", "relp_many_last_error", "relp_many_free",
+    # implicit upper bounds on that path, and the count of bound flips of both paths
+    "relp_many_create_with", "relp_many_get_bound_flips", "relp_get_bound_flips",
 ]
 
 
@@ -601,6 +608,12 @@ class Solver:
         self._check(lib().relp_get_basis(self._h, _ptr(out, C.c_int32)))
         return out
 
+    def bound_flips(self):
+        """``implicit_bounds``: iterations of the last solve / iterate that moved the entering variable to its other bound."""
+        count = C.c_int64()
+        self._check(lib().relp_get_bound_flips(self._h, C.byref(count)))
+        return count.value
+
     def set_basis(self, basis):
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_set_basis(self._h, _ptr(arr, C.c_int32)))
@@ -773,15 +786,22 @@ class Batch:
 class Many:
     """``relp_many_*``: independent LPs of at most 512 rows solved in ONE launch, one workgroup per LP.
     ``models``: ``Model`` objects (kept alive here).  Options as for ``Solver``; ``.solve()`` returns one ``ManyResult`` per model, in
-    the given order, and leaves the launch time in ``.kernel_seconds``."""
+    the given order, and leaves the launch time in ``.kernel_seconds``.  ``bounded=True`` (``relp_many_config.implicit_bounds``): upper
+    bounds and ranges are kept by the bounded-variable ratio test instead of rows, so the 512-row limit and the LDS tier count the
+    constraint rows; bases and solutions keep the reference's formulation."""
 
-    def __init__(self, models, options=None, **overrides):
+    def __init__(self, models, options=None, bounded=False, **overrides):
         self.models = list(models)
         self.options = options or default_options(**overrides)
+        self.bounded = bool(bounded)
         self._h = C.c_void_p()
         handles = (C.c_void_p * len(self.models))(*[m._h for m in self.models])
         error = C.create_string_buffer(512)
-        status = lib().relp_many_create(handles, len(self.models), C.byref(self.options), C.byref(self._h), error, 512)
+        if self.bounded:
+            config = ManyConfig(C.sizeof(ManyConfig), 1)
+            status = lib().relp_many_create_with(handles, len(self.models), C.byref(self.options), C.byref(config), C.byref(self._h), error, 512)
+        else:
+            status = lib().relp_many_create(handles, len(self.models), C.byref(self.options), C.byref(self._h), error, 512)
         if status != OK:
             self._h = None
             raise RelpError(status, error.value.decode() or "relp_many_create failed")
@@ -823,6 +843,12 @@ class Many:
         out = np.zeros(max(1, self._dimensions(i)[1]))
         self._check(lib().relp_many_get_solution(self._h, int(i), _ptr(out, C.c_double)))
         return out[:self._dimensions(i)[1]]
+
+    def bound_flips(self, i):
+        """Bound flips among the iterations of model ``i`` in the last solve (``bounded=True``; 0 otherwise)."""
+        count = C.c_int64()
+        self._check(lib().relp_many_get_bound_flips(self._h, int(i), C.byref(count)))
+        return count.value
 
     def objective_exact(self, i):
         length = C.c_int32()

@@ -870,6 +870,12 @@ int32_t relp_get_basis(const relp_handle* h, int32_t* basis) {
     return guarded(const_cast<relp_handle*>(h), [&] { h->solver->get_basis(basis); });
 }
 
+int32_t relp_get_bound_flips(const relp_handle* h, int64_t* bound_flips) {
+    REQUIRE_LOADED(h);
+    if (!bound_flips) return RELP_ERR_ARGUMENT;
+    return guarded(const_cast<relp_handle*>(h), [&] { *bound_flips = h->solver->bound_flips(); });
+}
+
 int32_t relp_set_basis(relp_handle* h, const int32_t* basis_columns) {
     REQUIRE_LOADED(h);
     if (!basis_columns) return RELP_ERR_ARGUMENT;

@@ -8,6 +8,7 @@
 // scale their own integers and need the numbering only).
 #pragma once
 #include <cmath>
+#include <limits>
 #include <vector>
 
 #include "model.hpp"
@@ -86,5 +87,57 @@ struct DeviceMatrix {
         return small_integers;
     }
 };
+
+// ---- implicit upper bounds: between the device LP (constraint rows, the first four column groups) and the reference's formulation
+// (every row of MatrixData, the VariableBound / SlackBound rows and their slack columns of matrix_data.rs:104-145 included) ----------
+
+// Upper bound of each device column: structurals with one, range slacks (their range); +inf for the others.
+inline std::vector<double> implicit_upper_bounds(const MatrixData& md, const DeviceColumns& c) {
+    std::vector<double> ub(c.n(), std::numeric_limits<double>::infinity());
+    for (int j = 0; j < md.nr_normal_variables(); ++j)
+        if (md.variables[j].has_upper) ub[c.n_art + j] = md.variables[j].upper.to_double();
+    for (int k = 0; k < md.nr_range; ++k) ub[c.n_art + md.col_end[0] + k] = md.ranges[k].to_double();
+    return ub;
+}
+
+// The basis of the reference's formulation that a device state stands for (`basis`: device column per constraint row; `pos`: per
+// device column, -2 = non-basic at its upper bound).  On every bound row the bound slack is basic when the variable is below its
+// bound and the variable itself when it sits at it.
+inline std::vector<int> explicit_basis(const MatrixData& md, const DeviceColumns& c, const std::vector<int>& basis, const std::vector<int>& pos) {
+    std::vector<int> out(md.nr_rows(), -1);
+    for (int i = 0; i < c.m; ++i) out[i] = c.to_provider(basis[i]);
+    const int nb = (int)md.bound_to_variable.size();
+    for (int k2 = 0; k2 < nb; ++k2) {
+        const int j = md.bound_to_variable[k2];
+        out[md.row_end[3] + k2] = pos[c.n_art + j] == -2 ? j : md.col_end[3] + k2;
+    }
+    for (int k2 = 0; k2 < md.nr_range; ++k2) {
+        const int j = md.col_end[0] + k2;
+        out[md.row_end[4] + k2] = pos[c.n_art + j] == -2 ? j : md.col_end[4] + k2;
+    }
+    return out;
+}
+
+// The values of every column of MatrixData (`x`, zero-filled, nr_columns() long) from x_B of the device LP: the value of a
+// complemented variable is u_j - x'_j, a complemented non-basic variable sits at its upper bound, and the bound slack of a variable
+// below its bound takes up the rest.
+inline void explicit_solution(const MatrixData& md, const DeviceColumns& c, const std::vector<int>& basis, const double* xb, const std::vector<int>& flipped,
+                              const std::vector<int>& pos, const std::vector<double>& ub, std::vector<double>& x) {
+    for (int i = 0; i < c.m; ++i) {
+        const int dev = basis[i];
+        if (dev >= c.n_art) x[dev - c.n_art] = flipped[dev] ? ub[dev] - xb[i] : xb[i];
+    }
+    for (int j = c.n_art; j < c.n(); ++j)
+        if (pos[j] == -2) x[j - c.n_art] = ub[j];
+    const int nb = (int)md.bound_to_variable.size();
+    for (int k2 = 0; k2 < nb; ++k2) {  // VariableBound rows: the bound slack of a variable below its bound
+        const int j = md.bound_to_variable[k2];
+        if (pos[c.n_art + j] != -2) x[md.col_end[3] + k2] = ub[c.n_art + j] - x[j];
+    }
+    for (int k2 = 0; k2 < md.nr_range; ++k2) {  // SlackBound rows (range slacks)
+        const int j = md.col_end[0] + k2;
+        if (pos[c.n_art + j] != -2) x[md.col_end[4] + k2] = ub[c.n_art + j] - x[j];
+    }
+}
 
 }  // namespace relp

@@ -17,9 +17,18 @@
 // The explicit inverse is re-inverted from the basis columns by Gauss-Jordan with partial pivoting every `polish_period` pivots and
 // before every verdict (the role of `BasisInverse::invert`, lower_upper/mod.rs:78-92).
 //
-// Two tiers of storage for B^-1 (f64, column-major, ld = m), one kernel source: `many_kernel<true>` keeps it in the workgroup's LDS,
-// `many_kernel<false>` in a per-LP slab of global memory.  Everything else of the LP's state -- x_B, -pi, rho_p, w, alpha, the basis
-// -- is in LDS in both.  Columns, costs, steepest-edge weights and column positions stay in global memory.
+// Two tiers of storage for B^-1 (f64, column-major, ld = m), one kernel source: `many_kernel<true, .>` keeps it in the workgroup's
+// LDS, `many_kernel<false, .>` in a per-LP slab of global memory.  Everything else of the LP's state -- x_B, -pi, rho_p, w, alpha, the
+// basis -- is in LDS in both.  Columns, costs, steepest-edge weights and column positions stay in global memory.
+//
+// Implicit upper bounds (`many_kernel<., true>`, relp_many_config.implicit_bounds): the device LP has the constraint rows only and
+// the bounds of the structurals and the ranges of the range slacks are kept by the bounded-variable ratio test, as a `Solver` with
+// relp_options.implicit_bounds does (kernels.hip, ftran_ratio_fast_kernel): complemented columns (`flipped`, pos -2) priced and
+// entered with the opposite sign, rows with alpha_i < 0 leaving at the upper bound of their basic variable, bound flips of the
+// entering variable, zero-width columns never priced (pos -3).  Two more vectors per LP in LDS: `xub` (the bound of the variable
+// basic in row i) and the mutable right-hand side b' = b - sum over the complemented columns of u_j a_j; 8 m words instead of 6 m, so
+// the LDS tier of a bounded LP ends at 138 rows.  `flipped` and `ub` are in global memory beside `pos`.  An LP without a finite bound
+// runs the plain instantiation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,21 +51,25 @@ constexpr int MANY_MAX_ROWS = 512;
 constexpr size_t MANY_LDS_BYTES = 160 * 1024;        // a CU of gfx950
 constexpr size_t MANY_STATIC_LDS = 1024;             // the kernel's __shared__ scalars (below), rounded up
 constexpr double MANY_RESIDUAL_BOUND = 1e-6;         // max |B B^-1 - I| a fresh inversion must reach, else RELP_ERR_NUMERICAL
+constexpr int MANY_TIERS = 4;                        // launch groups per instantiation: three LDS sizes and the global tier
+constexpr int MANY_GROUPS = 2 * MANY_TIERS;          // ... of the plain and of the bounded kernel
 constexpr double MANY_ZERO_LEVEL_TOL = 1e-7;         // row scan of a zero-level pivot (as Solver::drive_out_artificials)
 
 // Words (8 bytes) of the per-LP vectors in LDS: x_B, -pi, rho_p, w, alpha, then the basis and the pivot rows of the inversion
-// (2 m ints), and in the LDS tier the m x m inverse.
-__host__ __device__ constexpr size_t many_vector_words(int m) { return (size_t)6 * m; }
-__host__ __device__ constexpr size_t many_lds_bytes(int m, bool inverse_in_lds) {
-    return 8 * (many_vector_words(m) + (inverse_in_lds ? (size_t)m * m : 0));
+// (2 m ints), with implicit bounds xub and b' too, and in the LDS tier the m x m inverse.
+__host__ __device__ constexpr size_t many_vector_words(int m, bool bounded = false) { return (size_t)(bounded ? 8 : 6) * m; }
+__host__ __device__ constexpr size_t many_lds_bytes(int m, bool inverse_in_lds, bool bounded = false) {
+    return 8 * (many_vector_words(m, bounded) + (inverse_in_lds ? (size_t)m * m : 0));
 }
-// Largest m whose LDS tier fits a CU: 139 rows (139 x 139 x 8 + 6 x 139 x 8 = 161 240 bytes, plus the static part).
-constexpr int many_lds_tier_rows() {
+// Largest m whose LDS tier fits a CU: 139 rows (139 x 139 x 8 + 6 x 139 x 8 = 161 240 bytes, plus the static part); with implicit
+// bounds 138 rows (138 x 138 x 8 + 8 x 138 x 8 = 161 184 bytes; 139 rows would need 163 464).
+constexpr int many_lds_tier_rows(bool bounded = false) {
     int m = 1;
-    while (m < MANY_MAX_ROWS && many_lds_bytes(m + 1, true) + MANY_STATIC_LDS <= MANY_LDS_BYTES) ++m;
+    while (m < MANY_MAX_ROWS && many_lds_bytes(m + 1, true, bounded) + MANY_STATIC_LDS <= MANY_LDS_BYTES) ++m;
     return m;
 }
 static_assert(many_lds_tier_rows() == 139, "the documented cut-off of the LDS tier");
+static_assert(many_lds_tier_rows(true) == 138, "the documented cut-off of the LDS tier with implicit bounds");
 
 struct ManyLP {
     int m, n, n_art, textbook;
@@ -74,6 +87,7 @@ struct ManyOut {
     int entering;      // device column of the ray (UNBOUNDED)
     int redundant;     // rows left on a zero-level artificial
     long long pivots_phase_one, pivots_phase_two, reinversions;
+    long long bound_flips;  // implicit bounds: iterations that moved the entering variable to its other bound (counted in the pivots too)
     double minus_obj;
     double max_residual;
 };
@@ -89,6 +103,8 @@ struct ManyArgs {
     const int* basis0;
     double* gamma;
     int* pos;
+    const double* ub;  // implicit bounds: [n] per LP beside `pos` (+inf: none), and which columns are held in complemented form
+    int* flipped;
     double* inverse;
     int* basis_out;
     double* xb_out;
@@ -100,7 +116,7 @@ struct ManyArgs {
 
 enum : int { MANY_PIVOTED = 0, MANY_NO_ENTERING = 1, MANY_UNBOUNDED = 2 };
 
-template <bool LDS_INVERSE>
+template <bool LDS_INVERSE, bool BOUNDED>
 __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ double s_akey[MANY_WAVES];
@@ -123,21 +139,47 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
     double* alpha = w + m;
     int* basis = reinterpret_cast<int*>(alpha + m);
     int* pivot_row = basis + m;
-    double* inv = LDS_INVERSE ? smem + many_vector_words(m) : a.inverse + L.inv_off;
+    // implicit bounds: the bound of the variable basic in row i, the right-hand side b' of the complemented LP; per column the bound
+    // and whether the column is held in complemented form (x'_j = u_j - x_j, column and cost negated)
+    double* xub = BOUNDED ? smem + many_vector_words(m) : nullptr;
+    double* bprime = BOUNDED ? xub + m : nullptr;
+    const double* ub = BOUNDED ? a.ub + L.c_off : nullptr;
+    int* flipped = BOUNDED ? a.flipped + L.c_off : nullptr;
+    double* inv = LDS_INVERSE ? smem + many_vector_words(m, BOUNDED) : a.inverse + L.inv_off;
     const bool steepest = a.rule == RELP_PIVOT_STEEPEST_EDGE;
     const double slack = L.textbook ? 0.0 : a.harris_delta;
 
     int phase = n_art > 0 ? 1 : 2;
     auto cost = [&](int j) { return phase == 1 ? (j < n_art ? 1.0 : 0.0) : cost2[j]; };
+    // cost and entries of a column as the basis holds it: a complemented column with the opposite sign (cb_kernel, invert_kernel)
+    auto basic_cost = [&](int j) {
+        if constexpr (BOUNDED) return flipped[j] ? -cost(j) : cost(j);
+        else return cost(j);
+    };
+    auto basic_value = [&](int j, int e) {
+        if constexpr (BOUNDED) return flipped[j] ? -va[e] : va[e];
+        else return va[e];
+    };
     auto block_sum = [&](double v) { return block_reduce<0>(v, s_red); };
     auto block_max = [&](double v) { return -block_reduce<1>(-v, s_red); };
 
     // ---- Tableau::new over Partially (partially.rs:125-205): B = I, artificial k on its row, slack pivots on the others ----
-    for (int j = tid; j < n; j += MANY_THREADS) pos[j] = -1;
+    if constexpr (BOUNDED) {  // nothing is complemented; a variable whose two bounds coincide is never priced (-3)
+        for (int j = tid; j < n; j += MANY_THREADS) {
+            pos[j] = ub[j] == 0.0 ? -3 : -1;
+            flipped[j] = 0;
+        }
+    } else {
+        for (int j = tid; j < n; j += MANY_THREADS) pos[j] = -1;
+    }
     for (int i = tid; i < m; i += MANY_THREADS) {
         basis[i] = a.basis0[L.r_off + i];
         xb[i] = rhs[i];
         rho[i] = w[i] = 0.0;
+        if constexpr (BOUNDED) {  // (the initial basic variables, artificials and slacks, have no upper bound)
+            xub[i] = INFINITY;
+            bprime[i] = rhs[i];
+        }
     }
     __syncthreads();
     for (int i = tid; i < m; i += MANY_THREADS) pos[basis[i]] = i;
@@ -146,7 +188,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
     __syncthreads();
 
     double minus_obj = 0.0, max_residual = 0.0;
-    long long pivots[2] = {0, 0}, reinversions = 0, since = 0;
+    long long pivots[2] = {0, 0}, reinversions = 0, since = 0, bound_flips = 0;
     int pending = 0, leaving = -1, status = RELP_OK, kind = RELP_RESULT_NONE, entering = -1, redundant = 0;
     double gamma_q = 1.0, alpha_pq = 1.0;
 
@@ -154,19 +196,23 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
     auto refresh_pi = [&]() {
         for (int j = wave; j < m; j += MANY_WAVES) {
             double acc = 0.0;
-            for (int i = lane; i < m; i += WAVE) acc += cost(basis[i]) * inv[(size_t)j * ld + i];
+            for (int i = lane; i < m; i += WAVE) acc += basic_cost(basis[i]) * inv[(size_t)j * ld + i];
             acc = wave_sum(acc);
             if (lane == LAST) mpi[j] = -acc;
         }
         double v = 0.0;
-        for (int i = tid; i < m; i += MANY_THREADS) v += xb[i] * cost(basis[i]);
+        for (int i = tid; i < m; i += MANY_THREADS) v += xb[i] * basic_cost(basis[i]);
+        if constexpr (BOUNDED)  // the constant of the complemented variables: sum u_j c_j
+            for (int j = tid; j < n; j += MANY_THREADS)
+                if (flipped[j]) v += ub[j] * cost(j);
         minus_obj = -block_sum(v);  // (its barriers publish -pi too)
     };
-    // x_B = B^-1 b (xb_kernel)
+    // x_B = B^-1 b (xb_kernel); with implicit bounds b is b'
     auto refresh_xb = [&]() {
+        const double* b = BOUNDED ? bprime : rhs;
         for (int i = tid; i < m; i += MANY_THREADS) {
             double acc = 0.0;
-            for (int j = 0; j < m; ++j) acc += inv[(size_t)j * ld + i] * rhs[j];
+            for (int j = 0; j < m; ++j) acc += inv[(size_t)j * ld + i] * b[j];
             xb[i] = acc;
         }
         __syncthreads();
@@ -199,7 +245,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
             for (int k = 0; k < m; ++k) {
                 const int col = basis[k];
                 double acc = i == k ? 1.0 : 0.0;
-                for (int e = cs[col]; e < cs[col + 1]; ++e) acc -= va[e] * inv[(size_t)ri[e] * ld + i];
+                for (int e = cs[col]; e < cs[col + 1]; ++e) acc -= basic_value(col, e) * inv[(size_t)ri[e] * ld + i];
                 worst = fmax(worst, fabs(acc));
                 if (acc != acc) worst = INFINITY;  // (NaN)
             }
@@ -216,7 +262,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         __syncthreads();
         for (int k = wave; k < m; k += MANY_WAVES) {
             const int col = basis[k];
-            for (int e = cs[col] + lane; e < cs[col + 1]; e += WAVE) inv[(size_t)k * ld + ri[e]] = va[e];
+            for (int e = cs[col] + lane; e < cs[col + 1]; e += WAVE) inv[(size_t)k * ld + ri[e]] = basic_value(col, e);
         }
         __syncthreads();
         for (int k = 0; k < m; ++k) {
@@ -271,11 +317,34 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
     };
     // One pricing pass (with the pending steepest-edge update) and, unless `forced_q` >= 0, the entering column; then FTRAN, the
     // ratio test (or the given row) and the basis change.  Returns MANY_PIVOTED / MANY_NO_ENTERING / MANY_UNBOUNDED.
+    // With implicit bounds (ftran_ratio_fast_kernel): a row with alpha_i < 0 whose basic variable has a bound is eligible with the
+    // room to that bound, and the entering variable may reach its own bound first: a bound flip, MANY_PIVOTED without a basis change.
+    // `room`: distance of the basic variable of row i to the bound it moves towards.
+    auto ratio_row = [&](int i, double al, double& room) -> bool {
+        const bool allowed = !(phase == 2 && basis[i] < n_art);
+        bool eligible = al > a.tol_pivot && allowed;
+        room = fmax(xb[i], 0.0);
+        if constexpr (BOUNDED) {
+            if (allowed && al < -a.tol_pivot) {
+                const double up = xub[i];
+                if (up < INFINITY) {
+                    eligible = true;
+                    room = fmax(up - xb[i], 0.0);
+                }
+            }
+        }
+        return eligible;
+    };
     auto pivot = [&](int forced_q, int forced_p) -> int {
         double key = 0.0;
         unsigned long long rank = RANK_NONE;
         for (int j = n_art + tid; j < n; j += MANY_THREADS) {
-            if (pos[j] != -1) continue;
+            const int pos_j = pos[j];
+            if constexpr (BOUNDED) {
+                if (pos_j != -1 && pos_j != -2) continue;  // (-3: a fixed variable, never priced)
+            } else {
+                if (pos_j != -1) continue;
+            }
             double d_pi = 0.0, d_rho = 0.0, d_w = 0.0;
             for (int e = cs[j]; e < cs[j + 1]; ++e) {
                 const int r = ri[e];
@@ -286,7 +355,9 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
                     d_w += v * w[r];
                 }
             }
-            const double cbar = cost(j) + d_pi;
+            double cbar = cost(j) + d_pi;
+            if constexpr (BOUNDED)
+                if (pos_j == -2) cbar = -cbar;  // a complemented column
             double g = 1.0;
             if (steepest) {
                 g = gamma[j];
@@ -319,15 +390,22 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         }
         double cbar_q = cost(q);  // (every thread: the same sum in the same order as the pricing pass)
         for (int e = cs[q]; e < cs[q + 1]; ++e) cbar_q += va[e] * mpi[ri[e]];
-        // FTRAN: alpha = B^-1 a_q
+        double sgn_q = 1.0, ub_q = INFINITY;
+        if constexpr (BOUNDED) {
+            sgn_q = flipped[q] ? -1.0 : 1.0;
+            ub_q = ub[q];
+            cbar_q *= sgn_q;
+        }
+        // FTRAN: alpha = B^-1 a_q (of the complemented column: with the opposite sign)
         double sumsq = 0.0, theta = INFINITY;
         for (int i = tid; i < m; i += MANY_THREADS) {
             double acc = 0.0;
             for (int e = cs[q]; e < cs[q + 1]; ++e) acc += inv[(size_t)ri[e] * ld + i] * va[e];
+            if constexpr (BOUNDED) acc *= sgn_q;
             alpha[i] = acc;
             sumsq += acc * acc;
-            const bool eligible = acc > a.tol_pivot && !(phase == 2 && basis[i] < n_art);
-            if (eligible) theta = fmin(theta, (fmax(xb[i], 0.0) + slack) / fabs(acc));
+            double room;
+            if (ratio_row(i, acc, room)) theta = fmin(theta, (room + slack) / fabs(acc));
         }
         gamma_q = 1.0 + block_sum(sumsq);  // pivot_rule.rs:258
         const double theta_max = block_reduce<1>(theta, s_red);
@@ -337,10 +415,11 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         rank = RANK_NONE;
         for (int i = tid; i < m; i += MANY_THREADS) {
             const double al = alpha[i];
-            const bool eligible = al > a.tol_pivot && !(phase == 2 && basis[i] < n_art);
+            double room;
+            const bool eligible = ratio_row(i, al, room);
             const double mag = fabs(al);
             const double k = L.textbook ? 1.0 : mag;
-            if (forced_p >= 0 ? i == forced_p : (eligible && fmax(xb[i], 0.0) / mag <= theta_max)) {
+            if (forced_p >= 0 ? i == forced_p : (eligible && room / mag <= theta_max)) {
                 const unsigned long long r = ((unsigned long long)(unsigned)basis[i] << 32) | (unsigned)i;
                 if (rank == RANK_NONE || k > key || (k == key && r < rank)) {
                     key = k;
@@ -349,6 +428,35 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
             }
         }
         block_argbest(key, rank, s_akey, s_arank);
+        // step length: to the bound of the leaving variable, or (forced zero-level pivots) as the reference computes it
+        double step = INFINITY, ub_leaving = INFINITY;
+        if constexpr (BOUNDED) {
+            if (rank != RANK_NONE) {
+                const int row = (int)(rank & 0xffffffffu);
+                double room;
+                ratio_row(row, alpha[row], room);
+                step = forced_p >= 0 ? fmax(xb[row], 0.0) / alpha[row] : room / fabs(alpha[row]);
+                ub_leaving = xb[row] + room;  // (a row that leaves at its upper bound: x_p + room is that bound)
+            }
+            if (forced_p < 0 && ub_q < INFINITY && (rank == RANK_NONE || ub_q <= step)) {
+                // bound flip: x_q runs from 0 to u_q and is complemented so that it sits at 0 again; the basis does not change, so
+                // neither the inverse nor -pi nor the weights do
+                __syncthreads();  // (x_B read by every thread)
+                for (int i = tid; i < m; i += MANY_THREADS) xb[i] -= alpha[i] * ub_q;
+                for (int e = cs[q] + tid; e < cs[q + 1]; e += MANY_THREADS) bprime[ri[e]] -= ub_q * sgn_q * va[e];
+                if (tid == 0) {
+                    const int now_flipped = sgn_q < 0.0 ? 0 : 1;
+                    flipped[q] = now_flipped;
+                    pos[q] = now_flipped ? -2 : -1;
+                }
+                minus_obj -= cbar_q * ub_q;
+                ++pivots[phase - 1];
+                ++bound_flips;
+                ++since;
+                __syncthreads();
+                return MANY_PIVOTED;
+            }
+        }
         if (rank == RANK_NONE) {
             entering = q;
             return MANY_UNBOUNDED;
@@ -360,9 +468,18 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
             return MANY_UNBOUNDED;  // (a forced row whose element vanished: never from the ratio test, which needs alpha > tol_pivot)
         }
         leaving = basis[p];
-        const double xp = fmax(xb[p], 0.0) / alpha_pq;
-        __syncthreads();  // x_B[p] and basis[p] read by every thread
+        const double xp = BOUNDED ? step : fmax(xb[p], 0.0) / alpha_pq;
+        // the leaving variable reached its upper bound: it is held in complemented form from now on
+        const bool leaves_at_upper = BOUNDED && forced_p < 0 && alpha_pq < 0.0;
+        int leaving_flipped = 0;
+        if constexpr (BOUNDED) leaving_flipped = flipped[leaving];
+        __syncthreads();  // x_B[p], basis[p] and flipped[leaving] read by every thread
         for (int i = tid; i < m; i += MANY_THREADS) xb[i] = i == p ? xp : xb[i] - alpha[i] * xp;
+        if constexpr (BOUNDED)
+            if (leaves_at_upper) {
+                const double sgn_l = leaving_flipped ? -1.0 : 1.0;
+                for (int e = cs[leaving] + tid; e < cs[leaving + 1]; e += MANY_THREADS) bprime[ri[e]] -= ub_leaving * sgn_l * va[e];
+            }
         minus_obj -= cbar_q * xp;
         // rank-one update of B^-1 by columns, with rho_p, w = alpha' B^-1_old and -pi (pivot_fused_kernel)
         for (int j = wave; j < m; j += MANY_WAVES) {
@@ -384,7 +501,14 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         if (tid == 0) {
             basis[p] = q;
             pos[q] = p;
-            pos[leaving] = -1;
+            if constexpr (BOUNDED) {
+                int fl = leaving_flipped;
+                if (leaves_at_upper) flipped[leaving] = fl ^= 1;
+                pos[leaving] = fl ? -2 : -1;
+                xub[p] = ub_q;
+            } else {
+                pos[leaving] = -1;
+            }
         }
         pending = steepest ? 1 : 0;
         ++pivots[phase - 1];
@@ -422,7 +546,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
             if (basis[r] >= n_art) continue;
             unsigned long long first = RANK_NONE;
             for (int j = n_art + tid; j < n; j += MANY_THREADS) {
-                if (pos[j] != -1) continue;
+                if (BOUNDED ? pos[j] >= 0 : pos[j] != -1) continue;  // (every non-basic column, as row_scan_kernel: fixed ones too)
                 double acc = 0.0;
                 for (int e = cs[j]; e < cs[j + 1]; ++e) acc += va[e] * inv[(size_t)ri[e] * ld + r];
                 if (fabs(acc) > MANY_ZERO_LEVEL_TOL && first == RANK_NONE) first = (unsigned long long)j;
@@ -442,6 +566,16 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         set_phase(2);
     }
     __syncthreads();
+    if constexpr (BOUNDED) {
+        // A fixed variable sits at both of its bounds at once; which of the two the reference's formulation sees is decided by its
+        // reduced cost (Solver::resolve_fixed_columns): negative -> at the upper bound (-2), else the bound slack is basic (-1).
+        for (int j = n_art + tid; j < n; j += MANY_THREADS) {
+            if (pos[j] != -3) continue;
+            double cbar = cost(j);
+            for (int e = cs[j]; e < cs[j + 1]; ++e) cbar += va[e] * mpi[ri[e]];
+            pos[j] = cbar < 0.0 ? -2 : -1;
+        }
+    }
     for (int i = tid; i < m; i += MANY_THREADS) {
         a.basis_out[L.r_off + i] = basis[i];
         a.xb_out[L.r_off + i] = xb[i];
@@ -455,6 +589,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         o.pivots_phase_one = pivots[0];
         o.pivots_phase_two = pivots[1];
         o.reinversions = reinversions;
+        o.bound_flips = bound_flips;
         o.minus_obj = minus_obj;
         o.max_residual = max_residual;
         a.out[a.order[blockIdx.x]] = o;
@@ -470,26 +605,37 @@ double many_now() {
 constexpr unsigned MANY_REFUSED_SWITCHES = RELP_SW_ELL_WIDE | RELP_SW_PRICE_UNIT_PAIRS | RELP_SW_NO_RHO_BITS | RELP_SW_NETWORK_STATS;
 }  // namespace
 
-// One LP as the device sees it (the index space and the data a `Solver` with the explicit carry and no implicit bounds has), and
-// what is this path's own: the tier, the launch group and the work estimate.
+// One LP as the device sees it (the index space and the data a `Solver` with the explicit carry has, with or without implicit
+// bounds), and what is this path's own: the tier, the launch group and the work estimate.
 struct ManyHostLP {
-    int m = 0, n = 0, n_art = 0, textbook = 0, lds = 0, bucket = 0;
+    int m = 0, n = 0, n_art = 0, textbook = 0, lds = 0, bucket = 0, bounded = 0;
     DeviceColumns cols;
     DeviceMatrix data;
+    std::vector<double> ub;  // bounded: [n] upper bound of each device column, +inf where there is none
     double work = 0.0;  // estimated solve time, for the launch order
 };
 
-ManyHostLP many_host_lp(const StandardForm& form, const relp_options& o) {
+// Rows of the device LP: with implicit bounds the constraint rows of an LP that has a bound, else every row of the standard form.
+int many_device_rows(const MatrixData& md, bool implicit_bounds) {
+    return implicit_bounds && md.nr_variable_bounds() > 0 ? md.nr_constraints() : md.nr_rows();
+}
+
+ManyHostLP many_host_lp(const StandardForm& form, const relp_options& o, bool implicit_bounds) {
     ManyHostLP lp;
-    lp.cols = DeviceColumns(form.data);
-    lp.data = DeviceMatrix(lp.cols, form.data);
+    const MatrixData& md = form.data;
+    // as Solver::upload: an LP without a finite bound is not a bounded one; a bounded one has the constraint rows and the first four
+    // column groups, and the bounds of the structurals and the ranges of the range slacks per column
+    lp.bounded = implicit_bounds && md.nr_variable_bounds() > 0;
+    lp.cols = lp.bounded ? DeviceColumns(md, md.nr_constraints(), md.col_end[3]) : DeviceColumns(md);
+    lp.data = DeviceMatrix(lp.cols, md);
     const int m = lp.m = lp.cols.m, n = lp.n = lp.cols.n();
     lp.n_art = lp.cols.n_art;
+    if (lp.bounded) lp.ub = implicit_upper_bounds(md, lp.cols);
     // RELP_RATIO_AUTO as Solver::upload resolves it (every LP here has at most 512 rows: the kernels have the textbook rule)
     lp.textbook = o.ratio_rule == RELP_RATIO_TEXTBOOK || (o.ratio_rule == RELP_RATIO_AUTO && lp.data.small_integer_data());
-    lp.lds = m <= many_lds_tier_rows() && !(o.switches & RELP_SW_MANY_GLOBAL_TIER);
-    // launch groups: three LDS sizes (7, 2 and 1 workgroups per CU) and the global tier
-    lp.bucket = !lp.lds ? 3 : m <= 48 ? 0 : m <= 96 ? 1 : 2;
+    lp.lds = m <= many_lds_tier_rows(lp.bounded) && !(o.switches & RELP_SW_MANY_GLOBAL_TIER);
+    // launch groups: three LDS sizes (7, 2 and 1 workgroups per CU) and the global tier; the bounded LPs in four groups of their own
+    lp.bucket = (!lp.lds ? 3 : m <= 48 ? 0 : m <= 96 ? 1 : 2) + (lp.bounded ? MANY_TIERS : 0);
     lp.work = (double)(m + n) * m * ((double)m + (double)lp.data.row_index.size() / std::max(1, n));
     return lp;
 }
@@ -507,10 +653,14 @@ struct relp_many {
     ManyLP* d_lps = nullptr;
     int *d_order = nullptr, *d_col_start = nullptr, *d_row_index = nullptr, *d_basis0 = nullptr, *d_pos = nullptr, *d_basis_out = nullptr;
     double *d_value = nullptr, *d_cost2 = nullptr, *d_rhs = nullptr, *d_gamma = nullptr, *d_inverse = nullptr, *d_xb_out = nullptr;
+    double* d_ub = nullptr;     // implicit bounds (allocated when an LP of the list is bounded)
+    int* d_flipped = nullptr;
     ManyOut* d_out = nullptr;
+    bool implicit_bounds = false;     // relp_many_config.implicit_bounds
+    bool any_bounded = false;
     std::vector<int> order;           // LP indices, grouped by bucket, longest first within a bucket
-    int bucket_first[5] = {0, 0, 0, 0, 0};
-    int bucket_rows[4] = {0, 0, 0, 0};  // largest m of each bucket
+    int bucket_first[MANY_GROUPS + 1] = {};
+    int bucket_rows[MANY_GROUPS] = {};  // largest m of each bucket
     hipStream_t streams[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_done[4] = {nullptr, nullptr, nullptr, nullptr};
     DeviceAllocations memory;  // every device array above
@@ -518,7 +668,8 @@ struct relp_many {
     // results of the last solve
     bool solved = false;
     std::vector<relp_many_result> results;
-    std::vector<std::vector<int>> bases;      // provider codes (DeviceColumns::to_provider)
+    std::vector<long long> bound_flips;
+    std::vector<std::vector<int>> bases;      // provider codes (DeviceColumns::to_provider); bounded: of the reference's formulation
     std::vector<std::vector<double>> solutions;  // every column of MatrixData
     std::vector<std::string> exact;
     std::string error;
@@ -564,6 +715,11 @@ extern "C" {
 
 int32_t relp_many_create(const relp_model* const* models, int32_t n_models, const relp_options* options, relp_many** out, char* error,
                          int32_t error_capacity) {
+    return relp_many_create_with(models, n_models, options, nullptr, out, error, error_capacity);
+}
+
+int32_t relp_many_create_with(const relp_model* const* models, int32_t n_models, const relp_options* options, const relp_many_config* config,
+                              relp_many** out, char* error, int32_t error_capacity) {
     if (out) *out = nullptr;
     if (!models || n_models <= 0 || !out) {
         many_set_error(error, error_capacity, "models, n_models > 0 and out are required");
@@ -579,21 +735,32 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
         many_set_error(error, error_capacity, refused);
         return RELP_ERR_ARGUMENT;
     }
+    if (config && config->struct_size != (int32_t)sizeof(relp_many_config)) {  // (the one size this struct has had)
+        many_set_error(error, error_capacity, "relp_many_config.struct_size is not a size this library's header ever had");
+        return RELP_ERR_ARGUMENT;
+    }
+    if (config && config->implicit_bounds != 0 && config->implicit_bounds != 1) {
+        many_set_error(error, error_capacity, "relp_many_config.implicit_bounds must be 0 or 1");
+        return RELP_ERR_ARGUMENT;
+    }
+    const bool implicit_bounds = config && config->implicit_bounds == 1;
     // every model is checked before the device is touched
     for (int32_t k = 0; k < n_models; ++k) {
         if (!models[k]) {
             many_set_error(error, error_capacity, "model " + std::to_string(k) + ": null");
             return RELP_ERR_ARGUMENT;
         }
-        const int rows = models[k]->form.data.nr_rows();
+        const int rows = many_device_rows(models[k]->form.data, implicit_bounds);
         if (rows < 1 || rows > MANY_MAX_ROWS) {
             many_set_error(error, error_capacity, "model " + std::to_string(k) + ": " + std::to_string(rows) +
-                                                      " rows in standard form; relp_many takes 1 to " + std::to_string(MANY_MAX_ROWS));
+                                                      (implicit_bounds ? " constraint rows" : " rows in standard form") + "; relp_many takes 1 to " +
+                                                      std::to_string(MANY_MAX_ROWS));
             return RELP_ERR_ARGUMENT;
         }
     }
     auto many = std::make_unique<relp_many>();
     many->options = adopted;
+    many->implicit_bounds = implicit_bounds;
     many->device = adopted.device;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || adopted.device < 0 || adopted.device >= count ||
@@ -606,11 +773,12 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
         const int n = n_models;
         many->forms.reserve(n);
         for (int k = 0; k < n; ++k) many->forms.push_back(models[k]->form);
-        for (int k = 0; k < n; ++k) many->lps.push_back(many_host_lp(many->forms[k], adopted));
+        for (int k = 0; k < n; ++k) many->lps.push_back(many_host_lp(many->forms[k], adopted, implicit_bounds));
+        for (const ManyHostLP& lp : many->lps) many->any_bounded |= lp.bounded != 0;
         // pack: CSC, costs, right-hand sides, initial bases; per-LP offsets
         std::vector<ManyLP> desc(n);
         std::vector<int> col_start, row_index, basis0;
-        std::vector<double> value, cost2, rhs;
+        std::vector<double> value, cost2, rhs, ub;
         long long inverse_words = 0;
         for (int k = 0; k < n; ++k) {
             const ManyHostLP& lp = many->lps[k];
@@ -632,6 +800,10 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
             cost2.insert(cost2.end(), lp.data.cost2.begin(), lp.data.cost2.end());
             rhs.insert(rhs.end(), lp.data.rhs.begin(), lp.data.rhs.end());
             basis0.insert(basis0.end(), lp.cols.basis0.begin(), lp.cols.basis0.end());
+            if (many->any_bounded) {  // (one entry per column of every LP, as `pos`: a plain LP's are not read)
+                if (lp.bounded) ub.insert(ub.end(), lp.ub.begin(), lp.ub.end());
+                else ub.insert(ub.end(), (size_t)lp.n, std::numeric_limits<double>::infinity());
+            }
         }
         // launch order: by bucket, then the longest estimated solve first (ties: the caller's order)
         std::vector<int> order(n);
@@ -642,7 +814,7 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
             return a.work > b.work;
         });
         many->order = order;
-        for (int b = 0; b < 4; ++b) {
+        for (int b = 0; b < MANY_GROUPS; ++b) {
             many->bucket_first[b + 1] = many->bucket_first[b];
             for (int k : order)
                 if (many->lps[k].bucket == b) {
@@ -660,6 +832,10 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
         many->d_basis0 = many_upload(many->memory, basis0);
         many->d_gamma = many->memory.alloc<double>(cost2.size());
         many->d_pos = many->memory.alloc<int>(cost2.size());
+        if (many->any_bounded) {
+            many->d_ub = many_upload(many->memory, ub);
+            many->d_flipped = many->memory.alloc<int>(cost2.size());
+        }
         many->d_inverse = many->memory.alloc<double>((size_t)inverse_words);
         many->d_basis_out = many->memory.alloc<int>(rhs.size());
         many->d_xb_out = many->memory.alloc<double>(rhs.size());
@@ -670,9 +846,9 @@ int32_t relp_many_create(const relp_model* const* models, int32_t n_models, cons
         for (hipEvent_t& e : many->ev_done) RELP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         static PerDeviceOnce once;
         once.run([] {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&many_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(MANY_LDS_BYTES - MANY_STATIC_LDS)) != hipSuccess)
-                (void)hipGetLastError();
+            for (const void* kernel : {reinterpret_cast<const void*>(&many_kernel<true, false>), reinterpret_cast<const void*>(&many_kernel<true, true>)})
+                if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MANY_LDS_BYTES - MANY_STATIC_LDS)) != hipSuccess)
+                    (void)hipGetLastError();
         });
     } catch (const DeviceError& e) {
         many_set_error(error, error_capacity, e.what());
@@ -704,6 +880,8 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
         args.basis0 = many->d_basis0;
         args.gamma = many->d_gamma;
         args.pos = many->d_pos;
+        args.ub = many->d_ub;
+        args.flipped = many->d_flipped;
         args.inverse = many->d_inverse;
         args.basis_out = many->d_basis_out;
         args.xb_out = many->d_xb_out;
@@ -715,22 +893,25 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
         args.harris_delta = o.harris_delta;
         args.tol_feasible = o.tol_feasible;
         RELP_HIP(hipEventRecord(many->ev_start, many->streams[0]));
-        for (int b = 0; b < 4; ++b) {
-            const int blocks = many->bucket_first[b + 1] - many->bucket_first[b];
-            hipStream_t s = many->streams[b];
-            if (b > 0) RELP_HIP(hipStreamWaitEvent(s, many->ev_start, 0));
-            if (blocks > 0) {
+        for (int t = 0; t < MANY_TIERS; ++t) {  // a stream per tier: its plain group, then its bounded group
+            hipStream_t s = many->streams[t];
+            if (t > 0) RELP_HIP(hipStreamWaitEvent(s, many->ev_start, 0));
+            for (int b : {t, t + MANY_TIERS}) {
+                const int blocks = many->bucket_first[b + 1] - many->bucket_first[b];
+                if (blocks == 0) continue;
                 ManyArgs part = args;
                 part.order = many->d_order + many->bucket_first[b];
-                const bool lds = b < 3;
-                const size_t bytes = many_lds_bytes(many->bucket_rows[b], lds);
-                if (lds) hipLaunchKernelGGL(many_kernel<true>, dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
-                else hipLaunchKernelGGL(many_kernel<false>, dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
+                const bool lds = t < 3, bounded = b >= MANY_TIERS;
+                const size_t bytes = many_lds_bytes(many->bucket_rows[b], lds, bounded);
+                if (lds && bounded) hipLaunchKernelGGL((many_kernel<true, true>), dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
+                else if (lds) hipLaunchKernelGGL((many_kernel<true, false>), dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
+                else if (bounded) hipLaunchKernelGGL((many_kernel<false, true>), dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
+                else hipLaunchKernelGGL((many_kernel<false, false>), dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
                 RELP_HIP(hipGetLastError());
             }
-            if (b > 0) {
-                RELP_HIP(hipEventRecord(many->ev_done[b], s));
-                RELP_HIP(hipStreamWaitEvent(many->streams[0], many->ev_done[b], 0));
+            if (t > 0) {
+                RELP_HIP(hipEventRecord(many->ev_done[t], s));
+                RELP_HIP(hipStreamWaitEvent(many->streams[0], many->ev_done[t], 0));
             }
         }
         RELP_HIP(hipEventRecord(many->ev_stop, many->streams[0]));
@@ -745,11 +926,21 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
         RELP_HIP(hipMemcpy(outs.data(), many->d_out, n * sizeof(ManyOut), hipMemcpyDeviceToHost));
         RELP_HIP(hipMemcpy(basis.data(), many->d_basis_out, rows * sizeof(int), hipMemcpyDeviceToHost));
         RELP_HIP(hipMemcpy(xb.data(), many->d_xb_out, rows * sizeof(double), hipMemcpyDeviceToHost));
+        std::vector<int> all_pos, all_flipped;  // implicit bounds: per column of every LP
+        if (many->any_bounded) {
+            size_t columns = 0;
+            for (const ManyHostLP& lp : many->lps) columns += (size_t)lp.n;
+            all_pos.resize(columns);
+            all_flipped.resize(columns);
+            RELP_HIP(hipMemcpy(all_pos.data(), many->d_pos, columns * sizeof(int), hipMemcpyDeviceToHost));
+            RELP_HIP(hipMemcpy(all_flipped.data(), many->d_flipped, columns * sizeof(int), hipMemcpyDeviceToHost));
+        }
+        many->bound_flips.assign(n, 0);
         many->results.assign(n, relp_many_result{});
         many->bases.assign(n, std::vector<int>());
         many->solutions.assign(n, std::vector<double>());
         many->exact.assign(n, std::string());
-        size_t r0 = 0;
+        size_t r0 = 0, c0 = 0;
         for (int k = 0; k < n; ++k) {
             const ManyHostLP& lp = many->lps[k];
             const StandardForm& form = many->forms[k];
@@ -762,6 +953,7 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
             res.pivots_phase_two = oc.pivots_phase_two;
             res.reinversions = oc.reinversions;
             res.max_residual = oc.max_residual;
+            many->bound_flips[k] = oc.bound_flips;
             res.objective = (oc.status == RELP_OK && oc.kind == RELP_RESULT_FINITE_OPTIMUM) ? -oc.minus_obj + form.fixed_cost.to_double()
                                                                                            : std::nan("");
             // Carry::current_bfs + reconstruct_solution (carry/mod.rs:636-645, matrix_data.rs:402-411); device values are checked first
@@ -773,11 +965,20 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
                 const int dev = basis[r0 + i];
                 if (dev < 0 || dev >= lp.n) throw std::runtime_error("model " + std::to_string(k) + ": the device returned an invalid basis");
                 provider_basis[i] = lp.cols.to_provider(dev);
-                if (dev >= lp.n_art) x[dev - lp.n_art] = xb[r0 + i];
+                if (!lp.bounded && dev >= lp.n_art) x[dev - lp.n_art] = xb[r0 + i];
+            }
+            if (lp.bounded) {  // back to the reference's formulation, as a handle with implicit bounds reports it
+                const std::vector<int> device_basis(basis.begin() + r0, basis.begin() + r0 + lp.m);
+                const std::vector<int> pos(all_pos.begin() + c0, all_pos.begin() + c0 + lp.n);
+                const std::vector<int> flipped(all_flipped.begin() + c0, all_flipped.begin() + c0 + lp.n);
+                provider_basis = explicit_basis(form.data, lp.cols, device_basis, pos);
+                explicit_solution(form.data, lp.cols, device_basis, xb.data() + r0, flipped, pos, lp.ub, x);
             }
             r0 += lp.m;
+            c0 += lp.n;
+            // (with implicit bounds the explicit basis proves an optimum; the two other verdicts stay uncertified, as on a handle)
             if (o.certify && oc.status == RELP_OK &&
-                (oc.kind == RELP_RESULT_FINITE_OPTIMUM || oc.kind == RELP_RESULT_INFEASIBLE || oc.kind == RELP_RESULT_UNBOUNDED)) {
+                (oc.kind == RELP_RESULT_FINITE_OPTIMUM || (!lp.bounded && (oc.kind == RELP_RESULT_INFEASIBLE || oc.kind == RELP_RESULT_UNBOUNDED)))) {
                 const double t0 = many_now();
                 bool ok = false;
                 long long repairs = 0;
@@ -844,8 +1045,15 @@ int32_t relp_many_get_objective_exact(const relp_many* many, int32_t model, char
 
 int32_t relp_many_dimensions(const relp_many* many, int32_t model, int32_t* nr_rows, int32_t* nr_structural) {
     if (!many || model < 0 || model >= (int32_t)many->lps.size()) return RELP_ERR_ARGUMENT;
-    if (nr_rows) *nr_rows = many->lps[model].m;
+    if (nr_rows) *nr_rows = many->forms[model].data.nr_rows();
     if (nr_structural) *nr_structural = many->forms[model].data.nr_normal_variables();
+    return RELP_OK;
+}
+
+int32_t relp_many_get_bound_flips(const relp_many* many, int32_t model, int64_t* bound_flips) {
+    if (!many || !bound_flips || model < 0 || model >= (int32_t)many->lps.size()) return RELP_ERR_ARGUMENT;
+    if (!many->solved) return RELP_ERR_STATE;
+    *bound_flips = many->bound_flips[model];
     return RELP_OK;
 }
 

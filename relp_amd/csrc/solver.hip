@@ -421,10 +421,7 @@ void Solver::upload() {
     }
     d_.rhs0 = device_alloc<double>(m);
     if (bounded_) {
-        std::vector<double> ub(n, std::numeric_limits<double>::infinity());
-        for (int j = 0; j < md.nr_normal_variables(); ++j)
-            if (md.variables[j].has_upper) ub[n_art + j] = md.variables[j].upper.to_double();
-        for (int k = 0; k < md.nr_range; ++k) ub[n_art + md.col_end[0] + k] = md.ranges[k].to_double();
+        const std::vector<double> ub = implicit_upper_bounds(md, cols_);
         zero_width_.assign(n, 0);
         for (int j = 0; j < n; ++j) zero_width_[j] = ub[j] == 0.0 ? 1 : 0;
         d_.ub = device_alloc<double>(n);
@@ -1413,21 +1410,7 @@ void Solver::solve(relp_result* result) {
         RELP_HIP(hipStreamSynchronize(stream_));
         resolve_fixed_columns(pos);
         h_basis_ = explicit_basis(basis, pos);
-        for (int i = 0; i < m; ++i) {
-            const int dev = basis[i];
-            if (dev >= d_.n_art) h_solution_[dev - d_.n_art] = flipped[dev] ? ub[dev] - xb[i] : xb[i];
-        }
-        for (int j = d_.n_art; j < d_.n; ++j)
-            if (pos[j] == -2) h_solution_[j - d_.n_art] = ub[j];
-        const int nb = (int)md.bound_to_variable.size();
-        for (int k2 = 0; k2 < nb; ++k2) {  // VariableBound rows: the bound slack of a variable below its bound
-            const int j = md.bound_to_variable[k2];
-            if (pos[d_.n_art + j] != -2) h_solution_[md.col_end[3] + k2] = ub[d_.n_art + j] - h_solution_[j];
-        }
-        for (int k2 = 0; k2 < md.nr_range; ++k2) {  // SlackBound rows (range slacks)
-            const int j = md.col_end[0] + k2;
-            if (pos[d_.n_art + j] != -2) h_solution_[md.col_end[4] + k2] = ub[d_.n_art + j] - h_solution_[j];
-        }
+        explicit_solution(md, cols_, basis, xb.data(), flipped, pos, ub, h_solution_);
     }
     if (net_.stats) {
         net_stats_.assign(NS_WORDS, 0);
@@ -1471,19 +1454,7 @@ void Solver::resolve_fixed_columns(std::vector<int>& pos) {
 }
 
 std::vector<int> Solver::explicit_basis(const std::vector<int>& basis, const std::vector<int>& pos) const {
-    const MatrixData& md = form_.data;
-    std::vector<int> out(md.nr_rows(), -1);
-    for (int i = 0; i < d_.m; ++i) out[i] = cols_.to_provider(basis[i]);
-    const int nb = (int)md.bound_to_variable.size();
-    for (int k2 = 0; k2 < nb; ++k2) {
-        const int j = md.bound_to_variable[k2];
-        out[md.row_end[3] + k2] = pos[d_.n_art + j] == -2 ? j : md.col_end[3] + k2;
-    }
-    for (int k2 = 0; k2 < md.nr_range; ++k2) {
-        const int j = md.col_end[0] + k2;
-        out[md.row_end[4] + k2] = pos[d_.n_art + j] == -2 ? j : md.col_end[4] + k2;
-    }
-    return out;
+    return relp::explicit_basis(form_.data, cols_, basis, pos);
 }
 
 void Solver::certify(relp_result* result) {
@@ -1996,6 +1967,12 @@ void Solver::get_b(double* out) {
     RELP_HIP(hipStreamSynchronize(stream_));
 }
 double Solver::objective() { return -read_ctl().minus_obj; }
+long long Solver::bound_flips() {
+    if (!bounded_ || phase_ == 0) return 0;
+    RELP_HIP(hipSetDevice(opt_.device));
+    return read_ctl().bound_flips;
+}
+
 void Solver::get_basis(int* out) {
     std::vector<int> basis(d_.m);
     RELP_HIP(hipMemcpyAsync(basis.data(), d_.basis, d_.m * sizeof(int), hipMemcpyDeviceToHost, stream_));

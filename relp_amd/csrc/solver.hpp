@@ -332,6 +332,7 @@ public:
     void get_b(double* out);
     double objective();
     void get_basis(int* out);
+    long long bound_flips();  // implicit bounds: Ctl::bound_flips since begin_phase_one
     void get_solution(double* x) const;
     double profile_kernel(int which, int repetitions);
     void debug_stamps(unsigned long long* out64);

@@ -87,7 +87,8 @@ def resource_usage():
     for line in open(path):
         name = re.search(r"Function Name: (\S+)", line)
         if name:
-            current = "lds_tier" if "ILb1E" in name.group(1) else "global_tier"
+            flags = re.search(r"ILb(\d)ELb(\d)E", name.group(1))  # many_kernel<LDS_INVERSE, BOUNDED>
+            current = ("lds_tier" if flags.group(1) == "1" else "global_tier") + ("_bounded" if flags.group(2) == "1" else "")
             out[current] = {"symbol": name.group(1)}
             continue
         field = re.search(r"remark:\s+([A-Za-z][^:\[]*?)\s*(?:\[[^\]]*\])?:\s*(\d+)", line)
