@@ -21,6 +21,7 @@
 #include <utility>
 
 #include "kernels.hpp"
+#include "pivot_step.hpp"
 #include "solver.hpp"
 #include "wave_ops.hpp"
 
@@ -1492,11 +1493,19 @@ __global__ void eta_reset_kernel(DeviceLP lp) {
 //                 lower_upper/mod.rs:180-210 (explicit inverse: basis_inverse_rows.rs:139-152)
 //             Tableau::select_primal_pivot_row                                           tableau/mod.rs:287-313
 //             Carry::update_b and the basis bookkeeping                                  carry/mod.rs:295-325,561-604
-// The ratio test is the two-pass Harris variant (f64 needs a pivot-size preference the exact reference does
-// not); ties keep the reference's Bland rule (lowest leaving column).
+// The ratio test, the step decision and the bookkeeping are those of pivot_step.hpp (two-pass Harris only here).
 // mode 0: full iteration | 1: stop after the entering-column choice | 2: stop after the ratio test (no update)
 // ---------------------------------------------------------------------------------------------------
 constexpr int K2_THREADS = 1024;
+// column p of the stored inverse stops being a unit vector (explicit carry without the deferred product form)
+__device__ __forceinline__ void push_touched(const DeviceLP& lp, Ctl& c, int p) {
+    if (lp.track_touched && lp.eta_cap == 0 && !lp.touched[p]) {
+        const int count = c.touched_count;
+        lp.touched[p] = 1;
+        lp.tlist[count] = p;
+        c.touched_count = count + 1;
+    }
+}
 constexpr int K2_COL_CHUNK = 1024;  // entries of the entering column staged per pass
 template <int RULE>
 __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, int n_price_blocks, double tol_pivot,
@@ -1510,10 +1519,7 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
     Ctl* ctl = lp.ctl;
     if (ctl->status != ST_RUNNING) return;
     if (mode == 0 && ctl->iters >= ctl->budget) {
-        if (threadIdx.x == 0) {
-            ctl->status = ST_BUDGET;
-            ctl->pending = 0;
-        }
+        if (threadIdx.x == 0) ctl_budget(*ctl);
         return;
     }
     const int m = lp.m;
@@ -1549,20 +1555,11 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
     const int q = s_q;
     const double cbar_q = s_cbar;
     if (q < 0) {
-        if (threadIdx.x == 0) {
-            if (mode == 0) ctl->status = ST_NO_ENTERING;
-            ctl->q = -1;
-            ctl->pending = 0;
-            if (mode == 0) ctl->last_selected = -1;
-        }
+        if (threadIdx.x == 0) ctl_no_entering(*ctl, mode);
         return;
     }
     if (mode == 1) {
-        if (threadIdx.x == 0) {
-            ctl->q = q;
-            ctl->cbar_q = cbar_q;
-            ctl->pending = 0;
-        }
+        if (threadIdx.x == 0) ctl_entering_only(*ctl, q, cbar_q);
         return;
     }
 
@@ -1572,7 +1569,7 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
     constexpr int K2_U = 8;
     const int ca = lp.col_start[q], cb_ = lp.col_start[q + 1];
     const bool single = (cb_ - ca) <= K2_COL_CHUNK;
-    // Implicit upper bounds: see ftran_ratio_fast_kernel (same rules, alpha kept in global memory here).
+    // (alpha kept in global memory here)
     const bool bounded = lp.ub != nullptr;
     const double sgn_q = (bounded && lp.flipped[q]) ? -1.0 : 1.0;
     const double ub_q = bounded ? lp.ub[q] : INFINITY;
@@ -1621,9 +1618,8 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
                 const double a = acc[u] * sgn_q;  // gamma_q and Harris pass 1 fused into the last FTRAN pass
                 lp.alpha[i] = a;
                 sumsq += a * a;
-                if (skip_artificial_rows && basv[u] < lp.n_art) continue;
-                if (a > tol_pivot) theta = fmin(theta, (fmax(xbv[u], 0.0) + harris_delta) / a);
-                else if (bounded && a < -tol_pivot && upv[u] < INFINITY) theta = fmin(theta, (fmax(upv[u] - xbv[u], 0.0) + harris_delta) / -a);
+                const RowRoom row = row_room(a, xbv[u], [&] { return upv[u]; }, !(skip_artificial_rows && basv[u] < lp.n_art), bounded, tol_pivot);
+                if (row.eligible) theta = fmin(theta, harris_pass1(row.room, harris_delta, a));
             }
         }
     }
@@ -1650,14 +1646,12 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
 #pragma unroll
             for (int u = 0; u < K2_U; ++u) {
                 const int i = i0 + u * blockDim.x;
-                if (i >= m || (skip_artificial_rows && basv[u] < lp.n_art)) continue;
+                if (i >= m) continue;
                 const double a = av[u];
-                double room = -1.0;
-                if (a > tol_pivot) room = fmax(xbv[u], 0.0);
-                else if (bounded && a < -tol_pivot && upv[u] < INFINITY) room = fmax(upv[u] - xbv[u], 0.0);
-                if (room >= 0.0 && room / fabs(a) <= theta_max) {
+                const RowRoom row = row_room(a, xbv[u], [&] { return upv[u]; }, !(skip_artificial_rows && basv[u] < lp.n_art), bounded, tol_pivot);
+                if (row.eligible && harris_accepts(row.room, fabs(a), theta_max)) {
                     Cand o;
-                    o.key = fabs(a);
+                    o.key = harris_key(false, fabs(a));
                     o.idx = i;
                     o.aux = basv[u];
                     c = better<TIE_SMALLER_AUX>(c, o);
@@ -1670,31 +1664,16 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
     const double alpha_pq = p >= 0 ? lp.alpha[p] : 1.0;
     const double xb_p = p >= 0 ? lp.xB[p] : 0.0;
     const double up_p = (bounded && p >= 0) ? lp.xub[p] : INFINITY;
-    const bool leaves_at_upper = bounded && forced_p < 0 && p >= 0 && alpha_pq < 0.0;
-    const double xp = (forced_p >= 0 || !bounded) ? fmax(xb_p, 0.0) / alpha_pq
-                                                  : (leaves_at_upper ? fmax(up_p - xb_p, 0.0) : fmax(xb_p, 0.0)) / fabs(alpha_pq);
-    const bool flip = bounded && forced_p < 0 && ub_q < INFINITY && (p < 0 || ub_q <= xp);
+    Step step = step_decision(bounded, forced_p >= 0, p, alpha_pq, xb_p, row_room(alpha_pq, xb_p, [&] { return up_p; }, true, bounded, tol_pivot).room, ub_q);
+    step.ub_leaving = up_p;  // (the bound itself is at hand here)
+    const double xp = step.xp;
+    const bool flip = step.flip;
     if (p < 0 && !flip) {
-        if (threadIdx.x == 0) {
-            if (mode == 0) ctl->status = ST_UNBOUNDED;
-            ctl->q = q;
-            ctl->p = -1;
-            ctl->pending = 0;
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-        }
+        if (threadIdx.x == 0) ctl_unbounded(*ctl, q, mode);
         return;
     }
     if (mode == 2) {
-        if (threadIdx.x == 0) {
-            ctl->q = q;
-            ctl->p = flip ? -1 : p;
-            ctl->cbar_q = cbar_signed;
-            ctl->gamma_q = gamma_q;
-            ctl->pending = 0;
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-        }
+        if (threadIdx.x == 0) ctl_ratio_only(*ctl, q, p, flip, cbar_signed, gamma_q);
         return;
     }
     const int leaving = p >= 0 ? lp.basis[p] : -1;
@@ -1705,22 +1684,7 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
         for (int i = threadIdx.x; i < m; i += blockDim.x) lp.xB[i] -= lp.alpha[i] * ub_q;
         for (int e = lp.col_start[q] + threadIdx.x; e < lp.col_start[q + 1]; e += blockDim.x)
             lp.rhs[lp.row_index[e]] -= ub_q * sgn_q * lp.value[e];
-        if (threadIdx.x == 0) {
-            const int now_flipped = (sgn_q < 0.0) ? 0 : 1;
-            lp.flipped[q] = now_flipped;
-            lp.pos[q] = now_flipped ? -2 : -1;
-            ctl->flip_cost += (now_flipped ? 1.0 : -1.0) * ub_q * lp.cost[q];
-            ctl->q = q;
-            ctl->p = -1;
-            ctl->cbar_q = cbar_signed;
-            ctl->minus_obj -= cbar_signed * ub_q;
-            ctl->iters += 1;
-            ctl->bound_flips += 1;
-            ctl->pending = 0;
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-            ctl->last_selected = q;
-        }
+        if (threadIdx.x == 0) ctl_bound_flip(lp, *ctl, q, sgn_q, ub_q, cbar_signed, ctl->minus_obj, ctl->iters);
         return;
     }
 
@@ -1770,47 +1734,16 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
         }
         total += s_nz_wave[K2_U * K2_NW];
     }
-    if (leaves_at_upper) {  // the leaving variable reached its upper bound: hold it in complemented form from now on
+    if (step.leaves_at_upper) {  // the leaving variable reached its upper bound: hold it in complemented form from now on
         const double sgn_l = leaving_flipped ? -1.0 : 1.0;
         for (int e = lp.col_start[leaving] + threadIdx.x; e < lp.col_start[leaving + 1]; e += blockDim.x)
             lp.rhs[lp.row_index[e]] -= up_p * sgn_l * lp.value[e];
     }
     if (threadIdx.x == 0) {
         lp.basis[p] = q;
-        if (lp.track_touched && lp.eta_cap == 0 && !lp.touched[p]) {  // column p of the inverse stops being a unit vector
-            const int count = ctl->touched_count;
-            lp.touched[p] = 1;
-            lp.tlist[count] = p;
-            ctl->touched_count = count + 1;
-        }
-        lp.pos[q] = p;
-        if (bounded) {
-            int fl = leaving_flipped;
-            if (leaves_at_upper) {
-                fl ^= 1;
-                lp.flipped[leaving] = fl;
-                ctl->flip_cost += (fl ? 1.0 : -1.0) * up_p * lp.cost[leaving];
-            }
-            lp.pos[leaving] = fl ? -2 : -1;
-            lp.xub[p] = ub_q;
-        } else {
-            lp.pos[leaving] = -1;
-        }
-        ctl->q = q;
-        ctl->p = p;
-        ctl->leaving = leaving;
-        ctl->cbar_q = cbar_signed;
-        ctl->alpha_pq = alpha_pq;
-        ctl->gamma_q = gamma_q;
-        ctl->xp = xp;
-        ctl->nz_count = total;
-        ctl->minus_obj -= cbar_signed * xp;
-        ctl->iters += 1;
-        ctl->pending = 1;
+        push_touched(lp, *ctl, p);
+        ctl_basis_change(lp, *ctl, bounded, q, p, leaving, leaving_flipped, step, ub_q, cbar_signed, alpha_pq, gamma_q, total, ctl->minus_obj, ctl->iters);
         ctl->rho_buf ^= 1;  // (the update of this pivot marks the other half of rho_bits)
-        ctl->forced_q = -1;
-        ctl->forced_p = -1;
-        ctl->last_selected = q;
     }
 }
 
@@ -1824,7 +1757,7 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
 //   k2l_apply   every workgroup takes the decision (pivot row, step length, bound flip or pivot) from those candidates,
 //               updates x_B on its rows and writes its piece of the ordered list of touched rows for K3;
 //               workgroup 0 does the O(1) bookkeeping
-// Same rules and tie-breaks as ftran_ratio_kernel (mode 0 only; the fine-grained operations keep that kernel).
+// Rules and bookkeeping: pivot_step.hpp (mode 0 only; the fine-grained operations keep ftran_ratio_kernel).
 // ---------------------------------------------------------------------------------------------------
 constexpr int K2L_THREADS = 1024;
 constexpr int K2L_PD = 8;  // doubles per workgroup in k2_partd: |alpha|^2 sum, pass-1 minimum, candidate key, its alpha, x_B, upper bound
@@ -1867,10 +1800,7 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_ftran_kernel(DeviceLP lp, int
     if (status != ST_RUNNING) return;
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
     if (iters >= budget) {
-        if (publisher) {
-            ctl->status = ST_BUDGET;
-            ctl->pending = 0;
-        }
+        if (publisher) ctl_budget(*ctl);
         return;
     }
     if (forced_q < 0) {
@@ -1924,11 +1854,7 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_ftran_kernel(DeviceLP lp, int
     if (publisher) {
         ctl->q = q;
         ctl->cbar_q = s_cbar;
-        if (q < 0) {
-            ctl->status = ST_NO_ENTERING;
-            ctl->pending = 0;
-            ctl->last_selected = -1;
-        }
+        if (q < 0) ctl_no_entering(*ctl, 0);
     }
     if (q < 0) return;
     const double sgn_q = (bounded && lp.flipped[q]) ? -1.0 : 1.0;
@@ -1981,10 +1907,8 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_ftran_kernel(DeviceLP lp, int
     if (i < m) {
         lp.alpha[i] = a;
         sumsq = a * a;
-        if (!(skip_artificial_rows && bas < lp.n_art)) {
-            if (a > tol_pivot) theta = (fmax(xb, 0.0) + harris_delta) / a;
-            else if (bounded && a < -tol_pivot && up < INFINITY) theta = (fmax(up - xb, 0.0) + harris_delta) / -a;
-        }
+        const RowRoom row = row_room(a, xb, [&] { return up; }, !(skip_artificial_rows && bas < lp.n_art), bounded, tol_pivot);
+        if (row.eligible) theta = harris_pass1(row.room, harris_delta, a);
     }
     sumsq = block_reduce<0>(sumsq, s_red);
     __syncthreads();
@@ -2036,12 +1960,10 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_harris_kernel(DeviceLP lp, in
             c.idx = i;
             c.aux = bas;
         }
-    } else if (i < m && !(skip_artificial_rows && bas < lp.n_art)) {
-        double room = -1.0;
-        if (a > tol_pivot) room = fmax(xb, 0.0);
-        else if (bounded && a < -tol_pivot && up < INFINITY) room = fmax(up - xb, 0.0);
-        if (room >= 0.0 && room / fabs(a) <= theta_max) {
-            c.key = fabs(a);
+    } else if (i < m) {
+        const RowRoom row = row_room(a, xb, [&] { return up; }, !(skip_artificial_rows && bas < lp.n_art), bounded, tol_pivot);
+        if (row.eligible && harris_accepts(row.room, fabs(a), theta_max)) {
+            c.key = harris_key(false, fabs(a));
             c.idx = i;
             c.aux = bas;
         }
@@ -2086,10 +2008,8 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_preselected_kernel(DeviceLP l
     if (i < m) {
         lp.alpha[i] = a;
         sumsq = a * a;
-        if (!(skip_artificial_rows && bas < lp.n_art)) {
-            if (a > tol_pivot) theta = (fmax(xb, 0.0) + harris_delta) / a;
-            else if (bounded && a < -tol_pivot && up < INFINITY) theta = (fmax(up - xb, 0.0) + harris_delta) / -a;
-        }
+        const RowRoom row = row_room(a, xb, [&] { return up; }, !(skip_artificial_rows && bas < lp.n_art), bounded, tol_pivot);
+        if (row.eligible) theta = harris_pass1(row.room, harris_delta, a);
     }
     sumsq = block_reduce<0>(sumsq, s_red);
     __syncthreads();
@@ -2151,10 +2071,12 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_apply_kernel(DeviceLP lp, int
     const double up_p = p >= 0 ? lp.k2_partd[K2L_PD * wb + 5] : INFINITY;
     const int leaving = c.aux;
     const double ub_q = bounded ? lp.ub[q] : INFINITY;
-    const bool leaves_at_upper = bounded && !forced && p >= 0 && alpha_pq < 0.0;
-    const double xp = (forced || !bounded) ? fmax(xb_p, 0.0) / alpha_pq
-                                           : (leaves_at_upper ? fmax(up_p - xb_p, 0.0) : fmax(xb_p, 0.0)) / fabs(alpha_pq);
-    const bool flip = bounded && !forced && ub_q < INFINITY && (p < 0 || ub_q <= xp);
+    // (row p passed the ratio test, or was given: only the sign of alpha_pq says which bound it moves towards)
+    const double room_p = (bounded && alpha_pq < 0.0) ? fmax(up_p - xb_p, 0.0) : fmax(xb_p, 0.0);
+    Step step = step_decision(bounded, forced, p, alpha_pq, xb_p, room_p, ub_q);
+    step.ub_leaving = up_p;  // (the bound itself is at hand here)
+    const double xp = step.xp;
+    const bool flip = step.flip;
     if (p >= 0 || flip) {
         if (flip) {
             if (i < m) lp.xB[i] = xb_i - a * ub_q;
@@ -2175,7 +2097,7 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_apply_kernel(DeviceLP lp, int
         }
     }
     if (blockIdx.x != 0) return;
-    // ---- bookkeeping (workgroup 0): same statements as the tail of ftran_ratio_kernel ----------------------------
+    // ---- bookkeeping (workgroup 0) ---------------------------------------------------------------------------------
     __shared__ int s_toggle;
     __shared__ double s_amount;
     if (threadIdx.x == 0) {
@@ -2183,59 +2105,24 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_apply_kernel(DeviceLP lp, int
         int toggle = -1;
         double amount = 0.0;
         if (p < 0 && !flip) {
-            ctl->status = ST_UNBOUNDED;
-            ctl->p = -1;
-            ctl->pending = 0;
+            ctl_unbounded(*ctl, q, 0);
         } else if (flip) {
-            const int was = lp.flipped[q];
+            const double sgn_q = lp.flipped[q] ? -1.0 : 1.0;
             toggle = q;
-            amount = ub_q * (was ? -1.0 : 1.0);  // rhs -= ub * (signed column)
-            lp.flipped[q] = was ^ 1;
-            lp.pos[q] = (was ^ 1) ? -2 : -1;
-            ctl->flip_cost += ((was ^ 1) ? 1.0 : -1.0) * ub_q * lp.cost[q];
-            ctl->p = -1;
+            amount = ub_q * sgn_q;  // rhs -= ub * (signed column)
+            ctl_bound_flip(lp, *ctl, q, sgn_q, ub_q, cbar_q, ctl->minus_obj, ctl->iters);
             ctl->xp = ub_q;
-            ctl->minus_obj -= cbar_q * ub_q;
-            ctl->iters += 1;
-            ctl->bound_flips += 1;
-            ctl->pending = 0;
-            ctl->last_selected = q;
         } else {
+            const int leaving_flipped = bounded ? lp.flipped[leaving] : 0;
+            if (step.leaves_at_upper) {
+                toggle = leaving;
+                amount = up_p * (leaving_flipped ? -1.0 : 1.0);
+            }
             lp.basis[p] = q;
-            if (lp.track_touched && lp.eta_cap == 0 && !lp.touched[p]) {  // column p of the inverse stops being a unit vector
-                const int count = ctl->touched_count;
-                lp.touched[p] = 1;
-                lp.tlist[count] = p;
-                ctl->touched_count = count + 1;
-            }
-            lp.pos[q] = p;
-            if (bounded) {
-                int fl = lp.flipped[leaving];
-                if (leaves_at_upper) {
-                    toggle = leaving;
-                    amount = up_p * (fl ? -1.0 : 1.0);
-                    fl ^= 1;
-                    lp.flipped[leaving] = fl;
-                    ctl->flip_cost += (fl ? 1.0 : -1.0) * up_p * lp.cost[leaving];
-                }
-                lp.pos[leaving] = fl ? -2 : -1;
-                lp.xub[p] = ub_q;
-            } else {
-                lp.pos[leaving] = -1;
-            }
-            ctl->p = p;
-            ctl->leaving = leaving;
-            ctl->alpha_pq = alpha_pq;
-            ctl->xp = xp;
-            ctl->nz_count = total;
-            ctl->minus_obj -= cbar_q * xp;
-            ctl->iters += 1;
-            ctl->pending = 1;
+            push_touched(lp, *ctl, p);
+            ctl_basis_change(lp, *ctl, bounded, q, p, leaving, leaving_flipped, step, ub_q, cbar_q, alpha_pq, ctl->gamma_q, total, ctl->minus_obj, ctl->iters);
             ctl->rho_buf ^= 1;  // (the update of this pivot marks the other half of rho_bits)
-            ctl->last_selected = q;
         }
-        ctl->forced_q = -1;
-        ctl->forced_p = -1;
         s_toggle = toggle;
         s_amount = amount;
     }
@@ -2248,6 +2135,233 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_apply_kernel(DeviceLP lp, int
     }
 }
 
+constexpr int K2F_THREADS = 512;
+constexpr int K2F_NW = K2F_THREADS / WAVE;
+constexpr int K2F_MAX_BLOCKS = 2048;
+constexpr int K2F_INLINE_BLOCKS = 128;  // candidate columns staged with the candidates when there are at most this many
+
+// ---- The front half that ftran_ratio_fast_kernel<RULE, R> and pivot_fused_kernel<RULE, R> share: 512 threads, thread tid owns the
+// rows tid + r * K2F_THREADS (r < R) and keeps their alpha_i, x_B,i and basis_i in registers.  `T` is the inverse to read.  The order of
+// the floating-point operations is part of the contract (tests/test_gpu_fused.py compares the two kernels' pivots bit for bit).
+struct K2fShared {
+    double akey[K2F_NW];
+    unsigned long long arank[K2F_NW];
+    double red[K2F_NW + 2];
+    double red2[K2F_NW + 2];
+    double cbarv[K2F_MAX_BLOCKS];
+    int crows[K2F_INLINE_BLOCKS * ELL_W];
+    double cvals[K2F_INLINE_BLOCKS * ELL_W];
+    int clen[K2F_INLINE_BLOCKS];
+    int rows[K2_COL_CHUNK];
+    double vals[K2_COL_CHUNK];
+    double bcast[4];  // [0] scratch of the caller | the pivot row's alpha, x_B and room
+    int ibcast[2];    // its basic column
+};
+// The candidates of the pricing workgroups: this thread's best (key, rank), every reduced cost into LDS and -- when there are few
+// enough -- the padded entries of every candidate column, so that the FTRAN starts without another fetch.
+template <int RULE>
+__device__ __forceinline__ void k2f_candidates(const DeviceLP& lp, int n_price_blocks, K2fShared& sm, double& ckey, unsigned long long& crank) {
+    const int tid = threadIdx.x;
+    for (int b = tid; b < n_price_blocks; b += K2F_THREADS) {
+        const int j = lp.cand_j[b];
+        const double k = lp.cand_key[b];
+        sm.cbarv[b] = lp.cand_cbar[b];
+        if (j >= 0) keep_better(k, entering_rank<RULE>(j, b), ckey, crank);
+    }
+    if (n_price_blocks <= K2F_INLINE_BLOCKS) {
+        for (int e = tid; e < n_price_blocks * ELL_W; e += K2F_THREADS) {
+            sm.crows[e] = lp.cand_rows[e];
+            sm.cvals[e] = lp.cand_vals[e];
+        }
+        for (int b = tid; b < n_price_blocks; b += K2F_THREADS) sm.clen[b] = lp.cand_len[b];
+    }
+}
+// The winner among them: q (-1: none), its reduced cost and the pricing workgroup that offered it.
+template <int RULE>
+__device__ __forceinline__ int k2f_entering(double ckey, unsigned long long crank, K2fShared& sm, double& cbar_q, int& winner_block) {
+    block_argbest(ckey, crank, sm.akey, sm.arank);
+    if (crank == RANK_NONE) {
+        cbar_q = 0.0;
+        return -1;
+    }
+    winner_block = entering_block(crank);
+    cbar_q = sm.cbarv[winner_block];
+    return entering_column<RULE>(crank);
+}
+// FTRAN of the winner's padded entries (staged by k2f_candidates); [ca, cb_) becomes what the CSC still has to add -- the rest of
+// a long column, or all of a dense one (len < 0): rare.
+template <int R>
+__device__ __forceinline__ void k2f_ftran_inline(const DeviceLP& lp, const double* T, const K2fShared& sm, int q, int winner_block,
+                                                 double (&al)[R], int& ca, int& cb_) {
+    const int tid = threadIdx.x, m = lp.m, ld = lp.ld;
+    const int len = sm.clen[winner_block];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = tid + r * K2F_THREADS;
+        if (i >= m || len < 0) continue;
+        const double* col = T + i;
+        double t[ELL_W];
+#pragma unroll
+        for (int e = 0; e < ELL_W; ++e) t[e] = col[(size_t)sm.crows[winner_block * ELL_W + e] * ld];  // padding: row 0, value 0
+        double a0 = 0.0;
+#pragma unroll
+        for (int e = 0; e < ELL_W; ++e) a0 += t[e] * sm.cvals[winner_block * ELL_W + e];
+        al[r] = a0;
+    }
+    if (len > ELL_W || len < 0) {
+        ca = lp.col_start[q] + (len < 0 ? 0 : ELL_W);
+        cb_ = lp.col_start[q + 1];
+    }
+}
+// al += T * (entries [ca, cb_) of the CSC), the entries staged through LDS a chunk at a time.  Per row and chunk: four chains over the
+// entries e = 0, 1, 2, 3 (mod 4), leftovers onto the first, (a0 + a1) + (a2 + a3).  Up to eight rows per thread go through the entry
+// loop TOGETHER: 4 R loads in flight per thread instead of 4 (a row at a time, this one-workgroup FTRAN was a chain of round trips:
+// 7 of the 17 us of the fast kernel on GREENBEA); with sixteen that form spills, and the rows go one after the other.
+template <int R>
+__device__ __forceinline__ void k2f_ftran_csc(const DeviceLP& lp, const double* T, K2fShared& sm, int ca, int cb_, double (&al)[R]) {
+    const int tid = threadIdx.x, m = lp.m, ld = lp.ld;
+    for (int c0 = ca; c0 < cb_; c0 += K2_COL_CHUNK) {
+        const int cnt = min(K2_COL_CHUNK, cb_ - c0);
+        __syncthreads();
+        for (int e = tid; e < cnt; e += K2F_THREADS) {
+            sm.rows[e] = lp.row_index[c0 + e];
+            sm.vals[e] = lp.value[c0 + e];
+        }
+        __syncthreads();
+        if constexpr (R <= 8) {
+            double acc[R][4];
+            int row[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = tid + r * K2F_THREADS;
+                row[r] = i < m ? i : 0;  // (rows past m read row 0 and are dropped below)
+                acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
+            }
+            int e = 0;
+            for (; e + 4 <= cnt; e += 4) {
+                const size_t o0 = (size_t)sm.rows[e] * ld, o1 = (size_t)sm.rows[e + 1] * ld, o2 = (size_t)sm.rows[e + 2] * ld, o3 = (size_t)sm.rows[e + 3] * ld;
+                const double v0 = sm.vals[e], v1 = sm.vals[e + 1], v2 = sm.vals[e + 2], v3 = sm.vals[e + 3];
+                double x[R][4];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    x[r][0] = T[o0 + row[r]];
+                    x[r][1] = T[o1 + row[r]];
+                    x[r][2] = T[o2 + row[r]];
+                    x[r][3] = T[o3 + row[r]];
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    acc[r][0] += x[r][0] * v0;
+                    acc[r][1] += x[r][1] * v1;
+                    acc[r][2] += x[r][2] * v2;
+                    acc[r][3] += x[r][3] * v3;
+                }
+            }
+            for (; e < cnt; ++e) {
+                const size_t o = (size_t)sm.rows[e] * ld;
+                const double v = sm.vals[e];
+                double x[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) x[r] = T[o + row[r]];
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[r][0] += x[r] * v;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (tid + r * K2F_THREADS < m) al[r] += (acc[r][0] + acc[r][1]) + (acc[r][2] + acc[r][3]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = tid + r * K2F_THREADS;
+                if (i >= m) continue;
+                const double* col = T + i;
+                double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+                int e = 0;
+                for (; e + 4 <= cnt; e += 4) {
+                    a0 += col[(size_t)sm.rows[e] * ld] * sm.vals[e];
+                    a1 += col[(size_t)sm.rows[e + 1] * ld] * sm.vals[e + 1];
+                    a2 += col[(size_t)sm.rows[e + 2] * ld] * sm.vals[e + 2];
+                    a3 += col[(size_t)sm.rows[e + 3] * ld] * sm.vals[e + 3];
+                }
+                for (; e < cnt; ++e) a0 += col[(size_t)sm.rows[e] * ld] * sm.vals[e];
+                al[r] += (a0 + a1) + (a2 + a3);
+            }
+        }
+    }
+}
+// This thread's share of |alpha_q|^2 and of Harris pass 1, with the eligibility and room of its rows for pass 2 (pivot_step.hpp).
+template <int R>
+__device__ __forceinline__ void k2f_pass1(const DeviceLP& lp, bool bounded, const double (&al)[R], const double (&xb)[R], const int (&bas)[R],
+                                          double tol_pivot, double slack, int skip_artificial_rows, bool (&eligible)[R], double (&room)[R],
+                                          double& sumsq, double& theta) {
+    const int tid = threadIdx.x, m = lp.m;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = tid + r * K2F_THREADS;
+        const double a = al[r];
+        sumsq += a * a;
+        const bool allowed = i < m && !(skip_artificial_rows && bas[r] < lp.n_art);
+        const RowRoom row = row_room(a, xb[r], [&] { return lp.xub[i]; }, allowed, bounded, tol_pivot);
+        eligible[r] = row.eligible;
+        room[r] = row.room;
+        if (row.eligible) theta = fmin(theta, harris_pass1(row.room, slack, a));
+    }
+}
+// gamma_q = 1 + |alpha_q|^2 (pivot_rule.rs:258) and theta_max in ONE combined block reduction.
+__device__ __forceinline__ void k2f_reduce(K2fShared& sm, double sumsq, double theta, double& gamma_q, double& theta_max) {
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    sumsq = wave_sum(sumsq);
+    theta = wave_min(theta);
+    if (lane == LAST) {
+        sm.red[wave] = sumsq;
+        sm.red2[wave] = theta;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        double t1 = lane < K2F_NW ? sm.red[lane] : 0.0;
+        double t2 = lane < K2F_NW ? sm.red2[lane] : INFINITY;
+        t1 = wave_sum(t1);
+        t2 = wave_min(t2);
+        if (lane == LAST) {
+            sm.red[K2F_NW] = t1;
+            sm.red2[K2F_NW] = t2;
+        }
+    }
+    __syncthreads();
+    gamma_q = 1.0 + sm.red[K2F_NW];
+    theta_max = sm.red2[K2F_NW];
+}
+// Harris pass 2: the pivot row, or -1.
+template <int R>
+__device__ __forceinline__ int k2f_pass2(bool textbook, const double (&al)[R], const bool (&eligible)[R], const double (&room)[R],
+                                         const int (&bas)[R], double theta_max, K2fShared& sm) {
+    double hkey = 0.0;
+    unsigned long long hrank = RANK_NONE;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const double mag = fabs(al[r]);
+        if (eligible[r] && harris_accepts(room[r], mag, theta_max))
+            keep_better(harris_key(textbook, mag), leaving_rank(bas[r], threadIdx.x + r * K2F_THREADS), hkey, hrank);
+    }
+    block_argbest(hkey, hrank, sm.akey, sm.arank);
+    return leaving_row(hrank);
+}
+// The pivot row's scalars from the registers of its owner to every thread (sm.bcast[1..3], sm.ibcast[0]).
+template <int R>
+__device__ __forceinline__ void k2f_broadcast_row(int p, const double (&al)[R], const double (&xb)[R], const double (&room)[R],
+                                                  const int (&bas)[R], K2fShared& sm) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if ((int)threadIdx.x + r * K2F_THREADS == p) {
+            sm.bcast[1] = al[r];
+            sm.bcast[2] = xb[r];
+            sm.bcast[3] = room[r];
+            sm.ibcast[0] = bas[r];
+        }
+    }
+    __syncthreads();
+}
+
 // ---------------------------------------------------------------------------------------------------
 // K2, register-resident variant for m <= R*K2F_THREADS (the common case).  Same contract as ftran_ratio_kernel, but
 // the dependent chain of global-memory round trips (~1.2 k cycles each when the data was produced by the previous
@@ -2255,30 +2369,16 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_apply_kernel(DeviceLP lp, int
 // {column entries} -> {inverse columns}.  alpha_i, x_B,i and basis_i of the rows a thread owns stay in registers;
 // scalars are exchanged through LDS.
 // ---------------------------------------------------------------------------------------------------
-constexpr int K2F_THREADS = 512;
-constexpr int K2F_MAX_BLOCKS = 2048;
-constexpr int K2F_INLINE_BLOCKS = 128;  // candidate columns staged with the candidates when there are at most this many
 template <int RULE, int R>
 __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP lp, int n_price_blocks, double tol_pivot,
                                                                      double harris_delta, int skip_artificial_rows,
                                                                      int mode, int n_alpha_slices) {
     // n_alpha_slices > 0: q was chosen by select_kernel and alpha comes from ftran_partial_kernel's slices
-    __shared__ double s_akey[K2F_THREADS / WAVE];
-    __shared__ unsigned long long s_arank[K2F_THREADS / WAVE];
-    __shared__ double s_red[K2F_THREADS / WAVE + 2];
-    __shared__ double s_red2[K2F_THREADS / WAVE + 2];
-    __shared__ double s_cbarv[K2F_MAX_BLOCKS];
-    __shared__ int s_crows[K2F_INLINE_BLOCKS * ELL_W];
-    __shared__ double s_cvals[K2F_INLINE_BLOCKS * ELL_W];
-    __shared__ int s_clen[K2F_INLINE_BLOCKS];
-    __shared__ int s_rows[K2_COL_CHUNK];
-    __shared__ double s_vals[K2_COL_CHUNK];
-    __shared__ double s_bcast[4];
-    __shared__ int s_ibcast[2];
+    __shared__ K2fShared sm;
     Ctl* ctl = lp.ctl;
     STAMP_INIT;
     const int tid = threadIdx.x;
-    const int m = lp.m, ld = lp.ld;
+    const int m = lp.m;
     // ---- round trip 1: everything that does not depend on q -----------------------------------------
     const int status = ctl->status;
     const long long iters = ctl->iters;
@@ -2294,7 +2394,6 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
         xb[r] = i < m ? lp.xB[i] : 0.0;
         bas[r] = i < m ? lp.basis[i] : 0x7fffffff;
     }
-    // candidate of this thread: key, rank = (tie rule on the column index) << 16 | pricing workgroup
     double ckey = 0.0;
     unsigned long long crank = RANK_NONE;
     const bool preselected = n_alpha_slices > 0;
@@ -2307,36 +2406,13 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
         const int i = tid + r * K2F_THREADS;
         ain[r] = (preselected && i < m) ? lp.alpha_in[i] : 0.0;
     }
-    if (!preselected) {  // NOT conditional on forced_q (a value still in flight): that would put these loads a round trip later
-        for (int b = tid; b < n_price_blocks; b += K2F_THREADS) {
-            const int j = lp.cand_j[b];
-            const double k = lp.cand_key[b];
-            s_cbarv[b] = lp.cand_cbar[b];
-            if (j >= 0) {
-                const unsigned long long order = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j;
-                const unsigned long long r = (order << 16) | (unsigned long long)b;
-                if (crank == RANK_NONE || k > ckey || (k == ckey && r < crank)) {
-                    ckey = k;
-                    crank = r;
-                }
-            }
-        }
-        if (n_price_blocks <= K2F_INLINE_BLOCKS) {
-            for (int e = tid; e < n_price_blocks * ELL_W; e += K2F_THREADS) {
-                s_crows[e] = lp.cand_rows[e];
-                s_cvals[e] = lp.cand_vals[e];
-            }
-            for (int b = tid; b < n_price_blocks; b += K2F_THREADS) s_clen[b] = lp.cand_len[b];
-        }
-    }
+    // NOT conditional on forced_q (a value still in flight): that would put these loads a round trip later
+    if (!preselected) k2f_candidates<RULE>(lp, n_price_blocks, sm, ckey, crank);
     const bool inline_column = forced_q < 0 && !preselected && n_price_blocks <= K2F_INLINE_BLOCKS;
     if (status != ST_RUNNING) return;
     STAMP(0);
     if (mode == 0 && iters >= budget) {
-        if (tid == 0) {
-            ctl->status = ST_BUDGET;
-            ctl->pending = 0;
-        }
+        if (tid == 0) ctl_budget(*ctl);
         return;
     }
     // ---- entering column --------------------------------------------------------------------------
@@ -2347,43 +2423,25 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
         q = q_pre;
         cbar_q = cbar_pre;
     } else if (forced_q < 0) {
-        block_argbest(ckey, crank, s_akey, s_arank);
-        if (crank == RANK_NONE) {
-            q = -1;
-            cbar_q = 0.0;
-        } else {
-            winner_block = (int)(crank & 0xffff);
-            const int order = (int)(crank >> 16);
-            q = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? 0x7fffffff - order : order;
-            cbar_q = s_cbarv[winner_block];
-        }
+        q = k2f_entering<RULE>(ckey, crank, sm, cbar_q, winner_block);
     } else {
         q = forced_q;
         if (tid == 0) {
             double cb = lp.cost[forced_q];
             for (int e = lp.col_start[forced_q]; e < lp.col_start[forced_q + 1]; ++e) cb += lp.value[e] * lp.minus_pi[lp.row_index[e]];
-            s_bcast[0] = cb;
+            sm.bcast[0] = cb;
         }
         __syncthreads();
-        cbar_q = s_bcast[0];
+        cbar_q = sm.bcast[0];
         __syncthreads();
     }
     STAMP(1);
     if (q < 0) {
-        if (tid == 0) {
-            if (mode == 0) ctl->status = ST_NO_ENTERING;
-            ctl->q = -1;
-            ctl->pending = 0;
-            if (mode == 0) ctl->last_selected = -1;
-        }
+        if (tid == 0) ctl_no_entering(*ctl, mode);
         return;
     }
     if (mode == 1) {
-        if (tid == 0) {
-            ctl->q = q;
-            ctl->cbar_q = cbar_q;
-            ctl->pending = 0;
-        }
+        if (tid == 0) ctl_entering_only(*ctl, q, cbar_q);
         return;
     }
     // ---- FTRAN (round trips 2-4) --------------------------------------------------------------------
@@ -2392,25 +2450,7 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
     for (int r = 0; r < R; ++r) al[r] = 0.0;
     int ca = 0, cb_ = 0;
     if (inline_column) {
-        // the padded entries of the winning column arrived with the candidates: FTRAN starts without another fetch
-        const int len = s_clen[winner_block];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int i = tid + r * K2F_THREADS;
-            if (i >= m || len < 0) continue;
-            const double* col = lp.Binv + i;
-            double t[ELL_W];
-#pragma unroll
-            for (int e = 0; e < ELL_W; ++e) t[e] = col[(size_t)s_crows[winner_block * ELL_W + e] * ld];  // padding: row 0, value 0
-            double a0 = 0.0;
-#pragma unroll
-            for (int e = 0; e < ELL_W; ++e) a0 += t[e] * s_cvals[winner_block * ELL_W + e];
-            al[r] = a0;
-        }
-        if (len > ELL_W || len < 0) {  // rare: the rest of a long column (or all of a dense one) from the CSC
-            ca = lp.col_start[q] + (len < 0 ? 0 : ELL_W);
-            cb_ = lp.col_start[q + 1];
-        }
+        k2f_ftran_inline<R>(lp, lp.Binv, sm, q, winner_block, al, ca, cb_);
     } else if (!preselected) {
         ca = lp.col_start[q];
         cb_ = lp.col_start[q + 1];
@@ -2419,88 +2459,9 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
 #pragma unroll
         for (int r = 0; r < R; ++r) al[r] += ain[r];
     }
-    for (int c0 = ca; c0 < cb_; c0 += K2_COL_CHUNK) {
-        const int cnt = min(K2_COL_CHUNK, cb_ - c0);
-        __syncthreads();
-        for (int e = tid; e < cnt; e += K2F_THREADS) {
-            s_rows[e] = lp.row_index[c0 + e];
-            s_vals[e] = lp.value[c0 + e];
-        }
-        __syncthreads();
-        // Per row: four chains over the entries e = 0, 1, 2, 3 (mod 4), leftovers onto the first, (a0 + a1) + (a2 + a3) -- the
-        // arithmetic of pivot_fused_kernel, bit for bit.  The rows of a thread go through the entry loop TOGETHER, up to eight at a
-        // time: 32 loads in flight per thread instead of 4 (a row at a time, this one-workgroup FTRAN was a chain of round trips:
-        // 7 of the 17 us of this kernel on GREENBEA).
-        constexpr int RG = R <= 8 ? R : 1;
-        if constexpr (R <= 8) {
-#pragma unroll
-        for (int r0 = 0; r0 < R; r0 += RG) {
-            double acc[RG][4];
-            int row[RG];
-#pragma unroll
-            for (int r = 0; r < RG; ++r) {
-                const int i = tid + (r0 + r) * K2F_THREADS;
-                row[r] = i < m ? i : 0;  // (rows past m read row 0 and are dropped below)
-                acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
-            }
-            const double* T = lp.Binv;
-            int e = 0;
-            for (; e + 4 <= cnt; e += 4) {
-                const size_t o0 = (size_t)s_rows[e] * ld, o1 = (size_t)s_rows[e + 1] * ld, o2 = (size_t)s_rows[e + 2] * ld, o3 = (size_t)s_rows[e + 3] * ld;
-                const double v0 = s_vals[e], v1 = s_vals[e + 1], v2 = s_vals[e + 2], v3 = s_vals[e + 3];
-                double x[RG][4];
-#pragma unroll
-                for (int r = 0; r < RG; ++r) {
-                    x[r][0] = T[o0 + row[r]];
-                    x[r][1] = T[o1 + row[r]];
-                    x[r][2] = T[o2 + row[r]];
-                    x[r][3] = T[o3 + row[r]];
-                }
-#pragma unroll
-                for (int r = 0; r < RG; ++r) {
-                    acc[r][0] += x[r][0] * v0;
-                    acc[r][1] += x[r][1] * v1;
-                    acc[r][2] += x[r][2] * v2;
-                    acc[r][3] += x[r][3] * v3;
-                }
-            }
-            for (; e < cnt; ++e) {
-                const size_t o = (size_t)s_rows[e] * ld;
-                const double v = s_vals[e];
-                double x[RG];
-#pragma unroll
-                for (int r = 0; r < RG; ++r) x[r] = T[o + row[r]];
-#pragma unroll
-                for (int r = 0; r < RG; ++r) acc[r][0] += x[r] * v;
-            }
-#pragma unroll
-            for (int r = 0; r < RG; ++r)
-                if (tid + (r0 + r) * K2F_THREADS < m) al[r0 + r] += (acc[r][0] + acc[r][1]) + (acc[r][2] + acc[r][3]);
-        }
-        } else {  // (16 rows per thread: the grouped form spills)
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int i = tid + r * K2F_THREADS;
-                if (i >= m) continue;
-                const double* col = lp.Binv + i;
-                double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-                int e = 0;
-                for (; e + 4 <= cnt; e += 4) {
-                    a0 += col[(size_t)s_rows[e] * ld] * s_vals[e];
-                    a1 += col[(size_t)s_rows[e + 1] * ld] * s_vals[e + 1];
-                    a2 += col[(size_t)s_rows[e + 2] * ld] * s_vals[e + 2];
-                    a3 += col[(size_t)s_rows[e + 3] * ld] * s_vals[e + 3];
-                }
-                for (; e < cnt; ++e) a0 += col[(size_t)s_rows[e] * ld] * s_vals[e];
-                al[r] += (a0 + a1) + (a2 + a3);
-            }
-        }
-    }
+    k2f_ftran_csc<R>(lp, lp.Binv, sm, ca, cb_, al);
     STAMP(2);
-    // ---- gamma_q and Harris pass 1, one combined block reduction ----------------------------------------
-    // Implicit upper bounds (lp.ub): a basic variable may also leave at its upper bound -- rows with alpha_i < 0 whose
-    // basic variable has one -- and the entering variable may run into its own bound first (a "bound flip", no basis
-    // change).  Complemented columns enter with the opposite sign.
+    // ---- gamma_q and Harris pass 1 --------------------------------------------------------------------
     const bool bounded = lp.ub != nullptr;
     double sgn_q = 1.0, ub_q = INFINITY;
     if (bounded) {
@@ -2508,110 +2469,35 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
         ub_q = lp.ub[q];
         if (forced_q >= 0) cbar_q *= sgn_q;  // the candidates of the pricing pass carry the sign already
     }
-    // harris_delta < 0 selects the reference's ratio test (tableau/mod.rs:287-313): the exact minimum ratio, ties to the lowest
-    // leaving column (Bland) -- for data on which f64 is exact; the default is the Harris two-pass test f64 needs in general.
-    const bool textbook = harris_delta < 0.0;
-    const double harris_slack = textbook ? 0.0 : harris_delta;
+    const HarrisRule harris = harris_rule(harris_delta);
+#pragma unroll
+    for (int r = 0; r < R; ++r) al[r] *= sgn_q;  // a complemented column enters with the opposite sign
     double sumsq = 0.0, theta = INFINITY;
     bool eligible[R];
-    double room[R];  // distance of the basic variable to the bound it moves towards
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = tid + r * K2F_THREADS;
-        al[r] *= sgn_q;
-        const double a = al[r];
-        sumsq += a * a;
-        const bool allowed = i < m && !(skip_artificial_rows && bas[r] < lp.n_art);
-        room[r] = fmax(xb[r], 0.0);
-        eligible[r] = allowed && a > tol_pivot;
-        if (bounded && allowed && a < -tol_pivot) {
-            const double up = lp.xub[i];
-            if (up < INFINITY) {
-                eligible[r] = true;
-                room[r] = fmax(up - xb[r], 0.0);
-            }
-        }
-        if (eligible[r]) theta = fmin(theta, (room[r] + harris_slack) / fabs(a));
-    }
-    {
-        const int lane = tid & (WAVE - 1), wave = tid / WAVE;
-        sumsq = wave_sum(sumsq);
-        theta = wave_min(theta);
-        if (lane == LAST) {
-            s_red[wave] = sumsq;
-            s_red2[wave] = theta;
-        }
-        __syncthreads();
-        if (wave == 0) {
-            double t1 = lane < K2F_THREADS / WAVE ? s_red[lane] : 0.0;
-            double t2 = lane < K2F_THREADS / WAVE ? s_red2[lane] : INFINITY;
-            t1 = wave_sum(t1);
-            t2 = wave_min(t2);
-            if (lane == LAST) {
-                s_red[K2F_THREADS / WAVE] = t1;
-                s_red2[K2F_THREADS / WAVE] = t2;
-            }
-        }
-        __syncthreads();
-    }
-    const double gamma_q = 1.0 + s_red[K2F_THREADS / WAVE];  // pivot_rule.rs:258
-    const double theta_max = s_red2[K2F_THREADS / WAVE];
+    double room[R];
+    k2f_pass1<R>(lp, bounded, al, xb, bas, tol_pivot, harris.slack, skip_artificial_rows, eligible, room, sumsq, theta);
+    double gamma_q, theta_max;
+    k2f_reduce(sm, sumsq, theta, gamma_q, theta_max);
     STAMP(3);
     // ---- Harris pass 2 ---------------------------------------------------------------------------------
     int p = forced_p;
-    if (forced_p < 0) {
-        // largest eligible pivot, ties by the lowest leaving column (Bland, tableau/mod.rs:295), then the lowest row
-        double hkey = 0.0;
-        unsigned long long hrank = RANK_NONE;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const double mag = fabs(al[r]);
-            const double key = textbook ? 1.0 : mag;
-            if (eligible[r] && room[r] / mag <= theta_max) {
-                const unsigned long long rk = ((unsigned long long)(unsigned)bas[r] << 32) | (unsigned)(tid + r * K2F_THREADS);
-                if (hrank == RANK_NONE || key > hkey || (key == hkey && rk < hrank)) {
-                    hkey = key;
-                    hrank = rk;
-                }
-            }
-        }
-        block_argbest(hkey, hrank, s_akey, s_arank);
-        p = hrank == RANK_NONE ? -1 : (int)(hrank & 0xffffffffu);
-    }
+    if (forced_p < 0) p = k2f_pass2<R>(harris.textbook, al, eligible, room, bas, theta_max, sm);
     STAMP(4);
-    // ---- broadcast the pivot row's scalars (its owner has them in registers) ------------------------------
+    // ---- the pivot row's scalars (defaults for "no row") -------------------------------------------------
     if (tid == 0) {
-        s_bcast[1] = 1.0;
-        s_bcast[2] = 0.0;
-        s_bcast[3] = INFINITY;
-        s_ibcast[0] = -1;
+        sm.bcast[1] = 1.0;
+        sm.bcast[2] = 0.0;
+        sm.bcast[3] = INFINITY;
+        sm.ibcast[0] = -1;
     }
     __syncthreads();
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (tid + r * K2F_THREADS == p) {
-            s_bcast[1] = al[r];
-            s_bcast[2] = xb[r];
-            s_bcast[3] = room[r];
-            s_ibcast[0] = bas[r];
-        }
-    }
-    __syncthreads();
-    const double alpha_pq = s_bcast[1];
-    const int leaving = s_ibcast[0];
-    // step length: to the bound of the leaving variable, or (forced zero-level pivots) as the reference computes it
-    double xp = (forced_p >= 0 || !bounded) ? fmax(s_bcast[2], 0.0) / alpha_pq : s_bcast[3] / fabs(alpha_pq);
-    const bool leaves_at_upper = bounded && forced_p < 0 && p >= 0 && alpha_pq < 0.0;
-    const bool flip = bounded && forced_p < 0 && ub_q < INFINITY && (p < 0 || ub_q <= xp);
-    if (p < 0 && !flip) {
-        if (tid == 0) {
-            if (mode == 0) ctl->status = ST_UNBOUNDED;
-            ctl->q = q;
-            ctl->p = -1;
-            ctl->pending = 0;
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-        }
+    k2f_broadcast_row<R>(p, al, xb, room, bas, sm);
+    const double alpha_pq = sm.bcast[1];
+    const int leaving = sm.ibcast[0];
+    const Step step = step_decision(bounded, forced_p >= 0, p, alpha_pq, sm.bcast[2], sm.bcast[3], ub_q);
+    const double xp = step.xp;
+    if (p < 0 && !step.flip) {
+        if (tid == 0) ctl_unbounded(*ctl, q, mode);
         return;
     }
     if (mode == 2) {
@@ -2620,18 +2506,10 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
             const int i = tid + r * K2F_THREADS;
             if (i < m) lp.alpha[i] = al[r];
         }
-        if (tid == 0) {
-            ctl->q = q;
-            ctl->p = flip ? -1 : p;
-            ctl->cbar_q = cbar_q;
-            ctl->gamma_q = gamma_q;
-            ctl->pending = 0;
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-        }
+        if (tid == 0) ctl_ratio_only(*ctl, q, p, step.flip, cbar_q, gamma_q);
         return;
     }
-    if (flip) {
+    if (step.flip) {
         // ---- bound flip: x_q runs from 0 to ub_q, the basis does not change; x_q is complemented so that it sits at 0 again
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -2640,22 +2518,7 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
         }
         for (int e = lp.col_start[q] + tid; e < lp.col_start[q + 1]; e += K2F_THREADS)
             lp.rhs[lp.row_index[e]] -= ub_q * sgn_q * lp.value[e];
-        if (tid == 0) {
-            const int now_flipped = lp.flipped[q] ^ 1;
-            lp.flipped[q] = now_flipped;
-            lp.pos[q] = now_flipped ? -2 : -1;
-            ctl->flip_cost += (now_flipped ? 1.0 : -1.0) * ub_q * lp.cost[q];
-            ctl->q = q;
-            ctl->p = -1;
-            ctl->cbar_q = cbar_q;
-            ctl->minus_obj = minus_obj - cbar_q * ub_q;
-            ctl->iters = iters + 1;
-            ctl->bound_flips += 1;
-            ctl->pending = 0;  // no basis change: no inverse update, no weight update
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-            ctl->last_selected = q;
-        }
+        if (tid == 0) ctl_bound_flip(lp, *ctl, q, sgn_q, ub_q, cbar_q, minus_obj, iters);
         return;
     }
     // ---- x_B update (carry/mod.rs:295-325) and alpha for K3 ------------------------------------------------
@@ -2713,22 +2576,15 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
     }
     STAMP(5);
     const int leaving_flipped = bounded ? lp.flipped[leaving] : 0;
-    if (leaves_at_upper) {  // the leaving variable reached its upper bound: hold it in complemented form from now on
-        const double ub_l = s_bcast[2] + s_bcast[3];  // x_p + room = its upper bound
+    if (step.leaves_at_upper) {  // the leaving variable reached its upper bound: hold it in complemented form from now on
         const double sgn_l = leaving_flipped ? -1.0 : 1.0;
         for (int e = lp.col_start[leaving] + tid; e < lp.col_start[leaving + 1]; e += K2F_THREADS)
-            lp.rhs[lp.row_index[e]] -= ub_l * sgn_l * lp.value[e];
+            lp.rhs[lp.row_index[e]] -= step.ub_leaving * sgn_l * lp.value[e];
     }
     if (bounded) __syncthreads();  // every thread has read flipped[leaving] before thread 0 rewrites it
     if (tid == 0) {
         lp.basis[p] = q;
-        if (lp.track_touched && lp.eta_cap == 0 && !lp.touched[p]) {  // column p of the inverse stops being a unit vector
-            const int count = ctl->touched_count;
-            lp.touched[p] = 1;
-            lp.tlist[count] = p;
-            ctl->touched_count = count + 1;
-        }
-        lp.pos[q] = p;
+        push_touched(lp, *ctl, p);
         if (lp.eta_cap > 0) {  // deferred product form: row p gets a kept column of M unless it has one; one more version of them
             int is_new = 0;
             if (eta_slot_p < 0) {
@@ -2741,33 +2597,8 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
             ctl->eta_new = is_new;
             ctl->eta_version = ctl->eta_version + 1;
         }
-        if (bounded) {
-            int fl = leaving_flipped;
-            if (leaves_at_upper) {
-                fl ^= 1;
-                lp.flipped[leaving] = fl;
-                ctl->flip_cost += (fl ? 1.0 : -1.0) * (s_bcast[2] + s_bcast[3]) * lp.cost[leaving];
-            }
-            lp.pos[leaving] = fl ? -2 : -1;
-            lp.xub[p] = ub_q;
-        } else {
-            lp.pos[leaving] = -1;
-        }
-        ctl->q = q;
-        ctl->p = p;
-        ctl->leaving = leaving;
-        ctl->cbar_q = cbar_q;
-        ctl->alpha_pq = alpha_pq;
-        ctl->gamma_q = gamma_q;
-        ctl->xp = xp;
-        ctl->nz_count = total;
-        ctl->minus_obj = minus_obj - cbar_q * xp;
-        ctl->iters = iters + 1;
-        ctl->pending = 1;
+        ctl_basis_change(lp, *ctl, bounded, q, p, leaving, leaving_flipped, step, ub_q, cbar_q, alpha_pq, gamma_q, total, minus_obj, iters);
         ctl->rho_buf ^= 1;  // (the update of this pivot marks the other half of rho_bits)
-        ctl->forced_q = -1;
-        ctl->forced_p = -1;
-        ctl->last_selected = q;
     }
     STAMP(6);
 }
@@ -2786,13 +2617,14 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
 //     next pricing pass;
 //   * `begin_batch_kernel` / `commit_kernel` move the canonical arrays into copy 0 and the last copy (and the inverse) back, so
 //     everything outside a batch of pivots sees the canonical arrays only.
-// Same arithmetic in the same order as ftran_ratio_fast_kernel<RULE, R> + update_kernel<true>: the pivot sequence and every
-// number are BIT-IDENTICAL with the three-kernel pivot (tests/test_gpu_fused.py).
+// The front half IS that of ftran_ratio_fast_kernel<RULE, R> (the k2f_* templates above) and the column update keeps the arithmetic
+// of update_kernel<true> in the same order: the pivot sequence and every number are bit-identical with the three-kernel pivot
+// (tests/test_gpu_fused.py).
 // Measured and dropped: one wave per workgroup with all rows in registers (a wave cannot keep enough loads in
 // flight: 25 us), wave-local decisions out of LDS (16 rows and 32 divisions per lane: 14 us), and ONE launch per pivot with
 // every workgroup pricing all columns (360 KB of conflicting LDS gathers per workgroup: 21 us).
 // ---------------------------------------------------------------------------------------------------
-constexpr int KF_THREADS = 512;
+constexpr int KF_THREADS = K2F_THREADS;    // (the k2f_* front half)
 constexpr int KF_NW = KF_THREADS / WAVE;  // waves = columns of the inverse per workgroup
 constexpr int KF_MAX_R = 4;               // rows per thread: 2 up to 1024 rows, 4 up to 2048 (as ftran_ratio_fast_kernel<RULE, R>)
 constexpr int KF_MAX_M = KF_MAX_R * KF_THREADS;
@@ -2802,19 +2634,8 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
     constexpr int R = KF_R;
     constexpr int KF_U = KF_R * KF_THREADS / WAVE;  // rows of a column per lane
     constexpr int KF_M = KF_R * KF_THREADS;
-    __shared__ double s_akey[KF_NW];
-    __shared__ unsigned long long s_arank[KF_NW];
-    __shared__ double s_red[KF_NW + 2];
-    __shared__ double s_red2[KF_NW + 2];
-    __shared__ double s_cbarv[K2F_MAX_BLOCKS];
-    __shared__ int s_crows[K2F_INLINE_BLOCKS * ELL_W];
-    __shared__ double s_cvals[K2F_INLINE_BLOCKS * ELL_W];
-    __shared__ int s_clen[K2F_INLINE_BLOCKS];
-    __shared__ int s_rows[K2_COL_CHUNK];
-    __shared__ double s_vals[K2_COL_CHUNK];
+    __shared__ K2fShared sm;
     __shared__ double s_alpha[KF_M];
-    __shared__ double s_bcast[4];
-    __shared__ int s_ibcast[2];
     const Ctl* ctl = in.ctl;  // (the two copies are kernel arguments: no dependent load to find them)
     const int tid = threadIdx.x;
     const int lane = tid & (WAVE - 1), wave = tid / WAVE;
@@ -2843,29 +2664,10 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
     }
     double ckey = 0.0;
     unsigned long long crank = RANK_NONE;
-    for (int b = tid; b < n_price_blocks; b += KF_THREADS) {
-        const int j = lp.cand_j[b];
-        const double k = lp.cand_key[b];
-        s_cbarv[b] = lp.cand_cbar[b];
-        if (j >= 0) {
-            const unsigned long long order = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j;
-            const unsigned long long r = (order << 16) | (unsigned long long)b;
-            if (crank == RANK_NONE || k > ckey || (k == ckey && r < crank)) {
-                ckey = k;
-                crank = r;
-            }
-        }
-    }
+    k2f_candidates<RULE>(lp, n_price_blocks, sm, ckey, crank);
     const bool inline_column = n_price_blocks <= K2F_INLINE_BLOCKS;
-    if (inline_column) {
-        for (int e = tid; e < n_price_blocks * ELL_W; e += KF_THREADS) {
-            s_crows[e] = lp.cand_rows[e];
-            s_cvals[e] = lp.cand_vals[e];
-        }
-        for (int b = tid; b < n_price_blocks; b += KF_THREADS) s_clen[b] = lp.cand_len[b];
-    }
-    // workgroup 0 hands the state on when no pivot is made: x_B and the basis unchanged, the control block edited
-    auto hand_on = [&](int new_status, int new_q, bool clear_last) {
+    // workgroup 0 hands the state on when no pivot is made: x_B and the basis unchanged, the control block edited by `verdict`
+    auto hand_on = [&](auto verdict) {
         if (!writer) return;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -2877,37 +2679,29 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
         }
         if (tid == 0) {
             Ctl c = *ctl;  // (read again by one thread: preloading the whole block in round trip 1 was measured slower)
-            if (new_status >= 0) {
-                c.status = new_status;
-                c.pending = 0;
-                c.q = new_q;
-                if (new_status == ST_UNBOUNDED) c.p = -1;
-                if (clear_last) c.last_selected = -1;
-            }
+            verdict(c);
             c.forced_q = -1;
             c.forced_p = -1;
             *out.ctl = c;
         }
     };
     if (status != ST_RUNNING) {
-        hand_on(-1, 0, false);
+        hand_on([](Ctl&) {});
         return;
     }
     FSTAMP(0);
     if (iters >= budget) {
-        hand_on(ST_BUDGET, ctl->q, false);
+        hand_on([](Ctl& c) { ctl_budget(c); });
         return;
     }
     // ---- entering column --------------------------------------------------------------------------
-    block_argbest(ckey, crank, s_akey, s_arank);
-    if (crank == RANK_NONE) {
-        hand_on(ST_NO_ENTERING, -1, true);
+    double cbar_q;
+    int winner_block = 0;
+    const int q = k2f_entering<RULE>(ckey, crank, sm, cbar_q, winner_block);
+    if (q < 0) {
+        hand_on([](Ctl& c) { ctl_no_entering(c, 0); });
         return;
     }
-    const int winner_block = (int)(crank & 0xffff);
-    const int order = (int)(crank >> 16);
-    const int q = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? 0x7fffffff - order : order;
-    const double cbar_q = s_cbarv[winner_block];
     FSTAMP(1);
     // ---- this wave's column of the inverse: issued together with the FTRAN loads (both only needed round trip 1) ---
     const int j_own = blockIdx.x * KF_NW + wave;
@@ -2928,153 +2722,36 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
     for (int r = 0; r < R; ++r) al[r] = 0.0;
     int ca = 0, cb_ = 0;
     if (inline_column) {
-        const int len = s_clen[winner_block];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int i = tid + r * KF_THREADS;
-            if (i >= m || len < 0) continue;
-            const double* col = t_old + i;
-            double t[ELL_W];
-#pragma unroll
-            for (int e = 0; e < ELL_W; ++e) t[e] = col[(size_t)s_crows[winner_block * ELL_W + e] * ld];  // padding: row 0, value 0
-            double a0 = 0.0;
-#pragma unroll
-            for (int e = 0; e < ELL_W; ++e) a0 += t[e] * s_cvals[winner_block * ELL_W + e];
-            al[r] = a0;
-        }
-        if (len > ELL_W || len < 0) {
-            ca = lp.col_start[q] + (len < 0 ? 0 : ELL_W);
-            cb_ = lp.col_start[q + 1];
-        }
+        k2f_ftran_inline<R>(lp, t_old, sm, q, winner_block, al, ca, cb_);
     } else {
         ca = lp.col_start[q];
         cb_ = lp.col_start[q + 1];
     }
-    for (int c0_ = ca; c0_ < cb_; c0_ += K2_COL_CHUNK) {
-        const int cnt = min(K2_COL_CHUNK, cb_ - c0_);
-        __syncthreads();
-        for (int e = tid; e < cnt; e += KF_THREADS) {
-            s_rows[e] = lp.row_index[c0_ + e];
-            s_vals[e] = lp.value[c0_ + e];
-        }
-        __syncthreads();
-        // (the rows of a thread share the entry loop -- 4 R loads in flight -- with the per-row arithmetic of
-        // ftran_ratio_fast_kernel, bit for bit: four chains over e mod 4, leftovers onto the first, (a0 + a1) + (a2 + a3))
-        double acc[R][4];
-        int row[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int i = tid + r * KF_THREADS;
-            row[r] = i < m ? i : 0;  // (rows past m read row 0 and are dropped below)
-            acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
-        }
-        int e = 0;
-        for (; e + 4 <= cnt; e += 4) {
-            const size_t o0 = (size_t)s_rows[e] * ld, o1 = (size_t)s_rows[e + 1] * ld, o2 = (size_t)s_rows[e + 2] * ld, o3 = (size_t)s_rows[e + 3] * ld;
-            const double v0 = s_vals[e], v1 = s_vals[e + 1], v2 = s_vals[e + 2], v3 = s_vals[e + 3];
-            double x[R][4];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                x[r][0] = t_old[o0 + row[r]];
-                x[r][1] = t_old[o1 + row[r]];
-                x[r][2] = t_old[o2 + row[r]];
-                x[r][3] = t_old[o3 + row[r]];
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                acc[r][0] += x[r][0] * v0;
-                acc[r][1] += x[r][1] * v1;
-                acc[r][2] += x[r][2] * v2;
-                acc[r][3] += x[r][3] * v3;
-            }
-        }
-        for (; e < cnt; ++e) {
-            const size_t o_e = (size_t)s_rows[e] * ld;
-            const double v = s_vals[e];
-            double x[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) x[r] = t_old[o_e + row[r]];
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r][0] += x[r] * v;
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            if (tid + r * KF_THREADS < m) al[r] += (acc[r][0] + acc[r][1]) + (acc[r][2] + acc[r][3]);
-    }
+    k2f_ftran_csc<R>(lp, t_old, sm, ca, cb_, al);
     FSTAMP(2);
-    // ---- gamma_q and Harris pass 1, one combined block reduction (see ftran_ratio_fast_kernel) ---------------------
-    const bool textbook = harris_delta < 0.0;
-    const double harris_slack = textbook ? 0.0 : harris_delta;
+    // ---- gamma_q and Harris pass 1 (never bounded here); alpha into LDS for the column updates ---------------------
+    const HarrisRule harris = harris_rule(harris_delta);
     double sumsq = 0.0, theta = INFINITY;
     bool eligible[R];
     double room[R];
+    k2f_pass1<R>(lp, false, al, xb, bas, tol_pivot, harris.slack, skip_artificial_rows, eligible, room, sumsq, theta);
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = tid + r * KF_THREADS;
-        const double a = al[r];
-        sumsq += a * a;
-        const bool allowed = i < m && !(skip_artificial_rows && bas[r] < lp.n_art);
-        room[r] = fmax(xb[r], 0.0);
-        eligible[r] = allowed && a > tol_pivot;
-        if (eligible[r]) theta = fmin(theta, (room[r] + harris_slack) / fabs(a));
-        s_alpha[i] = a;
-    }
-    sumsq = wave_sum(sumsq);
-    theta = wave_min(theta);
-    if (lane == LAST) {
-        s_red[wave] = sumsq;
-        s_red2[wave] = theta;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        double t1 = lane < KF_NW ? s_red[lane] : 0.0;
-        double t2 = lane < KF_NW ? s_red2[lane] : INFINITY;
-        t1 = wave_sum(t1);
-        t2 = wave_min(t2);
-        if (lane == LAST) {
-            s_red[KF_NW] = t1;
-            s_red2[KF_NW] = t2;
-        }
-    }
-    __syncthreads();
-    const double gamma_q = 1.0 + s_red[KF_NW];  // pivot_rule.rs:258
-    const double theta_max = s_red2[KF_NW];
+    for (int r = 0; r < R; ++r) s_alpha[tid + r * KF_THREADS] = al[r];
+    double gamma_q, theta_max;
+    k2f_reduce(sm, sumsq, theta, gamma_q, theta_max);
     FSTAMP(3);
-    // ---- Harris pass 2: largest eligible pivot, ties by the lowest leaving column (Bland), then the lowest row ----------
-    double hkey = 0.0;
-    unsigned long long hrank = RANK_NONE;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const double mag = fabs(al[r]);
-        const double key = textbook ? 1.0 : mag;
-        if (eligible[r] && room[r] / mag <= theta_max) {
-            const unsigned long long rk = ((unsigned long long)(unsigned)bas[r] << 32) | (unsigned)(tid + r * KF_THREADS);
-            if (hrank == RANK_NONE || key > hkey || (key == hkey && rk < hrank)) {
-                hkey = key;
-                hrank = rk;
-            }
-        }
-    }
-    block_argbest(hkey, hrank, s_akey, s_arank);
-    const int p = hrank == RANK_NONE ? -1 : (int)(hrank & 0xffffffffu);
+    // ---- Harris pass 2 ---------------------------------------------------------------------------------
+    const int p = k2f_pass2<R>(harris.textbook, al, eligible, room, bas, theta_max, sm);
     if (p < 0) {
-        hand_on(ST_UNBOUNDED, q, false);
+        hand_on([q](Ctl& c) { ctl_unbounded(c, q, 0); });
         return;
     }
     FSTAMP(4);
-    // ---- the pivot row's scalars (its owner has them in registers) --------------------------------------------
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (tid + r * KF_THREADS == p) {
-            s_bcast[1] = al[r];
-            s_bcast[2] = xb[r];
-            s_ibcast[0] = bas[r];
-        }
-    }
-    __syncthreads();
-    const double alpha_pq = s_bcast[1];
-    const int leaving = s_ibcast[0];
-    const double xp = fmax(s_bcast[2], 0.0) / alpha_pq;
+    k2f_broadcast_row<R>(p, al, xb, room, bas, sm);
+    const double alpha_pq = sm.bcast[1];
+    const int leaving = sm.ibcast[0];
+    const Step step = step_decision(false, false, p, alpha_pq, sm.bcast[2], sm.bcast[3], INFINITY);
+    const double xp = step.xp;
     // ---- workgroup 0: x_B update (carry/mod.rs:295-325), basis bookkeeping, control block -----------------------
     if (writer) {
 #pragma unroll
@@ -3087,23 +2764,8 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
             }
         }
         if (tid == 0) {
-            lp.pos[q] = p;
-            lp.pos[leaving] = -1;
             Ctl c = *ctl;  // (read again by one thread: preloading the whole block in round trip 1 was measured slower)
-            c.q = q;
-            c.p = p;
-            c.leaving = leaving;
-            c.cbar_q = cbar_q;
-            c.alpha_pq = alpha_pq;
-            c.gamma_q = gamma_q;
-            c.xp = xp;
-            c.nz_count = 0;
-            c.minus_obj = minus_obj - cbar_q * xp;
-            c.iters = iters + 1;
-            c.pending = 1;
-            c.forced_q = -1;
-            c.forced_p = -1;
-            c.last_selected = q;
+            ctl_basis_change(lp, c, false, q, p, leaving, 0, step, INFINITY, cbar_q, alpha_pq, gamma_q, 0, minus_obj, iters);
             c.t_buf = t_buf ^ 1;
             *out.ctl = c;
         }

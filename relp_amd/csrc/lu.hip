@@ -32,6 +32,7 @@
 #include <string>
 #include <thread>
 
+#include "pivot_step.hpp"
 #include "solver.hpp"
 #include "wave_ops.hpp"
 
@@ -2005,21 +2006,11 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
     for (int b = tid; b < n_price_blocks; b += T) {
         const int j = lp.cand_j[b];
         const double k = lp.cand_key[b];
-        if (j >= 0) {
-            const unsigned long long order = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j;
-            const unsigned long long r = (order << 16) | (unsigned long long)b;
-            if (crank == RANK_NONE || k > ckey || (k == ckey && r < crank)) {
-                ckey = k;
-                crank = r;
-            }
-        }
+        if (j >= 0) keep_better(k, entering_rank<RULE>(j, b), ckey, crank);
     }
     if (status != ST_RUNNING) return;
     if (mode == 0 && iters >= budget) {
-        if (tid == 0) {
-            ctl->status = ST_BUDGET;
-            ctl->pending = 0;
-        }
+        if (tid == 0) ctl_budget(*ctl);
         return;
     }
     // ---- entering column ----------------------------------------------------------------------------------------------
@@ -2031,9 +2022,8 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
             q = -1;
             cbar_q = 0.0;
         } else {
-            const int order = (int)(crank >> 16);
-            q = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? 0x7fffffff - order : order;
-            cbar_q = lp.cand_cbar[(int)(crank & 0xffff)];
+            q = entering_column<RULE>(crank);
+            cbar_q = lp.cand_cbar[entering_block(crank)];
         }
     } else {
         q = forced_q;
@@ -2047,20 +2037,11 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
         __syncthreads();
     }
     if (q < 0) {
-        if (tid == 0) {
-            if (mode == 0) ctl->status = ST_NO_ENTERING;
-            ctl->q = -1;
-            ctl->pending = 0;
-            if (mode == 0) ctl->last_selected = -1;
-        }
+        if (tid == 0) ctl_no_entering(*ctl, mode);
         return;
     }
     if (mode == 1) {
-        if (tid == 0) {
-            ctl->q = q;
-            ctl->cbar_q = cbar_q;
-            ctl->pending = 0;
-        }
+        if (tid == 0) ctl_entering_only(*ctl, q, cbar_q);
         return;
     }
     // ---- FTRAN ------------------------------------------------------------------------------------------------------------
@@ -2131,26 +2112,10 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
     const LuSlot upper_record = INV ? LuSlot{} : lu_load_slot(lu, 2, tid);  // BTRAN's first solve: lands during the ratio test
     if constexpr (INV) inv_upper_cols = lui_load_slot(lu, 2, tid);
     // ---- alpha per basis slot (kept in x1), gamma_q, Harris pass 1 ----------------------------------------------------------
-    // harris_delta < 0: the reference's ratio test (exact minimum, ties to the lowest leaving column; tableau/mod.rs:287-313).
-    // With implicit bounds a basic variable may also leave at its upper bound -- rows with alpha_i < 0 whose basic variable has
-    // one -- and the entering variable may run into its own bound first (a bound flip, no basis change): the rules of
-    // ftran_ratio_fast_kernel (kernels.hip).
-    const bool textbook = harris_delta < 0.0;
-    const double harris_slack = textbook ? 0.0 : harris_delta;
-    // eligibility of row s and the distance of its basic variable to the bound it moves towards
-    auto row_room = [&](int s, double a, double* room) {
-        const bool allowed = !(skip_artificial_rows && lp.basis[s] < lp.n_art);
-        const double xs = lp.xB[s];
-        *room = fmax(xs, 0.0);
-        bool eligible = allowed && a > tol_pivot;
-        if (bounded && allowed && a < -tol_pivot) {
-            const double up = lp.xub[s];
-            if (up < INFINITY) {
-                eligible = true;
-                *room = fmax(up - xs, 0.0);
-            }
-        }
-        return eligible;
+    // (the ratio test, the step decision and the bookkeeping: pivot_step.hpp)
+    const HarrisRule harris = harris_rule(harris_delta);
+    auto row = [&](int s, double a) {
+        return row_room(a, lp.xB[s], [&] { return lp.xub[s]; }, !(skip_artificial_rows && lp.basis[s] < lp.n_art), bounded, tol_pivot);
     };
     double sumsq = 0.0, theta = INFINITY;
     for (int s = tid; s < m; s += T) {
@@ -2158,98 +2123,55 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
         sh.x1[s] = a;
         lp.alpha[s] = a;
         sumsq += a * a;
-        double room;
-        if (row_room(s, a, &room)) theta = fmin(theta, (room + harris_slack) / fabs(a));
+        const RowRoom rr = row(s, a);
+        if (rr.eligible) theta = fmin(theta, harris_pass1(rr.room, harris.slack, a));
     }
     const double gamma_q = 1.0 + block_reduce<0>(sumsq, sh.red);  // pivot_rule.rs:258
     const double theta_max = block_reduce<1>(theta, sh.red + 32);
-    // ---- Harris pass 2: the largest eligible pivot, ties by the lowest leaving column (Bland, tableau/mod.rs:295) -------------
     int p = forced_p;
     if (forced_p < 0) {
         double hkey = 0.0;
         unsigned long long hrank = RANK_NONE;
         for (int s = tid; s < m; s += T) {
             const double a = sh.x1[s];
-            double room;
-            if (!row_room(s, a, &room)) continue;
+            const RowRoom rr = row(s, a);
+            if (!rr.eligible) continue;
             const double mag = fabs(a);
-            if (room / mag <= theta_max) {
-                const unsigned long long rk = ((unsigned long long)(unsigned)lp.basis[s] << 32) | (unsigned)s;
-                const double key = textbook ? 1.0 : mag;
-                if (hrank == RANK_NONE || key > hkey || (key == hkey && rk < hrank)) {
-                    hkey = key;
-                    hrank = rk;
-                }
-            }
+            if (harris_accepts(rr.room, mag, theta_max)) keep_better(harris_key(harris.textbook, mag), leaving_rank(lp.basis[s], s), hkey, hrank);
         }
         block_argbest(hkey, hrank, s_akey, s_arank);
-        p = hrank == RANK_NONE ? -1 : (int)(hrank & 0xffffffffu);
+        p = leaving_row(hrank);
     }
     const double alpha_pq = p >= 0 ? sh.x1[p] : 1.0;
-    double room_p = 0.0;
-    if (p >= 0) (void)row_room(p, alpha_pq, &room_p);
-    // step length: to the bound of the leaving variable, or (forced zero-level pivots) as the reference computes it
-    double xp = p < 0 ? INFINITY : ((forced_p >= 0 || !bounded) ? fmax(lp.xB[p], 0.0) / alpha_pq : room_p / fabs(alpha_pq));
-    const bool leaves_at_upper = bounded && forced_p < 0 && p >= 0 && alpha_pq < 0.0;
-    const bool flip = bounded && forced_p < 0 && ub_q < INFINITY && (p < 0 || ub_q <= xp);
-    if (p < 0 && !flip) {
-        if (tid == 0) {
-            if (mode == 0) ctl->status = ST_UNBOUNDED;
-            ctl->q = q;
-            ctl->p = -1;
-            ctl->pending = 0;
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-        }
+    const double xb_p = p >= 0 ? lp.xB[p] : 0.0;
+    const Step step = step_decision(bounded, forced_p >= 0, p, alpha_pq, xb_p, p >= 0 ? row(p, alpha_pq).room : 0.0, ub_q);
+    const double xp = step.xp;
+    if (p < 0 && !step.flip) {
+        if (tid == 0) ctl_unbounded(*ctl, q, mode);
         return;
     }
     lu_stamp(sh, 5);
     if (mode == 2) {
-        if (tid == 0) {
-            ctl->q = q;
-            ctl->p = flip ? -1 : p;
-            ctl->cbar_q = cbar_q;
-            ctl->gamma_q = gamma_q;
-            ctl->pending = 0;
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-        }
+        if (tid == 0) ctl_ratio_only(*ctl, q, p, step.flip, cbar_q, gamma_q);
         return;
     }
-    if (flip) {
+    if (step.flip) {
         // ---- bound flip: x_q runs from 0 to ub_q, the basis does not change; x_q is complemented so that it sits at 0 again ------
         __syncthreads();
         for (int s = tid; s < m; s += T) lp.xB[s] = lp.xB[s] - sh.x1[s] * ub_q;
         for (int e = lp.col_start[q] + tid; e < lp.col_start[q + 1]; e += T) lp.rhs[lp.row_index[e]] -= ub_q * sgn_q * lp.value[e];
-        if (tid == 0) {
-            const int now_flipped = lp.flipped[q] ^ 1;
-            lp.flipped[q] = now_flipped;
-            lp.pos[q] = now_flipped ? -2 : -1;
-            ctl->flip_cost += (now_flipped ? 1.0 : -1.0) * ub_q * lp.cost[q];
-            ctl->q = q;
-            ctl->p = -1;
-            ctl->cbar_q = cbar_q;
-            ctl->minus_obj = minus_obj - cbar_q * ub_q;
-            ctl->iters = iters + 1;
-            ctl->bound_flips += 1;
-            ctl->pending = 0;  // no basis change: no update of the factors, no weight update
-            ctl->forced_q = -1;
-            ctl->forced_p = -1;
-            ctl->last_selected = q;
-        }
+        if (tid == 0) ctl_bound_flip(lp, *ctl, q, sgn_q, ub_q, cbar_q, minus_obj, iters);
         return;
     }
     if (alpha_pq == 0.0) return;  // (a forced pivot on a zero element: the host sees that nothing happened)
     const int leaving = lp.basis[p];
-    const double xb_p = lp.xB[p];
     const int leaving_flipped = bounded ? lp.flipped[leaving] : 0;
     __syncthreads();  // every thread has read basis[p] / xB[p] / flipped[leaving] before they change
     // ---- x_B update (carry/mod.rs:295-325) ------------------------------------------------------------------------------
     for (int s = tid; s < m; s += T) lp.xB[s] = (s == p) ? xp : lp.xB[s] - sh.x1[s] * xp;
-    if (leaves_at_upper) {  // the leaving variable reached its upper bound: it is held in complemented form from now on
-        const double ub_l = xb_p + room_p;
+    if (step.leaves_at_upper) {  // the leaving variable reached its upper bound: it is held in complemented form from now on
         const double sgn_l = leaving_flipped ? -1.0 : 1.0;
-        for (int e = lp.col_start[leaving] + tid; e < lp.col_start[leaving + 1]; e += T) lp.rhs[lp.row_index[e]] -= ub_l * sgn_l * lp.value[e];
+        for (int e = lp.col_start[leaving] + tid; e < lp.col_start[leaving + 1]; e += T) lp.rhs[lp.row_index[e]] -= step.ub_leaving * sgn_l * lp.value[e];
     }
     // ---- BTRAN with two right-hand sides: x0 <- e_p, x1 <- alpha (both per basis slot -> position space) -----------------------
     const int t = lu.colpos[p];
@@ -2430,34 +2352,8 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
     }
     if (tid == 0) {
         lp.basis[p] = q;
-        lp.pos[q] = p;
-        if (bounded) {
-            int fl = leaving_flipped;
-            if (leaves_at_upper) {
-                fl ^= 1;
-                lp.flipped[leaving] = fl;
-                ctl->flip_cost += (fl ? 1.0 : -1.0) * (xb_p + room_p) * lp.cost[leaving];
-            }
-            lp.pos[leaving] = fl ? -2 : -1;
-            lp.xub[p] = ub_q;
-        } else {
-            lp.pos[leaving] = -1;
-        }
-        ctl->q = q;
-        ctl->p = p;
-        ctl->leaving = leaving;
-        ctl->cbar_q = cbar_q;
-        ctl->alpha_pq = alpha_pq;
-        ctl->gamma_q = gamma_q;
-        ctl->xp = xp;
-        ctl->nz_count = 0;
-        ctl->minus_obj = minus_obj - cbar_q * xp;
-        ctl->iters = iters + 1;
-        ctl->pending = 1;
+        ctl_basis_change(lp, *ctl, bounded, q, p, leaving, leaving_flipped, step, ub_q, cbar_q, alpha_pq, gamma_q, 0, minus_obj, iters);
         ctl->rho_buf = rho_buf;
-        ctl->forced_q = -1;
-        ctl->forced_p = -1;
-        ctl->last_selected = q;
         if (refactor) ctl->status = ST_REFACTOR;
     }
     lu_stamp(sh, 12);

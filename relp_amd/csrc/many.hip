@@ -40,6 +40,7 @@
 #include <string>
 #include <vector>
 
+#include "pivot_step.hpp"
 #include "solver.hpp"
 #include "wave_ops.hpp"
 
@@ -317,23 +318,9 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
     };
     // One pricing pass (with the pending steepest-edge update) and, unless `forced_q` >= 0, the entering column; then FTRAN, the
     // ratio test (or the given row) and the basis change.  Returns MANY_PIVOTED / MANY_NO_ENTERING / MANY_UNBOUNDED.
-    // With implicit bounds (ftran_ratio_fast_kernel): a row with alpha_i < 0 whose basic variable has a bound is eligible with the
-    // room to that bound, and the entering variable may reach its own bound first: a bound flip, MANY_PIVOTED without a basis change.
-    // `room`: distance of the basic variable of row i to the bound it moves towards.
-    auto ratio_row = [&](int i, double al, double& room) -> bool {
-        const bool allowed = !(phase == 2 && basis[i] < n_art);
-        bool eligible = al > a.tol_pivot && allowed;
-        room = fmax(xb[i], 0.0);
-        if constexpr (BOUNDED) {
-            if (allowed && al < -a.tol_pivot) {
-                const double up = xub[i];
-                if (up < INFINITY) {
-                    eligible = true;
-                    room = fmax(up - xb[i], 0.0);
-                }
-            }
-        }
-        return eligible;
+    // The ratio test and the step decision are those of pivot_step.hpp; a bound flip is MANY_PIVOTED without a basis change.
+    auto ratio_row = [&](int i, double al) {
+        return row_room(al, xb[i], [&] { return xub[i]; }, !(phase == 2 && basis[i] < n_art), BOUNDED, a.tol_pivot);
     };
     auto pivot = [&](int forced_q, int forced_p) -> int {
         double key = 0.0;
@@ -374,11 +361,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
             if (cbar < -a.tol_dual) {
                 // steepest edge: cbar^2 / gamma, ties to the larger column; Dantzig: -cbar, ties to the smaller one
                 const double k = steepest ? cbar * cbar / g : -cbar;
-                const unsigned long long r = steepest ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j;
-                if (rank == RANK_NONE || k > key || (k == key && r < rank)) {
-                    key = k;
-                    rank = r;
-                }
+                keep_better(k, steepest ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j, key, rank);
             }
         }
         pending = 0;
@@ -404,8 +387,8 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
             if constexpr (BOUNDED) acc *= sgn_q;
             alpha[i] = acc;
             sumsq += acc * acc;
-            double room;
-            if (ratio_row(i, acc, room)) theta = fmin(theta, (room + slack) / fabs(acc));
+            const RowRoom row = ratio_row(i, acc);
+            if (row.eligible) theta = fmin(theta, harris_pass1(row.room, slack, acc));
         }
         gamma_q = 1.0 + block_sum(sumsq);  // pivot_rule.rs:258
         const double theta_max = block_reduce<1>(theta, s_red);
@@ -415,40 +398,24 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         rank = RANK_NONE;
         for (int i = tid; i < m; i += MANY_THREADS) {
             const double al = alpha[i];
-            double room;
-            const bool eligible = ratio_row(i, al, room);
+            const RowRoom row = ratio_row(i, al);
             const double mag = fabs(al);
-            const double k = L.textbook ? 1.0 : mag;
-            if (forced_p >= 0 ? i == forced_p : (eligible && room / mag <= theta_max)) {
-                const unsigned long long r = ((unsigned long long)(unsigned)basis[i] << 32) | (unsigned)i;
-                if (rank == RANK_NONE || k > key || (k == key && r < rank)) {
-                    key = k;
-                    rank = r;
-                }
-            }
+            if (forced_p >= 0 ? i == forced_p : (row.eligible && harris_accepts(row.room, mag, theta_max)))
+                keep_better(harris_key(L.textbook, mag), leaving_rank(basis[i], i), key, rank);
         }
         block_argbest(key, rank, s_akey, s_arank);
-        // step length: to the bound of the leaving variable, or (forced zero-level pivots) as the reference computes it
-        double step = INFINITY, ub_leaving = INFINITY;
+        const int p = leaving_row(rank);
+        const double alpha_p = p >= 0 ? alpha[p] : 1.0;
+        const double xb_p = p >= 0 ? xb[p] : 0.0;
+        const Step step = step_decision(BOUNDED, forced_p >= 0, p, alpha_p, xb_p, p >= 0 ? ratio_row(p, alpha_p).room : 0.0, ub_q);
         if constexpr (BOUNDED) {
-            if (rank != RANK_NONE) {
-                const int row = (int)(rank & 0xffffffffu);
-                double room;
-                ratio_row(row, alpha[row], room);
-                step = forced_p >= 0 ? fmax(xb[row], 0.0) / alpha[row] : room / fabs(alpha[row]);
-                ub_leaving = xb[row] + room;  // (a row that leaves at its upper bound: x_p + room is that bound)
-            }
-            if (forced_p < 0 && ub_q < INFINITY && (rank == RANK_NONE || ub_q <= step)) {
+            if (step.flip) {
                 // bound flip: x_q runs from 0 to u_q and is complemented so that it sits at 0 again; the basis does not change, so
                 // neither the inverse nor -pi nor the weights do
                 __syncthreads();  // (x_B read by every thread)
                 for (int i = tid; i < m; i += MANY_THREADS) xb[i] -= alpha[i] * ub_q;
                 for (int e = cs[q] + tid; e < cs[q + 1]; e += MANY_THREADS) bprime[ri[e]] -= ub_q * sgn_q * va[e];
-                if (tid == 0) {
-                    const int now_flipped = sgn_q < 0.0 ? 0 : 1;
-                    flipped[q] = now_flipped;
-                    pos[q] = now_flipped ? -2 : -1;
-                }
+                if (tid == 0) flip_column(pos, flipped, q, sgn_q);
                 minus_obj -= cbar_q * ub_q;
                 ++pivots[phase - 1];
                 ++bound_flips;
@@ -457,28 +424,25 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
                 return MANY_PIVOTED;
             }
         }
-        if (rank == RANK_NONE) {
+        if (p < 0) {
             entering = q;
             return MANY_UNBOUNDED;
         }
-        const int p = (int)(rank & 0xffffffffu);
-        alpha_pq = alpha[p];
+        alpha_pq = alpha_p;
         if (alpha_pq == 0.0) {
             entering = q;
             return MANY_UNBOUNDED;  // (a forced row whose element vanished: never from the ratio test, which needs alpha > tol_pivot)
         }
         leaving = basis[p];
-        const double xp = BOUNDED ? step : fmax(xb[p], 0.0) / alpha_pq;
-        // the leaving variable reached its upper bound: it is held in complemented form from now on
-        const bool leaves_at_upper = BOUNDED && forced_p < 0 && alpha_pq < 0.0;
+        const double xp = step.xp;
         int leaving_flipped = 0;
         if constexpr (BOUNDED) leaving_flipped = flipped[leaving];
         __syncthreads();  // x_B[p], basis[p] and flipped[leaving] read by every thread
         for (int i = tid; i < m; i += MANY_THREADS) xb[i] = i == p ? xp : xb[i] - alpha[i] * xp;
         if constexpr (BOUNDED)
-            if (leaves_at_upper) {
+            if (step.leaves_at_upper) {  // the leaving variable reached its upper bound: it is held in complemented form from now on
                 const double sgn_l = leaving_flipped ? -1.0 : 1.0;
-                for (int e = cs[leaving] + tid; e < cs[leaving + 1]; e += MANY_THREADS) bprime[ri[e]] -= ub_leaving * sgn_l * va[e];
+                for (int e = cs[leaving] + tid; e < cs[leaving + 1]; e += MANY_THREADS) bprime[ri[e]] -= step.ub_leaving * sgn_l * va[e];
             }
         minus_obj -= cbar_q * xp;
         // rank-one update of B^-1 by columns, with rho_p, w = alpha' B^-1_old and -pi (pivot_fused_kernel)
@@ -500,15 +464,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         }
         if (tid == 0) {
             basis[p] = q;
-            pos[q] = p;
-            if constexpr (BOUNDED) {
-                int fl = leaving_flipped;
-                if (leaves_at_upper) flipped[leaving] = fl ^= 1;
-                pos[leaving] = fl ? -2 : -1;
-                xub[p] = ub_q;
-            } else {
-                pos[leaving] = -1;
-            }
+            exchange_columns(pos, flipped, xub, BOUNDED, q, p, leaving, leaving_flipped, step.leaves_at_upper, ub_q);
         }
         pending = steepest ? 1 : 0;
         ++pivots[phase - 1];
