@@ -22,6 +22,7 @@
 
 #include "kernels.hpp"
 #include "pivot_step.hpp"
+#include "price_step.hpp"
 #include "solver.hpp"
 #include "wave_ops.hpp"
 
@@ -82,8 +83,8 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
         sgn_j = 1.0;
         if (j < col_last) {
             const int pos_j = lp.pos[j];
-            nonbasic = pos_j == -1 || pos_j == -2;  // -3: fixed variable (implicit bounds), never priced
-            sgn_j = pos_j == -2 ? -1.0 : 1.0;
+            nonbasic = column_priced(pos_j);
+            sgn_j = column_sign(pos_j);
             if (LPC != 2) {  // width 2: no column is longer than the padded copy, the CSC is not needed
                 a = lp.col_start[j];
                 b = lp.col_start[j + 1];
@@ -138,10 +139,7 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
     if (status != ST_RUNNING) return;  // uniform: every thread read the same word
     if (USE_LDS) __syncthreads();
 
-    Cand best;
-    best.key = 0.0;
-    best.idx = -1;
-    best.aux = 0;
+    Cand best = no_candidate();
     double best_cbar = 0.0;
     int best_row = 0, best_len = 0;  // this lane's padded entry of the group's best column so far
     double best_val = 0.0;
@@ -213,36 +211,12 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
         if (sub == 0 && nonbasic && (!UNIT || weight_changes || cbar < -tol_dual)) {
             double gam = g_j;
             if (UNIT && RULE == RELP_PIVOT_STEEPEST_EDGE) gam = lp.gamma[j];
-            if (weight_changes) {
-                if (j == leaving) {
-                    gam = gamma_q / (alpha_pq * alpha_pq);  // pivot_rule.rs:294-295
-                } else {
-                    const double sq = d_rho * d_rho;  // pivot_rule.rs:262-288 (Goldfarb-Reid)
-                    gam = gam - 2.0 * d_rho * d_w + sq * gamma_q;
-                    gam = fmax(gam, 1.0 + sq);
-                }
-                lp.gamma[j] = gam;
-            }
-            bool candidate = cbar < -tol_dual;
-            Cand c;
-            c.idx = j;
-            c.aux = 0;
-            c.key = 0.0;
-            if (RULE == RELP_PIVOT_STEEPEST_EDGE) c.key = cbar * cbar / gam;
-            else if (RULE == RELP_PIVOT_DANTZIG) c.key = -cbar;
-            else if (RULE == RELP_PIVOT_FIRST_PROFITABLE) c.key = -(double)j;
-            else {
-                if (last >= 0 && j == last) candidate = false;
-                const long long rank = (last < 0) ? j : (j > last ? (long long)j - last - 1 : (long long)j + lp.n - last);
-                c.key = -(double)rank;
-            }
-            if (candidate) {
-                Cand nb = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? better<TIE_LARGER_IDX>(best, c) : better<TIE_SMALLER_IDX>(best, c);
-                if (nb.idx == j) {
-                    best_cbar = cbar;
-                    improved = 1;
-                }
-                best = nb;
+            if (weight_changes) lp.gamma[j] = gam = weight_after_pivot(gam, d_rho, d_w, gamma_q, alpha_pq, j == leaving);
+            bool candidate;
+            const double key = price_key<RULE>(cbar, tol_dual, gam, j, last, lp.n, candidate);
+            if (candidate && offer_candidate<RULE>(best, key, j)) {
+                best_cbar = cbar;
+                improved = 1;
             }
         }
         improved = __shfl(improved, threadIdx.x & (WAVE - 1) & ~(LPC - 1));  // the group's lane 0 decides
@@ -254,21 +228,13 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
         base += gridDim.x * CPB;
         if (base < col_last) load_column(base + g);
     }
-    Cand blk = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? block_best<TIE_LARGER_IDX>(best, s_cand)
-                                                  : block_best<TIE_SMALLER_IDX>(best, s_cand);
+    const Cand blk = block_best_candidate<RULE>(best, s_cand);
+    const int slot = cand_offset + blockIdx.x;
     int winner = (sub == 0 && blk.idx >= 0 && blk.idx == best.idx) ? 1 : 0;
-    if (winner) {  // the winning thread publishes
-        lp.cand_key[cand_offset + blockIdx.x] = blk.key;
-        lp.cand_j[cand_offset + blockIdx.x] = blk.idx;
-        lp.cand_cbar[cand_offset + blockIdx.x] = best_cbar;
-        lp.cand_len[cand_offset + blockIdx.x] = best_len;
-    }
+    if (winner) publish_candidate(lp, slot, blk.key, blk.idx, best_cbar, best_len);  // the winning thread publishes
     winner = __shfl(winner, threadIdx.x & (WAVE - 1) & ~(LPC - 1));
-    if (winner) {  // its group publishes the column's padded entries
-        lp.cand_rows[(size_t)(cand_offset + blockIdx.x) * ELL_W + sub] = best_row;
-        lp.cand_vals[(size_t)(cand_offset + blockIdx.x) * ELL_W + sub] = best_val;
-    }
-    if (blk.idx < 0 && threadIdx.x == 0) lp.cand_j[cand_offset + blockIdx.x] = -1;
+    if (winner) publish_entry(lp, slot, sub, best_row, best_val);  // its group publishes the column's padded entries
+    if (blk.idx < 0 && threadIdx.x == 0) publish_no_candidate(lp, slot);
 }
 
 constexpr int PRICE_UNIT_ARCS = 4;  // arcs per lane of price_unit_kernel
@@ -341,10 +307,7 @@ __global__ void __launch_bounds__(256) price_unit_kernel(DeviceLP lp, int skip_w
     if (status != ST_RUNNING) return;  // uniform
     if (rho_words && pending) __syncthreads();
     USTAMP(0);
-    Cand best;
-    best.key = 0.0;
-    best.idx = -1;
-    best.aux = 0;
+    Cand best = no_candidate();
     double best_cbar = 0.0;
     int best_ra = 0, best_rb = 0;
     double best_va = 0.0, best_vb = 0.0;
@@ -357,7 +320,7 @@ __global__ void __launch_bounds__(256) price_unit_kernel(DeviceLP lp, int skip_w
         int hit[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            nonbasic[u] = pos[u] == -1 || pos[u] == -2;  // -3: fixed variable (implicit bounds), never priced
+            nonbasic[u] = column_priced(pos[u]);
             const bool has_a = nonbasic[u] && ca[u] != 0x7fffffffu, has_b = nonbasic[u] && cb[u] != 0x7fffffffu;
             ra[u] = ca[u] == 0x7fffffffu ? 0 : (int)(ca[u] & 0x7fffffffu);
             rb[u] = cb[u] == 0x7fffffffu ? 0 : (int)(cb[u] & 0x7fffffffu);
@@ -378,8 +341,7 @@ __global__ void __launch_bounds__(256) price_unit_kernel(DeviceLP lp, int skip_w
         for (int u = 0; u < U; ++u) {
             const int j = base + u * 256 + threadIdx.x;
             const bool has_a = nonbasic[u] && ca[u] != 0x7fffffffu, has_b = nonbasic[u] && cb[u] != 0x7fffffffu;
-            const double sgn = pos[u] == -2 ? -1.0 : 1.0;  // the column is held in complemented form (implicit upper bounds)
-            cbar[u] = sgn * (cost[u] + ((has_a ? va[u] * pa[u] : 0.0) + (has_b ? vb[u] * pb[u] : 0.0)));
+            cbar[u] = column_sign(pos[u]) * (cost[u] + ((has_a ? va[u] * pa[u] : 0.0) + (has_b ? vb[u] * pb[u] : 0.0)));
             d_rho[u] = d_w[u] = 0.0;
             if (hit[u]) {  // (rare: the columns with an entry where rho_p is non-zero)
                 d_rho[u] = (has_a ? va[u] * lp.rho[ra[u]] : 0.0) + (has_b ? vb[u] * lp.rho[rb[u]] : 0.0);
@@ -397,57 +359,27 @@ __global__ void __launch_bounds__(256) price_unit_kernel(DeviceLP lp, int skip_w
             const int j = base + u * 256 + threadIdx.x;
             if (!wanted[u]) continue;
             double g = gam[u];
-            if (weight_changes[u]) {
-                if (j == leaving) {
-                    g = gamma_q / (alpha_pq * alpha_pq);  // pivot_rule.rs:294-295
-                } else {
-                    const double sq = d_rho[u] * d_rho[u];  // pivot_rule.rs:262-288 (Goldfarb-Reid)
-                    g = g - 2.0 * d_rho[u] * d_w[u] + sq * gamma_q;
-                    g = fmax(g, 1.0 + sq);
-                }
-                lp.gamma[j] = g;
-            }
-            bool candidate = cbar[u] < -tol_dual;
-            Cand c;
-            c.idx = j;
-            c.aux = 0;
-            c.key = 0.0;
-            if (RULE == RELP_PIVOT_STEEPEST_EDGE) c.key = cbar[u] * cbar[u] / g;
-            else if (RULE == RELP_PIVOT_DANTZIG) c.key = -cbar[u];
-            else if (RULE == RELP_PIVOT_FIRST_PROFITABLE) c.key = -(double)j;
-            else {
-                if (last >= 0 && j == last) candidate = false;
-                const long long rank = (last < 0) ? j : (j > last ? (long long)j - last - 1 : (long long)j + lp.n - last);
-                c.key = -(double)rank;
-            }
-            if (candidate) {
-                const Cand nb = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? better<TIE_LARGER_IDX>(best, c) : better<TIE_SMALLER_IDX>(best, c);
-                if (nb.idx == j) {
-                    best_cbar = cbar[u];
-                    best_ra = ra[u];
-                    best_rb = rb[u];
-                    best_va = va[u];
-                    best_vb = vb[u];
-                }
-                best = nb;
+            if (weight_changes[u]) lp.gamma[j] = g = weight_after_pivot(g, d_rho[u], d_w[u], gamma_q, alpha_pq, j == leaving);
+            bool candidate;
+            const double key = price_key<RULE>(cbar[u], tol_dual, g, j, last, lp.n, candidate);
+            if (candidate && offer_candidate<RULE>(best, key, j)) {
+                best_cbar = cbar[u];
+                best_ra = ra[u];
+                best_rb = rb[u];
+                best_va = va[u];
+                best_vb = vb[u];
             }
         }
     }
     USTAMP(4);
-    const Cand blk = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? block_best<TIE_LARGER_IDX>(best, s_cand)
-                                                        : block_best<TIE_SMALLER_IDX>(best, s_cand);
+    const Cand blk = block_best_candidate<RULE>(best, s_cand);
+    const int slot = cand_offset + blockIdx.x;
     if (blk.idx >= 0 && blk.idx == best.idx) {  // the winning thread publishes the candidate and its column's two entries
-        const size_t slot = (size_t)(cand_offset + blockIdx.x);
-        lp.cand_key[slot] = blk.key;
-        lp.cand_j[slot] = blk.idx;
-        lp.cand_cbar[slot] = best_cbar;
-        lp.cand_len[slot] = 2;
-        lp.cand_rows[slot * ELL_W] = best_ra;
-        lp.cand_rows[slot * ELL_W + 1] = best_rb;
-        lp.cand_vals[slot * ELL_W] = best_va;
-        lp.cand_vals[slot * ELL_W + 1] = best_vb;
+        publish_candidate(lp, slot, blk.key, blk.idx, best_cbar, 2);
+        publish_entry(lp, slot, 0, best_ra, best_va);
+        publish_entry(lp, slot, 1, best_rb, best_vb);
     }
-    if (blk.idx < 0 && threadIdx.x == 0) lp.cand_j[cand_offset + blockIdx.x] = -1;
+    if (blk.idx < 0 && threadIdx.x == 0) publish_no_candidate(lp, slot);
     USTAMP(5);
 #ifdef RELP_STAMPS
     if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1) lp.dbg[50] += wall_clock64() - *(volatile unsigned long long*)(lp.dbg + 49);
@@ -496,10 +428,7 @@ __global__ void __launch_bounds__(K1D_THREADS) price_dense_kernel(DeviceLP lp, i
     __syncthreads();
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int waves_total = gridDim.x * (K1D_THREADS / WAVE);
-    Cand best;
-    best.key = 0.0;
-    best.idx = -1;
-    best.aux = 0;
+    Cand best = no_candidate();
     double best_cbar = 0.0;
     const int half = mp / 2;
     auto finish_column = [&](int j, int pos_j, double gamma_j, double cost_j, double d_pi, double d_rho, double d_w) {
@@ -508,26 +437,11 @@ __global__ void __launch_bounds__(K1D_THREADS) price_dense_kernel(DeviceLP lp, i
         d_w = wave_sum(d_w);
         if (lane == LAST) {
             double gam = gamma_j;
-            if (pending) {
-                if (j == leaving) {
-                    gam = gamma_q / (alpha_pq * alpha_pq);
-                } else {
-                    const double sq = d_rho * d_rho;
-                    gam = gam - 2.0 * d_rho * d_w + sq * gamma_q;
-                    gam = fmax(gam, 1.0 + sq);
-                }
-                lp.gamma[j] = gam;
-            }
-            const double cbar = (pos_j == -2 ? -1.0 : 1.0) * (cost_j + d_pi);
-            if (cbar < -tol_dual) {
-                Cand c;
-                c.idx = j;
-                c.aux = 0;
-                c.key = cbar * cbar / gam;
-                Cand nb = better<TIE_LARGER_IDX>(best, c);
-                if (nb.idx == j) best_cbar = cbar;
-                best = nb;
-            }
+            if (pending) lp.gamma[j] = gam = weight_after_pivot(gam, d_rho, d_w, gamma_q, alpha_pq, j == leaving);
+            const double cbar = column_sign(pos_j) * (cost_j + d_pi);
+            bool candidate;
+            const double key = price_key<RELP_PIVOT_STEEPEST_EDGE>(cbar, tol_dual, gam, j, -1, 0, candidate);
+            if (candidate && offer_candidate<RELP_PIVOT_STEEPEST_EDGE>(best, key, j)) best_cbar = cbar;
         }
     };
     if (I8) {
@@ -641,44 +555,15 @@ __global__ void __launch_bounds__(K1D_THREADS) price_dense_kernel(DeviceLP lp, i
                 }
             }
         }
-        d_pi = wave_sum(d_pi);
-        d_rho = wave_sum(d_rho);
-        d_w = wave_sum(d_w);
-        if (lane == LAST) {
-            double gam = gamma_j;
-            if (pending) {
-                if (j == leaving) {
-                    gam = gamma_q / (alpha_pq * alpha_pq);
-                } else {
-                    const double sq = d_rho * d_rho;
-                    gam = gam - 2.0 * d_rho * d_w + sq * gamma_q;
-                    gam = fmax(gam, 1.0 + sq);
-                }
-                lp.gamma[j] = gam;
-            }
-            const double cbar = (pos_j == -2 ? -1.0 : 1.0) * (cost_j + d_pi);
-            if (cbar < -tol_dual) {
-                Cand c;
-                c.idx = j;
-                c.aux = 0;
-                c.key = cbar * cbar / gam;
-                Cand nb = better<TIE_LARGER_IDX>(best, c);
-                if (nb.idx == j) best_cbar = cbar;
-                best = nb;
-            }
-        }
+        finish_column(j, pos_j, gamma_j, cost_j, d_pi, d_rho, d_w);
     }
     if (lane == LAST) s_cbar[wave] = best_cbar;
     best.aux = wave;
     if (lane != LAST) best.idx = -1;
-    Cand blk = block_best<TIE_LARGER_IDX>(best, s_cand);
-    if (threadIdx.x == 0) {
-        lp.cand_j[cand_offset + blockIdx.x] = blk.idx;
-        lp.cand_len[cand_offset + blockIdx.x] = -1;  // column not inlined with the candidate: K2 reads it from the CSC
-        if (blk.idx >= 0) {
-            lp.cand_key[cand_offset + blockIdx.x] = blk.key;
-            lp.cand_cbar[cand_offset + blockIdx.x] = s_cbar[blk.aux];
-        }
+    const Cand blk = block_best_candidate<RELP_PIVOT_STEEPEST_EDGE>(best, s_cand);
+    if (threadIdx.x == 0) {  // (column not inlined with the candidate: K2 reads it from the CSC)
+        if (blk.idx >= 0) publish_candidate(lp, cand_offset + blockIdx.x, blk.key, blk.idx, s_cbar[blk.aux], -1);
+        else publish_no_candidate(lp, cand_offset + blockIdx.x);
     }
 }
 
@@ -843,40 +728,26 @@ __global__ void __launch_bounds__(K1C_MAX_THREADS) price_dense_lane_kernel(Devic
         }
     }
     const double d_pi = sum, d_rho = __shfl(sum, (lane & 15) + 16), d_w = __shfl(sum, (lane & 15) + 32);
-    Cand best;
-    best.key = 0.0;
-    best.idx = -1;
-    best.aux = lane;
+    Cand best = no_candidate(lane);
     double best_cbar = 0.0;
     if (finisher && pos_j < 0) {
         double gam = gamma_j;
-        if (pending) {
-            if (j == leaving) {
-                gam = gamma_q / (alpha_pq * alpha_pq);
-            } else {
-                const double sq = d_rho * d_rho;
-                gam = gam - 2.0 * d_rho * d_w + sq * gamma_q;
-                gam = fmax(gam, 1.0 + sq);
-            }
-            lp.gamma[j] = gam;
-        }
-        const double cbar = (pos_j == -2 ? -1.0 : 1.0) * (cost_j + d_pi);
-        if (cbar < -tol_dual) {
+        if (pending) lp.gamma[j] = gam = weight_after_pivot(gam, d_rho, d_w, gamma_q, alpha_pq, j == leaving);
+        const double cbar = column_sign(pos_j) * (cost_j + d_pi);
+        bool candidate;
+        const double key = price_key<RELP_PIVOT_STEEPEST_EDGE>(cbar, tol_dual, gam, j, -1, 0, candidate);
+        if (candidate) {  // (one column per lane: nothing to offer it against)
             best.idx = j;
-            best.key = cbar * cbar / gam;
+            best.key = key;
             best_cbar = cbar;
         }
     }
     const Cand blk = wave_best<TIE_LARGER_IDX>(best);  // lane 63
     const int winner = __shfl(blk.aux, LAST);
     best_cbar = __shfl(best_cbar, winner);
-    if (lane == LAST) {
-        lp.cand_j[cand_offset + blockIdx.x] = blk.idx;
-        lp.cand_len[cand_offset + blockIdx.x] = -1;  // column not inlined with the candidate: K2 reads it from the CSC
-        if (blk.idx >= 0) {
-            lp.cand_key[cand_offset + blockIdx.x] = blk.key;
-            lp.cand_cbar[cand_offset + blockIdx.x] = best_cbar;
-        }
+    if (lane == LAST) {  // (column not inlined with the candidate: K2 reads it from the CSC)
+        if (blk.idx >= 0) publish_candidate(lp, cand_offset + blockIdx.x, blk.key, blk.idx, best_cbar, -1);
+        else publish_no_candidate(lp, cand_offset + blockIdx.x);
     }
 }
 int dense_lane_slots(int n_dense) { return (n_dense + K1C_COLS - 1) / K1C_COLS; }
@@ -892,7 +763,8 @@ __global__ void __launch_bounds__(256) ftran_partial_kernel(DeviceLP lp, int n_s
     __shared__ int s_rows[256];
     __shared__ double s_vals[256];
     __shared__ double s_unit[256];
-    __shared__ Cand s_cand[8];
+    __shared__ double s_akey[256 / WAVE];
+    __shared__ unsigned long long s_arank[256 / WAVE];
     Ctl* ctl = lp.ctl;
     // round trip 1: the control block AND this thread's first four candidate slots (they do not depend on it)
     constexpr int PRE = 4;
@@ -912,47 +784,34 @@ __global__ void __launch_bounds__(256) ftran_partial_kernel(DeviceLP lp, int n_s
     s_unit[threadIdx.x] = 0.0;
     const bool publisher = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
     if (iters_now >= budget) {
-        if (publisher) {
-            ctl->status = ST_BUDGET;
-            ctl->pending = 0;
-        }
+        if (publisher) ctl_budget(*ctl);
         return;
     }
     if (q >= 0) {
         if (publisher) ctl->q = q;
     } else {
-        Cand c;
-        c.key = 0.0;
-        c.idx = -1;
-        c.aux = 0;
+        const bool steepest = rule == RELP_PIVOT_STEEPEST_EDGE;  // (every other rule breaks ties as Dantzig does)
+        double ckey = 0.0;
+        unsigned long long crank = RANK_NONE;
+        auto offer = [&](double key, int j, int b) {
+            if (steepest) offer_entering<RELP_PIVOT_STEEPEST_EDGE>(key, j, b, ckey, crank);
+            else offer_entering<RELP_PIVOT_DANTZIG>(key, j, b, ckey, crank);
+        };
 #pragma unroll
         for (int u = 0; u < PRE; ++u) {
             const int b = threadIdx.x + u * 256;
-            if (b < n_price_blocks) {
-                Cand o;
-                o.idx = pre_j[u];
-                o.key = o.idx >= 0 ? pre_key[u] : 0.0;
-                o.aux = b;
-                c = (rule == RELP_PIVOT_STEEPEST_EDGE) ? better<TIE_LARGER_IDX>(c, o) : better<TIE_SMALLER_IDX>(c, o);
-            }
+            if (b < n_price_blocks) offer(pre_key[u], pre_j[u], b);
         }
-        for (int b = threadIdx.x + PRE * 256; b < n_price_blocks; b += 256) {
-            Cand o;
-            o.idx = lp.cand_j[b];
-            o.key = o.idx >= 0 ? lp.cand_key[b] : 0.0;
-            o.aux = b;
-            c = (rule == RELP_PIVOT_STEEPEST_EDGE) ? better<TIE_LARGER_IDX>(c, o) : better<TIE_SMALLER_IDX>(c, o);
-        }
-        c = (rule == RELP_PIVOT_STEEPEST_EDGE) ? block_best<TIE_LARGER_IDX>(c, s_cand) : block_best<TIE_SMALLER_IDX>(c, s_cand);
-        q = c.idx;
+        for (int b = threadIdx.x + PRE * 256; b < n_price_blocks; b += 256) offer(lp.cand_key[b], lp.cand_j[b], b);
+        int block = 0;
+        q = steepest ? entering_winner<RELP_PIVOT_STEEPEST_EDGE>(ckey, crank, s_akey, s_arank, block)
+                     : entering_winner<RELP_PIVOT_DANTZIG>(ckey, crank, s_akey, s_arank, block);
         if (publisher) {
-            ctl->q = q;
             if (q >= 0) {
-                ctl->cbar_q = lp.cand_cbar[c.aux];
+                ctl->q = q;
+                ctl->cbar_q = lp.cand_cbar[block];
             } else {
-                ctl->status = ST_NO_ENTERING;
-                ctl->pending = 0;
-                ctl->last_selected = -1;
+                ctl_no_entering(*ctl, 0);
             }
         }
     }
@@ -1156,10 +1015,7 @@ __global__ void __launch_bounds__(BT_THREADS) btran_pass_kernel(DeviceLP lp, dou
     const int leaving = ctl->leaving;
     const int n_touched = ctl->touched_count;
     if (status != ST_RUNNING || !pending_now) return;
-    Cand best;
-    best.key = 0.0;
-    best.idx = -1;
-    best.aux = 0;
+    Cand best = no_candidate();
     double best_cbar = 0.0, best_val = 0.0;
     int best_row = 0;
     // the slack column's own data is fetched BEFORE the column sweep it belongs to (no dependent round trip at the end)
@@ -1181,20 +1037,13 @@ __global__ void __launch_bounds__(BT_THREADS) btran_pass_kernel(DeviceLP lp, dou
     auto slack_fetch = [&](int j) { return slack_data(lp.slack_of_row[j]); };
     auto slack = [&](const SlackData& d, int j, double pi_new, double rho_j, double w_j) {
         const int js = d.js;
-        if (js < 0 || d.pos != -1) return;
+        if (js < 0 || !column_priced(d.pos, false)) return;  // (the slack columns have no upper bounds)
         const double v = d.v;
         const double d_pi = v * pi_new, d_rho = v * rho_j, d_w = v * w_j;
-        double gam = d.gam;
-        if (js == leaving) {
-            gam = gamma_q / (alpha_pq_c * alpha_pq_c);  // pivot_rule.rs:294-295
-        } else {
-            const double sq = d_rho * d_rho;  // pivot_rule.rs:262-288 (Goldfarb-Reid)
-            gam = gam - 2.0 * d_rho * d_w + sq * gamma_q;
-            gam = fmax(gam, 1.0 + sq);
-        }
+        const double gam = weight_after_pivot(d.gam, d_rho, d_w, gamma_q, alpha_pq_c, js == leaving);
         lp.gamma[js] = gam;
         const double cbar = d.cost + d_pi;
-        if (cbar < -tol_dual) {
+        if (cbar < -tol_dual) {  // price_key and offer_candidate for steepest edge, spelled out: through them this kernel spills ten more VGPRs
             Cand c;
             c.idx = js;
             c.aux = 0;
@@ -1377,19 +1226,13 @@ __global__ void __launch_bounds__(BT_THREADS) btran_pass_kernel(DeviceLP lp, dou
         __syncthreads();
     }
     if (price_slacks) {  // this workgroup's best slack column for the next pivot, in price_kernel's candidate format
-        const Cand blk = block_best<TIE_LARGER_IDX>(best, s_cand);
+        const Cand blk = block_best_candidate<RELP_PIVOT_STEEPEST_EDGE>(best, s_cand);
         if (blk.idx >= 0 && blk.idx == best.idx) {
-            lp.cand_key[blockIdx.x] = blk.key;
-            lp.cand_j[blockIdx.x] = blk.idx;
-            lp.cand_cbar[blockIdx.x] = best_cbar;
-            lp.cand_len[blockIdx.x] = 1;
+            publish_candidate(lp, blockIdx.x, blk.key, blk.idx, best_cbar, 1);
 #pragma unroll
-            for (int e = 0; e < ELL_W; ++e) {
-                lp.cand_rows[(size_t)blockIdx.x * ELL_W + e] = e == 0 ? best_row : 0;
-                lp.cand_vals[(size_t)blockIdx.x * ELL_W + e] = e == 0 ? best_val : 0.0;
-            }
+            for (int e = 0; e < ELL_W; ++e) publish_entry(lp, blockIdx.x, e, e == 0 ? best_row : 0, e == 0 ? best_val : 0.0);
         }
-        if (blk.idx < 0 && threadIdx.x == 0) lp.cand_j[blockIdx.x] = -1;
+        if (blk.idx < 0 && threadIdx.x == 0) publish_no_candidate(lp, blockIdx.x);
     }
 }
 
@@ -1512,6 +1355,8 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
                                                                double harris_delta, int skip_artificial_rows, int mode) {
     __shared__ Cand s_cand[18];
     __shared__ double s_red[18];
+    __shared__ double s_akey[K2_THREADS / WAVE];
+    __shared__ unsigned long long s_arank[K2_THREADS / WAVE];
     __shared__ int s_q;
     __shared__ double s_cbar;
     __shared__ int s_rows[K2_COL_CHUNK];
@@ -1529,27 +1374,18 @@ __global__ void __launch_bounds__(K2_THREADS) ftran_ratio_kernel(DeviceLP lp, in
 
     // ---- entering column ------------------------------------------------------------------------
     if (forced_q < 0) {
-        Cand c;
-        c.key = 0.0;
-        c.idx = -1;
-        c.aux = 0;
-        for (int b = threadIdx.x; b < n_price_blocks; b += blockDim.x) {
-            Cand o;
-            o.idx = lp.cand_j[b];
-            o.key = o.idx >= 0 ? lp.cand_key[b] : 0.0;
-            o.aux = b;
-            c = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? better<TIE_LARGER_IDX>(c, o) : better<TIE_SMALLER_IDX>(c, o);
-        }
-        c = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? block_best<TIE_LARGER_IDX>(c, s_cand) : block_best<TIE_SMALLER_IDX>(c, s_cand);
+        double ckey = 0.0;
+        unsigned long long crank = RANK_NONE;
+        fold_candidates<RULE>(lp.cand_j, lp.cand_key, n_price_blocks, threadIdx.x, blockDim.x, ckey, crank);
+        int block = 0;
+        const int winner = entering_winner<RULE>(ckey, crank, s_akey, s_arank, block);
         if (threadIdx.x == 0) {
-            s_q = c.idx;
-            s_cbar = c.idx >= 0 ? lp.cand_cbar[c.aux] : 0.0;
+            s_q = winner;
+            s_cbar = winner >= 0 ? lp.cand_cbar[block] : 0.0;
         }
     } else if (threadIdx.x == 0) {
         s_q = forced_q;
-        double cb = lp.cost[forced_q];
-        for (int e = lp.col_start[forced_q]; e < lp.col_start[forced_q + 1]; ++e) cb += lp.value[e] * lp.minus_pi[lp.row_index[e]];
-        s_cbar = cb;
+        s_cbar = reduced_cost_of(lp.cost[forced_q], lp.col_start, lp.row_index, lp.value, lp.minus_pi, forced_q);  // (signed below)
     }
     __syncthreads();
     const int q = s_q;
@@ -1804,10 +1640,8 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_ftran_kernel(DeviceLP lp, int
         return;
     }
     if (forced_q < 0) {
-        Cand c;
-        c.key = 0.0;
-        c.idx = -1;
-        c.aux = 0;
+        // (stays on Cand and block_best: folded with (key, rank) and block_argbest this kernel measured 14 % slower, 6.7 -> 7.7 us)
+        Cand c = no_candidate();
         for (int b = threadIdx.x; b < n_price_blocks; b += blockDim.x) {
             Cand o;
             o.idx = b == b_mine ? mine_j : lp.cand_j[b];
@@ -1815,19 +1649,20 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_ftran_kernel(DeviceLP lp, int
             o.aux = b;
             c = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? better<TIE_LARGER_IDX>(c, o) : better<TIE_SMALLER_IDX>(c, o);
         }
-        c = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? block_best<TIE_LARGER_IDX>(c, s_cand) : block_best<TIE_SMALLER_IDX>(c, s_cand);
-        if (c.idx < 0) {
+        c = block_best_candidate<RULE>(c, s_cand);
+        const int winner = c.idx, block = c.aux;
+        if (winner < 0) {
             if (threadIdx.x == 0) {
                 s_q = -1;
                 s_cbar = 0.0;
                 s_inline = -1;
                 s_short = 0;
             }
-        } else if (c.aux < (int)blockDim.x) {  // the winner is some thread's preloaded candidate: that thread publishes it
-            if ((int)threadIdx.x == c.aux) {
-                s_q = c.idx;
+        } else if (block < (int)blockDim.x) {  // the winner is some thread's preloaded candidate: that thread publishes it
+            if ((int)threadIdx.x == block) {
+                s_q = winner;
                 s_cbar = mine_cbar;
-                s_inline = (mine_len >= 0 && mine_len <= ELL_W) ? c.aux : -1;
+                s_inline = (mine_len >= 0 && mine_len <= ELL_W) ? block : -1;
                 s_short = mine_len >= 0 && mine_len <= 2;
                 s_rows[0] = mine_row0;
                 s_rows[1] = mine_row1;
@@ -1835,17 +1670,16 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_ftran_kernel(DeviceLP lp, int
                 s_vals[1] = mine_len >= 2 ? mine_val1 : 0.0;
             }
         } else if (threadIdx.x == 0) {  // (more pricing workgroups than threads here: the later ones are read now)
-            s_q = c.idx;
-            s_cbar = lp.cand_cbar[c.aux];
-            s_inline = (lp.cand_len[c.aux] >= 0 && lp.cand_len[c.aux] <= ELL_W) ? c.aux : -1;
+            s_q = winner;
+            s_cbar = lp.cand_cbar[block];
+            s_inline = (lp.cand_len[block] >= 0 && lp.cand_len[block] <= ELL_W) ? block : -1;
             s_short = 0;
         }
     } else if (threadIdx.x == 0) {
         s_inline = -1;
         s_short = 0;
         s_q = forced_q;
-        double cb = lp.cost[forced_q];
-        for (int e = lp.col_start[forced_q]; e < lp.col_start[forced_q + 1]; ++e) cb += lp.value[e] * lp.minus_pi[lp.row_index[e]];
+        double cb = reduced_cost_of(lp.cost[forced_q], lp.col_start, lp.row_index, lp.value, lp.minus_pi, forced_q);
         if (lp.ub && lp.flipped[forced_q]) cb = -cb;
         s_cbar = cb;
     }
@@ -2166,7 +2000,7 @@ __device__ __forceinline__ void k2f_candidates(const DeviceLP& lp, int n_price_b
         const int j = lp.cand_j[b];
         const double k = lp.cand_key[b];
         sm.cbarv[b] = lp.cand_cbar[b];
-        if (j >= 0) keep_better(k, entering_rank<RULE>(j, b), ckey, crank);
+        offer_entering<RULE>(k, j, b, ckey, crank);
     }
     if (n_price_blocks <= K2F_INLINE_BLOCKS) {
         for (int e = tid; e < n_price_blocks * ELL_W; e += K2F_THREADS) {
@@ -2179,14 +2013,9 @@ __device__ __forceinline__ void k2f_candidates(const DeviceLP& lp, int n_price_b
 // The winner among them: q (-1: none), its reduced cost and the pricing workgroup that offered it.
 template <int RULE>
 __device__ __forceinline__ int k2f_entering(double ckey, unsigned long long crank, K2fShared& sm, double& cbar_q, int& winner_block) {
-    block_argbest(ckey, crank, sm.akey, sm.arank);
-    if (crank == RANK_NONE) {
-        cbar_q = 0.0;
-        return -1;
-    }
-    winner_block = entering_block(crank);
-    cbar_q = sm.cbarv[winner_block];
-    return entering_column<RULE>(crank);
+    const int q = entering_winner<RULE>(ckey, crank, sm.akey, sm.arank, winner_block);
+    cbar_q = q >= 0 ? sm.cbarv[winner_block] : 0.0;
+    return q;
 }
 // FTRAN of the winner's padded entries (staged by k2f_candidates); [ca, cb_) becomes what the CSC still has to add -- the rest of
 // a long column, or all of a dense one (len < 0): rare.

@@ -33,6 +33,7 @@
 #include <thread>
 
 #include "pivot_step.hpp"
+#include "price_step.hpp"
 #include "solver.hpp"
 #include "wave_ops.hpp"
 
@@ -2003,10 +2004,10 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
     }
     double ckey = 0.0;
     unsigned long long crank = RANK_NONE;
-    for (int b = tid; b < n_price_blocks; b += T) {
+    for (int b = tid; b < n_price_blocks; b += T) {  // (fold_candidates, spelled out: through the call this kernel spills more)
         const int j = lp.cand_j[b];
         const double k = lp.cand_key[b];
-        if (j >= 0) keep_better(k, entering_rank<RULE>(j, b), ckey, crank);
+        offer_entering<RULE>(k, j, b, ckey, crank);
     }
     if (status != ST_RUNNING) return;
     if (mode == 0 && iters >= budget) {
@@ -2017,21 +2018,12 @@ __global__ void __launch_bounds__(LU_THREADS) lu_pivot_kernel(DeviceLP lp, Devic
     int q;
     double cbar_q;
     if (forced_q < 0) {
-        block_argbest(ckey, crank, s_akey, s_arank);
-        if (crank == RANK_NONE) {
-            q = -1;
-            cbar_q = 0.0;
-        } else {
-            q = entering_column<RULE>(crank);
-            cbar_q = lp.cand_cbar[entering_block(crank)];
-        }
+        int block = 0;
+        q = entering_winner<RULE>(ckey, crank, s_akey, s_arank, block);
+        cbar_q = q >= 0 ? lp.cand_cbar[block] : 0.0;
     } else {
         q = forced_q;
-        if (tid == 0) {
-            double cb = lp.cost[forced_q];
-            for (int e = lp.col_start[forced_q]; e < lp.col_start[forced_q + 1]; ++e) cb += lp.value[e] * lp.minus_pi[lp.row_index[e]];
-            s_bcast[0] = cb;
-        }
+        if (tid == 0) s_bcast[0] = reduced_cost_of(lp.cost[forced_q], lp.col_start, lp.row_index, lp.value, lp.minus_pi, forced_q);
         __syncthreads();
         cbar_q = s_bcast[0];
         __syncthreads();

@@ -182,15 +182,7 @@ __device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, FactorShare
     *total = sh.scan[LUF_WAVES];
     return sh.scan[wave] + incl - v;
 }
-__device__ __forceinline__ int wave_min_i32(int v) {
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, DPP_QUAD_1032, 0xF, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, DPP_QUAD_2301, 0xF, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, DPP_ROW_ROR4, 0xF, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, DPP_ROW_ROR8, 0xF, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, DPP_ROW_BCAST15, 0xA, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, DPP_ROW_BCAST31, 0xC, 0xF, false));
-    return __builtin_amdgcn_readlane(v, WAVE - 1);
-}
+__device__ __forceinline__ int wave_min_lane63(int v) { return __builtin_amdgcn_readlane(wave_min_i32(v), WAVE - 1); }
 __device__ __forceinline__ double wave_max_f64(double v) { return lane63_f64(wave_max(v)); }
 // broadcast of lane `y` (wave-uniform): v_readlane, an SGPR move -- __shfl is a ds_bpermute, an LDS-crossbar round trip
 __device__ __forceinline__ int lane_value(int v, int y) { return __builtin_amdgcn_readlane(v, y); }
@@ -255,7 +247,7 @@ __device__ __forceinline__ void eliminate_row(const LuFactorWork& w, FactorShare
 #pragma unroll
         for (int s = 0; s < SLOTS; ++s)
             if (pk[s] >= 0) mine = min(mine, pk[s]);
-        const int k = wave_min_i32(mine);
+        const int k = wave_min_lane63(mine);
         if (k == 0x7fffffff) break;
         count(4);
         double a = 0.0;
@@ -428,7 +420,7 @@ __device__ __forceinline__ void factor_round(LuFactorWork& w, FactorShared& sh, 
             const unsigned key = w.rowbest[act[t]];
             if (key != NONE32) mine = min(mine, (int)(key >> 20));
         }
-        mine = wave_min_i32(mine);
+        mine = wave_min_lane63(mine);
         if (lane == 0 && mine != 0x7fffffff) atomicMin(&sh.smin, mine);
         __syncthreads();
         const int smin = sh.smin;

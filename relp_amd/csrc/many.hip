@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "pivot_step.hpp"
+#include "price_step.hpp"
 #include "solver.hpp"
 #include "wave_ops.hpp"
 
@@ -327,11 +328,7 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
         unsigned long long rank = RANK_NONE;
         for (int j = n_art + tid; j < n; j += MANY_THREADS) {
             const int pos_j = pos[j];
-            if constexpr (BOUNDED) {
-                if (pos_j != -1 && pos_j != -2) continue;  // (-3: a fixed variable, never priced)
-            } else {
-                if (pos_j != -1) continue;
-            }
+            if (!column_priced(pos_j, BOUNDED)) continue;
             double d_pi = 0.0, d_rho = 0.0, d_w = 0.0;
             for (int e = cs[j]; e < cs[j + 1]; ++e) {
                 const int r = ri[e];
@@ -342,37 +339,30 @@ __global__ void __launch_bounds__(MANY_THREADS) many_kernel(ManyArgs a) {
                     d_w += v * w[r];
                 }
             }
-            double cbar = cost(j) + d_pi;
-            if constexpr (BOUNDED)
-                if (pos_j == -2) cbar = -cbar;  // a complemented column
+            const double cbar = column_sign(pos_j, BOUNDED) * (cost(j) + d_pi);
             double g = 1.0;
             if (steepest) {
                 g = gamma[j];
-                if (pending) {
-                    if (j == leaving) {
-                        g = gamma_q / (alpha_pq * alpha_pq);  // pivot_rule.rs:294-295
-                    } else {
-                        const double sq = d_rho * d_rho;  // pivot_rule.rs:262-288 (Goldfarb-Reid)
-                        g = fmax(g - 2.0 * d_rho * d_w + sq * gamma_q, 1.0 + sq);
-                    }
-                    gamma[j] = g;
-                }
+                if (pending) gamma[j] = g = weight_after_pivot(g, d_rho, d_w, gamma_q, alpha_pq, j == leaving);
             }
-            if (cbar < -a.tol_dual) {
-                // steepest edge: cbar^2 / gamma, ties to the larger column; Dantzig: -cbar, ties to the smaller one
-                const double k = steepest ? cbar * cbar / g : -cbar;
-                keep_better(k, steepest ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j, key, rank);
+            bool candidate;
+            const double k = steepest ? price_key<RELP_PIVOT_STEEPEST_EDGE>(cbar, a.tol_dual, g, j, -1, n, candidate)
+                                      : price_key<RELP_PIVOT_DANTZIG>(cbar, a.tol_dual, g, j, -1, n, candidate);
+            if (candidate) {  // (one workgroup prices every column: slot 0)
+                if (steepest) offer_entering<RELP_PIVOT_STEEPEST_EDGE>(k, j, 0, key, rank);
+                else offer_entering<RELP_PIVOT_DANTZIG>(k, j, 0, key, rank);
             }
         }
         pending = 0;
-        block_argbest(key, rank, s_akey, s_arank);
+        int block = 0;
+        const int winner = steepest ? entering_winner<RELP_PIVOT_STEEPEST_EDGE>(key, rank, s_akey, s_arank, block)
+                                    : entering_winner<RELP_PIVOT_DANTZIG>(key, rank, s_akey, s_arank, block);
         int q = forced_q;
         if (q < 0) {
-            if (rank == RANK_NONE) return MANY_NO_ENTERING;
-            q = steepest ? 0x7fffffff - (int)rank : (int)rank;
+            if (winner < 0) return MANY_NO_ENTERING;
+            q = winner;
         }
-        double cbar_q = cost(q);  // (every thread: the same sum in the same order as the pricing pass)
-        for (int e = cs[q]; e < cs[q + 1]; ++e) cbar_q += va[e] * mpi[ri[e]];
+        double cbar_q = reduced_cost_of(cost(q), cs, ri, va, mpi, q);  // (every thread: the same sum in the same order as the pricing pass)
         double sgn_q = 1.0, ub_q = INFINITY;
         if constexpr (BOUNDED) {
             sgn_q = flipped[q] ? -1.0 : 1.0;

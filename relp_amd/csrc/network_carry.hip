@@ -11,6 +11,7 @@
 // beyond -- the reference's rule at every size, see net_enqueue_pivot), net_update_kernel (rho_p, w = B^-T alpha, the -pi shift: one thread per row walks its root path in the OLD
 // forest) and net_rehang_kernel (the path from the entering endpoint to the leaving arc reversed, one thread).  No array is m x m.
 #include "kernels.hpp"
+#include "price_step.hpp"
 #include "solver.hpp"
 
 #include <algorithm>
@@ -27,7 +28,6 @@ namespace {
 double now_seconds_net() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 constexpr int NET_THREADS = 256;
 constexpr int NET_WAVE = 64;
-constexpr unsigned long long NET_RANK_NONE = ~0ull;
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -37,8 +37,8 @@ constexpr unsigned long long NET_RANK_NONE = ~0ull;
 // ---------------------------------------------------------------------------------------------------
 template <int RULE>
 __global__ void __launch_bounds__(NET_THREADS) net_ftran_kernel(DeviceLP lp, NetTree t, int n_price_blocks, int mode) {
-    __shared__ double s_key[NET_THREADS];
-    __shared__ unsigned long long s_rank[NET_THREADS];
+    __shared__ double s_key[NET_THREADS / NET_WAVE];
+    __shared__ unsigned long long s_rank[NET_THREADS / NET_WAVE];
     Ctl* ctl = lp.ctl;
     const int tid = threadIdx.x, m = lp.m;
     const int status = ctl->status;
@@ -46,63 +46,30 @@ __global__ void __launch_bounds__(NET_THREADS) net_ftran_kernel(DeviceLP lp, Net
     const int forced_q = ctl->forced_q;
     if (status != ST_RUNNING) return;
     if (mode == 0 && iters >= budget) {
-        if (tid == 0) {
-            ctl->status = ST_BUDGET;
-            ctl->pending = 0;
-        }
+        if (tid == 0) ctl_budget(*ctl);
         return;
     }
     const int old_len = t.state[1];
     for (int k = tid; k < old_len; k += NET_THREADS) lp.alpha_in[t.path[k]] = 0.0;
     double key = 0.0;
-    unsigned long long rank = NET_RANK_NONE;
-    if (forced_q < 0)
-        for (int b = tid; b < n_price_blocks; b += NET_THREADS) {
-            const int j = lp.cand_j[b];
-            if (j < 0) continue;
-            const double k = lp.cand_key[b];
-            const unsigned long long order = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j;
-            const unsigned long long r = (order << 16) | (unsigned long long)b;
-            if (rank == NET_RANK_NONE || k > key || (k == key && r < rank)) {
-                key = k;
-                rank = r;
-            }
-        }
-    s_key[tid] = key;
-    s_rank[tid] = rank;
-    __syncthreads();
-    for (int half = NET_THREADS / 2; half > 0; half >>= 1) {
-        if (tid < half) {
-            const double k = s_key[tid + half];
-            const unsigned long long r = s_rank[tid + half];
-            if (r != NET_RANK_NONE && (s_rank[tid] == NET_RANK_NONE || k > s_key[tid] || (k == s_key[tid] && r < s_rank[tid]))) {
-                s_key[tid] = k;
-                s_rank[tid] = r;
-            }
-        }
-        __syncthreads();
-    }
+    unsigned long long rank = RANK_NONE;
+    if (forced_q < 0) fold_candidates<RULE>(lp.cand_j, lp.cand_key, n_price_blocks, tid, NET_THREADS, key, rank);
+    int block = 0;
+    const int winner = entering_winner<RULE>(key, rank, s_key, s_rank, block);
     if (tid != 0) return;
     int q = -1;
     double cbar = 0.0;
     if (forced_q >= 0) {
         q = forced_q;
-        double cb = lp.cost[q];
-        for (int e = lp.col_start[q]; e < lp.col_start[q + 1]; ++e) cb += lp.value[e] * lp.minus_pi[lp.row_index[e]];
+        double cb = reduced_cost_of(lp.cost[q], lp.col_start, lp.row_index, lp.value, lp.minus_pi, q);
         if (lp.ub && lp.flipped[q]) cb = -cb;
         cbar = cb;
-    } else if (s_rank[0] != NET_RANK_NONE) {
-        const int b = (int)(s_rank[0] & 0xffff), order = (int)(s_rank[0] >> 16);
-        q = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? 0x7fffffff - order : order;
-        cbar = lp.cand_cbar[b];
+    } else if (winner >= 0) {
+        q = winner;
+        cbar = lp.cand_cbar[block];
     }
     if (q < 0) {
-        if (mode == 0) {
-            ctl->status = ST_NO_ENTERING;
-            ctl->last_selected = -1;
-        }
-        ctl->q = -1;
-        ctl->pending = 0;
+        ctl_no_entering(*ctl, mode);
         t.state[1] = 0;
         return;
     }

@@ -18,25 +18,13 @@
 
 namespace relp {
 
-// ---- candidates: (key, rank), the larger key wins, ties to the smaller rank -----------------------------------------------------
+// ---- candidates: (key, rank), the larger key wins, ties to the smaller rank (entering columns: price_step.hpp) ------------------
 __device__ __forceinline__ void keep_better(double key, unsigned long long rank, double& best_key, unsigned long long& best_rank) {
     if (best_rank == RANK_NONE || key > best_key || (key == best_key && rank < best_rank)) {
         best_key = key;
         best_rank = rank;
     }
 }
-// entering column j offered by pricing workgroup `block`: steepest edge breaks ties to the larger column, Dantzig to the smaller one
-template <int RULE>
-__device__ __forceinline__ unsigned long long entering_rank(int j, int block) {
-    const unsigned long long order = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? (unsigned long long)(0x7fffffff - j) : (unsigned long long)j;
-    return (order << 16) | (unsigned long long)block;
-}
-template <int RULE>
-__device__ __forceinline__ int entering_column(unsigned long long rank) {
-    const int order = (int)(rank >> 16);
-    return (RULE == RELP_PIVOT_STEEPEST_EDGE) ? 0x7fffffff - order : order;
-}
-__device__ __forceinline__ int entering_block(unsigned long long rank) { return (int)(rank & 0xffff); }
 // leaving row: the lowest basic column, then the lowest row
 __device__ __forceinline__ unsigned long long leaving_rank(int basic_column, int row) {
     return ((unsigned long long)(unsigned)basic_column << 32) | (unsigned)row;

@@ -73,66 +73,41 @@ __device__ __forceinline__ Cand dpp_cand(Cand v) {  // masked-off rows see their
     return o;
 }
 
-// result valid in lane 63
+// The ladder, once: six DPP moves, after which lane 63 holds `op` over the wave's 64 values.  `moved(v)` is v of the lane the step
+// reads from; in the rows a step masks off (the two broadcasts) the lane sees `FILL_SELF ? its own v : neutral` instead.
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_move(double old, double v) { return dpp_f64<CTRL, ROW_MASK>(old, v); }
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_move(int old, int v) { return dpp_i32<CTRL, ROW_MASK>(old, v); }
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ Cand dpp_move(Cand, Cand v) { return dpp_cand<CTRL, ROW_MASK>(v); }
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ unsigned long long dpp_move(unsigned long long old, unsigned long long v) {
+    const int lo = dpp_i32<CTRL, ROW_MASK>((int)(unsigned)old, (int)(unsigned)v);
+    const int hi = dpp_i32<CTRL, ROW_MASK>((int)(unsigned)(old >> 32), (int)(unsigned)(v >> 32));
+    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+template <bool FILL_SELF, class T, class Op>
+__device__ __forceinline__ T wave_ladder(T v, T neutral, Op op) {  // lane 63
+    v = op(v, dpp_move<DPP_QUAD_1032, 0xF>(FILL_SELF ? v : neutral, v));
+    v = op(v, dpp_move<DPP_QUAD_2301, 0xF>(FILL_SELF ? v : neutral, v));
+    v = op(v, dpp_move<DPP_ROW_ROR4, 0xF>(FILL_SELF ? v : neutral, v));
+    v = op(v, dpp_move<DPP_ROW_ROR8, 0xF>(FILL_SELF ? v : neutral, v));
+    v = op(v, dpp_move<DPP_ROW_BCAST15, 0xA>(FILL_SELF ? v : neutral, v));
+    v = op(v, dpp_move<DPP_ROW_BCAST31, 0xC>(FILL_SELF ? v : neutral, v));
+    return v;
+}
 template <int TIE>
-__device__ __forceinline__ Cand wave_best(Cand v) {
-    v = better<TIE>(v, dpp_cand<DPP_QUAD_1032, 0xF>(v));
-    v = better<TIE>(v, dpp_cand<DPP_QUAD_2301, 0xF>(v));
-    v = better<TIE>(v, dpp_cand<DPP_ROW_ROR4, 0xF>(v));
-    v = better<TIE>(v, dpp_cand<DPP_ROW_ROR8, 0xF>(v));
-    v = better<TIE>(v, dpp_cand<DPP_ROW_BCAST15, 0xA>(v));
-    v = better<TIE>(v, dpp_cand<DPP_ROW_BCAST31, 0xC>(v));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {  // lane 63
-    v += dpp_f64<DPP_QUAD_1032, 0xF>(0.0, v);
-    v += dpp_f64<DPP_QUAD_2301, 0xF>(0.0, v);
-    v += dpp_f64<DPP_ROW_ROR4, 0xF>(0.0, v);
-    v += dpp_f64<DPP_ROW_ROR8, 0xF>(0.0, v);
-    v += dpp_f64<DPP_ROW_BCAST15, 0xA>(0.0, v);
-    v += dpp_f64<DPP_ROW_BCAST31, 0xC>(0.0, v);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {  // lane 63
-    v = fmin(v, dpp_f64<DPP_QUAD_1032, 0xF>(v, v));
-    v = fmin(v, dpp_f64<DPP_QUAD_2301, 0xF>(v, v));
-    v = fmin(v, dpp_f64<DPP_ROW_ROR4, 0xF>(v, v));
-    v = fmin(v, dpp_f64<DPP_ROW_ROR8, 0xF>(v, v));
-    v = fmin(v, dpp_f64<DPP_ROW_BCAST15, 0xA>(v, v));
-    v = fmin(v, dpp_f64<DPP_ROW_BCAST31, 0xC>(v, v));
-    return v;
-}
+__device__ __forceinline__ Cand wave_best(Cand v) { return wave_ladder<true>(v, v, [](Cand a, Cand b) { return better<TIE>(a, b); }); }
+__device__ __forceinline__ double wave_sum(double v) { return wave_ladder<false>(v, 0.0, [](double a, double b) { return a + b; }); }
+__device__ __forceinline__ double wave_min(double v) { return wave_ladder<true>(v, v, [](double a, double b) { return fmin(a, b); }); }
 constexpr int LAST = WAVE - 1;
 
 // ---- cheap block-wide arg-max: max of the f64 key, then min of a 64-bit rank among the ties ----------------------
 // A candidate is (key, rank); an empty one has key = -inf.  Two scalar DPP reductions (18 + 30 VALU instructions)
 // replace the struct reduction (about 150), the wave results go through LDS once and EVERY thread scans them, so there is
 // one barrier instead of three.  rank encodes the tie rule (smaller wins) and may carry a payload in its low bits.
-__device__ __forceinline__ double wave_max(double v) {  // lane 63
-    v = fmax(v, dpp_f64<DPP_QUAD_1032, 0xF>(v, v));
-    v = fmax(v, dpp_f64<DPP_QUAD_2301, 0xF>(v, v));
-    v = fmax(v, dpp_f64<DPP_ROW_ROR4, 0xF>(v, v));
-    v = fmax(v, dpp_f64<DPP_ROW_ROR8, 0xF>(v, v));
-    v = fmax(v, dpp_f64<DPP_ROW_BCAST15, 0xA>(v, v));
-    v = fmax(v, dpp_f64<DPP_ROW_BCAST31, 0xC>(v, v));
-    return v;
+__device__ __forceinline__ double wave_max(double v) { return wave_ladder<true>(v, v, [](double a, double b) { return fmax(a, b); }); }
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+    return wave_ladder<true>(v, v, [](unsigned long long a, unsigned long long b) { return a < b ? a : b; });
 }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
-    const int lo = dpp_i32<CTRL, ROW_MASK>((int)(unsigned)v, (int)(unsigned)v);
-    const int hi = dpp_i32<CTRL, ROW_MASK>((int)(unsigned)(v >> 32), (int)(unsigned)(v >> 32));
-    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ unsigned long long umin64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {  // lane 63
-    v = umin64(v, dpp_u64<DPP_QUAD_1032, 0xF>(v));
-    v = umin64(v, dpp_u64<DPP_QUAD_2301, 0xF>(v));
-    v = umin64(v, dpp_u64<DPP_ROW_ROR4, 0xF>(v));
-    v = umin64(v, dpp_u64<DPP_ROW_ROR8, 0xF>(v));
-    v = umin64(v, dpp_u64<DPP_ROW_BCAST15, 0xA>(v));
-    v = umin64(v, dpp_u64<DPP_ROW_BCAST31, 0xC>(v));
-    return v;
-}
+__device__ __forceinline__ int wave_min_i32(int v) { return wave_ladder<true>(v, v, [](int a, int b) { return min(a, b); }); }
 __device__ __forceinline__ double lane63_f64(double v) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
