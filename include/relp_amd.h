@@ -764,6 +764,39 @@ int32_t relp_many_get_bound_flips(const relp_many* many, int32_t model, int64_t*
 const char* relp_many_last_error(const relp_many* many);
 int32_t relp_many_free(relp_many* many);
 
+/* ---- the exact certificate of every LP of the last relp_many_solve in one further launch (relp_amd/csrc/many_certify.hip) ----------
+ * One workgroup per LP inverts the row-scaled integer basis modulo a prime and lifts B x = b and B' y = c_B for a number of p-adic
+ * digits the host fixed beforehand (Hadamard's bound); after one download every LP is finished on the host by the code of the
+ * serial certificate (rational reconstruction, verification by exact substitution, sign checks of x_B and of the reduced costs of
+ * all non-basic columns, exact objective), on at most 16 threads.  An LP the batched stage does not take, or whose batched proof
+ * does not close, goes through the serial certificate of options.certify (its other primes and exact repair pivots included) --
+ * per LP, never for the launch.  relp_many_fallback_reason says why. */
+typedef enum relp_many_fallback_reason {
+    RELP_MANY_FALLBACK_NONE = 0,            /* the batched stage took it */
+    RELP_MANY_FALLBACK_KIND = 1,            /* INFEASIBLE or UNBOUNDED: these certificates stay serial */
+    RELP_MANY_FALLBACK_WIDTH = 2,           /* a scaled coefficient, cost or right-hand side entry does not fit 62 bits, or the 128-bit residual overflowed */
+    RELP_MANY_FALLBACK_SINGULAR_MOD_P = 3,  /* no pivot found modulo the prime */
+    RELP_MANY_FALLBACK_DIGITS = 4,          /* more digits than the cap (512 per solve), or the reconstruction failed its exact verification */
+    RELP_MANY_FALLBACK_SIGN = 5             /* a sign check failed: the basis needs exact repair pivots */
+} relp_many_fallback_reason;
+typedef struct relp_many_certificate {
+    int32_t struct_size;      /* in: sizeof of the caller's header, in element 0 */
+    int32_t certified;        /* the exact certificate holds */
+    int32_t path;             /* 1: the batched stage proved it, 2: the serial certificate did, 0: nothing to prove (status != 0) */
+    int32_t fallback_reason;  /* relp_many_fallback_reason */
+    int32_t digits_primal, digits_dual;  /* p-adic digits of the two solves (0 on path 2) */
+    int64_t repair_pivots;    /* exact repair pivots (serial path only) */
+    double  host_seconds;     /* this LP's host stage */
+} relp_many_certificate;
+/* Proves the results of the last relp_many_solve; out[k]: model k.  mode 0: batched (one launch for all LPs, fallback per LP);
+ * mode 1: every LP by the serial certificate, as options.certify does, reported in the same struct.
+ * *device_seconds: the batched launch (HIP events; 0 in mode 1); *wall_seconds: the whole call.  Afterwards
+ * relp_many_get_objective_exact returns the proved values.  A NULL handle or `out`, a mode other than 0 and 1 or a struct_size no
+ * header ever had is RELP_ERR_ARGUMENT, a call before relp_many_solve RELP_ERR_STATE; both are checked before the device is touched. */
+int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* out, double* device_seconds, double* wall_seconds);
+/* Rows up to which the batched certificate keeps its work matrix in LDS (198); a per-LP slab of global memory beyond, up to 512. */
+int32_t relp_many_certify_lds_rows(void);
+
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);
 

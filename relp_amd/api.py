@@ -136,6 +136,17 @@ class ManyConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("implicit_bounds", C.c_int32)]
 
 
+class ManyCertificate(C.Structure):
+    """``relp_many_certificate``: how model k of a ``Many`` was proved (``Many.certify``)."""
+    _fields_ = [("struct_size", C.c_int32), ("certified", C.c_int32), ("path", C.c_int32), ("fallback_reason", C.c_int32),
+                ("digits_primal", C.c_int32), ("digits_dual", C.c_int32), ("repair_pivots", C.c_int64), ("host_seconds", C.c_double)]
+
+
+# relp_many_fallback_reason
+MANY_FALLBACK_NONE, MANY_FALLBACK_KIND, MANY_FALLBACK_WIDTH, MANY_FALLBACK_SINGULAR_MOD_P, MANY_FALLBACK_DIGITS, MANY_FALLBACK_SIGN = range(6)
+MANY_FALLBACK_NAMES = ["NONE", "KIND", "WIDTH", "SINGULAR_MOD_P", "DIGITS", "SIGN"]
+
+
 class Stats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("price_launches", C.c_int64), ("price_seconds", C.c_double),
                 ("update_seconds", C.c_double), ("ftran_seconds", C.c_double), ("price_bytes", C.c_int64),
@@ -171,6 +182,8 @@ SYMBOLS = [
     "relp_many_dimensions", "relp_many_last_error", "relp_many_free",
     # implicit upper bounds on that path, and the count of bound flips of both paths
     "relp_many_create_with", "relp_many_get_bound_flips", "relp_get_bound_flips",
+    # the exact certificate of every LP of a relp_many launch in one further launch (relp_amd/csrc/many_certify.hip)
+    "relp_many_certify", "relp_many_certify_lds_rows",
 ]
 
 
@@ -186,6 +199,7 @@ def lib():
         _lib.relp_last_error.argtypes = [C.c_void_p]
         _lib.relp_many_last_error.restype = C.c_char_p
         _lib.relp_many_last_error.argtypes = [C.c_void_p]
+        _lib.relp_many_certify.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ManyCertificate), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return _lib
 
 
@@ -806,6 +820,8 @@ class Many:
             self._h = None
             raise RelpError(status, error.value.decode() or "relp_many_create failed")
         self.kernel_seconds = 0.0
+        self.certify_device_seconds = 0.0
+        self.certify_wall_seconds = 0.0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -827,6 +843,18 @@ class Many:
         self._check(lib().relp_many_solve(self._h, results, C.byref(seconds)))
         self.kernel_seconds = seconds.value
         return list(results)
+
+    def certify(self, mode=0):
+        """Proves the results of the last ``solve()``: one ``ManyCertificate`` per model.  ``mode=0``: one further launch for all
+        LPs, the serial certificate for what it does not take; ``mode=1``: every LP by the serial certificate.  Leaves the launch
+        time in ``.certify_device_seconds`` and the time of the call in ``.certify_wall_seconds``; ``objective_exact(i)`` then
+        returns the proved value."""
+        out = (ManyCertificate * len(self.models))()
+        out[0].struct_size = C.sizeof(ManyCertificate)
+        device, wall = C.c_double(), C.c_double()
+        self._check(lib().relp_many_certify(self._h, int(mode), out, C.byref(device), C.byref(wall)))
+        self.certify_device_seconds, self.certify_wall_seconds = device.value, wall.value
+        return list(out)
 
     def _dimensions(self, i):
         rows, structural = C.c_int32(), C.c_int32()

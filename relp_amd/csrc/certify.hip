@@ -26,6 +26,7 @@
 #include <thread>
 
 #include "bigint.hpp"
+#include "certify_parts.hpp"
 #include "rational_reconstruct.hpp"
 #include "lu_host.hpp"
 #include "solver.hpp"
@@ -41,17 +42,6 @@ using i64 = long long;
 // ---------------------------------------------------------------------------------------------------
 // device: Z_p kernels
 // ---------------------------------------------------------------------------------------------------
-// v mod p for v < 2^64; p = 2^31 - 1 (the first trial prime) folds instead of dividing
-__device__ __forceinline__ u32 reduce64(u64 v, u32 p) {
-    if (p == 0x7fffffffu) {
-        v = (v & 0x7fffffffu) + (v >> 31);   // < 2^34
-        v = (v & 0x7fffffffu) + (v >> 31);   // < 2^31 + 8
-        u32 r = (u32)v;
-        return r >= p ? r - p : r;
-    }
-    return (u32)(v % p);
-}
-
 // All m columns of C = B^-1 mod p from the sparse factors P B Q = L U mod p: column j is the solve of e_j, one thread per
 // column; every thread walks the SAME factor entries in the same order (no divergence) and owns column j of the work matrix.
 //   l_* / u_*: strictly triangular parts by rows of the position space; dinv = 1 / diag mod p.
@@ -300,12 +290,6 @@ __global__ void __launch_bounds__(256) dixon_residual_kernel(int m, const int* r
     r[i] = (i64)acc;
 }
 
-// diagnostic timeline (RELP_TIME_CERTIFY=1): where the certificate's wall time goes
-struct CertifyTimes {
-    double device_digits = 0.0, host_assemble = 0.0, inverse = 0.0, setup = 0.0, checks = 0.0, reconstruct = 0.0, parallel = 0.0;
-    double unpack = 0.0, horner = 0.0, combine = 0.0, numerators = 0.0, verify = 0.0, normalise = 0.0;  // parts of host_assemble
-    int digit_launches = 0, solves = 0, reconstructs = 0;
-};
 thread_local CertifyTimes g_times;  // (per host thread: certificates of a batch run concurrently on its worker threads)
 double wall_now() {
     using clock = std::chrono::steady_clock;
@@ -444,18 +428,184 @@ u64 extract_bits(const BigInt& v, size_t lo, int count) {
     return (u64)(window & (((unsigned __int128)1 << count) - 1));
 }
 
-struct IntegerBasis {          // row-scaled integer basis, both orientations
-    int m = 0;
-    std::vector<int> col_start, row_index;   // CSC (columns = basis positions)
-    std::vector<i64> value;
-    std::vector<int> row_start, col_index;   // CSR
-    std::vector<i64> row_value;
-};
+}  // namespace
 
-struct ExactVector {           // numer[i] / denom
-    std::vector<BigInt> numer;
-    BigInt denom = BigInt(1);
-};
+bool dixon_reconstruct(const IntegerBasis& B, const std::vector<i64>& rhs, int transpose, u32 p, const std::vector<const u32*>& digits,
+                       bool parallel, ExactVector* out, CertifyTimes& times) {
+    const int m = B.m;
+    const int steps_done = (int)digits.size();
+    auto run_entries = [&](int n, auto&& fn) {
+        if (parallel) WorkerPool::get(transpose).run(n, fn);
+        else
+            for (int i = 0; i < n; ++i) fn(i);
+    };
+    double t_part = wall_now();
+    auto part = [&](double& sum) {
+        const double now = wall_now();
+        sum += now - t_part;
+        t_part = now;
+    };
+    part(times.unpack);
+    BigInt modulus(1);
+    for (int s = 0; s < steps_done; ++s) modulus.mul_add_small(p, 0);
+    part(times.horner);  // (no Horner pass any more: the numerators are formed from the digits directly, below)
+    bool ok = true;
+    BigInt denom(1);
+    std::vector<BigInt> numer(m);
+    const BigInt half = modulus / BigInt(2);
+    // numer_i = centred(residue_i * denom mod modulus) is the numerator as soon as denom is the common denominator: all
+    // entries in parallel; every entry that is still "large" contributes its own denominator (rational reconstruction,
+    // sequential: there are few), then the pass is repeated with the grown denominator.
+    std::vector<char> small(m);
+    {
+        // A random integer combination of the entries has, almost surely, the common denominator of all of them: ONE
+        // rational reconstruction instead of one per entry that brings a new factor (46 of them on 25FV47).  Whatever it
+        // misses is found by the loop below; every result is verified exactly anyway.
+        // (Formed on the digits: column sums of weight x digit stay below 2^57, one carry sweep in base p, one Horner pass --
+        // no big-integer arithmetic per entry.)
+        std::vector<unsigned long long> column(steps_done, 0);
+        std::vector<uint32_t> weight(m);
+        unsigned long long state = 0x9E3779B97F4A7C15ull;
+        for (int i = 0; i < m; ++i) {
+            state = state * 6364136223846793005ull + 1442695040888963407ull;
+            weight[i] = (uint32_t)(1 + ((state >> 33) & 0xffff));
+        }
+        for (int s = 0; s < steps_done; ++s) {
+            const u32* row = digits[s];
+            unsigned long long sum = 0;
+            for (int i = 0; i < m; ++i) sum += (unsigned long long)weight[i] * row[i];
+            column[s] = sum;
+        }
+        unsigned long long carry = 0;
+        for (int s = 0; s < steps_done; ++s) {  // (what is carried out of the top digit is a multiple of the modulus)
+            const unsigned long long v = column[s] + carry;
+            column[s] = v % p;
+            carry = v / p;
+        }
+        BigInt combo(0);
+        for (int s = steps_done; s-- > 0;) combo.mul_add_small(p, (uint32_t)column[s]);
+        combo.trim();
+        BigInt n, d;
+        const double t_rr = wall_now();
+        const bool found = rational_reconstruct(combo, modulus, n, d, true, p);
+        times.reconstruct += wall_now() - t_rr;
+        times.reconstructs++;
+        if (found && within_wang_bound(d, modulus)) denom = d;
+        else ok = false;  // not enough digits yet
+    }
+    part(times.combine);
+    // First pass: every entry against the denominator of the combination, in parallel.  What is still "large" then has a
+    // factor the combination lost (a small prime that happened to divide its numerator): one reconstruction finds it, the
+    // denominator grows by it, and the entries are multiplied by the factor -- the small ones stay small (no reduction), the
+    // others are reduced again.  denom is the lcm of reduced denominators at every point, so the result is in lowest terms
+    // (gcd(denom, all numerators) = 1: a prime power q^e || denom divides exactly the denominator of some entry, whose
+    // numerator q does not divide) and no gcd pass is needed afterwards.
+    // numer_i = (sum_s digit_s[i] p^s) denom  mod p^K  =  sum_s digit_s[i] W_s  mod p^K   with  W_s = denom p^s mod p^K:  the K
+    // multipliers are made once (each from the last by one small multiplication and a one-word quotient), and an entry is K
+    // multiply-adds of a 31-bit digit into 128-bit accumulators per 64-bit word, one carry sweep and one reduction by a two-word
+    // quotient -- instead of a Horner pass, a 4000 x 2000-bit product and a 6000 / 4000-bit division per entry on 32-bit limbs.
+    if (ok) {
+        typedef unsigned __int128 u128;
+        const int words = (int)((modulus.bits() + 63) / 64);
+        std::vector<u64> table((size_t)steps_done * words, 0);
+        {
+            BigInt w = denom % modulus;
+            for (int s = 0; s < steps_done; ++s) {
+                u64* row = table.data() + (size_t)s * words;
+                for (size_t l = 0; l < w.mag.size(); ++l) row[l / 2] |= (u64)w.mag[l] << (32 * (l % 2));
+                if (s + 1 < steps_done) {
+                    w.mul_add_small(p, 0);
+                    w = w % modulus;
+                }
+            }
+        }
+        run_entries(m, [&](int i) {
+            std::vector<u128> acc(words, 0);
+            for (int s = 0; s < steps_done; ++s) {
+                const u64 d = digits[s][i];
+                if (d == 0) continue;
+                const u64* row = table.data() + (size_t)s * words;
+                for (int l = 0; l < words; ++l) acc[l] += (u128)d * row[l];
+            }
+            BigInt t;
+            t.mag.reserve(2 * words + 4);
+            u128 carry = 0;
+            for (int l = 0; l < words; ++l) {
+                const u128 v = acc[l] + carry;  // (acc < 2^102, carry < 2^64)
+                t.mag.push_back((uint32_t)(u64)v);
+                t.mag.push_back((uint32_t)((u64)v >> 32));
+                carry = v >> 64;
+            }
+            while (carry != 0) {
+                t.mag.push_back((uint32_t)(u64)carry);
+                carry >>= 32;
+            }
+            t.trim();
+            t = t % modulus;
+            if (cmp(t, half) > 0) t = t - modulus;
+            small[i] = within_wang_bound(t, modulus) ? 1 : 0;
+            numer[i] = t;
+        });
+    }
+    if (ok) {
+        BigInt factor(1);  // product of the factors the combination lost
+        auto centred = [&](BigInt t) {
+            t = t % modulus;
+            if (cmp(t, half) > 0) t = t - modulus;
+            else if (t.sign() < 0 && cmp(t.abs(), half) > 0) t = t + modulus;
+            return t;
+        };
+        for (int i = 0; i < m && ok; ++i) {
+            if (small[i]) continue;
+            const BigInt t = centred(numer[i] * factor);
+            if (within_wang_bound(t, modulus)) continue;  // the factors found so far cover it
+            BigInt n, d;
+            const double t_rr = wall_now();
+            const bool found = rational_reconstruct(t, modulus, n, d, true, p);
+            times.reconstruct += wall_now() - t_rr;
+            times.reconstructs++;
+            if (!found || d == BigInt(1)) { ok = false; break; }  // (d = 1 with a large numerator: not enough digits)
+            factor = factor * d;
+            denom = denom * d;
+            if (!within_wang_bound(denom, modulus)) ok = false;
+        }
+        if (ok && !(factor == BigInt(1))) {
+            std::atomic<int> large{0};
+            run_entries(m, [&](int i) {
+                if (numer[i].is_zero()) return;
+                BigInt t = numer[i] * factor;
+                if (!small[i] || !within_wang_bound(t, modulus)) {
+                    t = centred(t);
+                    if (!within_wang_bound(t, modulus)) large.fetch_add(1);
+                }
+                numer[i] = t;
+            });
+            if (large.load() != 0) ok = false;
+        }
+    }
+    part(times.numerators);
+    if (ok) {
+        // exact verification: A numer == denom * rhs
+        std::atomic<int> bad{0};
+        run_entries(m, [&](int i) {
+            BigInt acc(0);
+            if (!transpose)
+                for (int e = B.row_start[i]; e < B.row_start[i + 1]; ++e) acc = acc + BigInt(B.row_value[e]) * numer[B.col_index[e]];
+            else
+                for (int e = B.col_start[i]; e < B.col_start[i + 1]; ++e) acc = acc + BigInt(B.value[e]) * numer[B.row_index[e]];
+            if (!(acc == denom * BigInt(rhs[i]))) bad.fetch_add(1);
+        });
+        if (bad.load() != 0) ok = false;
+    }
+    part(times.verify);
+    if (ok) {
+        out->numer = std::move(numer);
+        out->denom = denom;
+    }
+    return ok;
+}
+
+namespace {
 
 // Solve  A z = rhs  (transpose = 0: A = B;  transpose = 1: A = B')  by Dixon lifting; the result is verified exactly.
 bool dixon_solve(const IntegerBasis& B, const std::vector<i64>& rhs, int transpose, u32 p, const u32* dA,
@@ -515,170 +665,16 @@ bool dixon_solve(const IntegerBasis& B, const std::vector<i64>& rhs, int transpo
         for (int s = steps_done; s < target; ++s) digits.push_back(flat.data() + (size_t)(s - steps_done) * m);
         steps_done = target;
 
-        // ---- assemble, reconstruct with a common denominator, verify ---------------------------------
-        WorkerPool& pool = WorkerPool::get(transpose);
-        double t_part = t_host;
+        // ---- assemble, reconstruct with a common denominator, verify (dixon_reconstruct, above) ------------
+        const bool ok = dixon_reconstruct(B, rhs, transpose, p, digits, true, out, times);
+        double t_part = wall_now();
         auto part = [&](double& sum) {
             const double now = wall_now();
             sum += now - t_part;
             t_part = now;
         };
-        part(times.unpack);
-        BigInt modulus(1);
-        for (int s = 0; s < steps_done; ++s) modulus.mul_add_small(p, 0);
-        part(times.horner);  // (no Horner pass any more: the numerators are formed from the digits directly, below)
-        bool ok = true;
-        BigInt denom(1);
-        std::vector<BigInt> numer(m);
-        const BigInt half = modulus / BigInt(2);
-        // numer_i = centred(residue_i * denom mod modulus) is the numerator as soon as denom is the common denominator: all
-        // entries in parallel; every entry that is still "large" contributes its own denominator (rational reconstruction,
-        // sequential: there are few), then the pass is repeated with the grown denominator.
-        std::vector<char> small(m);
-        {
-            // A random integer combination of the entries has, almost surely, the common denominator of all of them: ONE
-            // rational reconstruction instead of one per entry that brings a new factor (46 of them on 25FV47).  Whatever it
-            // misses is found by the loop below; every result is verified exactly anyway.
-            // (Formed on the digits: column sums of weight x digit stay below 2^57, one carry sweep in base p, one Horner pass --
-            // no big-integer arithmetic per entry.)
-            std::vector<unsigned long long> column(steps_done, 0);
-            std::vector<uint32_t> weight(m);
-            unsigned long long state = 0x9E3779B97F4A7C15ull;
-            for (int i = 0; i < m; ++i) {
-                state = state * 6364136223846793005ull + 1442695040888963407ull;
-                weight[i] = (uint32_t)(1 + ((state >> 33) & 0xffff));
-            }
-            for (int s = 0; s < steps_done; ++s) {
-                const u32* row = digits[s];
-                unsigned long long sum = 0;
-                for (int i = 0; i < m; ++i) sum += (unsigned long long)weight[i] * row[i];
-                column[s] = sum;
-            }
-            unsigned long long carry = 0;
-            for (int s = 0; s < steps_done; ++s) {  // (what is carried out of the top digit is a multiple of the modulus)
-                const unsigned long long v = column[s] + carry;
-                column[s] = v % p;
-                carry = v / p;
-            }
-            BigInt combo(0);
-            for (int s = steps_done; s-- > 0;) combo.mul_add_small(p, (uint32_t)column[s]);
-            combo.trim();
-            BigInt n, d;
-            const double t_rr = wall_now();
-            const bool found = rational_reconstruct(combo, modulus, n, d, true, p);
-            times.reconstruct += wall_now() - t_rr;
-            times.reconstructs++;
-            if (found && within_wang_bound(d, modulus)) denom = d;
-            else ok = false;  // not enough digits yet
-        }
-        part(times.combine);
-        // First pass: every entry against the denominator of the combination, in parallel.  What is still "large" then has a
-        // factor the combination lost (a small prime that happened to divide its numerator): one reconstruction finds it, the
-        // denominator grows by it, and the entries are multiplied by the factor -- the small ones stay small (no reduction), the
-        // others are reduced again.  denom is the lcm of reduced denominators at every point, so the result is in lowest terms
-        // (gcd(denom, all numerators) = 1: a prime power q^e || denom divides exactly the denominator of some entry, whose
-        // numerator q does not divide) and no gcd pass is needed afterwards.
-        // numer_i = (sum_s digit_s[i] p^s) denom  mod p^K  =  sum_s digit_s[i] W_s  mod p^K   with  W_s = denom p^s mod p^K:  the K
-        // multipliers are made once (each from the last by one small multiplication and a one-word quotient), and an entry is K
-        // multiply-adds of a 31-bit digit into 128-bit accumulators per 64-bit word, one carry sweep and one reduction by a two-word
-        // quotient -- instead of a Horner pass, a 4000 x 2000-bit product and a 6000 / 4000-bit division per entry on 32-bit limbs.
         if (ok) {
-            typedef unsigned __int128 u128;
-            const int words = (int)((modulus.bits() + 63) / 64);
-            std::vector<u64> table((size_t)steps_done * words, 0);
-            {
-                BigInt w = denom % modulus;
-                for (int s = 0; s < steps_done; ++s) {
-                    u64* row = table.data() + (size_t)s * words;
-                    for (size_t l = 0; l < w.mag.size(); ++l) row[l / 2] |= (u64)w.mag[l] << (32 * (l % 2));
-                    if (s + 1 < steps_done) {
-                        w.mul_add_small(p, 0);
-                        w = w % modulus;
-                    }
-                }
-            }
-            pool.run(m, [&](int i) {
-                std::vector<u128> acc(words, 0);
-                for (int s = 0; s < steps_done; ++s) {
-                    const u64 d = digits[s][i];
-                    if (d == 0) continue;
-                    const u64* row = table.data() + (size_t)s * words;
-                    for (int l = 0; l < words; ++l) acc[l] += (u128)d * row[l];
-                }
-                BigInt t;
-                t.mag.reserve(2 * words + 4);
-                u128 carry = 0;
-                for (int l = 0; l < words; ++l) {
-                    const u128 v = acc[l] + carry;  // (acc < 2^102, carry < 2^64)
-                    t.mag.push_back((uint32_t)(u64)v);
-                    t.mag.push_back((uint32_t)((u64)v >> 32));
-                    carry = v >> 64;
-                }
-                while (carry != 0) {
-                    t.mag.push_back((uint32_t)(u64)carry);
-                    carry >>= 32;
-                }
-                t.trim();
-                t = t % modulus;
-                if (cmp(t, half) > 0) t = t - modulus;
-                small[i] = within_wang_bound(t, modulus) ? 1 : 0;
-                numer[i] = t;
-            });
-        }
-        if (ok) {
-            BigInt factor(1);  // product of the factors the combination lost
-            auto centred = [&](BigInt t) {
-                t = t % modulus;
-                if (cmp(t, half) > 0) t = t - modulus;
-                else if (t.sign() < 0 && cmp(t.abs(), half) > 0) t = t + modulus;
-                return t;
-            };
-            for (int i = 0; i < m && ok; ++i) {
-                if (small[i]) continue;
-                const BigInt t = centred(numer[i] * factor);
-                if (within_wang_bound(t, modulus)) continue;  // the factors found so far cover it
-                BigInt n, d;
-                const double t_rr = wall_now();
-                const bool found = rational_reconstruct(t, modulus, n, d, true, p);
-                times.reconstruct += wall_now() - t_rr;
-                times.reconstructs++;
-                if (!found || d == BigInt(1)) { ok = false; break; }  // (d = 1 with a large numerator: not enough digits)
-                factor = factor * d;
-                denom = denom * d;
-                if (!within_wang_bound(denom, modulus)) ok = false;
-            }
-            if (ok && !(factor == BigInt(1))) {
-                std::atomic<int> large{0};
-                pool.run(m, [&](int i) {
-                    if (numer[i].is_zero()) return;
-                    BigInt t = numer[i] * factor;
-                    if (!small[i] || !within_wang_bound(t, modulus)) {
-                        t = centred(t);
-                        if (!within_wang_bound(t, modulus)) large.fetch_add(1);
-                    }
-                    numer[i] = t;
-                });
-                if (large.load() != 0) ok = false;
-            }
-        }
-        part(times.numerators);
-        if (ok) {
-            // exact verification: A numer == denom * rhs
-            std::atomic<int> bad{0};
-            pool.run(m, [&](int i) {
-                BigInt acc(0);
-                if (!transpose)
-                    for (int e = B.row_start[i]; e < B.row_start[i + 1]; ++e) acc = acc + BigInt(B.row_value[e]) * numer[B.col_index[e]];
-                else
-                    for (int e = B.col_start[i]; e < B.col_start[i + 1]; ++e) acc = acc + BigInt(B.value[e]) * numer[B.row_index[e]];
-                if (!(acc == denom * BigInt(rhs[i]))) bad.fetch_add(1);
-            });
-            if (bad.load() != 0) ok = false;
-        }
-        part(times.verify);
-        if (ok) {
-            out->numer = std::move(numer);
-            out->denom = denom;
+            const BigInt& denom = out->denom;
             if (digits_used) {
                 // What the NEXT lifting of the same system should start with: the digits this solution needs by the bound used above
                 // (2 bits(v) + 2 <= bits(p^K) for its largest numerator and the denominator), plus a margin of four -- not the power
@@ -730,17 +726,6 @@ void CertifyScratch::release() {
 // ---------------------------------------------------------------------------------------------------
 // entry point
 // ---------------------------------------------------------------------------------------------------
-// What depends on the loaded LP only (kept by the handle between certificates, CertifyScratch::statics).
-struct CertifyStatic {
-    std::vector<SparseColumn> columns;
-    std::vector<Rat> rhs;
-    std::vector<i128> row_mult;
-    i128 cost_mult = 1;
-    DeviceColumns cols;
-    std::vector<BigInt> rhs_big;
-    BigInt rhs_den = BigInt(1);
-};
-
 // mode 0: the basis is optimal (x_B >= 0, zero artificials, every reduced cost >= 0) -> exact objective.
 // mode 1: the LP is INFEASIBLE: the same checks for the phase-one costs (1 on the artificial columns, 0 elsewhere;
 //         phase_one.rs:123-179) with a POSITIVE optimum -- the dual solution y is a Farkas certificate (y'A <= 0, y'b > 0).
@@ -777,6 +762,156 @@ std::shared_ptr<const ExactPrimal> make_exact_primal(const std::vector<int>& col
     primal->denom = denom;
     for (const Rat& v : values) primal->numer.push_back(BigInt::from_i128(v.n) * (denom / BigInt::from_i128(v.d)));
     return primal;
+}
+
+std::shared_ptr<const CertifyStatic> certify_static(const StandardForm& form, std::string* message) {
+    const MatrixData& md = form.data;
+    const int m = md.nr_rows();
+    const int n_p = md.nr_columns();
+    auto built = std::make_shared<CertifyStatic>();
+    built->columns.resize(n_p);
+    for (int j = 0; j < n_p; ++j) built->columns[j] = md.column(j);
+    built->rhs = md.right_hand_side();
+    built->row_mult.assign(m, 1);
+    try {
+        for (int j = 0; j < n_p; ++j)
+            for (size_t e = 0; e < built->columns[j].nnz(); ++e)
+                built->row_mult[built->columns[j].index[e]] = lcm128(built->row_mult[built->columns[j].index[e]], built->columns[j].value[e].d);
+    } catch (const RatOverflow&) {
+        *message = "row scaling overflows 128 bits";
+        return nullptr;
+    }
+    try {
+        for (int j = 0; j < n_p; ++j) built->cost_mult = lcm128(built->cost_mult, md.cost_value(j).d);
+    } catch (const RatOverflow&) {
+        built->cost_mult = 0;  // (only the phase-one certificate, which has its own costs, can do without)
+    }
+    // basis columns: provider column c >= 0, or artificial -1-k (unit column on its row, cost 0; redundant rows)
+    built->cols = DeviceColumns(md);
+    // b_i * row_mult_i = rhs_big[i] / rhs_den  (exact, arbitrary width)
+    built->rhs_big.resize(m);
+    {
+        std::vector<BigInt> numer(m);
+        std::vector<i128> denom(m);
+        for (int i = 0; i < m; ++i) {
+            const i128 g = gcd128(built->row_mult[i], built->rhs[i].d);
+            numer[i] = big_from_i128(built->rhs[i].n) * big_from_i128(built->row_mult[i] / g);
+            denom[i] = built->rhs[i].d / g;
+            const BigInt d = big_from_i128(denom[i]);
+            built->rhs_den = built->rhs_den / BigInt::gcd(built->rhs_den, d) * d;
+        }
+        for (int i = 0; i < m; ++i) built->rhs_big[i] = numer[i] * (built->rhs_den / big_from_i128(denom[i]));
+    }
+    return built;
+}
+
+namespace {
+i128 certify_scaled(const Rat& v, i128 mult) { return mul_checked(v.n, mult / v.d); }
+bool certify_fits(i128 v) { return v < ((i128)1 << 62) && v > -((i128)1 << 62); }
+}  // namespace
+
+bool certify_integer_basis(const CertifyStatic& statics, const MatrixData& md, const std::vector<int>& basis, int mode, IntegerBasis* out,
+                           std::vector<i64>* cost_out, std::vector<char>* in_basis_out, std::string* message) {
+    const std::vector<SparseColumn>& columns = statics.columns;
+    const std::vector<i128>& row_mult = statics.row_mult;
+    const DeviceColumns& cols = statics.cols;
+    const int m = md.nr_rows();
+    const int n_p = md.nr_columns();
+    IntegerBasis& B = *out;
+    B = IntegerBasis();
+    B.m = m;
+    B.col_start.assign(m + 1, 0);
+    std::vector<i64>& cost_basis = *cost_out;
+    std::vector<char>& in_basis = *in_basis_out;
+    cost_basis.assign(m, 0);
+    in_basis.assign(n_p, 0);
+    for (int k = 0; k < m; ++k) {
+        int c = basis[k];
+        if (c >= 0) {
+            in_basis[c] = 1;
+            for (size_t e = 0; e < columns[c].nnz(); ++e) {
+                i128 v = certify_scaled(columns[c].value[e], row_mult[columns[c].index[e]]);
+                if (!certify_fits(v)) { *message = "scaled coefficient does not fit 62 bits"; return false; }
+                B.row_index.push_back(columns[c].index[e]);
+                B.value.push_back((i64)v);
+            }
+            i128 cv = mode == 1 ? (i128)0 : certify_scaled(md.cost_value(c), statics.cost_mult);
+            if (!certify_fits(cv)) { *message = "scaled cost does not fit 62 bits"; return false; }
+            cost_basis[k] = (i64)cv;
+        } else {
+            int row = cols.artificial_rows.at(cols.to_device(c));
+            if (!certify_fits(row_mult[row])) { *message = "row multiplier does not fit 62 bits"; return false; }
+            B.row_index.push_back(row);
+            B.value.push_back((i64)row_mult[row]);
+            cost_basis[k] = mode == 1 ? 1 : 0;  // artificial::Cost::One in phase one (kind/artificial/partially.rs:42-50)
+        }
+        B.col_start[k + 1] = (int)B.row_index.size();
+    }
+    const size_t nnz = B.row_index.size();
+    B.row_start.assign(m + 1, 0);
+    B.col_index.resize(nnz);
+    B.row_value.resize(nnz);
+    for (size_t e = 0; e < nnz; ++e) B.row_start[B.row_index[e] + 1]++;
+    for (int i = 0; i < m; ++i) B.row_start[i + 1] += B.row_start[i];
+    {
+        std::vector<int> fill(B.row_start.begin(), B.row_start.end() - 1);
+        for (int k = 0; k < m; ++k)
+            for (int e = B.col_start[k]; e < B.col_start[k + 1]; ++e) {
+                int dst = fill[B.row_index[e]]++;
+                B.col_index[dst] = k;
+                B.row_value[dst] = B.value[e];
+            }
+    }
+    return true;
+}
+
+bool certify_signs(const CertifyStatic& statics, const MatrixData& md, const std::vector<int>& basis, const std::vector<char>& in_basis,
+                   int mode, const ExactVector& x, const ExactVector& y, bool parallel, CertifySigns* signs, std::string* message) {
+    const std::vector<SparseColumn>& columns = statics.columns;
+    const std::vector<i128>& row_mult = statics.row_mult;
+    const int m = md.nr_rows();
+    const int n_p = md.nr_columns();
+    int worst_row = -1;  // most negative x_B (all share the positive denominator)
+    for (int k = 0; k < m; ++k) {
+        if (mode != 1 && basis[k] < 0 && x.numer[k].sign() > 0) { *message = "artificial variable positive in exact arithmetic"; return false; }
+        if (x.numer[k].sign() < 0 && (worst_row < 0 || cmp(x.numer[k], x.numer[worst_row]) < 0)) worst_row = k;
+    }
+    // reduced costs (common positive denominator cost_mult * Dy):  c_j*cost_mult*Dy - sum_i a_ij*row_mult_i*Y_i
+    std::vector<BigInt>& dhat = signs->dhat;
+    dhat.assign(n_p, BigInt());
+    int worst_col = -1;
+    auto reduced_cost = [&](int j) {  // (independent columns; the most negative one is picked in order below)
+        if (in_basis[j]) return;
+        BigInt acc = big_from_i128(mode == 1 ? (i128)0 : certify_scaled(md.cost_value(j), statics.cost_mult)) * y.denom;
+        for (size_t e = 0; e < columns[j].nnz(); ++e)
+            acc = acc - big_from_i128(certify_scaled(columns[j].value[e], row_mult[columns[j].index[e]])) * y.numer[columns[j].index[e]];
+        dhat[j] = acc;
+    };
+    if (parallel) WorkerPool::get().run(n_p, reduced_cost);
+    else
+        for (int j = 0; j < n_p; ++j) reduced_cost(j);
+    for (int j = 0; j < n_p; ++j)
+        if (!in_basis[j] && dhat[j].sign() < 0 && (worst_col < 0 || cmp(dhat[j], dhat[worst_col]) < 0)) worst_col = j;
+    signs->worst_row = worst_row;
+    signs->worst_col = worst_col;
+    return true;
+}
+
+std::string certify_objective(const StandardForm& form, const CertifyStatic& statics, const std::vector<i64>& cost_basis, const ExactVector& x) {
+    const int m = (int)cost_basis.size();
+    BigInt num(0);
+    for (int k = 0; k < m; ++k)
+        if (cost_basis[k] != 0) num = num + BigInt(cost_basis[k]) * x.numer[k];
+    BigInt den = big_from_i128(statics.cost_mult) * x.denom;
+    const Rat& fixed = form.fixed_cost;
+    num = num * big_from_i128(fixed.d) + big_from_i128(fixed.n) * den;
+    den = den * big_from_i128(fixed.d);
+    BigInt g = BigInt::gcd(num, den);
+    if (!g.is_zero() && !(g == BigInt(1))) {
+        num = num / g;
+        den = den / g;
+    }
+    return num.to_string() + "/" + den.to_string();
 }
 
 void certify_basis(const StandardForm& form, const std::vector<int>& basis_columns, int device, hipStream_t stream,
@@ -823,41 +958,8 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
     //      on the LP only: built once per loaded LP and kept by the handle (0.5 ms of every certificate of 25FV47 otherwise) ----
     std::shared_ptr<const CertifyStatic> statics = scratch ? std::static_pointer_cast<const CertifyStatic>(scratch->statics) : nullptr;
     if (!statics) {
-        auto built = std::make_shared<CertifyStatic>();
-        built->columns.resize(n_p);
-        for (int j = 0; j < n_p; ++j) built->columns[j] = md.column(j);
-        built->rhs = md.right_hand_side();
-        built->row_mult.assign(m, 1);
-        try {
-            for (int j = 0; j < n_p; ++j)
-                for (size_t e = 0; e < built->columns[j].nnz(); ++e)
-                    built->row_mult[built->columns[j].index[e]] = lcm128(built->row_mult[built->columns[j].index[e]], built->columns[j].value[e].d);
-        } catch (const RatOverflow&) {
-            *message = "row scaling overflows 128 bits";
-            return;
-        }
-        try {
-            for (int j = 0; j < n_p; ++j) built->cost_mult = lcm128(built->cost_mult, md.cost_value(j).d);
-        } catch (const RatOverflow&) {
-            built->cost_mult = 0;  // (only the phase-one certificate, which has its own costs, can do without)
-        }
-        // basis columns: provider column c >= 0, or artificial -1-k (unit column on its row, cost 0; redundant rows)
-        built->cols = DeviceColumns(md);
-        // b_i * row_mult_i = rhs_big[i] / rhs_den  (exact, arbitrary width)
-        built->rhs_big.resize(m);
-        {
-            std::vector<BigInt> numer(m);
-            std::vector<i128> denom(m);
-            for (int i = 0; i < m; ++i) {
-                const i128 g = gcd128(built->row_mult[i], built->rhs[i].d);
-                numer[i] = big_from_i128(built->rhs[i].n) * big_from_i128(built->row_mult[i] / g);
-                denom[i] = built->rhs[i].d / g;
-                const BigInt d = big_from_i128(denom[i]);
-                built->rhs_den = built->rhs_den / BigInt::gcd(built->rhs_den, d) * d;
-            }
-            for (int i = 0; i < m; ++i) built->rhs_big[i] = numer[i] * (built->rhs_den / big_from_i128(denom[i]));
-        }
-        statics = built;
+        statics = certify_static(form, message);
+        if (!statics) return;
         if (scratch) scratch->statics = statics;
     }
     const std::vector<SparseColumn>& columns = statics->columns;
@@ -866,61 +968,21 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         *message = "cost scaling overflows 128 bits";
         return;
     }
-    const i128 cost_mult = mode == 1 ? (i128)1 : statics->cost_mult;
-    const DeviceColumns& cols = statics->cols;
     const std::vector<BigInt>& rhs_big = statics->rhs_big;
     const BigInt& rhs_den = statics->rhs_den;
     auto scaled = [&](const Rat& v, i128 mult) { return mul_checked(v.n, mult / v.d); };
-    auto scaled_cost = [&](int j) -> i128 { return mode == 1 ? (i128)0 : scaled(md.cost_value(j), cost_mult); };
     auto fits = [](i128 v) { return v < ((i128)1 << 62) && v > -((i128)1 << 62); };
     std::vector<int> basis = basis_columns;  // repaired in place by exact pivots when a check fails
     const int max_repairs = 200;
-    const u32 primes[] = {2147483647u, 2147483629u, 2147483587u, 2147483579u};
+    const auto& primes = CERTIFY_PRIMES;
 
     for (int round = 0; round <= max_repairs; ++round) {
         // ---- integer basis (CSC + CSR) ------------------------------------------------------------------
         IntegerBasis B;
-        B.m = m;
-        B.col_start.assign(m + 1, 0);
-        std::vector<i64> cost_basis(m, 0);
-        std::vector<char> in_basis(n_p, 0);
-        for (int k = 0; k < m; ++k) {
-            int c = basis[k];
-            if (c >= 0) {
-                in_basis[c] = 1;
-                for (size_t e = 0; e < columns[c].nnz(); ++e) {
-                    i128 v = scaled(columns[c].value[e], row_mult[columns[c].index[e]]);
-                    if (!fits(v)) { *message = "scaled coefficient does not fit 62 bits"; return; }
-                    B.row_index.push_back(columns[c].index[e]);
-                    B.value.push_back((i64)v);
-                }
-                i128 cv = scaled_cost(c);
-                if (!fits(cv)) { *message = "scaled cost does not fit 62 bits"; return; }
-                cost_basis[k] = (i64)cv;
-            } else {
-                int row = cols.artificial_rows.at(cols.to_device(c));
-                if (!fits(row_mult[row])) { *message = "row multiplier does not fit 62 bits"; return; }
-                B.row_index.push_back(row);
-                B.value.push_back((i64)row_mult[row]);
-                cost_basis[k] = mode == 1 ? 1 : 0;  // artificial::Cost::One in phase one (kind/artificial/partially.rs:42-50)
-            }
-            B.col_start[k + 1] = (int)B.row_index.size();
-        }
+        std::vector<i64> cost_basis;
+        std::vector<char> in_basis;
+        if (!certify_integer_basis(*statics, md, basis, mode, &B, &cost_basis, &in_basis, message)) return;
         const size_t nnz = B.row_index.size();
-        B.row_start.assign(m + 1, 0);
-        B.col_index.resize(nnz);
-        B.row_value.resize(nnz);
-        for (size_t e = 0; e < nnz; ++e) B.row_start[B.row_index[e] + 1]++;
-        for (int i = 0; i < m; ++i) B.row_start[i + 1] += B.row_start[i];
-        {
-            std::vector<int> fill(B.row_start.begin(), B.row_start.end() - 1);
-            for (int k = 0; k < m; ++k)
-                for (int e = B.col_start[k]; e < B.col_start[k + 1]; ++e) {
-                    int dst = fill[B.row_index[e]]++;
-                    B.col_index[dst] = k;
-                    B.row_value[dst] = B.value[e];
-                }
-        }
 
         g_times.setup += wall_now() - t_begin - g_times.setup - g_times.inverse - g_times.device_digits - g_times.host_assemble - g_times.checks;
         const double t_inverse = wall_now();
@@ -1153,23 +1215,10 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
             double t0;
             ~ChecksTimer() { g_times.checks += wall_now() - t0; }
         } checks_timer{t_checks};
-        int worst_row = -1;  // most negative x_B (all share the positive denominator)
-        for (int k = 0; k < m; ++k) {
-            if (mode != 1 && basis[k] < 0 && x.numer[k].sign() > 0) { *message = "artificial variable positive in exact arithmetic"; return; }
-            if (x.numer[k].sign() < 0 && (worst_row < 0 || cmp(x.numer[k], x.numer[worst_row]) < 0)) worst_row = k;
-        }
-        // reduced costs (common positive denominator cost_mult * Dy):  c_j*cost_mult*Dy - sum_i a_ij*row_mult_i*Y_i
-        std::vector<BigInt> dhat(n_p);
-        int worst_col = -1;
-        WorkerPool::get().run(n_p, [&](int j) {  // (independent columns; the most negative one is picked in order below)
-            if (in_basis[j]) return;
-            BigInt acc = big_from_i128(scaled_cost(j)) * y.denom;
-            for (size_t e = 0; e < columns[j].nnz(); ++e)
-                acc = acc - big_from_i128(scaled(columns[j].value[e], row_mult[columns[j].index[e]])) * y.numer[columns[j].index[e]];
-            dhat[j] = acc;
-        });
-        for (int j = 0; j < n_p; ++j)
-            if (!in_basis[j] && dhat[j].sign() < 0 && (worst_col < 0 || cmp(dhat[j], dhat[worst_col]) < 0)) worst_col = j;
+        CertifySigns signs;
+        if (!certify_signs(*statics, md, basis, in_basis, mode, x, y, true, &signs, message)) return;
+        const int worst_row = signs.worst_row, worst_col = signs.worst_col;
+        const std::vector<BigInt>& dhat = signs.dhat;
         if (mode == 2) {
             // ---- unbounded ray: x_B >= 0, cbar_q < 0, alpha = B^-1 a_q <= 0 (zero where an artificial is basic) ------------
             if (worst_row >= 0) { *message = "unbounded: the basis is not primal feasible in exact arithmetic"; return; }
@@ -1210,21 +1259,8 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         if (mode == 1) { *message = "infeasible: the final phase-one basis is not optimal in exact arithmetic"; return; }
         if (worst_row < 0 && worst_col < 0) {
             // ---- optimal: objective = (sum_k cost_basis[k] X_k) / (cost_mult * Dx) + fixed ----------------------
-            BigInt num(0);
-            for (int k = 0; k < m; ++k)
-                if (cost_basis[k] != 0) num = num + BigInt(cost_basis[k]) * x.numer[k];
-            BigInt den = big_from_i128(cost_mult) * x.denom;
-            const Rat& fixed = form.fixed_cost;
-            num = num * big_from_i128(fixed.d) + big_from_i128(fixed.n) * den;
-            den = den * big_from_i128(fixed.d);
-            BigInt g = BigInt::gcd(num, den);
-            if (!g.is_zero() && !(g == BigInt(1))) {
-                num = num / g;
-                den = den / g;
-            }
-            stamp("checks done, objective reduced");
-            *objective = num.to_string() + "/" + den.to_string();
-            stamp("objective as decimal text");
+            *objective = certify_objective(form, *statics, cost_basis, x);
+            stamp("checks done, objective as decimal text");
             *certified = true;
             *repair_pivots = round;
             if (primal) {  // OptimizationResult::FiniteOptimum(x) in exact form (algorithm/mod.rs:43-47), kept as integers over one denominator

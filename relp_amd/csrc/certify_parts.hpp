@@ -1,0 +1,92 @@
+// The parts of the exact certificate (certify.hip) that do not care where the p-adic digits came from: the integer scaling of an
+// LP, the row-scaled integer basis, the assembly of the digits with the combined-unknown rational reconstruction and the exact
+// substitution, the sign checks with the reduced costs of all non-basic columns, and the exact objective.  `certify_basis` (one
+// LP, a chain of launches) and the batched certificate of relp_many (many_certify.hip: one launch for all LPs) call the same
+// functions; what differs between them is only who produced the digits.
+#pragma once
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "bigint.hpp"
+#include "solver.hpp"
+
+namespace relp {
+
+// v mod p for v < 2^64; p = 2^31 - 1 (the first trial prime) folds instead of dividing
+__device__ __forceinline__ uint32_t reduce64(uint64_t v, uint32_t p) {
+    if (p == 0x7fffffffu) {
+        v = (v & 0x7fffffffu) + (v >> 31);   // < 2^34
+        v = (v & 0x7fffffffu) + (v >> 31);   // < 2^31 + 8
+        uint32_t r = (uint32_t)v;
+        return r >= p ? r - p : r;
+    }
+    return (uint32_t)(v % p);
+}
+
+// the trial primes of the modular inverse, in the order they are tried
+constexpr uint32_t CERTIFY_PRIMES[4] = {2147483647u, 2147483629u, 2147483587u, 2147483579u};
+
+// diagnostic timeline (RELP_TIME_CERTIFY=1): where the certificate's wall time goes
+struct CertifyTimes {
+    double device_digits = 0.0, host_assemble = 0.0, inverse = 0.0, setup = 0.0, checks = 0.0, reconstruct = 0.0, parallel = 0.0;
+    double unpack = 0.0, horner = 0.0, combine = 0.0, numerators = 0.0, verify = 0.0, normalise = 0.0;  // parts of host_assemble
+    int digit_launches = 0, solves = 0, reconstructs = 0;
+};
+
+struct IntegerBasis {          // row-scaled integer basis, both orientations
+    int m = 0;
+    std::vector<int> col_start, row_index;   // CSC (columns = basis positions)
+    std::vector<long long> value;
+    std::vector<int> row_start, col_index;   // CSR
+    std::vector<long long> row_value;
+};
+
+struct ExactVector {           // numer[i] / denom
+    std::vector<BigInt> numer;
+    BigInt denom = BigInt(1);
+};
+
+// What depends on the loaded LP only (kept by the handle between certificates, CertifyScratch::statics).
+struct CertifyStatic {
+    std::vector<SparseColumn> columns;
+    std::vector<Rat> rhs;
+    std::vector<i128> row_mult;
+    i128 cost_mult = 1;        // 0: the cost scaling overflows 128 bits (only the phase-one certificate can do without)
+    DeviceColumns cols;
+    std::vector<BigInt> rhs_big;
+    BigInt rhs_den = BigInt(1);
+};
+
+// Integer scaling of the LP: row multipliers (lcm of the denominators of the row's coefficients), cost multiplier, and the
+// right-hand side over its own common denominator.  Null with `message` set when the row scaling overflows 128 bits.
+std::shared_ptr<const CertifyStatic> certify_static(const StandardForm& form, std::string* message);
+
+// The basis in integers: B (CSC and CSR), the scaled basic costs (`mode` 1: the phase-one costs) and the membership flags of the
+// provider columns.  An artificial column -1-k is the unit column of its row scaled by the row multiplier.  False with `message`
+// set when an entry does not fit 62 bits.
+bool certify_integer_basis(const CertifyStatic& statics, const MatrixData& md, const std::vector<int>& basis, int mode, IntegerBasis* B,
+                           std::vector<long long>* cost_basis, std::vector<char>* in_basis, std::string* message);
+
+// From the first digits.size() p-adic digits of the solution of A z = rhs (transpose 0: A = B, 1: A = B'): the numerators over one
+// common denominator (one rational reconstruction of a random integer combination of the unknowns, then one per entry that
+// brings a factor the combination lost), VERIFIED by exact substitution A numer == denom rhs.  False when the digits do not
+// suffice (or are wrong).  `parallel`: the entries are spread over the certificate's worker pool; else they run on the caller.
+bool dixon_reconstruct(const IntegerBasis& B, const std::vector<long long>& rhs, int transpose, uint32_t p,
+                       const std::vector<const uint32_t*>& digits, bool parallel, ExactVector* out, CertifyTimes& times);
+
+// Sign checks of a basis with exact x_B = x.numer / x.denom (denom > 0) and y: the most negative basic value and, from the
+// reduced costs of ALL non-basic columns (`dhat`, over one positive denominator), the most negative of those; -1 where there is
+// none.  False with `message` set when an artificial variable is positive (modes 0 and 2).
+struct CertifySigns {
+    int worst_row = -1, worst_col = -1;
+    std::vector<BigInt> dhat;
+};
+bool certify_signs(const CertifyStatic& statics, const MatrixData& md, const std::vector<int>& basis, const std::vector<char>& in_basis,
+                   int mode, const ExactVector& x, const ExactVector& y, bool parallel, CertifySigns* signs, std::string* message);
+
+// objective = (sum_k cost_basis[k] X_k) / (cost_mult * Dx) + fixed cost, reduced, as "num/den"
+std::string certify_objective(const StandardForm& form, const CertifyStatic& statics, const std::vector<long long>& cost_basis,
+                              const ExactVector& x);
+
+}  // namespace relp

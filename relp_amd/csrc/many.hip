@@ -40,6 +40,7 @@
 #include <string>
 #include <vector>
 
+#include "many_certify.hpp"
 #include "pivot_step.hpp"
 #include "price_step.hpp"
 #include "solver.hpp"
@@ -618,6 +619,7 @@ struct relp_many {
     std::vector<std::vector<int>> bases;      // provider codes (DeviceColumns::to_provider); bounded: of the reference's formulation
     std::vector<std::vector<double>> solutions;  // every column of MatrixData
     std::vector<std::string> exact;
+    std::vector<int> entering;                // device column a verdict of UNBOUNDED names (the ray of its certificate)
     std::string error;
 
     void release() {
@@ -644,6 +646,43 @@ T* many_upload(DeviceAllocations& memory, const std::vector<T>& host) {
     if (!host.empty()) RELP_HIP(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     return p;
 }
+// (with implicit bounds the explicit basis proves an optimum; the two other verdicts stay uncertified, as on a handle)
+bool many_serial_certificate_applies(const relp_many& many, int k) {
+    const relp_many_result& res = many.results[k];
+    return res.status == RELP_OK && (res.kind == RELP_RESULT_FINITE_OPTIMUM ||
+                                     (!many.lps[k].bounded && (res.kind == RELP_RESULT_INFEASIBLE || res.kind == RELP_RESULT_UNBOUNDED)));
+}
+
+// The exact certificate of relp_solve_relaxation for model k of the last solve (certify_basis: its other primes and its exact repair
+// pivots included).  Sets results[k].certified and certify_seconds, and exact[k].
+bool many_serial_certificate(relp_many& many, int k, long long* repairs) {
+    const ManyHostLP& lp = many.lps[k];
+    relp_many_result& res = many.results[k];
+    const double t0 = many_now();
+    bool ok = false;
+    std::string message;
+    const int mode = res.kind == RELP_RESULT_INFEASIBLE ? 1 : res.kind == RELP_RESULT_UNBOUNDED ? 2 : 0;
+    const int entering = many.entering[k];
+    const int ray = res.kind == RELP_RESULT_UNBOUNDED && entering >= lp.n_art && entering < lp.n ? entering - lp.n_art : -1;
+    many.certify_scratch.statics.reset();  // (what it keeps belongs to one LP)
+    many.certify_scratch.digit_hints[0] = many.certify_scratch.digit_hints[1] = 0;
+    *repairs = 0;
+    try {
+        certify_basis(many.forms[k], many.bases[k], many.device, many.streams[0], &many.exact[k], &ok, repairs, &message, mode, ray, nullptr,
+                      &many.certify_scratch);
+    } catch (const RatOverflow& e) {  // the f64 result stands, uncertified
+        ok = false;
+        message = std::string("exact certificate: ") + e.what();
+    }
+    if (!ok) {
+        many.exact[k].clear();
+        if (many.error.empty()) many.error = "model " + std::to_string(k) + ": " + message;
+    }
+    res.certified = ok ? 1 : 0;
+    res.certify_seconds = many_now() - t0;
+    return ok;
+}
+
 // The options this path honours; the message names the first one it cannot.
 std::string many_refusal(const relp_options& o) {
     if (o.carry != RELP_CARRY_EXPLICIT) return "relp_many keeps an explicit inverse: carry must be RELP_CARRY_EXPLICIT";
@@ -886,6 +925,7 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
         many->bases.assign(n, std::vector<int>());
         many->solutions.assign(n, std::vector<double>());
         many->exact.assign(n, std::string());
+        many->entering.assign(n, -1);
         size_t r0 = 0, c0 = 0;
         for (int k = 0; k < n; ++k) {
             const ManyHostLP& lp = many->lps[k];
@@ -922,34 +962,88 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
             }
             r0 += lp.m;
             c0 += lp.n;
-            // (with implicit bounds the explicit basis proves an optimum; the two other verdicts stay uncertified, as on a handle)
-            if (o.certify && oc.status == RELP_OK &&
-                (oc.kind == RELP_RESULT_FINITE_OPTIMUM || (!lp.bounded && (oc.kind == RELP_RESULT_INFEASIBLE || oc.kind == RELP_RESULT_UNBOUNDED)))) {
-                const double t0 = many_now();
-                bool ok = false;
+            many->entering[k] = oc.entering;
+            if (o.certify && many_serial_certificate_applies(*many, k)) {
                 long long repairs = 0;
-                std::string message;
-                const int mode = oc.kind == RELP_RESULT_INFEASIBLE ? 1 : oc.kind == RELP_RESULT_UNBOUNDED ? 2 : 0;
-                const int ray = oc.kind == RELP_RESULT_UNBOUNDED && oc.entering >= lp.n_art && oc.entering < lp.n ? oc.entering - lp.n_art : -1;
-                many->certify_scratch.statics.reset();  // (what it keeps belongs to one LP)
-                many->certify_scratch.digit_hints[0] = many->certify_scratch.digit_hints[1] = 0;
-                try {
-                    certify_basis(form, provider_basis, many->device, many->streams[0], &many->exact[k], &ok, &repairs, &message, mode, ray,
-                                  nullptr, &many->certify_scratch);
-                } catch (const RatOverflow& e) {  // the f64 result stands, uncertified
-                    ok = false;
-                    message = std::string("exact certificate: ") + e.what();
-                }
-                if (!ok) {
-                    many->exact[k].clear();
-                    if (many->error.empty()) many->error = "model " + std::to_string(k) + ": " + message;
-                }
-                res.certified = ok ? 1 : 0;
-                res.certify_seconds = many_now() - t0;
+                many_serial_certificate(*many, k, &repairs);
             }
         }
         many->solved = true;
         if (results) std::copy(many->results.begin(), many->results.end(), results);
+        return RELP_OK;
+    } catch (const DeviceError& e) {
+        many->error = e.what();
+        return RELP_ERR_DEVICE;
+    } catch (const std::exception& e) {
+        many->error = e.what();
+        return RELP_ERR_STATE;
+    }
+}
+
+int32_t relp_many_certify_lds_rows(void) { return many_certify_lds_rows(); }
+
+int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* out, double* device_seconds, double* wall_seconds) {
+    if (device_seconds) *device_seconds = 0.0;
+    if (wall_seconds) *wall_seconds = 0.0;
+    // (`out` and its size first: nothing of the handle is read for a caller built against another header)
+    if (!out || out[0].struct_size != (int32_t)sizeof(relp_many_certificate)) return RELP_ERR_ARGUMENT;  // (the one size this struct has had)
+    if (!many || (mode != 0 && mode != 1)) return RELP_ERR_ARGUMENT;
+    if (!many->solved) {
+        many->error = "relp_many_certify needs the results of a relp_many_solve";
+        return RELP_ERR_STATE;
+    }
+    try {
+        const double t_begin = many_now();
+        RELP_HIP(hipSetDevice(many->device));
+        const int n = (int)many->lps.size();
+        many->error.clear();
+        for (int k = 0; k < n; ++k) {
+            out[k] = relp_many_certificate{};
+            out[k].struct_size = (int32_t)sizeof(relp_many_certificate);
+            many->exact[k].clear();
+            many->results[k].certified = 0;
+        }
+        // the batched stage takes the optima; everything else that has a certificate keeps the serial one
+        std::vector<int> batched;
+        std::vector<ManyCertifyItem> items;
+        std::vector<ManyCertifyOutcome> outcomes;
+        if (mode == 0) {
+            for (int k = 0; k < n; ++k)
+                if (many->results[k].status == RELP_OK && many->results[k].kind == RELP_RESULT_FINITE_OPTIMUM) {
+                    batched.push_back(k);
+                    items.push_back(ManyCertifyItem{&many->forms[k], &many->bases[k]});
+                }
+            many_certify_batched(items, many->device, many->streams, &outcomes, device_seconds);
+        }
+        std::vector<int> slot(n, -1);
+        for (size_t s = 0; s < batched.size(); ++s) slot[batched[s]] = (int)s;
+        for (int k = 0; k < n; ++k) {
+            relp_many_certificate& c = out[k];
+            if (!many_serial_certificate_applies(*many, k)) continue;  // path 0: nothing to prove
+            if (slot[k] >= 0) {
+                const ManyCertifyOutcome& oc = outcomes[slot[k]];
+                c.fallback_reason = oc.reason;
+                c.host_seconds = oc.host_seconds;
+                if (oc.reason == MANY_CERTIFY_NONE) {
+                    c.certified = 1;
+                    c.path = 1;
+                    c.digits_primal = oc.digits_primal;
+                    c.digits_dual = oc.digits_dual;
+                    many->exact[k] = oc.objective;
+                    many->results[k].certified = 1;
+                    many->results[k].certify_seconds = oc.host_seconds;
+                    continue;
+                }
+            } else if (mode == 0) {
+                c.fallback_reason = MANY_CERTIFY_KIND;
+            }
+            long long repairs = 0;
+            c.certified = many_serial_certificate(*many, k, &repairs) ? 1 : 0;
+            c.path = 2;
+            c.repair_pivots = repairs;
+            c.host_seconds += many->results[k].certify_seconds;
+        }
+        if (wall_seconds) *wall_seconds = many_now() - t_begin;
         return RELP_OK;
     } catch (const DeviceError& e) {
         many->error = e.what();

@@ -1,0 +1,43 @@
+// The batched exact certificate of relp_many (many_certify.hip): what relp_many_certify (many.hip) hands over and gets back.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "model.hpp"
+
+namespace relp {
+
+// Why the batched stage did not prove an LP (relp_many_certificate.fallback_reason, include/relp_amd.h)
+enum ManyCertifyReason {
+    MANY_CERTIFY_NONE = 0,
+    MANY_CERTIFY_KIND = 1,
+    MANY_CERTIFY_WIDTH = 2,
+    MANY_CERTIFY_SINGULAR_MOD_P = 3,
+    MANY_CERTIFY_DIGITS = 4,
+    MANY_CERTIFY_SIGN = 5
+};
+
+struct ManyCertifyItem {  // a FINITE_OPTIMUM and the basis it ended on (provider columns, -1-k for artificial k)
+    const StandardForm* form = nullptr;
+    const std::vector<int>* basis = nullptr;
+};
+
+struct ManyCertifyOutcome {
+    int reason = MANY_CERTIFY_NONE;  // NONE: proved, `objective` is the exact optimum
+    int digits_primal = 0, digits_dual = 0;
+    double host_seconds = 0.0;
+    std::string objective;
+    std::string message;
+};
+
+// Rows up to which the work matrix of the batched certificate lives in LDS.
+int many_certify_lds_rows();
+
+// One launch (a group per LDS size, as relp_many_solve launches) for all items, one download, then the host stage of every item on
+// at most 16 threads.  `streams`: four streams of the handle.  *device_seconds: the launch (HIP events).
+void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device, hipStream_t* streams, std::vector<ManyCertifyOutcome>* outcomes,
+                          double* device_seconds);
+
+}  // namespace relp
