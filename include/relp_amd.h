@@ -770,15 +770,25 @@ int32_t relp_many_free(relp_many* many);
  * serial certificate (rational reconstruction, verification by exact substitution, sign checks of x_B and of the reduced costs of
  * all non-basic columns, exact objective), on at most 16 threads.  An LP the batched stage does not take, or whose batched proof
  * does not close, goes through the serial certificate of options.certify (its other primes and exact repair pivots included) --
- * per LP, never for the launch.  relp_many_fallback_reason says why. */
+ * per LP, never for the launch.  relp_many_fallback_reason says why.
+ * RELP_MANY_CERTIFY_ALL_KINDS puts the INFEASIBLE and UNBOUNDED results into the same launch.  INFEASIBLE: the two solves on the final
+ * phase-one basis with the phase-one costs (1 on a basic artificial, 0 elsewhere); the proof is the sign checks and a positive
+ * phase-one optimum, which is the proved value.  UNBOUNDED: the two solves with the phase-two costs and a third, B alpha = a_q for
+ * the entering column the solve named; the proof is x_B >= 0, cbar_q < 0 and alpha <= 0 with alpha = 0 where an artificial is basic,
+ * and the proved value is "-inf".  These two have no repair pivots: what the batched stage refutes, the serial certificate refutes. */
 typedef enum relp_many_fallback_reason {
     RELP_MANY_FALLBACK_NONE = 0,            /* the batched stage took it */
-    RELP_MANY_FALLBACK_KIND = 1,            /* INFEASIBLE or UNBOUNDED: these certificates stay serial */
+    RELP_MANY_FALLBACK_KIND = 1,            /* INFEASIBLE or UNBOUNDED in RELP_MANY_CERTIFY_OPTIMA; in ALL_KINDS an UNBOUNDED without a usable entering column */
     RELP_MANY_FALLBACK_WIDTH = 2,           /* a scaled coefficient, cost or right-hand side entry does not fit 62 bits, or the 128-bit residual overflowed */
     RELP_MANY_FALLBACK_SINGULAR_MOD_P = 3,  /* no pivot found modulo the prime */
     RELP_MANY_FALLBACK_DIGITS = 4,          /* more digits than the cap (512 per solve), or the reconstruction failed its exact verification */
     RELP_MANY_FALLBACK_SIGN = 5             /* a sign check failed: the basis needs exact repair pivots */
 } relp_many_fallback_reason;
+typedef enum relp_many_certify_mode {
+    RELP_MANY_CERTIFY_OPTIMA = 0,     /* batched for every FINITE_OPTIMUM; INFEASIBLE and UNBOUNDED by the serial certificate (KIND) */
+    RELP_MANY_CERTIFY_SERIAL = 1,     /* every LP by the serial certificate, as options.certify does */
+    RELP_MANY_CERTIFY_ALL_KINDS = 2   /* batched for every kind: optima, Farkas proofs and rays in the one launch */
+} relp_many_certify_mode;
 typedef struct relp_many_certificate {
     int32_t struct_size;      /* in: sizeof of the caller's header, in element 0 */
     int32_t certified;        /* the exact certificate holds */
@@ -788,12 +798,18 @@ typedef struct relp_many_certificate {
     int64_t repair_pivots;    /* exact repair pivots (serial path only) */
     double  host_seconds;     /* this LP's host stage */
 } relp_many_certificate;
-/* Proves the results of the last relp_many_solve; out[k]: model k.  mode 0: batched (one launch for all LPs, fallback per LP);
- * mode 1: every LP by the serial certificate, as options.certify does, reported in the same struct.
+/* Proves the results of the last relp_many_solve; out[k]: model k.  `mode`: relp_many_certify_mode.  0: batched for the optima (one
+ * launch for all of them, fallback per LP); 1: every LP by the serial certificate, as options.certify does, reported in the same
+ * struct; 2: batched for every kind (results of LPs solved with implicit bounds keep path 0 for the two other verdicts).
  * *device_seconds: the batched launch (HIP events; 0 in mode 1); *wall_seconds: the whole call.  Afterwards
- * relp_many_get_objective_exact returns the proved values.  A NULL handle or `out`, a mode other than 0 and 1 or a struct_size no
- * header ever had is RELP_ERR_ARGUMENT, a call before relp_many_solve RELP_ERR_STATE; both are checked before the device is touched. */
+ * relp_many_get_objective_exact returns the proved values: the optimum, the phase-one optimum of an INFEASIBLE LP, "-inf" for an
+ * UNBOUNDED one.  A NULL handle or `out`, a mode that is none of the three or a struct_size no header ever had is RELP_ERR_ARGUMENT,
+ * a call before relp_many_solve RELP_ERR_STATE; both are checked before the device is touched. */
 int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* out, double* device_seconds, double* wall_seconds);
+/* p-adic digits of model `model` in the last relp_many_certify: digits[0] of B x = b, digits[1] of B' y = c_B, digits[2] of the ray
+ * B alpha = a_q (0 unless a batched UNBOUNDED proof with a non-empty entering column).  All 0 for an LP the batched stage did not
+ * prove.  RELP_ERR_STATE before a relp_many_certify of the last solve. */
+int32_t relp_many_get_certificate_digits(const relp_many* many, int32_t model, int32_t digits[3]);
 /* Rows up to which the batched certificate keeps its work matrix in LDS (198); a per-LP slab of global memory beyond, up to 512. */
 int32_t relp_many_certify_lds_rows(void);
 

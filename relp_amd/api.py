@@ -145,6 +145,9 @@ class ManyCertificate(C.Structure):
 # relp_many_fallback_reason
 MANY_FALLBACK_NONE, MANY_FALLBACK_KIND, MANY_FALLBACK_WIDTH, MANY_FALLBACK_SINGULAR_MOD_P, MANY_FALLBACK_DIGITS, MANY_FALLBACK_SIGN = range(6)
 MANY_FALLBACK_NAMES = ["NONE", "KIND", "WIDTH", "SINGULAR_MOD_P", "DIGITS", "SIGN"]
+# relp_many_certify_mode
+MANY_CERTIFY_OPTIMA, MANY_CERTIFY_SERIAL, MANY_CERTIFY_ALL_KINDS = range(3)
+MANY_CERTIFY_MODE_NAMES = ["OPTIMA", "SERIAL", "ALL_KINDS"]
 
 
 class Stats(C.Structure):
@@ -184,6 +187,8 @@ SYMBOLS = [
     "relp_many_create_with", "relp_many_get_bound_flips", "relp_get_bound_flips",
     # the exact certificate of every LP of a relp_many launch in one further launch (relp_amd/csrc/many_certify.hip)
     "relp_many_certify", "relp_many_certify_lds_rows",
+    # ... of every kind of result, and the digits of its three solves
+    "relp_many_get_certificate_digits",
 ]
 
 
@@ -200,6 +205,7 @@ def lib():
         _lib.relp_many_last_error.restype = C.c_char_p
         _lib.relp_many_last_error.argtypes = [C.c_void_p]
         _lib.relp_many_certify.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ManyCertificate), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        _lib.relp_many_get_certificate_digits.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     return _lib
 
 
@@ -846,15 +852,23 @@ class Many:
 
     def certify(self, mode=0):
         """Proves the results of the last ``solve()``: one ``ManyCertificate`` per model.  ``mode=0``: one further launch for all
-        LPs, the serial certificate for what it does not take; ``mode=1``: every LP by the serial certificate.  Leaves the launch
-        time in ``.certify_device_seconds`` and the time of the call in ``.certify_wall_seconds``; ``objective_exact(i)`` then
-        returns the proved value."""
+        optima, the serial certificate for what it does not take (INFEASIBLE and UNBOUNDED results among it); ``mode=1``: every LP
+        by the serial certificate; ``mode=2`` (``MANY_CERTIFY_ALL_KINDS``): INFEASIBLE and UNBOUNDED results are proved in the
+        same launch.  Leaves the launch time in ``.certify_device_seconds`` and the time of the call in
+        ``.certify_wall_seconds``; ``objective_exact(i)`` then returns the proved value (the phase-one optimum of an infeasible
+        LP, ``"-inf"`` for an unbounded one)."""
         out = (ManyCertificate * len(self.models))()
         out[0].struct_size = C.sizeof(ManyCertificate)
         device, wall = C.c_double(), C.c_double()
         self._check(lib().relp_many_certify(self._h, int(mode), out, C.byref(device), C.byref(wall)))
         self.certify_device_seconds, self.certify_wall_seconds = device.value, wall.value
         return list(out)
+
+    def certificate_digits(self, i):
+        """(primal, dual, ray) p-adic digits of model ``i`` in the last ``certify()``; zeros where the batched stage proved nothing."""
+        out = (C.c_int32 * 3)()
+        self._check(lib().relp_many_get_certificate_digits(self._h, int(i), out))
+        return tuple(out)
 
     def _dimensions(self, i):
         rows, structural = C.c_int32(), C.c_int32()

@@ -914,6 +914,52 @@ std::string certify_objective(const StandardForm& form, const CertifyStatic& sta
     return num.to_string() + "/" + den.to_string();
 }
 
+bool certify_infeasible(const CertifySigns& signs, const std::vector<i64>& cost_basis, const ExactVector& x, std::string* objective,
+                        std::string* message) {
+    if (signs.worst_row >= 0 || signs.worst_col >= 0) { *message = "infeasible: the final phase-one basis is not optimal in exact arithmetic"; return false; }
+    // ---- infeasible: the phase-one optimum (sum of the artificial variables) is positive -------------------------
+    const int m = (int)cost_basis.size();
+    BigInt num(0);
+    for (int k = 0; k < m; ++k)
+        if (cost_basis[k] != 0) num = num + x.numer[k];
+    if (num.sign() <= 0) { *message = "infeasible: the phase-one optimum is zero in exact arithmetic (the LP is feasible)"; return false; }
+    BigInt den = x.denom;
+    BigInt g = BigInt::gcd(num, den);
+    if (!g.is_zero() && !(g == BigInt(1))) {
+        num = num / g;
+        den = den / g;
+    }
+    *objective = num.to_string() + "/" + den.to_string();  // the exact phase-one optimum: the certified infeasibility
+    return true;
+}
+
+bool certify_unbounded_entering(const CertifySigns& signs, const std::vector<char>& in_basis, int entering, std::string* message) {
+    if (signs.worst_row >= 0) { *message = "unbounded: the basis is not primal feasible in exact arithmetic"; return false; }
+    if (entering < 0 || entering >= (int)in_basis.size() || in_basis[entering]) { *message = "unbounded: no entering column"; return false; }
+    if (signs.dhat[entering].sign() >= 0) { *message = "unbounded: the entering column's reduced cost is not negative in exact arithmetic"; return false; }
+    return true;
+}
+
+bool certify_scaled_column(const CertifyStatic& statics, int j, std::vector<i64>* out, std::string* message) {
+    const SparseColumn& column = statics.columns[j];
+    out->assign(statics.row_mult.size(), 0);
+    for (size_t e = 0; e < column.nnz(); ++e) {
+        const i128 v = certify_scaled(column.value[e], statics.row_mult[column.index[e]]);
+        if (!certify_fits(v)) { *message = "scaled coefficient does not fit 62 bits"; return false; }
+        (*out)[column.index[e]] = (i64)v;
+    }
+    return true;
+}
+
+bool certify_unbounded_ray(const std::vector<int>& basis, const ExactVector& alpha, std::string* objective, std::string* message) {
+    for (size_t k = 0; k < basis.size(); ++k) {
+        const int sgn = alpha.numer[k].sign();
+        if (sgn > 0 || (basis[k] < 0 && sgn != 0)) { *message = "unbounded: the ray leaves the feasible region in exact arithmetic"; return false; }
+    }
+    *objective = "-inf";
+    return true;
+}
+
 void certify_basis(const StandardForm& form, const std::vector<int>& basis_columns, int device, hipStream_t stream,
                    std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
                    std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch) {
@@ -971,7 +1017,6 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
     const std::vector<BigInt>& rhs_big = statics->rhs_big;
     const BigInt& rhs_den = statics->rhs_den;
     auto scaled = [&](const Rat& v, i128 mult) { return mul_checked(v.n, mult / v.d); };
-    auto fits = [](i128 v) { return v < ((i128)1 << 62) && v > -((i128)1 << 62); };
     std::vector<int> basis = basis_columns;  // repaired in place by exact pivots when a check fails
     const int max_repairs = 200;
     const auto& primes = CERTIFY_PRIMES;
@@ -1221,42 +1266,19 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         const std::vector<BigInt>& dhat = signs.dhat;
         if (mode == 2) {
             // ---- unbounded ray: x_B >= 0, cbar_q < 0, alpha = B^-1 a_q <= 0 (zero where an artificial is basic) ------------
-            if (worst_row >= 0) { *message = "unbounded: the basis is not primal feasible in exact arithmetic"; return; }
-            if (entering < 0 || entering >= n_p || in_basis[entering]) { *message = "unbounded: no entering column"; return; }
-            if (dhat[entering].sign() >= 0) { *message = "unbounded: the entering column's reduced cost is not negative in exact arithmetic"; return; }
-            std::vector<i64> aq(m, 0);
-            for (size_t e = 0; e < columns[entering].nnz(); ++e) {
-                const i128 v = scaled(columns[entering].value[e], row_mult[columns[entering].index[e]]);
-                if (!fits(v)) { *message = "scaled coefficient does not fit 62 bits"; return; }
-                aq[columns[entering].index[e]] = (i64)v;
-            }
+            if (!certify_unbounded_entering(signs, in_basis, entering, message)) return;
+            std::vector<i64> aq;
+            if (!certify_scaled_column(*statics, entering, &aq, message)) return;
             ExactVector alpha;
             if (!solve(aq, 0, &alpha)) return;
-            for (int k = 0; k < m; ++k) {
-                const int sgn = alpha.numer[k].sign();
-                if (sgn > 0 || (basis[k] < 0 && sgn != 0)) { *message = "unbounded: the ray leaves the feasible region in exact arithmetic"; return; }
-            }
-            *objective = "-inf";
-            *certified = true;
+            *certified = certify_unbounded_ray(basis, alpha, objective, message);
             return;
         }
-        if (mode == 1 && worst_row < 0 && worst_col < 0) {
-            // ---- infeasible: the phase-one optimum (sum of the artificial variables) is positive -------------------------
-            BigInt num(0);
-            for (int k = 0; k < m; ++k)
-                if (cost_basis[k] != 0) num = num + x.numer[k];
-            if (num.sign() <= 0) { *message = "infeasible: the phase-one optimum is zero in exact arithmetic (the LP is feasible)"; return; }
-            BigInt den = x.denom;
-            BigInt g = BigInt::gcd(num, den);
-            if (!g.is_zero() && !(g == BigInt(1))) {
-                num = num / g;
-                den = den / g;
-            }
-            *objective = num.to_string() + "/" + den.to_string();  // the exact phase-one optimum: the certified infeasibility
-            *certified = true;
+        if (mode == 1) {
+            // ---- infeasible: the final phase-one basis is optimal and its optimum is positive --------------------------------
+            *certified = certify_infeasible(signs, cost_basis, x, objective, message);
             return;
         }
-        if (mode == 1) { *message = "infeasible: the final phase-one basis is not optimal in exact arithmetic"; return; }
         if (worst_row < 0 && worst_col < 0) {
             // ---- optimal: objective = (sum_k cost_basis[k] X_k) / (cost_mult * Dx) + fixed ----------------------
             *objective = certify_objective(form, *statics, cost_basis, x);

@@ -89,4 +89,17 @@ bool certify_signs(const CertifyStatic& statics, const MatrixData& md, const std
 std::string certify_objective(const StandardForm& form, const CertifyStatic& statics, const std::vector<long long>& cost_basis,
                               const ExactVector& x);
 
+// ---- the final checks of the two other verdicts (after certify_signs with the same `mode`) -------------------------------------
+// Mode 1, INFEASIBLE: the final phase-one basis is optimal (no negative x_B, no negative reduced cost under the phase-one costs) and
+// its optimum, the sum of the basic artificial variables, is positive.  *objective: that optimum, reduced, as "num/den".
+bool certify_infeasible(const CertifySigns& signs, const std::vector<long long>& cost_basis, const ExactVector& x, std::string* objective,
+                        std::string* message);
+// Mode 2, UNBOUNDED, before the ray is solved for: x_B >= 0 and the provider column `entering` is non-basic with cbar_q < 0.
+bool certify_unbounded_entering(const CertifySigns& signs, const std::vector<char>& in_basis, int entering, std::string* message);
+// Provider column j scaled by the row multipliers, dense (the right-hand side of B alpha = a_q).  False with `message` set when an
+// entry does not fit 62 bits.
+bool certify_scaled_column(const CertifyStatic& statics, int j, std::vector<long long>* out, std::string* message);
+// Mode 2, the ray: alpha = B^-1 a_q <= 0, and exactly zero on a row whose basic variable is an artificial.  *objective: "-inf".
+bool certify_unbounded_ray(const std::vector<int>& basis, const ExactVector& alpha, std::string* objective, std::string* message);
+
 }  // namespace relp

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -620,6 +621,7 @@ struct relp_many {
     std::vector<std::vector<double>> solutions;  // every column of MatrixData
     std::vector<std::string> exact;
     std::vector<int> entering;                // device column a verdict of UNBOUNDED names (the ray of its certificate)
+    std::vector<std::array<int32_t, 3>> certificate_digits;  // of the last relp_many_certify: primal, dual, ray (empty before one)
     std::string error;
 
     void release() {
@@ -653,17 +655,24 @@ bool many_serial_certificate_applies(const relp_many& many, int k) {
                                      (!many.lps[k].bounded && (res.kind == RELP_RESULT_INFEASIBLE || res.kind == RELP_RESULT_UNBOUNDED)));
 }
 
+// The certificate of model k's verdict in certify_basis's terms: its mode, and for UNBOUNDED the provider column of the ray (-1: none).
+void many_certificate_kind(const relp_many& many, int k, int* mode, int* ray) {
+    const ManyHostLP& lp = many.lps[k];
+    const int kind = many.results[k].kind;
+    const int entering = many.entering[k];
+    *mode = kind == RELP_RESULT_INFEASIBLE ? 1 : kind == RELP_RESULT_UNBOUNDED ? 2 : 0;
+    *ray = kind == RELP_RESULT_UNBOUNDED && entering >= lp.n_art && entering < lp.n ? entering - lp.n_art : -1;
+}
+
 // The exact certificate of relp_solve_relaxation for model k of the last solve (certify_basis: its other primes and its exact repair
 // pivots included).  Sets results[k].certified and certify_seconds, and exact[k].
 bool many_serial_certificate(relp_many& many, int k, long long* repairs) {
-    const ManyHostLP& lp = many.lps[k];
     relp_many_result& res = many.results[k];
     const double t0 = many_now();
     bool ok = false;
     std::string message;
-    const int mode = res.kind == RELP_RESULT_INFEASIBLE ? 1 : res.kind == RELP_RESULT_UNBOUNDED ? 2 : 0;
-    const int entering = many.entering[k];
-    const int ray = res.kind == RELP_RESULT_UNBOUNDED && entering >= lp.n_art && entering < lp.n ? entering - lp.n_art : -1;
+    int mode = 0, ray = -1;
+    many_certificate_kind(many, k, &mode, &ray);
     many.certify_scratch.statics.reset();  // (what it keeps belongs to one LP)
     many.certify_scratch.digit_hints[0] = many.certify_scratch.digit_hints[1] = 0;
     *repairs = 0;
@@ -969,6 +978,7 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
             }
         }
         many->solved = true;
+        many->certificate_digits.clear();
         if (results) std::copy(many->results.begin(), many->results.end(), results);
         return RELP_OK;
     } catch (const DeviceError& e) {
@@ -987,7 +997,8 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
     if (wall_seconds) *wall_seconds = 0.0;
     // (`out` and its size first: nothing of the handle is read for a caller built against another header)
     if (!out || out[0].struct_size != (int32_t)sizeof(relp_many_certificate)) return RELP_ERR_ARGUMENT;  // (the one size this struct has had)
-    if (!many || (mode != 0 && mode != 1)) return RELP_ERR_ARGUMENT;
+    if (mode != RELP_MANY_CERTIFY_OPTIMA && mode != RELP_MANY_CERTIFY_SERIAL && mode != RELP_MANY_CERTIFY_ALL_KINDS) return RELP_ERR_ARGUMENT;
+    if (!many) return RELP_ERR_ARGUMENT;
     if (!many->solved) {
         many->error = "relp_many_certify needs the results of a relp_many_solve";
         return RELP_ERR_STATE;
@@ -1003,16 +1014,21 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
             many->exact[k].clear();
             many->results[k].certified = 0;
         }
-        // the batched stage takes the optima; everything else that has a certificate keeps the serial one
+        many->certificate_digits.assign(n, std::array<int32_t, 3>{0, 0, 0});
+        // the batched stage takes the optima, and in RELP_MANY_CERTIFY_ALL_KINDS the two other verdicts that have a certificate;
+        // everything else that has one keeps the serial certificate
         std::vector<int> batched;
         std::vector<ManyCertifyItem> items;
         std::vector<ManyCertifyOutcome> outcomes;
-        if (mode == 0) {
-            for (int k = 0; k < n; ++k)
-                if (many->results[k].status == RELP_OK && many->results[k].kind == RELP_RESULT_FINITE_OPTIMUM) {
-                    batched.push_back(k);
-                    items.push_back(ManyCertifyItem{&many->forms[k], &many->bases[k]});
-                }
+        if (mode != RELP_MANY_CERTIFY_SERIAL) {
+            for (int k = 0; k < n; ++k) {
+                const bool optimum = many->results[k].status == RELP_OK && many->results[k].kind == RELP_RESULT_FINITE_OPTIMUM;
+                if (!optimum && !(mode == RELP_MANY_CERTIFY_ALL_KINDS && many_serial_certificate_applies(*many, k))) continue;
+                ManyCertifyItem item{&many->forms[k], &many->bases[k]};
+                many_certificate_kind(*many, k, &item.mode, &item.ray);
+                batched.push_back(k);
+                items.push_back(item);
+            }
             many_certify_batched(items, many->device, many->streams, &outcomes, device_seconds);
         }
         std::vector<int> slot(n, -1);
@@ -1029,12 +1045,13 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
                     c.path = 1;
                     c.digits_primal = oc.digits_primal;
                     c.digits_dual = oc.digits_dual;
+                    many->certificate_digits[k] = {oc.digits_primal, oc.digits_dual, oc.digits_ray};
                     many->exact[k] = oc.objective;
                     many->results[k].certified = 1;
                     many->results[k].certify_seconds = oc.host_seconds;
                     continue;
                 }
-            } else if (mode == 0) {
+            } else if (mode == RELP_MANY_CERTIFY_OPTIMA) {
                 c.fallback_reason = MANY_CERTIFY_KIND;
             }
             long long repairs = 0;
@@ -1052,6 +1069,13 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
         many->error = e.what();
         return RELP_ERR_STATE;
     }
+}
+
+int32_t relp_many_get_certificate_digits(const relp_many* many, int32_t model, int32_t digits[3]) {
+    if (!many || !digits || model < 0 || model >= (int32_t)many->lps.size()) return RELP_ERR_ARGUMENT;
+    if (!many->solved || many->certificate_digits.size() != many->lps.size()) return RELP_ERR_STATE;
+    std::copy(many->certificate_digits[model].begin(), many->certificate_digits[model].end(), digits);
+    return RELP_OK;
 }
 
 int32_t relp_many_get_basis(const relp_many* many, int32_t model, int32_t* basis) {

@@ -11,16 +11,21 @@
 //      workgroup ends;
 //   b. lifts B x = b and B' y = c_B (Dixon): per digit x_s = C (r mod p) mod p, r <- (r - B x_s) / p exactly in 128-bit
 //      accumulators, with the "not divisible" and "overflow" flags of dixon_residual_kernel kept per LP.  Between the two solves the
-//      work matrix is transposed in place, so both run the same wave-per-row product.
+//      work matrix is transposed in place, so both run the same wave-per-row product.  An UNBOUNDED result has a third solve, the
+//      ray B alpha = a_q of the entering column the solve named: it runs against the untransposed matrix, after the primal lifting
+//      and before the transpose, through the same vectors of LDS.
+// The costs of the dual solve are the phase-two costs for an optimum and an unbounded LP and the phase-one costs (1 on a basic
+// artificial, 0 elsewhere) for an infeasible one, whose basis is the final phase-one basis: the kernel does not know the difference.
 // No atomics; every reduction runs in a fixed order (a wave's butterfly, then the waves in order), so the digits of an LP do not
-// depend on the launch it is in.  Digits go to global memory as digits[lp][solve][s][i].
+// depend on the launch it is in.  Digits go to global memory as digits[lp][solve][s][i], the solves in the order primal, dual, ray.
 //
 // Two tiers, one source: `many_certify_kernel<true>` keeps the work matrix in LDS (4 m^2 bytes beside 28 m bytes of vectors: up to
 // 198 rows), `many_certify_kernel<false>` in a per-LP slab of global memory (199 to 512 rows).
 //
 // After the one launch and one download every LP is finished on the host by the functions `certify_basis` uses (assembly of the
 // digits, combined-unknown rational reconstruction, VERIFICATION BY EXACT SUBSTITUTION, sign checks, reduced costs of all non-basic
-// columns, exact objective), on at most 16 threads, results written by index.
+// columns, exact objective; for the two other verdicts the final checks of certify_parts.hpp: a positive phase-one optimum, the
+// signs of the ray), on at most 16 threads, results written by index.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,7 +52,7 @@ constexpr int MC_MAX_ROWS = 512;
 constexpr size_t MC_LDS_BYTES = 160 * 1024;   // a CU of gfx950
 constexpr size_t MC_STATIC_LDS = 1024;        // the kernel's __shared__ scalars, rounded up
 constexpr int MC_TIERS = 4;                   // launch groups: three LDS sizes and the global tier
-// Digits per solve an LP may ask for.  The digit buffer of an LP is then at most 2 x 512 digits x 512 rows x 4 bytes = 2 MiB, and
+// Digits per solve an LP may ask for.  The digit buffer of an LP is then at most 3 x 512 digits x 512 rows x 4 bytes = 3 MiB, and
 // the buffer of a launch is kept within MC_DIGIT_BUDGET: an LP that would pass it falls back (DIGITS) like one above the cap.
 constexpr int MC_MAX_DIGITS = 512;
 constexpr size_t MC_DIGIT_BUDGET = (size_t)1 << 30;
@@ -69,10 +74,11 @@ struct ManyCertLP {
     int m;
     u32 p;
     int k_primal, k_dual;   // digits of B x = b and of B' y = c_B (0: the right-hand side is zero, nothing to lift)
+    int k_ray;              // digits of B alpha = a_q (0: no ray solve -- not UNBOUNDED, or an entering column without entries)
     long long start_off;    // row_start / col_start of this LP (m + 1 entries each)
     long long nz_off;       // its entries in col_index / row_value and row_index / value
-    long long vec_off;      // rhs / cost (m entries each)
-    long long digit_off;    // digits: k_primal x m, then k_dual x m
+    long long vec_off;      // rhs / cost / ray (m entries each)
+    long long digit_off;    // digits: k_primal x m, then k_dual x m, then k_ray x m
     long long slab_off;     // global tier: the work matrix in `slab`
 };
 
@@ -80,7 +86,7 @@ struct ManyCertArgs {
     const ManyCertLP* lps;
     const int* order;       // the LPs of this launch group
     const int *row_start, *col_index, *col_start, *row_index;
-    const i64 *row_value, *value, *rhs, *cost;
+    const i64 *row_value, *value, *rhs, *cost, *ray;
     u32* digits;
     u32* slab;
     int* flags;             // [lp][4]: singular mod p, residual not divisible, residual overflow, unused
@@ -249,12 +255,17 @@ __global__ void __launch_bounds__(MC_THREADS) many_certify_kernel(ManyCertArgs a
         __syncthreads();
     }
 
-    // ---- b. the two liftings -------------------------------------------------------------------------------------------------
+    // ---- b. the liftings: primal, ray (UNBOUNDED only), then dual against the transposed matrix -----------------------------------
     u32* digits = a.digits + lp.digit_off;
     if (lp.k_primal > 0) {
         for (int i = tid; i < m; i += MC_THREADS) s_r[i] = a.rhs[lp.vec_off + i];
         __syncthreads();
         mc_lift(C, m, p, lp.k_primal, row_start, col_index, row_value, s_r, s_rmod, s_x, digits, s_flags);
+    }
+    if (lp.k_ray > 0) {  // B alpha = a_q: the rows of B again, before the work matrix is transposed
+        for (int i = tid; i < m; i += MC_THREADS) s_r[i] = a.ray[lp.vec_off + i];
+        __syncthreads();
+        mc_lift(C, m, p, lp.k_ray, row_start, col_index, row_value, s_r, s_rmod, s_x, digits + (size_t)(lp.k_primal + lp.k_dual) * m, s_flags);
     }
     if (lp.k_dual > 0) {
         // (B')^-1 = (B^-1)': transposed in place; the rows of B' are the columns of B
@@ -282,9 +293,9 @@ double mc_now() {
 struct Prepared {
     std::shared_ptr<const CertifyStatic> statics;
     IntegerBasis B;
-    std::vector<i64> rhs, cost_basis;
+    std::vector<i64> rhs, cost_basis, ray;  // ray: a_q scaled by the row multipliers (mode 2), else zeros
     std::vector<char> in_basis;
-    int k_primal = 0, k_dual = 0;
+    int k_primal = 0, k_dual = 0, k_ray = 0;
     int slot = -1;  // index among the LPs of the launch, -1: not launched
     long long digit_off = 0;
     double work = 0.0;
@@ -358,13 +369,20 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
         Prepared& pr = prepared[k];
         try {
             const StandardForm& form = *items[k].form;
+            const int mode = items[k].mode, ray = items[k].ray;
             pr.statics = certify_static(form, &out.message);
-            if (pr.statics && pr.statics->cost_mult == 0) out.message = "cost scaling overflows 128 bits";
-            if (!pr.statics || pr.statics->cost_mult == 0 ||
-                !certify_integer_basis(*pr.statics, form.data, *items[k].basis, 0, &pr.B, &pr.cost_basis, &pr.in_basis, &out.message)) {
+            const bool no_costs = pr.statics && mode != 1 && pr.statics->cost_mult == 0;  // (the phase-one certificate has its own costs)
+            if (no_costs) out.message = "cost scaling overflows 128 bits";
+            if (!pr.statics || no_costs ||
+                !certify_integer_basis(*pr.statics, form.data, *items[k].basis, mode, &pr.B, &pr.cost_basis, &pr.in_basis, &out.message)) {
                 out.reason = MANY_CERTIFY_WIDTH;
+            } else if (mode == 2 && (ray < 0 || ray >= (int)pr.in_basis.size() || pr.in_basis[ray])) {
+                out.reason = MANY_CERTIFY_KIND;
+                out.message = "unbounded: no entering column";
             } else {
                 const int m = pr.B.m;
+                pr.ray.assign(m, 0);
+                if (mode == 2 && !certify_scaled_column(*pr.statics, ray, &pr.ray, &out.message)) out.reason = MANY_CERTIFY_WIDTH;
                 pr.rhs.resize(m);
                 for (int i = 0; i < m && out.reason == MANY_CERTIFY_NONE; ++i) {
                     const BigInt& v = pr.statics->rhs_big[i];
@@ -380,13 +398,14 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
                 if (out.reason == MANY_CERTIFY_NONE) {
                     pr.k_primal = mc_digit_count(pr.B, pr.rhs, 0, p);
                     pr.k_dual = mc_digit_count(pr.B, pr.cost_basis, 1, p);
-                    if (m > MC_MAX_ROWS || pr.k_primal > MC_MAX_DIGITS || pr.k_dual > MC_MAX_DIGITS) {
+                    pr.k_ray = mode == 2 ? mc_digit_count(pr.B, pr.ray, 0, p) : 0;
+                    if (m > MC_MAX_ROWS || pr.k_primal > MC_MAX_DIGITS || pr.k_dual > MC_MAX_DIGITS || pr.k_ray > MC_MAX_DIGITS) {
                         out.reason = MANY_CERTIFY_DIGITS;
                         out.message = "more p-adic digits than the batched certificate lifts";
                     }
                     const bool lds = m <= mc_lds_tier_rows();
                     pr.bucket = !lds ? 3 : m <= 48 ? 0 : m <= 96 ? 1 : 2;
-                    pr.work = (double)m * m * m + (double)(pr.k_primal + pr.k_dual) * ((double)m * m + (double)pr.B.value.size());
+                    pr.work = (double)m * m * m + (double)(pr.k_primal + pr.k_dual + pr.k_ray) * ((double)m * m + (double)pr.B.value.size());
                 }
             }
         } catch (const RatOverflow& e) {
@@ -399,14 +418,14 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
     // ---- pack: per-LP offsets; launch order by LDS size, longest estimated work first (ties: the caller's order) -----------------
     std::vector<ManyCertLP> desc;
     std::vector<int> lp_of_slot, row_start, col_index, col_start, row_index;
-    std::vector<i64> row_value, value, rhs, cost;
+    std::vector<i64> row_value, value, rhs, cost, ray;
     long long digit_words = 0, slab_words = 0;
     for (int k = 0; k < n; ++k) {
         ManyCertifyOutcome& out = (*outcomes)[k];
         Prepared& pr = prepared[k];
         if (out.reason != MANY_CERTIFY_NONE) continue;
         const int m = pr.B.m;
-        const long long own = (long long)(pr.k_primal + pr.k_dual) * m;
+        const long long own = (long long)(pr.k_primal + pr.k_dual + pr.k_ray) * m;
         if ((size_t)(digit_words + own) * sizeof(u32) > MC_DIGIT_BUDGET) {
             out.reason = MANY_CERTIFY_DIGITS;
             out.message = "the digit buffer of the launch is full";
@@ -417,6 +436,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
         d.p = p;
         d.k_primal = pr.k_primal;
         d.k_dual = pr.k_dual;
+        d.k_ray = pr.k_ray;
         d.start_off = (long long)row_start.size();
         d.nz_off = (long long)col_index.size();
         d.vec_off = (long long)rhs.size();
@@ -435,6 +455,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
         value.insert(value.end(), pr.B.value.begin(), pr.B.value.end());
         rhs.insert(rhs.end(), pr.rhs.begin(), pr.rhs.end());
         cost.insert(cost.end(), pr.cost_basis.begin(), pr.cost_basis.end());
+        ray.insert(ray.end(), pr.ray.begin(), pr.ray.end());
     }
     const int launched = (int)desc.size();
     std::vector<u32> digits((size_t)digit_words);
@@ -478,6 +499,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
         args.value = upload(value);
         args.rhs = upload(rhs);
         args.cost = upload(cost);
+        args.ray = upload(ray);
         args.digits = memory.alloc<u32>((size_t)digit_words);
         args.slab = memory.alloc<u32>((size_t)slab_words);
         args.flags = upload(flags);  // (zeros)
@@ -536,6 +558,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
         const double t0 = mc_now();
         out.digits_primal = pr.k_primal;
         out.digits_dual = pr.k_dual;
+        out.digits_ray = pr.k_ray;
         try {
             const int m = pr.B.m;
             const int* flag = flags.data() + (size_t)4 * pr.slot;
@@ -547,7 +570,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
                 out.message = flag[2] ? "Dixon residual overflow (coefficients too large for the 128-bit path)" : "Dixon residual not divisible by p";
             } else {
                 CertifyTimes times;
-                ExactVector x, y;
+                ExactVector x, y, alpha;
                 auto solve = [&](const std::vector<i64>& r, int transpose, int K, const u32* base, ExactVector* z) {
                     z->numer.assign(m, BigInt(0));
                     z->denom = BigInt(1);
@@ -558,19 +581,27 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
                 };
                 const u32* base = digits.data() + pr.digit_off;
                 const StandardForm& form = *items[k].form;
+                const std::vector<int>& basis = *items[k].basis;
+                const int mode = items[k].mode;
                 CertifySigns signs;
-                if (!solve(pr.rhs, 0, pr.k_primal, base, &x) || !solve(pr.cost_basis, 1, pr.k_dual, base + (size_t)pr.k_primal * m, &y)) {
+                if (!solve(pr.rhs, 0, pr.k_primal, base, &x) || !solve(pr.cost_basis, 1, pr.k_dual, base + (size_t)pr.k_primal * m, &y) ||
+                    !solve(pr.ray, 0, pr.k_ray, base + (size_t)(pr.k_primal + pr.k_dual) * m, &alpha)) {
                     out.reason = MANY_CERTIFY_DIGITS;
                     out.message = "the reconstruction from the digits of the batched certificate failed its exact verification";
                 } else {
                     x.denom = x.denom * pr.statics->rhs_den;  // x_B = numer / (denom * rhs_den); the sign checks only need denom > 0
-                    if (!certify_signs(*pr.statics, form.data, *items[k].basis, pr.in_basis, 0, x, y, false, &signs, &out.message) ||
-                        signs.worst_row >= 0 || signs.worst_col >= 0) {
-                        out.reason = MANY_CERTIFY_SIGN;
-                        if (out.message.empty()) out.message = "the basis is not optimal in exact arithmetic";
-                    } else {
-                        out.objective = certify_objective(form, *pr.statics, pr.cost_basis, x);
+                    bool holds = certify_signs(*pr.statics, form.data, basis, pr.in_basis, mode, x, y, false, &signs, &out.message);
+                    if (holds && mode == 0) {
+                        holds = signs.worst_row < 0 && signs.worst_col < 0;
+                        if (holds) out.objective = certify_objective(form, *pr.statics, pr.cost_basis, x);
+                        else out.message = "the basis is not optimal in exact arithmetic";
+                    } else if (holds && mode == 1) {
+                        holds = certify_infeasible(signs, pr.cost_basis, x, &out.objective, &out.message);
+                    } else if (holds) {
+                        holds = certify_unbounded_entering(signs, pr.in_basis, items[k].ray, &out.message) &&
+                                certify_unbounded_ray(basis, alpha, &out.objective, &out.message);
                     }
+                    if (!holds) out.reason = MANY_CERTIFY_SIGN;  // (modes 1 and 2 have no repair pivots: the serial certificate says the same)
                 }
             }
         } catch (const RatOverflow& e) {

@@ -19,14 +19,16 @@ enum ManyCertifyReason {
     MANY_CERTIFY_SIGN = 5
 };
 
-struct ManyCertifyItem {  // a FINITE_OPTIMUM and the basis it ended on (provider columns, -1-k for artificial k)
+struct ManyCertifyItem {  // a result and the basis it ended on (provider columns, -1-k for artificial k)
     const StandardForm* form = nullptr;
     const std::vector<int>* basis = nullptr;
+    int mode = 0;   // as certify_basis: 0 FINITE_OPTIMUM, 1 INFEASIBLE (the final phase-one basis), 2 UNBOUNDED
+    int ray = -1;   // mode 2: the provider column the solve named as entering (-1: none, the item falls back with KIND)
 };
 
 struct ManyCertifyOutcome {
-    int reason = MANY_CERTIFY_NONE;  // NONE: proved, `objective` is the exact optimum
-    int digits_primal = 0, digits_dual = 0;
+    int reason = MANY_CERTIFY_NONE;  // NONE: proved, `objective` is the exact optimum (mode 1: of phase one; mode 2: "-inf")
+    int digits_primal = 0, digits_dual = 0, digits_ray = 0;
     double host_seconds = 0.0;
     std::string objective;
     std::string message;
