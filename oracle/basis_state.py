@@ -1,0 +1,342 @@
+"""The exact state of a simplex basis (oracle side; test infrastructure only -- nothing here imports ``relp_amd``).
+
+Everything a handle holds after any number of pivots is a function of the current basis alone: the rows of ``B^-1``,
+``x_B = B^-1 b``, the objective ``c_B' x_B``, the reduced costs ``c_j - c_B' B^-1 a_j`` and the steepest-edge weights
+``gamma_j = 1 + |B^-1 a_j|^2`` (the recurrences that carry them are exact: pivot_rule.rs:243-296).  ``BasisState`` computes them
+from the basis WITHOUT walking a pivot path, so that paths no step-by-step oracle can follow (batched launches, the deferred
+product form, a polish inside the loop) are checked against the same truth.
+
+Index spaces are those of the binding: a basis entry >= 0 is a provider column (for ``load_dense_le``: structurals, then the
+slacks), ``-1 - k`` is artificial ``k``; every per-column result is indexed like ``Solver.relative_costs()`` -- the artificials
+first, then the provider's columns.
+
+``B^-1 = N / D`` comes from a fraction-free Gauss-Jordan elimination in Python integers (each step one rank-one update of a numpy
+``object`` array; every division is exact).  Basic columns with a single entry -- slacks, artificials -- are eliminated by hand
+first, so the elimination runs on the Schur block of the other columns only.  Each exact quantity ``q`` is returned as a pair of
+f64 arrays ``hi = float(q)``, ``lo = float(q - hi)``; products with the columns of ``A`` are then formed in ``np.longdouble``
+from ``hi + lo``.  Where ``longdouble`` is no wider than f64 (``EXTENDED`` false) the per-column quantities are exact integer dot
+products instead, on the sample of columns that ``columns_to_check`` returns.
+"""
+from fractions import Fraction
+from math import lcm
+
+import numpy as np
+
+EXTENDED = np.finfo(np.longdouble).nmant > 52
+
+
+def split(num, den):
+    """``num / den`` (Python integers) as ``(hi, lo)``: the nearest f64 and the f64 nearest to what it leaves."""
+    if num == 0:
+        return 0.0, 0.0
+    hi = num / den  # (int / int is correctly rounded)
+    p, q = hi.as_integer_ratio()
+    rest = num * q - p * den
+    return hi, (rest / (den * q) if rest else 0.0)
+
+
+def split_fraction(value):
+    value = Fraction(value)
+    return split(value.numerator, value.denominator)
+
+
+def long_double(hi, lo):
+    return np.asarray(hi, dtype=np.longdouble) + np.asarray(lo, dtype=np.longdouble)
+
+
+class DenseLE:
+    """The provider columns ``[A | I]`` of ``A x <= b`` as ``Solver.load_dense_le`` numbers them.  ``a``: (n, m) integers."""
+
+    def __init__(self, a_columns):
+        self.a = np.asarray(a_columns, dtype=np.int64)
+        self.n, self.m = self.a.shape
+
+    def __len__(self):
+        return self.n + self.m
+
+    def __getitem__(self, j):
+        if j < self.n:
+            return [(i, int(v)) for i, v in enumerate(self.a[j]) if v != 0]
+        return [(j - self.n, 1)]
+
+    def matrix(self):
+        return np.concatenate([self.a.T, np.eye(self.m, dtype=np.int64)], axis=1)
+
+
+def fraction_free_inverse(matrix):
+    """``(N, D)`` with ``matrix^-1 = N / D``: Gauss-Jordan on ``[matrix | I]`` whose entries stay integers (after step k every entry
+    is a minor of order k + 1, so the division by the previous pivot is exact).  ``matrix``: (s, s) ``object`` array of ints."""
+    s = matrix.shape[0]
+    if s == 0:
+        return np.zeros((0, 0), dtype=object), 1
+    work = np.concatenate([matrix.astype(object), np.array(np.eye(s, dtype=np.int64), dtype=object)], axis=1)
+    previous = 1
+    for k in range(s):
+        p = next((i for i in range(k, s) if work[i, k] != 0), None)
+        if p is None:
+            raise ZeroDivisionError("singular basis")
+        if p != k:
+            work[[k, p]] = work[[p, k]]
+        pivot = work[k, k]
+        column = work[:, k].copy()
+        column[k] = 0
+        row = work[k, k:].copy()
+        work[:, k:] = (work[:, k:] * pivot - np.outer(column, row)) // previous  # (columns before k are finished and not read again)
+        work[k, k:] = row
+        previous = pivot
+    return work[:, s:], previous
+
+
+class BasisState:
+    def __init__(self, columns, b, cost, basis, artificial_rows=(), phase=2, extended=None):
+        """``columns[j]``: provider column j as ``[(row, int or Fraction)]`` (a ``DenseLE``, or a list of such lists); ``b``, ``cost``:
+        right-hand side and provider costs; ``basis``: as ``Solver.basis()``; ``artificial_rows[k]``: the row of artificial k;
+        ``phase`` 1 prices the artificials at 1 and everything else at 0.  ``extended=False`` forces the exact integer path."""
+        self.columns = columns
+        self.m = len(b)
+        self.b = [Fraction(int(v)) if not isinstance(v, Fraction) else v for v in b]
+        self.artificial_rows = [int(r) for r in artificial_rows]
+        self.n_art = len(self.artificial_rows)
+        self.n = self.n_art + len(columns)
+        if phase == 1:
+            self.cost = [Fraction(1)] * self.n_art + [Fraction(0)] * len(columns)
+        else:
+            self.cost = [Fraction(0)] * self.n_art + [v if isinstance(v, Fraction) else Fraction(int(v)) for v in cost]
+            self.cost += [Fraction(0)] * (self.n - len(self.cost))  # (`cost` may stop at the last structural: slacks cost nothing)
+        self.basis = [self.n_art + int(c) if c >= 0 else -1 - int(c) for c in basis]
+        assert len(self.basis) == self.m and len(set(self.basis)) == self.m
+        self.extended = EXTENDED if extended is None else bool(extended)
+        self.is_basic = np.zeros(self.n, dtype=bool)
+        self.is_basic[self.basis] = True
+        self._invert()
+        self._vectors()
+        self._matrix = None
+
+    # ---- the columns ----------------------------------------------------------------------------
+    def column(self, j):
+        """Column j of ``[artificials | provider]`` as ``[(row, Fraction)]``."""
+        if j < self.n_art:
+            return [(self.artificial_rows[j], Fraction(1))]
+        return [(int(i), Fraction(v)) for i, v in self.columns[j - self.n_art] if v != 0]
+
+    def _integer_column(self, j):
+        """``(rows, integer values, scale)`` with column = values / scale."""
+        entries = self.column(j)
+        scale = lcm(*[v.denominator for _, v in entries]) if entries else 1
+        return [i for i, _ in entries], np.array([int(v * scale) for _, v in entries], dtype=object), scale
+
+    def matrix(self):
+        """All n columns as an (m, n) ``longdouble`` array (``hi + lo`` of every entry)."""
+        if self._matrix is None:
+            out = np.zeros((self.m, self.n), dtype=np.longdouble)
+            for k, row in enumerate(self.artificial_rows):
+                out[row, k] = 1
+            if hasattr(self.columns, "matrix"):
+                out[:, self.n_art:] = self.columns.matrix()
+            else:
+                for j in range(self.n_art, self.n):
+                    for i, v in self.column(j):
+                        hi, lo = split(v.numerator, v.denominator)
+                        out[i, j] = np.longdouble(hi) + np.longdouble(lo)
+            self._matrix = out
+        return self._matrix
+
+    def basis_matrix(self):
+        """``B`` in f64 (every entry rounded once, as the device holds it)."""
+        out = np.zeros((self.m, self.m))
+        for k, j in enumerate(self.basis):
+            for i, v in self.column(j):
+                out[i, k] = float(v)
+        return out
+
+    # ---- B^-1 = num[k, :] / den[k] ----------------------------------------------------------------
+    def _invert(self):
+        m = self.m
+        columns = [self.column(j) for j in self.basis]
+        scale = []  # B' = B diag(scale) is an integer matrix whose single-entry columns are unit vectors
+        for entries in columns:
+            if not entries:
+                raise ZeroDivisionError("singular basis")
+            scale.append(1 / entries[0][1] if len(entries) == 1 else Fraction(lcm(*[v.denominator for _, v in entries])))
+        unit = [k for k in range(m) if len(columns[k]) == 1]
+        unit_row = [columns[k][0][0] for k in unit]
+        if len(set(unit_row)) != len(unit_row):
+            raise ZeroDivisionError("singular basis")
+        other = [k for k in range(m) if len(columns[k]) != 1]
+        taken = set(unit_row)
+        rest = [i for i in range(m) if i not in taken]
+        scaled = np.zeros((m, len(other)), dtype=object)
+        for a, k in enumerate(other):
+            for i, v in columns[k]:
+                scaled[i, a] = int(v * scale[k])
+        # rows `rest` hold nothing of the unit columns: B'[rest, other] is the Schur block, and
+        #   x_other = B11^-1 y_rest,   x_u = y_row(u) - B'[row(u), other] x_other
+        block, det = fraction_free_inverse(scaled[rest, :])
+        num = np.zeros((m, m), dtype=object)
+        if other:
+            num[np.ix_(other, rest)] = block
+            if unit:
+                num[np.ix_(unit, rest)] = -scaled[unit_row, :].dot(block)
+        for k, row in zip(unit, unit_row):
+            num[k, row] = det
+        den = []
+        for k in range(m):
+            d = det * scale[k].denominator
+            if scale[k].numerator != 1:
+                num[k, :] = num[k, :] * scale[k].numerator
+            if d < 0:
+                d = -d
+                num[k, :] = -num[k, :]
+            den.append(d)
+        self.num, self.den = num, den
+        self.inverse_hi = np.zeros((m, m))
+        self.inverse_lo = np.zeros((m, m))
+        for k in range(m):
+            for i in np.flatnonzero(num[k, :] != 0):
+                self.inverse_hi[k, i], self.inverse_lo[k, i] = split(num[k, i], den[k])
+
+    def inverse_exact(self, k, i):
+        return Fraction(self.num[k, i], self.den[k])
+
+    def inverse_row(self, k):
+        """Row k of ``B^-1`` as ``(hi, lo)``."""
+        return self.inverse_hi[k], self.inverse_lo[k]
+
+    def inverse_long(self):
+        return long_double(self.inverse_hi, self.inverse_lo)
+
+    # ---- x_B, the objective, pi --------------------------------------------------------------------
+    def _vectors(self):
+        m = self.m
+        b_scale = lcm(*[v.denominator for v in self.b])
+        b_int = np.array([int(v * b_scale) for v in self.b], dtype=object)
+        x_num = self.num.dot(b_int)
+        self.x_exact = [Fraction(int(x_num[k]), self.den[k] * b_scale) for k in range(m)]
+        self.x_hi, self.x_lo = (np.array(v) for v in zip(*[split_fraction(x) for x in self.x_exact]))
+        c_basic = [self.cost[j] for j in self.basis]
+        self.objective_exact = sum((c * x for c, x in zip(c_basic, self.x_exact)), Fraction(0))
+        common = lcm(*self.den)
+        c_scale = lcm(*[c.denominator for c in c_basic])
+        weights = np.array([int(c * c_scale) * (common // d) for c, d in zip(c_basic, self.den)], dtype=object)
+        self.pi_num, self.pi_den = weights.dot(self.num), common * c_scale  # pi' = c_B' B^-1
+        self.pi_hi, self.pi_lo = (np.array(v) for v in zip(*[split(int(p), self.pi_den) for p in self.pi_num]))
+
+    def x_basic(self):
+        return self.x_hi, self.x_lo
+
+    def objective(self):
+        return split_fraction(self.objective_exact)
+
+    # ---- per-column quantities, exact ---------------------------------------------------------------
+    def reduced_cost_exact(self, j):
+        rows, values, scale = self._integer_column(j)
+        return self.cost[j] - Fraction(int(self.pi_num[rows].dot(values)), self.pi_den * scale)
+
+    def alpha_exact(self, j):
+        """``B^-1 a_j`` as m Fractions."""
+        rows, values, scale = self._integer_column(j)
+        products = self.num[:, rows].dot(values)
+        return [Fraction(int(products[k]), self.den[k] * scale) for k in range(self.m)]
+
+    def gamma_exact(self, j):
+        return 1 + sum((v * v for v in self.alpha_exact(j)), Fraction(0))
+
+    # ---- per-column quantities over many columns: longdouble from hi + lo, or exact on a sample ------
+    def columns_to_check(self, n_grouped=0, group=16, minimum=256):
+        """Every column where ``longdouble`` is extended.  Otherwise a sample for the exact integer path: the first and the last column
+        of every ``group`` of the first ``n_grouped`` provider columns, the whole last group, every single-entry column (their products
+        cost nothing) and evenly spaced further ones up to ``minimum``."""
+        if self.extended:
+            return np.arange(self.n)
+        first = self.n_art
+        chosen = set(range(self.n_art))
+        for start in range(0, n_grouped, group):
+            chosen.add(first + start)
+            chosen.add(first + min(start + group, n_grouped) - 1)
+        chosen.update(range(first + max(0, (n_grouped - 1) // group * group), first + n_grouped))
+        chosen.update(j for j in range(first + n_grouped, self.n) if len(self.columns[j - first]) == 1)
+        target = min(self.n, minimum)
+        if len(chosen) < target:
+            for j in np.linspace(0, self.n - 1, target - len(chosen)).astype(int):
+                chosen.add(int(j))
+        j = 0
+        while len(chosen) < target:
+            chosen.add(j)
+            j += 1
+        return np.array(sorted(chosen))
+
+    def reduced_costs(self, columns):
+        if not self.extended:
+            return np.array([float(self.reduced_cost_exact(int(j))) for j in columns], dtype=np.longdouble)
+        cost = long_double(*zip(*[split_fraction(self.cost[int(j)]) for j in columns]))
+        return cost - long_double(self.pi_hi, self.pi_lo) @ self.matrix()[:, columns]
+
+    def alpha(self, j):
+        if not self.extended:
+            return np.array([float(v) for v in self.alpha_exact(j)], dtype=np.longdouble)
+        return self.inverse_long() @ self.matrix()[:, j]
+
+    def gammas(self, columns):
+        if not self.extended:
+            return np.array([float(self.gamma_exact(int(j))) for j in columns], dtype=np.longdouble)
+        columns = np.asarray(columns)
+        inverse = self.inverse_long()
+        out = np.zeros(len(columns), dtype=np.longdouble)
+        for start in range(0, len(columns), 512):
+            alphas = inverse @ self.matrix()[:, columns[start:start + 512]]
+            out[start:start + 512] = 1 + (alphas * alphas).sum(axis=0)
+        return out
+
+    def right_multiply(self, rows, values):
+        """``v' B^-1`` for a sparse row ``v`` of small integers, as a ``longdouble`` vector (exact to its last bit or two)."""
+        total = [Fraction(0)] * self.m
+        for r, v in zip(rows, values):
+            for i in np.flatnonzero(self.num[int(r), :] != 0):
+                total[i] += int(v) * Fraction(self.num[int(r), i], self.den[int(r)])
+        return long_double(*zip(*[split_fraction(t) for t in total]))
+
+
+# ---- the f64 restatement of the Newton-Schulz inversion and polish (the yardstick for the device's error after either) ----------
+def newton_schulz_inverse(B):
+    """``Solver::invert_from_scratch`` in numpy f64: ``X0 = B' / (|B|_1 |B|_inf)``, ``X <- X + X (I - B X)``, its stop rule."""
+    m = B.shape[0]
+    identity = np.eye(m)
+    X = B.T / (np.abs(B).sum(axis=0).max() * np.abs(B).sum(axis=1).max())
+    previous = np.inf
+    for it in range(200):
+        R = identity - B @ X
+        residual = np.abs(R).max()
+        X = X + X @ R
+        if residual < 1e-11:
+            break
+        if it > 60 and residual >= previous:
+            break
+        previous = residual
+    return X
+
+
+def newton_schulz_polish(B, X):
+    """``Solver::polish`` in numpy f64: at most two steps from the drifted inverse ``X``, with its stop rule."""
+    identity = np.eye(B.shape[0])
+    X = np.array(X, dtype=np.float64)
+    for _ in range(2):
+        R = identity - B @ X
+        residual = np.abs(R).max()
+        if residual < 1e-12:
+            break
+        if residual >= 0.5:
+            return newton_schulz_inverse(B)
+        X = X + X @ R
+        if residual < 1e-8:
+            break
+    return X
+
+
+def polished_tolerance(reference, exact):
+    """The bound on the device's error after a polish or a from-scratch inversion: 16 times the error of the numpy f64 restatement
+    of the same iteration at the same basis (the matrix cores sum in another order than BLAS, and the restatement's error is one
+    sample of rounding noise), and never below 8 ulps of the largest entry.  ``exact``: ``longdouble``.  Returns (bound, error of
+    the restatement)."""
+    exact = np.asarray(exact, dtype=np.longdouble)
+    error = float(np.abs(np.asarray(reference, dtype=np.longdouble) - exact).max())
+    return max(16.0 * error, 8.0 * 2.0 ** -53 * float(np.abs(exact).max())), error

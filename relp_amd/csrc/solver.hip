@@ -1780,9 +1780,13 @@ void Solver::ratio(int column, int* row, double* alpha_out) {
     c.status = ST_RUNNING;
     c.forced_q = column;
     c.forced_p = -1;
+    // the multi-block FTRAN (ftran_partial_kernel) has no mode: it computes nothing once the budget of the last batch is used up,
+    // and the ratio test would then read the alpha of an earlier column
+    if (ftran_slices_ > 0) c.budget = c.iters + 1;
     write_ctl(c);
     enqueue_ftran_ratio(2);
     c = read_ctl();
+    c.budget = before.budget;
     *row = c.p;
     if (alpha_out) {
         RELP_HIP(hipMemcpyAsync(alpha_out, d_.alpha, d_.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
