@@ -313,6 +313,12 @@ int32_t relp_model_cost(const relp_model* model, int32_t j, double* cost);
 int32_t relp_model_right_hand_side(const relp_model* model, double* rhs);
 int32_t relp_model_initial_pivots(const relp_model* model, int32_t capacity, int32_t* count, int32_t* rows, int32_t* columns);
 int32_t relp_model_fixed_cost(const relp_model* model, double* fixed_cost);
+/* exact forms of cost_value(j), right_hand_side() (nr_rows pairs) and the fixed cost, as relp_model_column_exact gives a column:
+ * int64 pairs num/den (reduced, den > 0), RELP_ERR_OVERFLOW when a value does not fit int64.  With relp_model_column_exact they
+ * are all a caller needs to check a witness of relp_get_witness_exact without parsing the file again. */
+int32_t relp_model_cost_exact(const relp_model* model, int32_t j, int64_t* num, int64_t* den);
+int32_t relp_model_right_hand_side_exact(const relp_model* model, int64_t* num, int64_t* den);
+int32_t relp_model_fixed_cost_exact(const relp_model* model, int64_t* num, int64_t* den);
 
 /* Lifetime.  relp_create fails with RELP_ERR_DEVICE when no MI355X/HIP device is usable. */
 int32_t relp_create(const relp_options* options, relp_handle** out);
@@ -378,6 +384,29 @@ int32_t relp_get_objective_exact(const relp_handle* handle, char* buffer, int32_
  * buffer == NULL the call only reports the two sizes. */
 int32_t relp_get_solution_exact(const relp_handle* handle, int32_t original, int32_t capacity, int32_t* count, int32_t* index,
                                 char* buffer, int64_t buffer_capacity, int64_t* length);
+/* The exact vectors the certificate proved the last result with (needs options.certify and a certified result).  They refer to the
+ * standard form relp_model_* / relp_get_* describe: min c'x, A x = b, x >= 0 over the provider columns (structural columns, then
+ * slack columns: nr_columns of relp_get_dimensions; nr_rows rows).  Artificial columns are not part of that form: a basic
+ * artificial has value 0 and is never reported.
+ *   RELP_WITNESS_PRIMAL, by provider column, of a FINITE_OPTIMUM or UNBOUNDED result: A x = b, x >= 0; for an optimum
+ *                        c'x + fixed cost = the exact objective.
+ *   RELP_WITNESS_DUAL,   by row, of a FINITE_OPTIMUM: c_j - y'a_j >= 0 for EVERY provider column j and y'b + fixed cost = the exact
+ *                        objective; of an INFEASIBLE result (the Farkas vector): y'a_j <= 0 for every provider column j and
+ *                        y'b > 0, the value relp_get_objective_exact returns for it (the phase-one optimum).
+ *   RELP_WITNESS_RAY,    by provider column, of an UNBOUNDED result: d >= 0, A d = 0, c'd < 0; d_q = 1 for the entering column,
+ *                        d_basis[i] = -alpha_i where a provider column is basic, 0 elsewhere: x + t d is feasible for every t >= 0.
+ * After exact repair pivots the vectors are those of the basis that was finally proved.  Any other combination, and a result that
+ * is not certified, is RELP_ERR_STATE with relp_last_error naming it; a `which` outside the enum is RELP_ERR_ARGUMENT.  Under
+ * RELP_CARRY_NETWORK the optimum is proved from the forest: PRIMAL is returned, DUAL is RELP_ERR_STATE.
+ * Return protocol of relp_get_solution_exact: only non-zero entries, ascending index, "num/den" (reduced, den > 0) separated by
+ * '\n' and terminated by 0; with index == NULL and buffer == NULL the call only reports *count and *length. */
+typedef enum relp_witness {
+    RELP_WITNESS_PRIMAL = 0,
+    RELP_WITNESS_DUAL = 1,
+    RELP_WITNESS_RAY = 2
+} relp_witness;
+int32_t relp_get_witness_exact(const relp_handle* handle, int32_t which, int32_t capacity, int32_t* count, int32_t* index,
+                               char* buffer, int64_t buffer_capacity, int64_t* length);
 /* Name of variable j of the loaded file (the `String` of `Solution::solution_values`, data/linear_program/solution.rs:15-24);
  * "Xj" for providers built without names.  *length receives the full length. */
 int32_t relp_get_variable_name(const relp_handle* handle, int32_t j, char* buffer, int32_t capacity, int32_t* length);
@@ -812,6 +841,24 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
 int32_t relp_many_get_certificate_digits(const relp_many* many, int32_t model, int32_t digits[3]);
 /* Rows up to which the batched certificate keeps its work matrix in LDS (198); a per-LP slab of global memory beyond, up to 512. */
 int32_t relp_many_certify_lds_rows(void);
+
+/* ---- what the certificate of relp_many_certify proved, handed out --------------------------------------------------------------------
+ * relp_many_keep_witnesses(many, 1) BEFORE a relp_many_certify makes that call keep, per certified LP, the exact vectors of its
+ * proof: those of the batched stage on path 1, those of the serial certificate on path 2 (after its repair pivots).  The default is
+ * off -- three vectors of m big integers per LP are hundreds of megabytes for a few hundred 500-row LPs -- and then
+ * relp_many_certify keeps and returns exactly what it did before this switch existed.  The certificates themselves do not depend on
+ * the switch.  A new relp_many_solve or relp_many_certify drops what was kept.
+ * relp_many_get_witness_exact: as relp_get_witness_exact, for model `model` (the same table of `which`, index spaces and return
+ * protocol).  relp_many_get_solution_exact: as relp_get_solution_exact (original == 0: the structural columns; else the variables
+ * of the file), for a certified FINITE_OPTIMUM.  RELP_ERR_STATE with relp_many_last_error saying why: before a relp_many_certify
+ * of the last solve, after one with the switch off, for an LP that is not certified (path 0 among them: the INFEASIBLE and
+ * UNBOUNDED results of an LP solved with implicit bounds), for a witness its kind of result does not have.  RELP_ERR_ARGUMENT: a
+ * model index out of range, a `which` outside relp_witness, capacities that are too small. */
+int32_t relp_many_keep_witnesses(relp_many* many, int32_t on);
+int32_t relp_many_get_witness_exact(const relp_many* many, int32_t model, int32_t which, int32_t capacity, int32_t* count,
+                                    int32_t* index, char* buffer, int64_t buffer_capacity, int64_t* length);
+int32_t relp_many_get_solution_exact(const relp_many* many, int32_t model, int32_t original, int32_t capacity, int32_t* count,
+                                     int32_t* index, char* buffer, int64_t buffer_capacity, int64_t* length);
 
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);

@@ -8,4 +8,6 @@ from .api import (  # noqa: F401
     FINITE_OPTIMUM, INFEASIBLE, UNBOUNDED, ITERATION_LIMIT,
     STEEPEST_EDGE, DANTZIG, FIRST_PROFITABLE, FIRST_PROFITABLE_MEMORY,
     STOP_NO_ENTERING, STOP_UNBOUNDED, STOP_BUDGET,
+    WITNESS_PRIMAL, WITNESS_DUAL, WITNESS_RAY,
 )
+from .witness import WitnessError, check_optimum, check_infeasible, check_unbounded  # noqa: F401

@@ -19,6 +19,7 @@ STEEPEST_EDGE, DANTZIG, FIRST_PROFITABLE, FIRST_PROFITABLE_MEMORY = 0, 1, 2, 3
 STOP_NO_ENTERING, STOP_UNBOUNDED, STOP_BUDGET = 1, 2, 3
 CARRY_EXPLICIT, CARRY_LU, CARRY_LU_INVERSE, CARRY_NETWORK = 0, 1, 2, 3
 RATIO_HARRIS, RATIO_TEXTBOOK, RATIO_AUTO = 0, 1, 2
+WITNESS_PRIMAL, WITNESS_DUAL, WITNESS_RAY = 0, 1, 2  # relp_witness
 
 
 class RelpError(RuntimeError):
@@ -189,6 +190,9 @@ SYMBOLS = [
     "relp_many_certify", "relp_many_certify_lds_rows",
     # ... of every kind of result, and the digits of its three solves
     "relp_many_get_certificate_digits",
+    # the exact vectors behind a certified result (x, y / Farkas, ray), and the exact model data a caller checks them against
+    "relp_get_witness_exact", "relp_many_keep_witnesses", "relp_many_get_witness_exact", "relp_many_get_solution_exact",
+    "relp_model_cost_exact", "relp_model_right_hand_side_exact", "relp_model_fixed_cost_exact",
 ]
 
 
@@ -211,6 +215,21 @@ def lib():
 
 def _ptr(array, ctype):
     return array.ctypes.data_as(C.POINTER(ctype))
+
+
+def _exact_values(check, call):
+    """The return protocol of ``relp_get_solution_exact``: a size query, then the values.  ``call(capacity, count, index, buffer,
+    buffer_capacity, length)`` is the C function with its leading arguments bound.  Returns a dict index -> ``Fraction``."""
+    from fractions import Fraction
+    count, length = C.c_int32(), C.c_int64()
+    check(call(0, C.byref(count), None, None, C.c_int64(0), C.byref(length)))
+    if count.value == 0:
+        return {}
+    index = np.zeros(count.value, dtype=np.int32)
+    buf = C.create_string_buffer(length.value)
+    check(call(count.value, C.byref(count), _ptr(index, C.c_int32), buf, C.c_int64(length.value), C.byref(length)))
+    texts = buf.value.decode().split("\n")
+    return {int(index[k]): Fraction(texts[k]) for k in range(count.value)}
 
 
 def default_options(**overrides):
@@ -431,6 +450,34 @@ class Model:
         lib().relp_model_right_hand_side(self._h, _ptr(out, C.c_double))
         return out
 
+    def cost_exact(self, j):
+        """``cost_value(j)`` as a ``Fraction`` (``relp_model_cost_exact``)."""
+        from fractions import Fraction
+        num, den = C.c_int64(), C.c_int64()
+        status = lib().relp_model_cost_exact(self._h, int(j), C.byref(num), C.byref(den))
+        if status != OK:
+            raise RelpError(status, "cost_exact")
+        return Fraction(num.value, den.value)
+
+    def right_hand_side_exact(self):
+        """``right_hand_side()`` as a list of ``Fraction`` (``relp_model_right_hand_side_exact``)."""
+        from fractions import Fraction
+        num = np.zeros(max(1, self.nr_rows), dtype=np.int64)
+        den = np.ones(max(1, self.nr_rows), dtype=np.int64)
+        status = lib().relp_model_right_hand_side_exact(self._h, _ptr(num, C.c_int64), _ptr(den, C.c_int64))
+        if status != OK:
+            raise RelpError(status, "right_hand_side_exact")
+        return [Fraction(int(num[i]), int(den[i])) for i in range(self.nr_rows)]
+
+    def fixed_cost_exact(self):
+        """The fixed cost of the standard form as a ``Fraction`` (``relp_model_fixed_cost_exact``)."""
+        from fractions import Fraction
+        num, den = C.c_int64(), C.c_int64()
+        status = lib().relp_model_fixed_cost_exact(self._h, C.byref(num), C.byref(den))
+        if status != OK:
+            raise RelpError(status, "fixed_cost_exact")
+        return Fraction(num.value, den.value)
+
     def pivot_element_indices(self):
         count = C.c_int32()
         rows = np.zeros(self.nr_rows, dtype=np.int32)
@@ -604,17 +651,14 @@ class Solver:
         """``OptimizationResult::FiniteOptimum(SparseVector<RationalBig>)`` in exact form (``relp_get_solution_exact``): a dict
         index -> ``Fraction``.  ``original=False``: structural columns of the standard form after ``reconstruct_solution``;
         ``original=True``: the variables of the file (``compute_full_solution_with_reduced_solution``), by file order."""
-        from fractions import Fraction
-        count, length = C.c_int32(), C.c_int64()
-        self._check(lib().relp_get_solution_exact(self._h, int(bool(original)), 0, C.byref(count), None, None, C.c_int64(0), C.byref(length)))
-        if count.value == 0:
-            return {}
-        index = np.zeros(count.value, dtype=np.int32)
-        buf = C.create_string_buffer(length.value)
-        self._check(lib().relp_get_solution_exact(self._h, int(bool(original)), count.value, C.byref(count), _ptr(index, C.c_int32), buf,
-                                                  C.c_int64(length.value), C.byref(length)))
-        texts = buf.value.decode().split("\n")
-        return {int(index[k]): Fraction(texts[k]) for k in range(count.value)}
+        return _exact_values(self._check, lambda *rest: lib().relp_get_solution_exact(self._h, int(bool(original)), *rest))
+
+    def witness_exact(self, which):
+        """The exact vector the certificate proved the last result with (``relp_get_witness_exact``): a dict index -> ``Fraction``
+        of its non-zero entries.  ``WITNESS_PRIMAL`` (by provider column: FINITE_OPTIMUM, UNBOUNDED), ``WITNESS_DUAL`` (by row:
+        the dual solution of a FINITE_OPTIMUM, the Farkas vector of an INFEASIBLE result), ``WITNESS_RAY`` (by provider column:
+        UNBOUNDED).  ``relp_amd.witness`` checks them against the model without this library."""
+        return _exact_values(self._check, lambda *rest: lib().relp_get_witness_exact(self._h, int(which), *rest))
 
     def variable_name(self, j):
         length = C.c_int32()
@@ -850,13 +894,15 @@ class Many:
         self.kernel_seconds = seconds.value
         return list(results)
 
-    def certify(self, mode=0):
+    def certify(self, mode=0, witnesses=False):
         """Proves the results of the last ``solve()``: one ``ManyCertificate`` per model.  ``mode=0``: one further launch for all
         optima, the serial certificate for what it does not take (INFEASIBLE and UNBOUNDED results among it); ``mode=1``: every LP
         by the serial certificate; ``mode=2`` (``MANY_CERTIFY_ALL_KINDS``): INFEASIBLE and UNBOUNDED results are proved in the
         same launch.  Leaves the launch time in ``.certify_device_seconds`` and the time of the call in
         ``.certify_wall_seconds``; ``objective_exact(i)`` then returns the proved value (the phase-one optimum of an infeasible
-        LP, ``"-inf"`` for an unbounded one)."""
+        LP, ``"-inf"`` for an unbounded one).  ``witnesses=True`` (``relp_many_keep_witnesses``) keeps the exact vectors of every
+        proof for ``solution_exact(i)`` and ``witness_exact(i, which)``; the certificates are the same either way."""
+        self._check(lib().relp_many_keep_witnesses(self._h, int(bool(witnesses))))
         out = (ManyCertificate * len(self.models))()
         out[0].struct_size = C.sizeof(ManyCertificate)
         device, wall = C.c_double(), C.c_double()
@@ -898,3 +944,11 @@ class Many:
         buf = C.create_string_buffer(length.value + 1)
         self._check(lib().relp_many_get_objective_exact(self._h, int(i), buf, length.value + 1, C.byref(length)))
         return buf.value.decode()
+
+    def solution_exact(self, i, original=False):
+        """As ``Solver.solution_exact`` for model ``i``, a FINITE_OPTIMUM certified by ``certify(..., witnesses=True)``."""
+        return _exact_values(self._check, lambda *rest: lib().relp_many_get_solution_exact(self._h, int(i), int(bool(original)), *rest))
+
+    def witness_exact(self, i, which):
+        """As ``Solver.witness_exact`` for model ``i`` after ``certify(..., witnesses=True)``: a dict index -> ``Fraction``."""
+        return _exact_values(self._check, lambda *rest: lib().relp_many_get_witness_exact(self._h, int(i), int(which), *rest))

@@ -8,6 +8,7 @@
 
 #include "network.hpp"
 #include "presolve.hpp"
+#include "exact_values.hpp"
 #include "solver.hpp"
 
 using namespace relp;
@@ -375,6 +376,36 @@ int32_t relp_model_column_exact(const relp_model* model, int32_t j, int32_t capa
     }
     return RELP_OK;
 }
+namespace {
+bool fits_int64(const Rat& v) { return v.n <= INT64_MAX && v.n >= INT64_MIN && v.d <= INT64_MAX; }
+}  // namespace
+int32_t relp_model_cost_exact(const relp_model* model, int32_t j, int64_t* num, int64_t* den) {
+    if (!model || !num || !den || j < 0 || j >= model->form.data.nr_columns()) return RELP_ERR_ARGUMENT;
+    const Rat v = model->form.data.cost_value(j);
+    if (!fits_int64(v)) return RELP_ERR_OVERFLOW;
+    *num = (int64_t)v.n;
+    *den = (int64_t)v.d;
+    return RELP_OK;
+}
+int32_t relp_model_right_hand_side_exact(const relp_model* model, int64_t* num, int64_t* den) {
+    if (!model || !num || !den) return RELP_ERR_ARGUMENT;
+    const auto values = model->form.data.right_hand_side();
+    for (const Rat& v : values)
+        if (!fits_int64(v)) return RELP_ERR_OVERFLOW;
+    for (size_t i = 0; i < values.size(); ++i) {
+        num[i] = (int64_t)values[i].n;
+        den[i] = (int64_t)values[i].d;
+    }
+    return RELP_OK;
+}
+int32_t relp_model_fixed_cost_exact(const relp_model* model, int64_t* num, int64_t* den) {
+    if (!model || !num || !den) return RELP_ERR_ARGUMENT;
+    const Rat& v = model->form.fixed_cost;
+    if (!fits_int64(v)) return RELP_ERR_OVERFLOW;
+    *num = (int64_t)v.n;
+    *den = (int64_t)v.d;
+    return RELP_OK;
+}
 int32_t relp_model_cost(const relp_model* model, int32_t j, double* cost) {
     if (!model || !cost || j < 0 || j >= model->form.data.nr_columns()) return RELP_ERR_ARGUMENT;
     *cost = model->form.data.cost_value(j).to_double();
@@ -633,42 +664,6 @@ int32_t relp_get_original_solution(const relp_handle* h, int32_t capacity, doubl
     return RELP_OK;
 }
 
-// Exact back-mapping of general_form/mod.rs:753-771, 840-934 (the f64 twin is StandardForm::original_solution).
-static std::vector<BigRat> original_solution_exact(const StandardForm& form, const std::vector<BigRat>& standardised) {
-    const bool identity = form.active_to_original.empty();
-    std::vector<BigRat> out((size_t)form.nr_file_variables());
-    std::vector<char> known(out.size(), 0);
-    for (int j = 0; j < form.nr_original; ++j) {
-        BigRat x = standardised[j];
-        if (j < (int)form.free_negative_part.size() && form.free_negative_part[j] >= 0) x -= standardised[form.free_negative_part[j]];
-        x -= BigRat(form.data.variables[j].shift);
-        if (form.data.variables[j].flipped) x = -x;
-        const int original = identity ? j : form.active_to_original[j];
-        out[original] = x;
-        known[original] = 1;
-    }
-    bool progress = true;
-    while (progress) {
-        progress = false;
-        for (const auto& [original, how] : form.removed) {
-            if (known[original]) continue;
-            bool ready = true;
-            BigRat value(how.constant);
-            if (how.function_of_others)
-                for (const auto& [k, c] : how.coefficients) {
-                    if (!known[k]) { ready = false; break; }
-                    value -= BigRat(c) * out[k];
-                }
-            if (ready) {
-                out[original] = value;
-                known[original] = 1;
-                progress = true;
-            }
-        }
-    }
-    return out;
-}
-
 int32_t relp_get_solution_exact(const relp_handle* h, int32_t original, int32_t capacity, int32_t* count, int32_t* index,
                                 char* buffer, int64_t buffer_capacity, int64_t* length) {
     REQUIRE_LOADED(h);
@@ -679,35 +674,33 @@ int32_t relp_get_solution_exact(const relp_handle* h, int32_t original, int32_t 
         return RELP_ERR_STATE;
     }
     try {
-        const StandardForm& form = sv.form();
-        const int n_structural = form.data.nr_normal_variables();
-        std::vector<std::pair<int, std::string>> values;
-        const auto basics = exact_primal_values(*sv.exact_primal);  // every provider column, slacks included
-        if (!original) {
-            for (const auto& entry : basics)  // reconstruct_solution (matrix_data.rs:402-411): the slack columns are dropped
-                if (entry.first < n_structural) values.push_back(entry);
-        } else {
-            std::vector<BigRat> standardised((size_t)n_structural);
-            for (const auto& [j, text] : basics)
-                if (j < n_structural) standardised[j] = BigRat::parse(text);
-            const std::vector<BigRat> full = original_solution_exact(form, standardised);
-            for (size_t j = 0; j < full.size(); ++j)
-                if (!full[j].is_zero()) values.push_back({(int)j, full[j].to_string()});
-        }
-        *count = (int32_t)values.size();
-        int64_t needed = 0;
-        for (const auto& entry : values) needed += (int64_t)entry.second.size() + 1;
-        if (length) *length = needed;
-        if (!index && !buffer) return RELP_OK;  // size query
-        if (capacity < *count || buffer_capacity < needed || !index || !buffer) return RELP_ERR_ARGUMENT;
-        int64_t at = 0;
-        for (size_t k = 0; k < values.size(); ++k) {
-            index[k] = values[k].first;
-            std::memcpy(buffer + at, values[k].second.data(), values[k].second.size());
-            at += (int64_t)values[k].second.size();
-            buffer[at++] = k + 1 < values.size() ? '\n' : '\0';
-        }
-        return RELP_OK;
+        // (exact_primal_values: every provider column, slacks included)
+        const ExactValues values = exact_solution_values(sv.form(), exact_primal_values(*sv.exact_primal), original != 0);
+        return return_exact_values(values, capacity, count, index, buffer, buffer_capacity, length);
+    } catch (const std::exception& e) {
+        const_cast<relp_handle*>(h)->error = e.what();
+        return RELP_ERR_NUMERICAL;
+    }
+}
+
+int32_t relp_get_witness_exact(const relp_handle* h, int32_t which, int32_t capacity, int32_t* count, int32_t* index, char* buffer,
+                               int64_t buffer_capacity, int64_t* length) {
+    REQUIRE_LOADED(h);
+    if (!count || capacity < 0 || buffer_capacity < 0 || which < RELP_WITNESS_PRIMAL || which > RELP_WITNESS_RAY) return RELP_ERR_ARGUMENT;
+    const Solver& sv = *h->solver;
+    auto refuse = [&](const std::string& why) {
+        const_cast<relp_handle*>(h)->error = why;
+        return RELP_ERR_STATE;
+    };
+    if (!sv.last_result.certified || (!sv.exact_witnesses && !sv.exact_primal))
+        return refuse("no exact witness: the last result is not certified (set options.certify and solve)");
+    const std::string refusal = witness_refusal(sv.last_result.kind, which);
+    if (!refusal.empty()) return refuse(refusal);
+    if (!sv.exact_witnesses && which != RELP_WITNESS_PRIMAL)
+        return refuse("RELP_CARRY_NETWORK proves its optimum from the forest: it keeps the exact primal solution only, no dual solution and no ray");
+    try {
+        const ExactValues values = sv.exact_witnesses ? exact_witness_values(*sv.exact_witnesses, which) : exact_primal_values(*sv.exact_primal);
+        return return_exact_values(values, capacity, count, index, buffer, buffer_capacity, length);
     } catch (const std::exception& e) {
         const_cast<relp_handle*>(h)->error = e.what();
         return RELP_ERR_NUMERICAL;

@@ -736,18 +736,56 @@ struct ExactPrimal {  // (declared in solver.hpp)
     std::vector<BigInt> numer;  // x_B[k] = numer[k] / denom
     BigInt denom;
 };
+namespace {
+std::string reduced_text(BigInt n, BigInt d) {  // "num/den", den > 0
+    if (d.sign() < 0) { n = -n; d = -d; }
+    const BigInt g = BigInt::gcd(n, d);
+    if (!g.is_zero() && !(g == BigInt(1))) { n = n / g; d = d / g; }
+    return n.to_string() + "/" + d.to_string();
+}
+}  // namespace
 std::vector<std::pair<int, std::string>> exact_primal_values(const ExactPrimal& primal) {
     std::vector<std::pair<int, std::string>> out;
     for (size_t k = 0; k < primal.basis.size(); ++k) {
         if (primal.basis[k] < 0 || primal.numer[k].sign() == 0) continue;
-        BigInt n = primal.numer[k], d = primal.denom;
-        if (d.sign() < 0) { n = -n; d = -d; }
-        const BigInt g = BigInt::gcd(n, d);
-        if (!g.is_zero() && !(g == BigInt(1))) { n = n / g; d = d / g; }
-        out.push_back({primal.basis[k], n.to_string() + "/" + d.to_string()});
+        out.push_back({primal.basis[k], reduced_text(primal.numer[k], primal.denom)});
     }
     std::sort(out.begin(), out.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
     return out;
+}
+
+int exact_witness_mode(const ExactWitnesses& witnesses) { return witnesses.mode; }
+
+std::vector<std::pair<int, std::string>> exact_witness_values(const ExactWitnesses& w, int which) {
+    std::vector<std::pair<int, std::string>> out;
+    if (which == RELP_WITNESS_DUAL) {  // by row, already ascending
+        for (size_t i = 0; i < w.y.numer.size(); ++i)
+            if (w.y.numer[i].sign() != 0) out.push_back({(int)i, reduced_text(w.y.numer[i], w.y.denom)});
+        return out;
+    }
+    const bool ray = which == RELP_WITNESS_RAY;
+    const ExactVector& v = ray ? w.alpha : w.x;
+    for (size_t k = 0; k < w.basis.size() && k < v.numer.size(); ++k) {
+        if (w.basis[k] < 0 || v.numer[k].sign() == 0) continue;  // (an artificial: 0, checked by the certificate)
+        out.push_back({w.basis[k], reduced_text(ray ? -v.numer[k] : v.numer[k], v.denom)});
+    }
+    if (ray) out.push_back({w.entering, "1/1"});
+    std::sort(out.begin(), out.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    return out;
+}
+
+std::shared_ptr<const ExactWitnesses> make_exact_witnesses(const CertifyStatic& statics, int mode, const std::vector<int>& basis, int entering,
+                                                          ExactVector& x, ExactVector& y, ExactVector& alpha) {
+    auto kept = std::make_shared<ExactWitnesses>();
+    kept->mode = mode;
+    kept->basis = basis;
+    kept->entering = entering;
+    kept->x = std::move(x);
+    kept->y.numer.resize(y.numer.size());
+    for (size_t i = 0; i < y.numer.size(); ++i) kept->y.numer[i] = y.numer[i] * big_from_i128(statics.row_mult[i]);
+    kept->y.denom = mode == 1 ? y.denom : y.denom * big_from_i128(statics.cost_mult);
+    if (mode == 2) kept->alpha = std::move(alpha);
+    return kept;
 }
 
 std::shared_ptr<const ExactPrimal> make_exact_primal(const std::vector<int>& columns, const std::vector<Rat>& values) {
@@ -962,7 +1000,8 @@ bool certify_unbounded_ray(const std::vector<int>& basis, const ExactVector& alp
 
 void certify_basis(const StandardForm& form, const std::vector<int>& basis_columns, int device, hipStream_t stream,
                    std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
-                   std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch) {
+                   std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch,
+                   std::shared_ptr<const ExactWitnesses>* witnesses) {
     // digit_hints[0 / 1]: p-adic digits the primal / dual solve of this LP needed last time (0: unknown).  The number of digits is
     // found by doubling from 32 (Cramer's bound over-estimates it three-fold); a handle that solves the same LP again -- a warm
     // start, a batch pass, a re-solve after a bound change -- starts where the last certificate ended instead of paying for the
@@ -971,6 +1010,7 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
     int* digit_hints = scratch && mode == 0 ? scratch->digit_hints : no_hints;
     std::mutex scratch_guard;
     if (primal) primal->reset();
+    if (witnesses) witnesses->reset();
     objective->clear();
     *certified = false;
     *repair_pivots = 0;
@@ -1272,11 +1312,14 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
             ExactVector alpha;
             if (!solve(aq, 0, &alpha)) return;
             *certified = certify_unbounded_ray(basis, alpha, objective, message);
+            if (*certified && witnesses) *witnesses = make_exact_witnesses(*statics, mode, basis, entering, x, y, alpha);
             return;
         }
         if (mode == 1) {
             // ---- infeasible: the final phase-one basis is optimal and its optimum is positive --------------------------------
             *certified = certify_infeasible(signs, cost_basis, x, objective, message);
+            ExactVector no_ray;
+            if (*certified && witnesses) *witnesses = make_exact_witnesses(*statics, mode, basis, -1, x, y, no_ray);
             return;
         }
         if (worst_row < 0 && worst_col < 0) {
@@ -1288,10 +1331,12 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
             if (primal) {  // OptimizationResult::FiniteOptimum(x) in exact form (algorithm/mod.rs:43-47), kept as integers over one denominator
                 auto kept = std::make_shared<ExactPrimal>();
                 kept->basis = basis;
-                kept->numer = std::move(x.numer);
+                kept->numer = witnesses ? x.numer : std::move(x.numer);
                 kept->denom = x.denom;
                 *primal = kept;
             }
+            ExactVector no_ray;
+            if (witnesses) *witnesses = make_exact_witnesses(*statics, mode, basis, -1, x, y, no_ray);  // (of the basis after the repair pivots)
             return;
         }
         if (round == max_repairs) break;

@@ -47,6 +47,18 @@ struct ExactVector {           // numer[i] / denom
     BigInt denom = BigInt(1);
 };
 
+// The exact vectors a certificate proved its verdict with (declared in solver.hpp), in the terms of the caller's LP: the row and
+// cost multipliers of the integer scaling are folded in by make_exact_witnesses.  Big integers over one denominator per vector;
+// the "num/den" texts are made on demand (exact_witness_values).
+struct ExactWitnesses {
+    int mode = 0;               // as certify_basis: 0 FINITE_OPTIMUM, 1 INFEASIBLE, 2 UNBOUNDED
+    std::vector<int> basis;     // the basis that was finally proved: provider column per row (-1-k: artificial k)
+    int entering = -1;          // mode 2: the provider column q of the ray
+    ExactVector x;              // x_B[k] = x.numer[k] / x.denom
+    ExactVector y;              // y_i = y.numer[i] / y.denom per row: the dual solution (mode 1: the Farkas vector)
+    ExactVector alpha;          // mode 2: alpha = B^-1 a_q, d_{basis[k]} = -alpha_k
+};
+
 // What depends on the loaded LP only (kept by the handle between certificates, CertifyScratch::statics).
 struct CertifyStatic {
     std::vector<SparseColumn> columns;
@@ -101,5 +113,12 @@ bool certify_unbounded_entering(const CertifySigns& signs, const std::vector<cha
 bool certify_scaled_column(const CertifyStatic& statics, int j, std::vector<long long>* out, std::string* message);
 // Mode 2, the ray: alpha = B^-1 a_q <= 0, and exactly zero on a row whose basic variable is an artificial.  *objective: "-inf".
 bool certify_unbounded_ray(const std::vector<int>& basis, const ExactVector& alpha, std::string* objective, std::string* message);
+
+// ---- what a proved certificate hands out ----------------------------------------------------------------------------------------
+// `x` as the checks saw it (x.denom holds rhs_den already); `y` is the solution of the SCALED system (diag(r) B)' y^ = mu c_B with the
+// row multipliers r and the cost multiplier mu (mode 1: the phase-one costs, mu = 1), so the dual solution of the caller's LP is
+// y_i = r_i y^_i / mu: B' (r . y^) = mu c_B.  x and alpha do not see the row scaling.  The vectors are moved from.
+std::shared_ptr<const ExactWitnesses> make_exact_witnesses(const CertifyStatic& statics, int mode, const std::vector<int>& basis, int entering,
+                                                          ExactVector& x, ExactVector& y, ExactVector& alpha);
 
 }  // namespace relp

@@ -41,6 +41,7 @@
 #include <string>
 #include <vector>
 
+#include "exact_values.hpp"
 #include "many_certify.hpp"
 #include "pivot_step.hpp"
 #include "price_step.hpp"
@@ -622,6 +623,9 @@ struct relp_many {
     std::vector<std::string> exact;
     std::vector<int> entering;                // device column a verdict of UNBOUNDED names (the ray of its certificate)
     std::vector<std::array<int32_t, 3>> certificate_digits;  // of the last relp_many_certify: primal, dual, ray (empty before one)
+    bool keep_witnesses = false;              // relp_many_keep_witnesses
+    bool witnesses_kept = false;              // the last relp_many_certify ran with the switch on
+    std::vector<std::shared_ptr<const ExactWitnesses>> witnesses;  // of that call, per LP (null: not certified); empty with the switch off
     std::string error;
 
     void release() {
@@ -666,7 +670,7 @@ void many_certificate_kind(const relp_many& many, int k, int* mode, int* ray) {
 
 // The exact certificate of relp_solve_relaxation for model k of the last solve (certify_basis: its other primes and its exact repair
 // pivots included).  Sets results[k].certified and certify_seconds, and exact[k].
-bool many_serial_certificate(relp_many& many, int k, long long* repairs) {
+bool many_serial_certificate(relp_many& many, int k, long long* repairs, std::shared_ptr<const ExactWitnesses>* witnesses = nullptr) {
     relp_many_result& res = many.results[k];
     const double t0 = many_now();
     bool ok = false;
@@ -678,7 +682,7 @@ bool many_serial_certificate(relp_many& many, int k, long long* repairs) {
     *repairs = 0;
     try {
         certify_basis(many.forms[k], many.bases[k], many.device, many.streams[0], &many.exact[k], &ok, repairs, &message, mode, ray, nullptr,
-                      &many.certify_scratch);
+                      &many.certify_scratch, witnesses);
     } catch (const RatOverflow& e) {  // the f64 result stands, uncertified
         ok = false;
         message = std::string("exact certificate: ") + e.what();
@@ -979,6 +983,8 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
         }
         many->solved = true;
         many->certificate_digits.clear();
+        many->witnesses.clear();
+        many->witnesses_kept = false;
         if (results) std::copy(many->results.begin(), many->results.end(), results);
         return RELP_OK;
     } catch (const DeviceError& e) {
@@ -1015,6 +1021,10 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
             many->results[k].certified = 0;
         }
         many->certificate_digits.assign(n, std::array<int32_t, 3>{0, 0, 0});
+        many->witnesses.clear();
+        many->witnesses_kept = false;
+        const bool keep = many->keep_witnesses;
+        if (keep) many->witnesses.assign(n, nullptr);
         // the batched stage takes the optima, and in RELP_MANY_CERTIFY_ALL_KINDS the two other verdicts that have a certificate;
         // everything else that has one keeps the serial certificate
         std::vector<int> batched;
@@ -1029,7 +1039,7 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
                 batched.push_back(k);
                 items.push_back(item);
             }
-            many_certify_batched(items, many->device, many->streams, &outcomes, device_seconds);
+            many_certify_batched(items, many->device, many->streams, &outcomes, device_seconds, keep);
         }
         std::vector<int> slot(n, -1);
         for (size_t s = 0; s < batched.size(); ++s) slot[batched[s]] = (int)s;
@@ -1049,17 +1059,19 @@ int32_t relp_many_certify(relp_many* many, int32_t mode, relp_many_certificate* 
                     many->exact[k] = oc.objective;
                     many->results[k].certified = 1;
                     many->results[k].certify_seconds = oc.host_seconds;
+                    if (keep) many->witnesses[k] = oc.witnesses;
                     continue;
                 }
             } else if (mode == RELP_MANY_CERTIFY_OPTIMA) {
                 c.fallback_reason = MANY_CERTIFY_KIND;
             }
             long long repairs = 0;
-            c.certified = many_serial_certificate(*many, k, &repairs) ? 1 : 0;
+            c.certified = many_serial_certificate(*many, k, &repairs, keep ? &many->witnesses[k] : nullptr) ? 1 : 0;
             c.path = 2;
             c.repair_pivots = repairs;
             c.host_seconds += many->results[k].certify_seconds;
         }
+        many->witnesses_kept = keep;
         if (wall_seconds) *wall_seconds = many_now() - t_begin;
         return RELP_OK;
     } catch (const DeviceError& e) {
@@ -1076,6 +1088,64 @@ int32_t relp_many_get_certificate_digits(const relp_many* many, int32_t model, i
     if (!many->solved || many->certificate_digits.size() != many->lps.size()) return RELP_ERR_STATE;
     std::copy(many->certificate_digits[model].begin(), many->certificate_digits[model].end(), digits);
     return RELP_OK;
+}
+
+int32_t relp_many_keep_witnesses(relp_many* many, int32_t on) {
+    if (!many || (on != 0 && on != 1)) return RELP_ERR_ARGUMENT;
+    many->keep_witnesses = on == 1;
+    return RELP_OK;
+}
+
+// The witnesses of model `model` when the last relp_many_certify kept them and certified it; else null with the reason in many.error.
+static const ExactWitnesses* many_kept_witnesses(const relp_many* many, int32_t model) {
+    std::string& error = const_cast<relp_many*>(many)->error;
+    if (!many->solved || many->certificate_digits.size() != many->lps.size())
+        error = "no exact witnesses: there is no relp_many_certify of the last relp_many_solve";
+    else if (!many->witnesses_kept)
+        error = "no exact witnesses: relp_many_keep_witnesses was off when relp_many_certify ran";
+    else if (!many->witnesses[model] || !many->results[model].certified)
+        error = "no exact witnesses: model " + std::to_string(model) + " is not certified";
+    else
+        return many->witnesses[model].get();
+    return nullptr;
+}
+
+int32_t relp_many_get_witness_exact(const relp_many* many, int32_t model, int32_t which, int32_t capacity, int32_t* count, int32_t* index,
+                                    char* buffer, int64_t buffer_capacity, int64_t* length) {
+    if (!many || model < 0 || model >= (int32_t)many->lps.size() || !count || capacity < 0 || buffer_capacity < 0 ||
+        which < RELP_WITNESS_PRIMAL || which > RELP_WITNESS_RAY)
+        return RELP_ERR_ARGUMENT;
+    const ExactWitnesses* kept = many_kept_witnesses(many, model);
+    if (!kept) return RELP_ERR_STATE;
+    const std::string refusal = witness_refusal(many->results[model].kind, which);
+    if (!refusal.empty()) {
+        const_cast<relp_many*>(many)->error = "model " + std::to_string(model) + ": " + refusal;
+        return RELP_ERR_STATE;
+    }
+    try {
+        return return_exact_values(exact_witness_values(*kept, which), capacity, count, index, buffer, buffer_capacity, length);
+    } catch (const std::exception& e) {
+        const_cast<relp_many*>(many)->error = e.what();
+        return RELP_ERR_NUMERICAL;
+    }
+}
+
+int32_t relp_many_get_solution_exact(const relp_many* many, int32_t model, int32_t original, int32_t capacity, int32_t* count, int32_t* index,
+                                     char* buffer, int64_t buffer_capacity, int64_t* length) {
+    if (!many || model < 0 || model >= (int32_t)many->lps.size() || !count || capacity < 0 || buffer_capacity < 0) return RELP_ERR_ARGUMENT;
+    const ExactWitnesses* kept = many_kept_witnesses(many, model);
+    if (!kept) return RELP_ERR_STATE;
+    if (many->results[model].kind != RELP_RESULT_FINITE_OPTIMUM) {
+        const_cast<relp_many*>(many)->error = "model " + std::to_string(model) + ": no exact solution (not a certified finite optimum)";
+        return RELP_ERR_STATE;
+    }
+    try {
+        const ExactValues values = exact_solution_values(many->forms[model], exact_witness_values(*kept, RELP_WITNESS_PRIMAL), original != 0);
+        return return_exact_values(values, capacity, count, index, buffer, buffer_capacity, length);
+    } catch (const std::exception& e) {
+        const_cast<relp_many*>(many)->error = e.what();
+        return RELP_ERR_NUMERICAL;
+    }
 }
 
 int32_t relp_many_get_basis(const relp_many* many, int32_t model, int32_t* basis) {

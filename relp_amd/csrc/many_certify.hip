@@ -343,7 +343,7 @@ int mc_digit_count(const IntegerBasis& B, const std::vector<i64>& rhs, int trans
 int many_certify_lds_rows() { return mc_lds_tier_rows(); }
 
 void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device, hipStream_t* streams, std::vector<ManyCertifyOutcome>* outcomes,
-                          double* device_seconds) {
+                          double* device_seconds, bool keep_witnesses) {
     const int n = (int)items.size();
     outcomes->assign(n, ManyCertifyOutcome{});
     if (device_seconds) *device_seconds = 0.0;
@@ -602,6 +602,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
                                 certify_unbounded_ray(basis, alpha, &out.objective, &out.message);
                     }
                     if (!holds) out.reason = MANY_CERTIFY_SIGN;  // (modes 1 and 2 have no repair pivots: the serial certificate says the same)
+                    else if (keep_witnesses) out.witnesses = make_exact_witnesses(*pr.statics, mode, basis, items[k].ray, x, y, alpha);
                 }
             }
         } catch (const RatOverflow& e) {

@@ -2,12 +2,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "model.hpp"
 
 namespace relp {
+
+struct ExactWitnesses;  // x, y and the ray of a proved certificate (solver.hpp, certify_parts.hpp)
 
 // Why the batched stage did not prove an LP (relp_many_certificate.fallback_reason, include/relp_amd.h)
 enum ManyCertifyReason {
@@ -32,14 +35,16 @@ struct ManyCertifyOutcome {
     double host_seconds = 0.0;
     std::string objective;
     std::string message;
+    std::shared_ptr<const ExactWitnesses> witnesses;  // proved and asked for: the vectors of the proof, else null
 };
 
 // Rows up to which the work matrix of the batched certificate lives in LDS.
 int many_certify_lds_rows();
 
 // One launch (a group per LDS size, as relp_many_solve launches) for all items, one download, then the host stage of every item on
-// at most 16 threads.  `streams`: four streams of the handle.  *device_seconds: the launch (HIP events).
+// at most 16 threads.  `streams`: four streams of the handle.  *device_seconds: the launch (HIP events).  `keep_witnesses`: the
+// host stage keeps the reconstructed vectors of every proved item in its outcome instead of dropping them.
 void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device, hipStream_t* streams, std::vector<ManyCertifyOutcome>* outcomes,
-                          double* device_seconds);
+                          double* device_seconds, bool keep_witnesses = false);
 
 }  // namespace relp

@@ -92,6 +92,7 @@ void Solver::load(StandardForm&& form) {
     form_ = std::move(form);
     certify_scratch_.digit_hints[0] = certify_scratch_.digit_hints[1] = 0;  // (a new LP: nothing is known about its certificate)
     certify_scratch_.statics.reset();
+    exact_witnesses.reset();
     try {
         upload();
     } catch (...) {
@@ -1329,6 +1330,7 @@ void Solver::solve(relp_result* result) {
     relp_result res{};
     exact_objective.clear();
     exact_primal.reset();
+    exact_witnesses.reset();
     const bool timing = diagnostic("RELP_TIME_SOLVE");  // diagnostic: host-side timeline of one solve
     double t_last = t0;
     auto tick = [&](const char* what) {
@@ -1469,7 +1471,8 @@ void Solver::certify(relp_result* result) {
     std::string message;
     try {
         const int mode = result->kind == RELP_RESULT_INFEASIBLE ? 1 : result->kind == RELP_RESULT_UNBOUNDED ? 2 : 0;
-        certify_basis(form_, h_basis_, opt_.device, stream_, &exact_objective, &ok, &repairs, &message, mode, unbounded_column_, &exact_primal, &certify_scratch_);
+        certify_basis(form_, h_basis_, opt_.device, stream_, &exact_objective, &ok, &repairs, &message, mode, unbounded_column_, &exact_primal, &certify_scratch_,
+                      &exact_witnesses);
     } catch (const RatOverflow& e) {  // the f64 result stands; it is reported uncertified with the reason
         ok = false;
         message = std::string("exact certificate: ") + e.what();

@@ -26,6 +26,9 @@ namespace relp {
 
 // Exact primal solution of a certified basis: x_B[k] = numer[k] / denom for the provider column basis[k] (certify.hip).
 struct ExactPrimal;
+// The three exact vectors of a proved certificate, in the terms of the caller's LP (certify_parts.hpp): x_B, the dual solution y (the
+// Farkas vector of an INFEASIBLE verdict) and alpha = B^-1 a_q of an UNBOUNDED one.
+struct ExactWitnesses;
 // What a handle keeps between its certificates (certify.hip): the second stream of the dual lifting (creating and destroying a
 // stream costs 4 + 2 ms, as much as the rest of a certificate), the device buffers (returned to the handle, not to the driver) and
 // the p-adic digit counts the last certificate of the loaded LP needed.
@@ -48,10 +51,18 @@ std::vector<std::pair<int, std::string>> exact_primal_values(const ExactPrimal& 
 // The exact primal values of a certificate made elsewhere (network_carry.hip: the forest's): provider column and value, over one
 // common denominator.
 std::shared_ptr<const ExactPrimal> make_exact_primal(const std::vector<int>& columns, const std::vector<Rat>& values);
-// The exact certificate of a basis given in provider columns (certify.hip, where the modes are described).
+// The mode (as certify_basis) of the certificate the witnesses belong to.
+int exact_witness_mode(const ExactWitnesses& witnesses);
+// (index, "num/den" reduced, den > 0) of the non-zero entries of one witness, ascending index.  `which` (relp_witness): PRIMAL by
+// provider column (a basic artificial has value 0 and is not reported), DUAL by row, RAY by provider column: 1 on the entering
+// column, -alpha_k on basis[k].  The caller has checked that the mode has this witness.
+std::vector<std::pair<int, std::string>> exact_witness_values(const ExactWitnesses& witnesses, int which);
+// The exact certificate of a basis given in provider columns (certify.hip, where the modes are described).  `witnesses` (may be
+// null): the vectors the verdict was proved with, set only when *certified.
 void certify_basis(const StandardForm& form, const std::vector<int>& basis_provider_columns, int device, hipStream_t stream,
                    std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
-                   std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch);
+                   std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch,
+                   std::shared_ptr<const ExactWitnesses>* witnesses = nullptr);
 
 // Device control block, written by single-workgroup kernels, polled by the host.
 struct Ctl {
@@ -351,6 +362,8 @@ public:
     std::string exact_objective;  // filled by certify()
     // exact x_B of the certified optimal basis (certify.hip keeps the big integers; strings are made on demand)
     std::shared_ptr<const ExactPrimal> exact_primal;
+    // x, y and the ray of the last certified verdict (certify_basis; none under RELP_CARRY_NETWORK, whose proof comes from the forest)
+    std::shared_ptr<const ExactWitnesses> exact_witnesses;
     std::string last_error;
     relp_result last_result{};
 
