@@ -517,6 +517,10 @@ int32_t relp_profile_kernel(relp_handle* handle, int32_t which, int32_t repetiti
 
 /* Diagnostic builds only (-DRELP_STAMPS): per-segment cycle sums of the fused kernel; zeros otherwise. */
 int32_t relp_debug_stamps(relp_handle* handle, uint64_t* out64);
+/* Which kernels a handle created with `options` would run `model` on, and how it would size their arrays: the load-time plan
+ * (relp_amd/csrc/kernel_path.hpp) as one JSON object.  Host only: needs no device.  The return protocol of relp_get_record_json.
+ * RELP_ERR_ARGUMENT with the plan's message in `buffer` where a load would be refused (a carry or a ratio rule the LP cannot have). */
+int32_t relp_debug_kernel_path(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length);
 /* The switches and sizes of `options` for the test hooks that take no options of their own (relp_lu_factor_device), on the calling
  * thread, until the next call.  NULL restores the defaults. */
 int32_t relp_debug_set_tuning(const relp_options* options);

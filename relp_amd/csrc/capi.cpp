@@ -1036,6 +1036,30 @@ int32_t relp_debug_set_tuning(const relp_options* options) {
     thread_tuning() = tuning_of(adopted);
     return RELP_OK;
 }
+int32_t relp_debug_kernel_path(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+    relp_options o;
+    if (!model || adopt_options(options, &o) != RELP_OK) return RELP_ERR_ARGUMENT;
+    int32_t status = RELP_OK;
+    std::string text;
+    try {
+        const MatrixData& md = model->form.data;
+        const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
+        text = kernel_path_json(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
+    } catch (const std::invalid_argument& e) {
+        text = e.what();
+        status = RELP_ERR_ARGUMENT;
+    } catch (const std::exception& e) {
+        text = e.what();
+        status = RELP_ERR_STATE;
+    }
+    if (length) *length = (int32_t)text.size();
+    if (buffer && capacity > 0) {
+        const int32_t nbytes = std::min<int32_t>((int32_t)text.size(), capacity - 1);
+        std::memcpy(buffer, text.data(), nbytes);
+        buffer[nbytes] = 0;
+    }
+    return status;
+}
 int32_t relp_debug_stamps(relp_handle* h, uint64_t* out64) {
     REQUIRE_LOADED(h);
     if (!out64) return RELP_ERR_ARGUMENT;

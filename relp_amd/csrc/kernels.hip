@@ -237,7 +237,6 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
     if (blk.idx < 0 && threadIdx.x == 0) publish_no_candidate(lp, slot);
 }
 
-constexpr int PRICE_UNIT_ARCS = 4;  // arcs per lane of price_unit_kernel
 // ---------------------------------------------------------------------------------------------------
 // K1u: the pricing pass over GENERATED incidence columns (graph providers: examples/max_flow.rs:174-200, every value +-1, integer
 // costs), one LANE per arc and PRICE_UNIT_ARCS arcs per lane.  The two-lanes-per-arc form above kept one arc per lane pair in
@@ -582,7 +581,6 @@ __global__ void __launch_bounds__(K1D_THREADS) price_dense_kernel(DeviceLP lp, i
 // column, 20.5 us; 64 columns per wave with the vectors as SGPR operands from scalar loads (s_load latency exposed, and rows
 // split over workgroups that meet behind a per-group counter: the __threadfence() on either side writes back and
 // invalidates the XCD's whole L2, 3x slower per pivot), 11.8 us + 5.3 us for a second kernel that adds the splits.
-constexpr int K1C_MAX_THREADS = 512, K1C_U = 4, K1C_COLS = 16, K1C_TILE_ROWS = 64;
 template <int T>
 __device__ __forceinline__ void fmac_row_broadcast(double& acc, double a, double x) {  // acc += (a of lane T of this lane's row of 16) * x
     asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(a), "v"(x), "n"(T));
@@ -750,9 +748,6 @@ __global__ void __launch_bounds__(K1C_MAX_THREADS) price_dense_lane_kernel(Devic
         else publish_no_candidate(lp, cand_offset + blockIdx.x);
     }
 }
-int dense_lane_slots(int n_dense) { return (n_dense + K1C_COLS - 1) / K1C_COLS; }
-int dense_lane_threads(int m) { return m > 1024 ? 512 : 256; }
-int dense_lane_ld(int m) { const int unit = K1C_TILE_ROWS * (dense_lane_threads(m) / WAVE) * K1C_U; return (m + unit - 1) / unit * unit; }
 
 // Multi-block FTRAN for long entering columns: partial[c][i] = sum over the c-th slice of the entries of a_q of
 // v_e * Binv(i, r_e).  Grid (row tiles of 256, slices); coalesced over i; fixed slice order => deterministic.
@@ -883,7 +878,6 @@ __global__ void __launch_bounds__(256) ftran_partial_kernel(DeviceLP lp, int n_s
 
 // alpha_in[i] = sum_c alpha_part[c][i] (fixed order), so that the fused kernel reads one vector.  In the deferred product
 // form the pending etas are applied here, all at once and in parallel:  alpha = M y = y + sum_c (M[:, P_c] - e_{P_c}) y[P_c].
-constexpr int ETA_MAX = 32;
 __device__ __forceinline__ double sum_slices(const DeviceLP& lp, int n_slices, int i) {
     double acc = 0.0;
     for (int c0 = 0; c0 < n_slices; c0 += 8) {
@@ -1969,9 +1963,7 @@ __global__ void __launch_bounds__(K2L_THREADS) k2l_apply_kernel(DeviceLP lp, int
     }
 }
 
-constexpr int K2F_THREADS = 512;
 constexpr int K2F_NW = K2F_THREADS / WAVE;
-constexpr int K2F_MAX_BLOCKS = 2048;
 constexpr int K2F_INLINE_BLOCKS = 128;  // candidate columns staged with the candidates when there are at most this many
 
 // ---- The front half that ftran_ratio_fast_kernel<RULE, R> and pivot_fused_kernel<RULE, R> share: 512 threads, thread tid owns the
@@ -2455,8 +2447,6 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
 // ---------------------------------------------------------------------------------------------------
 constexpr int KF_THREADS = K2F_THREADS;    // (the k2f_* front half)
 constexpr int KF_NW = KF_THREADS / WAVE;  // waves = columns of the inverse per workgroup
-constexpr int KF_MAX_R = 4;               // rows per thread: 2 up to 1024 rows, 4 up to 2048 (as ftran_ratio_fast_kernel<RULE, R>)
-constexpr int KF_MAX_M = KF_MAX_R * KF_THREADS;
 template <int RULE, int KF_R>
 __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, DeviceLP::State in, DeviceLP::State out, int n_price_blocks,
                                                                  double tol_pivot, double harris_delta, int skip_artificial_rows) {
@@ -3331,7 +3321,6 @@ void take_launch_timer(int which, hipEvent_t* start, hipEvent_t* stop) {
         }                                                                                                    \
     } while (0)
 constexpr int PRICE_LPC = 8;  // lanes per sparse column in the pricing kernel
-int price_columns_per_block(int ell_w, bool generated) { return generated ? 256 * PRICE_UNIT_ARCS : 256 / ell_w; }
 
 template <int RULE>
 static void launch_price_rule(const DeviceLP& d, int blocks, size_t lds, bool use_lds, int skip_weights, double tol,
@@ -3424,7 +3413,6 @@ static void launch_ftran_ratio_rule(const DeviceLP& d, int n_price_blocks, doubl
 }
 
 // n_alpha_slices > 0 requires the register-resident kernel (m <= 8192 and <= 2048 pricing workgroups)
-bool fast_k2_available(const DeviceLP& d, int n_price_blocks) { return n_price_blocks <= K2F_MAX_BLOCKS && d.m <= 16 * K2F_THREADS; }
 
 void launch_ftran_ratio(const DeviceLP& d, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
                         int skip_artificial_rows, int mode, int n_alpha_slices, hipStream_t s) {
@@ -3434,7 +3422,6 @@ void launch_ftran_ratio(const DeviceLP& d, int rule, int n_price_blocks, double 
         launch_ftran_ratio_rule<RELP_PIVOT_DANTZIG>(d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices, s);
 }
 
-bool fused_pivot_available(const DeviceLP& d, int n_price_blocks) { return d.m <= KF_MAX_M && n_price_blocks <= K2F_MAX_BLOCKS; }
 void launch_pivot_fused(const DeviceLP& d, int rule, int parity, int n_price_blocks, double tol_pivot, double harris_delta,
                         int skip_artificial_rows, hipStream_t s) {
     const dim3 grid((d.m + KF_NW - 1) / KF_NW);
@@ -3533,13 +3520,11 @@ void launch_residual_dense(const DeviceLP& d, double* Bd, const double* T, doubl
 void launch_alpha_reduce(const DeviceLP& d, int n_slices, hipStream_t s) {
     hipLaunchKernelGGL(alpha_reduce_kernel, dim3((d.m + AR_ROWS - 1) / AR_ROWS), dim3(AR_ROWS * AR_GROUPS), 0, s, d, n_slices);
 }
-int eta_max() { return ETA_MAX; }
 void configure_btran_lds(size_t) {
     static PerDeviceOnce once;
     once.run([] { allow_full_lds(reinterpret_cast<const void*>(&btran_pass_kernel)); });
 }
 // deferred product form: fold the new eta into the kept columns, then one read-only pass for rho_p, w and -pi
-int btran_pass_blocks() { return 256; }
 void launch_eta_update(const DeviceLP& d, double tol_dual, hipStream_t s) {
     const size_t lds = (size_t)2 * ((d.m + 1) & ~1) * sizeof(double);
     RELP_LAUNCH(2, btran_pass_kernel, dim3(btran_pass_blocks()), dim3(BT_THREADS), lds, s, d, tol_dual);

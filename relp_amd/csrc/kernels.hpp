@@ -5,23 +5,18 @@
 
 namespace relp {
 
-// kernels.hip
+// kernels.hip (the limits the load-time plan reads -- dense_lane_slots, fast_k2_available, eta_max ... -- are in kernel_limits.hpp)
 void launch_price(const DeviceLP& d, int rule, int blocks, size_t lds, bool use_lds, int skip_weights, double tol,
                   int first, int last, int cand_offset, hipStream_t s);
 void launch_price_dense(const DeviceLP& d, int blocks, int skip_weights, double tol, int cand_offset, hipStream_t s);
 void configure_dense_lds(size_t lds);
-int dense_lane_slots(int n_dense);
-int dense_lane_ld(int m);
 void launch_ftran_partial(const DeviceLP& d, int n_slices, int n_price_blocks, int rule, hipStream_t s);
-bool fast_k2_available(const DeviceLP& d, int n_price_blocks);
 void arm_launch_timer(int which, hipEvent_t start, hipEvent_t stop);
 void take_launch_timer(int which, hipEvent_t* start, hipEvent_t* stop);
 void configure_lds(size_t price_lds);
-int price_columns_per_block(int ell_w, bool generated);
 void launch_ftran_ratio(const DeviceLP& d, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
                         int skip_artificial_rows, int mode, int n_alpha_slices, hipStream_t s);
 void launch_update(const DeviceLP& d, hipStream_t s);
-bool fused_pivot_available(const DeviceLP& d, int n_price_blocks);
 void launch_pivot_fused(const DeviceLP& d, int rule, int parity, int n_price_blocks, double tol_pivot, double harris_delta,
                         int skip_artificial_rows, hipStream_t s);
 void launch_begin_batch(const DeviceLP& d, long long add, hipStream_t s);
@@ -40,10 +35,8 @@ void launch_residual_dense(const DeviceLP& d, double* Bd, const double* T, doubl
 void launch_copy_rows(const double* src, double* dst, int m, int ld, const int* row_list, int n_rows, hipStream_t s);
 bool gemm_row_lists_supported();
 void launch_alpha_reduce(const DeviceLP& d, int n_slices, hipStream_t s);
-int eta_max();
 void configure_btran_lds(size_t lds);
 void launch_eta_update(const DeviceLP& d, double tol_dual, hipStream_t s);
-int btran_pass_blocks();
 void launch_eta_consolidate(const DeviceLP& d, hipStream_t s);
 void launch_mark_all_touched(const DeviceLP& d, hipStream_t s);
 void launch_scaled_basis(const DeviceLP& d, double* T, double scale, hipStream_t s);

@@ -572,8 +572,6 @@ DeviceLU bind_layout(const LuLayout& L, char* dev_, int m, int max_updates, int 
 }
 }  // namespace
 
-static int lu_inverse_vectors(int m, int max_updates);  // (below, with the LDS sizes)
-
 bool LuFactors::upload(const HostLU& factors, int max_updates, hipStream_t stream, bool inverse_factors) {
     // The inverse-factor form uploads L^-1 and U^-1 through the same task lists (every row in one level; lu.hpp).
     thread_local HostLU inverted;
@@ -898,35 +896,10 @@ void LuFactors::replay_log_of(const LuFactors& old, hipStream_t stream) {
     hipLaunchKernelGGL(lu_replay_rows_kernel, dim3((d_.m + LU_REPLAY_ROW_THREADS - 1) / LU_REPLAY_ROW_THREADS), dim3(LU_REPLAY_ROW_THREADS), 0, stream, d_, old.d_);
 }
 
-// LDS of the solve kernels: the two vectors (16 bytes per row), the mask of the replaced positions, one count per 64 rows for
-// the ordered compactions, reductions, and the trailing block T with its four slot vectors.
-// `inverse_vectors`: 0 = the Forrest-Tomlin form; 4 / 3 = the inverse-factor form with four vectors in LDS (a product is out of
-// place and the BTRAN has two right-hand sides) or, for the rows that leaves no room for, with three (the two right-hand sides go
-// through the factors one after the other: twice the passes over them).
-static size_t lu_lds_fixed_bytes(int m, int max_updates, int inverse_vectors = 0) {
-    const size_t mm = (size_t)((m + 1) & ~1);
-    if (inverse_vectors)  // no T / MF; the per-wave partials of M' r
-        return (size_t)inverse_vectors * mm * sizeof(double) + ((size_t)(m + 31) / 32 + 2) * sizeof(int) + ((size_t)(m + 63) / 64 + 4) * sizeof(int) + 64 * sizeof(double) +
-               ((size_t)4 * LU_MAX_SLOTS + (size_t)2 * (LU_THREADS / 64) * LU_MAX_SLOTS) * sizeof(double) + 256;
-    return 2 * mm * sizeof(double) + ((size_t)(m + 31) / 32 + 2) * sizeof(int) + ((size_t)(m + 63) / 64 + 4) * sizeof(int) + 64 * sizeof(double) +
-           ((size_t)2 * max_updates * (max_updates + 1) + 4 * LU_MAX_SLOTS) * sizeof(double) + 256;
-}
-constexpr size_t LU_LDS_TOTAL = 160 * 1024 - 1024;  // what a kernel may ask for (static LDS of the fused kernel comes on top)
 static size_t lu_lds_bytes_for(const DeviceLU& lu) {
     return std::min(LU_LDS_TOTAL - 2048, lu_lds_fixed_bytes(lu.m, lu.max_updates, lu.inverse_factors));
 }
 size_t LuFactors::lds_bytes(int) const { return lu_lds_bytes_for(d_); }
-static int lu_inverse_vectors(int m, int max_updates) {  // 4 when they fit, else 3, else 0 (does not fit at all)
-    for (int vectors = 4; vectors >= 3; --vectors)
-        if (lu_lds_fixed_bytes(m, max_updates, vectors) <= LU_LDS_TOTAL - 2048) return vectors;
-    return 0;
-}
-bool lu_fits_lds(int m, int max_updates, bool inverse_factors) {
-    if (max_updates < 1) max_updates = 1;
-    if (max_updates > LU_MAX_SLOTS) max_updates = LU_MAX_SLOTS;
-    if (inverse_factors) return lu_inverse_vectors(m, max_updates) != 0;
-    return lu_lds_fixed_bytes(m, max_updates, 0) <= LU_LDS_TOTAL - 2048;
-}
 
 // =====================================================================================================
 // device: synchronisation-free triangular solves out of LDS

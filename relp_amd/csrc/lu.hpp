@@ -26,6 +26,7 @@
 
 #include <vector>
 
+#include "kernel_limits.hpp"
 #include "lu_factor.hpp"
 #include "lu_host.hpp"
 
@@ -34,7 +35,6 @@ namespace relp {
 enum : int { LU_N_UPDATES = 0, LU_S_TOP = 1, LU_ETA_TOP = 2, LU_FLAGS = 3, LU_PF_COUNT = 4, LU_LOG_ON = 5, LU_LOG_COUNT = 6, LU_STATE_WORDS = 16 };
 constexpr int LU_LOG_CAPACITY = 40;  // pivots whose etas are logged while the next factors are built on another stream (round 5)
 enum : int { LU_FLAG_UNSTABLE = 1, LU_FLAG_OVERFLOW = 2 };
-constexpr int LU_MAX_SLOTS = 64;  // one wave solves T
 
 // A triangular factor in one orientation as a TASK LIST for the level-synchronous solve (lu.hip: lu_solve_tasks).  The rows
 // (columns) of the factor are sorted by dependency level.  A row without entries needs no solve (`z_pos`, `z_dinv`).  Every
@@ -182,8 +182,6 @@ private:
 };
 
 // kernels (lu.hip); all single-workgroup, stream-ordered
-constexpr int LU_THREADS = 1024;
-bool lu_fits_lds(int m, int max_updates, bool inverse_factors = false);  // max_updates: the update slots the kernels will be given (T is max_updates^2 doubles of LDS)
 // FTRAN of a sparse column (device arrays rows / vals, original row indices): out[slot] (m doubles); the spike stays in lu.spike
 void launch_lu_ftran(const DeviceLU& lu, const int* rows, const double* vals, int nnz, double* out, int keep_spike, hipStream_t s);
 // FTRAN of a dense right-hand side (original row order)

@@ -5,7 +5,7 @@
 // one LP for its whole two-phase solve -- `solve_relaxation` of two_phase/mod.rs:25-109 with the loops of phase_one.rs:134-178 and
 // phase_two.rs:36-58 -- inside ONE ordinary launch: no grid barrier, no cooperative launch, no communication between workgroups.
 //
-// Per LP the host builds what `Solver::upload` builds (the same `StandardForm` / `MatrixData`, artificial columns first, then the
+// Per LP the host builds what `Solver::load` builds (the same `StandardForm` / `MatrixData`, artificial columns first, then the
 // provider columns; the reference's initial slack pivots, artificials on the other rows), so that bases, pivot counts and index
 // spaces compare directly with a `Solver`'s.  Each step restates the single-LP f64 path (kernels.hip):
 //   pricing + steepest-edge update   price_kernel          (pivot_rule.rs:190-296, tableau/mod.rs:106-112)
@@ -572,16 +572,16 @@ int many_device_rows(const MatrixData& md, bool implicit_bounds) {
 ManyHostLP many_host_lp(const StandardForm& form, const relp_options& o, bool implicit_bounds) {
     ManyHostLP lp;
     const MatrixData& md = form.data;
-    // as Solver::upload: an LP without a finite bound is not a bounded one; a bounded one has the constraint rows and the first four
-    // column groups, and the bounds of the structurals and the ranges of the range slacks per column
+    // as for a Solver (kernel_path.hpp): an LP without a finite bound is not a bounded one; a bounded one has the constraint rows and the
+    // first four column groups, and the bounds of the structurals and the ranges of the range slacks per column
     lp.bounded = implicit_bounds && md.nr_variable_bounds() > 0;
-    lp.cols = lp.bounded ? DeviceColumns(md, md.nr_constraints(), md.col_end[3]) : DeviceColumns(md);
+    lp.cols = device_columns(md, lp.bounded);
     lp.data = DeviceMatrix(lp.cols, md);
     const int m = lp.m = lp.cols.m, n = lp.n = lp.cols.n();
     lp.n_art = lp.cols.n_art;
     if (lp.bounded) lp.ub = implicit_upper_bounds(md, lp.cols);
-    // RELP_RATIO_AUTO as Solver::upload resolves it (every LP here has at most 512 rows: the kernels have the textbook rule)
-    lp.textbook = o.ratio_rule == RELP_RATIO_TEXTBOOK || (o.ratio_rule == RELP_RATIO_AUTO && lp.data.small_integer_data());
+    // (every LP here has at most 512 rows: the kernels have the textbook rule)
+    lp.textbook = resolves_to_textbook(o, lp.data, true);
     lp.lds = m <= many_lds_tier_rows(lp.bounded) && !(o.switches & RELP_SW_MANY_GLOBAL_TIER);
     // launch groups: three LDS sizes (7, 2 and 1 workgroups per CU) and the global tier; the bounded LPs in four groups of their own
     lp.bucket = (!lp.lds ? 3 : m <= 48 ? 0 : m <= 96 ? 1 : 2) + (lp.bounded ? MANY_TIERS : 0);

@@ -333,7 +333,7 @@ HostTree Solver::net_download() {
     const int m = d_.m;
     std::vector<int> basis(m), flipped;
     RELP_HIP(hipMemcpyAsync(basis.data(), d_.basis, m * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    if (bounded_) {
+    if (path_.bounded) {
         flipped.resize(d_.n);
         RELP_HIP(hipMemcpyAsync(flipped.data(), d_.flipped, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
     }
@@ -429,7 +429,7 @@ bool Solver::net_crash(const std::vector<int>& basis) {
         if (t.parent[x] >= 0) sub[t.parent[x]] += sub[x];
     }
     std::vector<double> ub;
-    if (bounded_) {
+    if (path_.bounded) {
         ub.resize(n);
         RELP_HIP(hipMemcpyAsync(ub.data(), d_.ub, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
         RELP_HIP(hipStreamSynchronize(stream_));
@@ -438,11 +438,11 @@ bool Solver::net_crash(const std::vector<int>& basis) {
     for (int i = 0; i < m; ++i) scale = std::max(scale, std::fabs(host_.rhs[i]));
     for (int i = 0; i < m; ++i) {
         if (xb[i] < -1e-9 * scale) return false;
-        if (bounded_ && xb[i] > ub[basis[i]] + 1e-9 * scale) return false;
+        if (path_.bounded && xb[i] > ub[basis[i]] + 1e-9 * scale) return false;
         if (xb[i] < 0.0) xb[i] = 0.0;
     }
     std::vector<int> pos(n, -1);
-    if (bounded_)
+    if (path_.bounded)
         for (int j = d_.n_art; j < n; ++j)
             if (zero_width_[j]) pos[j] = -3;
     for (int i = 0; i < m; ++i) pos[basis[i]] = i;
@@ -453,7 +453,7 @@ bool Solver::net_crash(const std::vector<int>& basis) {
     RELP_HIP(hipMemcpyAsync(d_.pos, pos.data(), n * sizeof(int), hipMemcpyHostToDevice, stream_));
     RELP_HIP(hipMemcpyAsync(d_.xB, xb.data(), m * sizeof(double), hipMemcpyHostToDevice, stream_));
     RELP_HIP(hipMemcpyAsync(d_.gamma, gamma.data(), n * sizeof(double), hipMemcpyHostToDevice, stream_));
-    if (bounded_) {
+    if (path_.bounded) {
         std::vector<double> xub(m);
         for (int i = 0; i < m; ++i) xub[i] = ub[basis[i]];
         RELP_HIP(hipMemcpyAsync(d_.xub, xub.data(), m * sizeof(double), hipMemcpyHostToDevice, stream_));
@@ -468,25 +468,25 @@ void launch_net_row(const DeviceLP& d, const NetTree& t, int r, double* out, hip
     hipLaunchKernelGGL(net_row_kernel, dim3(net_grid(d.m)), dim3(NET_THREADS), 0, s, d, t, r, out);
 }
 
-int Solver::net_launches_per_pivot() const { return fast_k2_available(d_, price_blocks_ + dense_blocks_) ? 5 : 7; }
+int Solver::net_launches_per_pivot() const { return fast_k2_available(d_.m, path_.price_blocks + path_.dense_blocks) ? 5 : 7; }
 
 // parts: 1 entering column, path and ratio test; 2 the forest update (mode 0)
 void Solver::net_enqueue_pivot(int mode, int parts) {
-    const int slots = price_blocks_ + dense_blocks_;
+    const int slots = path_.price_blocks + path_.dense_blocks;
     const int skip_art = phase_ == 2 ? 1 : 0;
     if (parts & 1) {
         if (opt_.pivot_rule == RELP_PIVOT_STEEPEST_EDGE)
             hipLaunchKernelGGL(net_ftran_kernel<RELP_PIVOT_STEEPEST_EDGE>, dim3(1), dim3(NET_THREADS), 0, stream_, d_, net_, slots, mode);
         else
             hipLaunchKernelGGL(net_ftran_kernel<RELP_PIVOT_DANTZIG>, dim3(1), dim3(NET_THREADS), 0, stream_, d_, net_, slots, mode);
-        if (fast_k2_available(d_, slots)) {
+        if (fast_k2_available(d_.m, slots)) {
             launch_ftran_ratio(d_, opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, 1, stream_);
         } else {
             if (mode != 0) throw std::invalid_argument("RELP_CARRY_NETWORK: the ratio test without a basis change is implemented up to 8192 rows");
             // Every non-zero of alpha is +-1 on a network basis, so the two-pass test with a slack of 0 IS the reference's rule: pass 1
             // finds the exact minimum ratio, pass 2 takes, among the rows that reach it, the largest |alpha| (all 1) and then the lowest
             // leaving column (Bland) -- the textbook rule of the register-resident kernel, at any number of rows.
-            launch_k2l_preselected(d_, opt_.tol_pivot, ratio_textbook_ ? 0.0 : opt_.harris_delta, skip_art, stream_);
+            launch_k2l_preselected(d_, opt_.tol_pivot, path_.ratio_textbook ? 0.0 : opt_.harris_delta, skip_art, stream_);
         }
     }
     if (mode != 0 || !(parts & 2)) return;
@@ -509,7 +509,7 @@ void Solver::net_certify(relp_result* result) {
         std::vector<int> basis(m), pos(n), flipped;
         RELP_HIP(hipMemcpyAsync(basis.data(), d_.basis, m * sizeof(int), hipMemcpyDeviceToHost, stream_));
         RELP_HIP(hipMemcpyAsync(pos.data(), d_.pos, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
-        if (bounded_) {
+        if (path_.bounded) {
             flipped.resize(n);
             RELP_HIP(hipMemcpyAsync(flipped.data(), d_.flipped, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
         }
@@ -519,7 +519,7 @@ void Solver::net_certify(relp_result* result) {
         auto cost = [&](int j) { return j < n_art ? Rat(0) : md.cost_value(j - n_art); };
         std::vector<Rat> upper(n);
         std::vector<char> has_upper(n, 0);
-        if (bounded_) {
+        if (path_.bounded) {
             for (int j = 0; j < md.nr_normal_variables(); ++j)
                 if (md.variables[j].has_upper) { has_upper[n_art + j] = 1; upper[n_art + j] = md.variables[j].upper; }
             for (int k = 0; k < md.nr_range; ++k) { has_upper[n_art + md.col_end[0] + k] = 1; upper[n_art + md.col_end[0] + k] = md.ranges[k]; }
@@ -529,7 +529,7 @@ void Solver::net_certify(relp_result* result) {
         // every complemented column, basic or not, moves u_j a_j to the right-hand side (as the device and set_basis hold it: a
         // column keeps its complemented form when it enters the basis, and its basic value is then u_j - x_j)
         for (int j = n_art; j < n; ++j)
-            if (bounded_ && flipped[j])
+            if (path_.bounded && flipped[j])
                 for (int e = host_.col_start[j]; e < host_.col_start[j + 1]; ++e) rhs[host_.row_index[e]] = rhs[host_.row_index[e]] - upper[j] * Rat((long long)host_.value[e]);
         // x_B in B's own (possibly complemented) orientation: x_B[slot] = sign * (sum of rhs below)
         std::vector<Rat> below(rhs), xb(m);
@@ -544,7 +544,7 @@ void Solver::net_certify(relp_result* result) {
             const int x = t.order[k];
             const int j = basis[t.slot[x]];
             Rat c = cost(j);
-            if (bounded_ && flipped[j]) c = -c;
+            if (path_.bounded && flipped[j]) c = -c;
             const Rat term = t.sign[x] < 0 ? -c : c;
             y[x] = (t.parent[x] >= 0 ? y[t.parent[x]] : Rat(0)) + term;
         }
@@ -562,7 +562,7 @@ void Solver::net_certify(relp_result* result) {
                 if (!v.is_zero()) { feasible = false; bad = j; }
                 continue;
             }
-            if (bounded_ && has_upper[j]) {
+            if (path_.bounded && has_upper[j]) {
                 if (upper[j] < v) { feasible = false; bad = j; break; }
                 if (flipped[j]) v = upper[j] - v;
             }
@@ -573,7 +573,7 @@ void Solver::net_certify(relp_result* result) {
             if (pos[j] >= 0) continue;
             Rat d = cost(j);
             for (int e = host_.col_start[j]; e < host_.col_start[j + 1]; ++e) d = d - Rat((long long)host_.value[e]) * y[host_.row_index[e]];
-            const bool up = bounded_ && flipped[j];
+            const bool up = path_.bounded && flipped[j];
             if (up) {
                 objective = objective + md.cost_value(j - n_art) * upper[j];
                 if (!upper[j].is_zero()) { columns.push_back(j - n_art); values.push_back(upper[j]); }

@@ -93,6 +93,7 @@ void Solver::load(StandardForm&& form) {
     certify_scratch_.digit_hints[0] = certify_scratch_.digit_hints[1] = 0;  // (a new LP: nothing is known about its certificate)
     certify_scratch_.statics.reset();
     exact_witnesses.reset();
+    path_ = KernelPath{};  // (a refused load leaves no plan behind)
     try {
         upload();
     } catch (...) {
@@ -105,7 +106,8 @@ void Solver::load(StandardForm&& form) {
 // Materialise [artificials | provider columns] once (CSC + CSR) and upload.  The artificial columns are the virtual
 // identity columns of `Partially::original_column` (kind/artificial/partially.rs:52-60); the slack columns are the
 // virtual columns of `MatrixData::column` (matrix_data.rs:308-327): 12 bytes each, so materialising them costs nothing
-// and makes the pricing pass one uniform CSC sweep.
+// and makes the pricing pass one uniform CSC sweep.  Every choice between kernels is made by plan_kernel_path
+// (kernel_path.hpp) before anything is allocated; the functions below read `path_` and decide nothing.
 void Solver::upload() {
     const MatrixData& md = form_.data;
     const bool timing = diagnostic("RELP_TIME_UPLOAD");  // diagnostic: where the one-off load time goes
@@ -116,41 +118,41 @@ void Solver::upload() {
         fprintf(stderr, "[upload] %-28s %.3f s\n", what, t - t_last);
         t_last = t;
     };
-    // Implicit upper bounds: the device LP has the constraint rows only (E | R | <= | >=) and the provider columns of the
-    // first four groups (structurals, range slacks, <= slacks, >= slacks); the VariableBound / SlackBound rows and their
-    // slack columns (matrix_data.rs:104-145) become upper bounds of the structurals and the range slacks.
-    bounded_ = opt_.implicit_bounds != 0 && md.nr_variable_bounds() > 0;
-    // relp_options first; the environment variables of rounds 1-3 still override (A/B runs without a new handle's options)
-    const bool want_f64_block = opt_.dense_storage == RELP_DENSE_DOUBLE;
-    const bool want_f32_block = opt_.dense_storage == RELP_DENSE_FLOAT;
-    const bool product_form_off = opt_.product_form == 1;
-    const int ftran_min_nnz_opt = opt_.ftran_min_nnz > 0 ? opt_.ftran_min_nnz : 1024;
-    const auto sw = [&](unsigned bit) { return (opt_.switches & bit) != 0; };
-    const int m = bounded_ ? md.nr_constraints() : md.nr_rows();
-    const int n_p = bounded_ ? md.col_end[3] : md.nr_columns();
-    if (m < 1) throw std::runtime_error("LP without rows");
-    cols_ = DeviceColumns(md, m, n_p);
+    cols_ = device_columns(md, implicit_bounds_apply(opt_, md));
     host_ = DeviceMatrix(cols_, md);
-    const int n_art = cols_.n_art, n = cols_.n();
-    const std::vector<int>&col_start = host_.col_start, &row_index = host_.row_index;
-    const std::vector<double>&value = host_.value, &cost2 = host_.cost2, &rhs = host_.rhs;
     tick("columns -> CSC");
-    network_ = opt_.carry == RELP_CARRY_NETWORK;
-    if (network_) {  // a network LP: at most two entries per column, each +-1, of opposite signs when there are two
-        for (int j = n_art; j < n; ++j) {
-            const int a = col_start[j], len = col_start[j + 1] - a;
-            bool fits = len <= 2;
-            for (int e = a; fits && e < a + len; ++e) fits = value[e] == 1.0 || value[e] == -1.0;
-            if (fits && len == 2) fits = value[a] == -value[a + 1];
-            if (fits) continue;
-            const int c = j - n_art;
-            const std::string name = c < (int)form_.column_names.size() ? form_.column_names[c] : "slack";
-            std::string hint;
-            if (!bounded_ && md.nr_variable_bounds() > 0) hint = "; its upper bound is a row of the device LP: set implicit_bounds = 1";
-            throw std::invalid_argument("RELP_CARRY_NETWORK: column " + std::to_string(c) + " (" + name + ") is not a network column (" + std::to_string(len) +
-                                        " entries; at most two, each +-1, of opposite signs)" + hint);
-        }
-    }
+    path_ = plan_kernel_path(opt_, md, cols_, host_, &form_.column_names);
+    tick("kernel path");
+    const int m = path_.m, n = path_.n, n_art = path_.n_art;
+    d_.m = d_.ld = m, d_.n = n, d_.n_art = d_.dense_first = n_art;  // the decisions the kernels read
+    d_.n_dense = path_.n_dense, d_.dense_ld = path_.dense_ld, d_.dense_full = path_.dense_full, d_.dense_csc_start = path_.dense_csc_start;
+    d_.dense_lane = path_.dense_lane, d_.ell_w = path_.ell_w, d_.eta_cap = path_.eta_cap, d_.track_touched = path_.track_touched;
+    d_.price_unit_pairs = path_.price_unit_pairs, d_.rho_words = path_.rho_words;
+    upload_matrix();
+    tick("CSC, CSR, costs, rhs");
+    upload_pricing_copy();
+    tick("pricing copy");
+    upload_dense_block();
+    tick("dense block");
+    allocate_pivot_state();
+    configure_lds(std::min<size_t>(path_.price_lds, 160 * 1024 - 1024));
+    tick("pivot state");
+
+    stats_.price_bytes = (long long)(host_.col_start[n] - host_.col_start[path_.sparse_first]) * 12 + (long long)(n - n_art) * 24 +
+                         (long long)path_.n_dense * m * path_.dense_entry_bytes();  // upper bound: every dense column non-basic
+    if (path_.generated_columns) stats_.price_bytes = (long long)(n - n_art) * (8 + 1 + 4);  // endpoints, cost byte, pos (+ the weight of the few columns that need it)
+    stats_.update_bytes = path_.network ? 0 : (long long)2 * m * m * 8;
+    if (path_.network) net_allocate();
+    h_basis_.assign(m, -1);
+    h_solution_.assign(md.nr_columns(), 0.0);
+    if (!(path_.lu_mode || path_.network || opt_.crash)) host_ = DeviceMatrix{};  // (nothing on the host reads it after the upload)
+}
+
+// CSC and CSR of the device LP, the costs of both phases and the right-hand side.
+void Solver::upload_matrix() {
+    const int m = path_.m, n = path_.n, n_art = path_.n_art;
+    const std::vector<int>&col_start = host_.col_start, &row_index = host_.row_index;
+    const std::vector<double>& value = host_.value;
     const size_t nnz = row_index.size();
     std::vector<int> row_start(m + 1, 0), col_index(nnz);
     std::vector<double> row_value(nnz);
@@ -167,110 +169,6 @@ void Solver::upload() {
     }
     std::vector<double> cost1(n, 0.0);
     for (int k = 0; k < n_art; ++k) cost1[k] = 1.0;  // artificial::Cost::One (kind/artificial/partially.rs:42-50)
-
-    tick("CSR, costs, rhs");
-    d_.m = m;
-    d_.n = n;
-    d_.n_art = n_art;
-    d_.ld = m;
-    lu_mode_ = opt_.carry == RELP_CARRY_LU || opt_.carry == RELP_CARRY_LU_INVERSE;
-    lu_inverse_ = opt_.carry == RELP_CARRY_LU_INVERSE;
-    // (default: the reference's `should_refactor`, > 30 updates, for its Forrest-Tomlin form; 47 for the inverse-factor form, whose
-    //  kept columns cost less per update than its refactorisation per pivot: 25FV47 63 -> 59 us per pivot, CYCLE 87 -> 81)
-    refactor_period_ = std::min(opt_.refactor_period > 0 ? opt_.refactor_period : (lu_inverse_ ? 47 : 31), LU_MAX_SLOTS - 1);  // T is solved by one wave
-    // `BasisInverse::invert` as kernels (lu_factor.hip, lu_device_tasks.hip: the inverse-factor form) or on one host core:
-    // relp_options.lu_refactor, env RELP_REFACTOR=device|host.  AUTO is the host path today -- faster at every size measured.
-    {
-        int where = opt_.lu_refactor;
-        device_refactor_ = lu_inverse_ && (where == RELP_REFACTOR_DEVICE || where == RELP_REFACTOR_DEVICE_ASYNC) && m <= 65535;
-        async_refactor_ = device_refactor_ && where == RELP_REFACTOR_DEVICE_ASYNC;  // (only with the four-vector layout: checked where it starts)
-    }
-    // (a refactorisation on the device costs about twice the host's, so its period is the longest the kept columns allow: 25FV47 64.8 us
-    //  per pivot at 47, 60.3 at 63; GREENBEA 154.5 -> 142.3)
-    if (device_refactor_ && opt_.refactor_period <= 0) refactor_period_ = LU_MAX_SLOTS - 1;
-    if (lu_inverse_ && !lu_fits_lds(m, refactor_period_ + 1, true))
-        throw std::invalid_argument("the inverse-factor carry keeps its vectors in LDS (32 bytes per row, 24 beyond ~4300 rows): at most about 5800 rows (use the LU or the explicit carry beyond)");
-    if (lu_mode_ && !lu_inverse_) {
-        if (!lu_fits_lds(m, refactor_period_ + 1)) throw std::invalid_argument("the LU carry keeps its two solve vectors in LDS (16 bytes per row): at most about 8000 rows with this refactor period (use the explicit carry beyond)");
-    }
-    // dense block: the longest run of provider columns, starting at the first one, with nnz > m/2 (config 3: all
-    // structural columns); steepest edge only (the dense kernel implements that rule)
-    int n_dense = 0;
-    if (opt_.pivot_rule == RELP_PIVOT_STEEPEST_EDGE && m >= 64)
-        while (n_dense < n_p && (col_start[n_art + n_dense + 1] - col_start[n_art + n_dense]) * 2 > m) ++n_dense;
-    if (n_dense < 64 || bounded_ || lu_mode_ || network_) n_dense = 0;  // (the dense pipeline belongs to the explicit inverse)
-    d_.n_dense = n_dense;
-    d_.dense_first = n_art;
-    d_.dense_ld = (m + 3) & ~3;
-    sparse_first_ = n_art + n_dense;
-    price_lds_ = (size_t)3 * m * sizeof(double);
-    {   // graph LPs (at most two entries per column) beyond the LDS-resident size: width-2 padded copy, 4x less padding to stream
-        int longest = 0;
-        for (int j = 0; j < n; ++j) longest = std::max(longest, col_start[j + 1] - col_start[j]);
-        d_.ell_w = (longest <= 2 && n_dense == 0 && price_lds_ > 160 * 1024 - 1024 && !sw(RELP_SW_ELL_WIDE)) ? 2 : ELL_W;
-    }
-    // incidence columns (graph providers, examples/max_flow.rs:174-200): every value +-1 and small integer costs -- the
-    // pricing pass then GENERATES the column from 8 bytes per arc (row | sign) instead of streaming 24 + 8 bytes of it
-    bool unit = d_.ell_w == 2 && !sw(RELP_SW_NO_GENERATED_COLUMNS);
-    for (size_t e = 0; unit && e < value.size(); ++e) unit = value[e] == 1.0 || value[e] == -1.0;
-    for (int j = 0; unit && j < n; ++j) unit = cost2[j] == std::floor(cost2[j]) && std::fabs(cost2[j]) <= 127.0;
-    const int cpb = price_columns_per_block(d_.ell_w, unit);
-    price_blocks_ = std::min(d_.ell_w == 2 && !unit ? 2048 : 1024, (n - sparse_first_ + cpb - 1) / cpb);
-    // Dense pipeline whose sparse columns are one single-entry column per row at most (the slack columns of config 3): the BTRAN
-    // pass of a pivot prices them for the next one (btran_pass_kernel), one candidate slot per workgroup of that pass.
-    std::vector<int> slack_of_row;
-    {
-        bool eligible = n_dense > 0 && opt_.pivot_rule == RELP_PIVOT_STEEPEST_EDGE && m % 2 == 0 && m <= 4096 &&
-                        !product_form_off && !sw(RELP_SW_NO_SLACK_IN_BTRAN) && n > sparse_first_;
-        if (eligible) {  // (the deferred product form needs the multi-block FTRAN: a column longer than its threshold)
-            int longest = 0;
-            for (int j = n_art; j < n; ++j) longest = std::max(longest, col_start[j + 1] - col_start[j]);
-            eligible = longest > ftran_min_nnz_opt;
-        }
-        if (eligible) {
-            slack_of_row.assign(m, -1);
-            for (int j = sparse_first_; eligible && j < n; ++j) {
-                eligible = col_start[j + 1] - col_start[j] == 1 && slack_of_row[row_index[col_start[j]]] < 0;
-                if (eligible) slack_of_row[row_index[col_start[j]]] = j;
-            }
-        }
-        if (!eligible) slack_of_row.clear();
-        else price_blocks_ = btran_pass_blocks();
-    }
-    dense_blocks_ = n_dense > 0 ? std::min(opt_.dense_blocks > 0 ? opt_.dense_blocks : 256, (n_dense + 15) / 16) : 0;  // 16 waves per workgroup, one workgroup per CU (96 KB of LDS each)
-    bool dense_bytes = n_dense > 0 && !want_f64_block && !want_f32_block;  // narrowest exact storage type
-    for (int jd = 0; dense_bytes && jd < n_dense; ++jd)
-        for (int e = col_start[n_art + jd]; dense_bytes && e < col_start[n_art + jd + 1]; ++e)
-            dense_bytes = value[e] >= -128.0 && value[e] <= 127.0 && value[e] == std::floor(value[e]);
-    {
-        bool full = n_dense > 0;
-        for (int jd = 0; full && jd < n_dense; ++jd) {
-            full = col_start[n_art + jd + 1] - col_start[n_art + jd] == m;
-            for (int e = col_start[n_art + jd], i = 0; full && i < m; ++e, ++i) full = row_index[e] == i;
-        }
-        d_.dense_full = full ? 1 : 0;
-        d_.dense_csc_start = n_dense > 0 ? col_start[n_art] : 0;
-    }
-    bool dense_floats = n_dense > 0 && !dense_bytes && !want_f64_block;  // float holds every entry exactly
-    for (int jd = 0; dense_floats && jd < n_dense; ++jd)
-        for (int e = col_start[n_art + jd]; dense_floats && e < col_start[n_art + jd + 1]; ++e) dense_floats = (double)(float)value[e] == value[e];
-    int vector_len = m;  // -pi, rho, w: zero-padded to the dense block's row count when the column-per-lane pricing reads them
-    if (n_dense > 0 && dense_lane_slots(n_dense) <= 1024 && !sw(RELP_SW_NO_DENSE_LANE)) {
-        // column-per-lane pricing: one workgroup and one candidate slot per group of 16 columns
-        d_.dense_lane = 1;
-        d_.dense_ld = dense_lane_ld(m);
-        dense_blocks_ = dense_lane_slots(n_dense);
-        vector_len = d_.dense_ld;
-    }
-    if (price_blocks_ + dense_blocks_ == 0) price_blocks_ = 1;
-    price_lds_ = (size_t)3 * m * sizeof(double);
-    int max_nnz = 0;
-    for (int j = n_art; j < n; ++j) max_nnz = std::max(max_nnz, col_start[j + 1] - col_start[j]);
-    ftran_slices_ = 0;
-    // columns longer than this take the multi-block FTRAN pipeline (RELP_FTRAN_MIN_NNZ: test hook to exercise it on small LPs)
-    const int ftran_min_nnz = ftran_min_nnz_opt;
-    if (max_nnz > ftran_min_nnz && fast_k2_available(d_, price_blocks_ + dense_blocks_)) ftran_slices_ = opt_.ftran_slices > 0 ? opt_.ftran_slices : std::min(64, (max_nnz + 255) / 256);  // (4096 x 8192: 8 / 16 / 32 / 64 slices = 20.8k / 21.2k / 20.8k / 19.7k pivots/s)
-
     d_.col_start = device_alloc<int>(n + 1);
     d_.row_index = device_alloc<int>(nnz);
     d_.value = device_alloc<double>(nnz);
@@ -281,83 +179,149 @@ void Solver::upload() {
     d_.cost1 = device_alloc<double>(n);
     d_.cost2 = device_alloc<double>(n);
     d_.rhs = device_alloc<double>(m);
+    d_.rhs0 = device_alloc<double>(m);
+    upload_vec(d_.col_start, col_start, stream_);
+    upload_vec(d_.row_index, row_index, stream_);
+    upload_vec(d_.value, value, stream_);
+    upload_vec(d_.row_start, row_start, stream_);
+    upload_vec(d_.col_index, col_index, stream_);
+    upload_vec(d_.row_value, row_value, stream_);
+    upload_vec(d_.cost1, cost1, stream_);
+    upload_vec(d_.cost2, host_.cost2, stream_);
+    upload_vec(d_.rhs, host_.rhs, stream_);
+    upload_vec(d_.rhs0, host_.rhs, stream_);
+    RELP_HIP(hipStreamSynchronize(stream_));
+    if (opt_.crash) {  // the rows by columns too (the crash walks them)
+        h_row_start_ = std::move(row_start);
+        h_col_index_ = std::move(col_index);
+    }
+}
+
+// What the pricing pass streams instead of the CSC: the first ell_w entries of every column, padded; generated incidence columns as
+// (row | sign) and a cost byte; and, at width 2, the per-row records or tables of -pi, rho_p and w.
+void Solver::upload_pricing_copy() {
+    const int m = path_.m, n = path_.n, width = path_.ell_w;
+    const std::vector<int>&col_start = host_.col_start, &row_index = host_.row_index;
+    const std::vector<double>& value = host_.value;
+    std::vector<int> er((size_t)n * width, 0);
+    std::vector<double> ev((size_t)n * width, 0.0);
+    for (int j = 0; j < n; ++j)
+        for (int e = col_start[j], k = 0; e < col_start[j + 1] && k < width; ++e, ++k) {
+            er[(size_t)j * width + k] = row_index[e];
+            ev[(size_t)j * width + k] = value[e];
+        }
+    if (path_.generated_columns) {
+        for (int j = 0; j < n; ++j)
+            for (int k = 0; k < width; ++k) {
+                const int len = col_start[j + 1] - col_start[j];
+                er[(size_t)j * width + k] = k < len ? (int)((unsigned)row_index[col_start[j] + k] | (value[col_start[j] + k] < 0.0 ? 0x80000000u : 0u))
+                                                    : 0x7fffffff;
+            }
+        std::vector<signed char> c8(n);
+        for (int j = 0; j < n; ++j) c8[j] = (signed char)host_.cost2[j];
+        d_.cost8 = device_alloc<signed char>(n);
+        d_.cost8_2 = device_alloc<signed char>(n);
+        upload_vec(d_.cost8_2, c8, stream_);
+    } else {
+        d_.ell_vals = device_alloc<double>(ev.size());
+        upload_vec(d_.ell_vals, ev, stream_);
+    }
+    d_.ell_rows = device_alloc<int>(er.size());
+    upload_vec(d_.ell_rows, er, stream_);
+    if (width == 2 && !path_.generated_columns) {  // columns with values: the packed records of price_kernel<.., 2>
+        d_.prw = device_alloc<double>((size_t)4 * m);
+        RELP_HIP(hipMemsetAsync(d_.prw, 0, (size_t)4 * m * sizeof(double), stream_));
+    } else if (path_.rho_words) {  // generated columns: -pi from its own vector, rho_p's non-zero rows as bits ...
+        d_.rho_bits = device_alloc<unsigned>((size_t)2 * path_.rho_words);
+        RELP_HIP(hipMemsetAsync(d_.rho_bits, 0, (size_t)2 * path_.rho_words * sizeof(unsigned), stream_));
+    } else if (path_.generated_columns) {  // ... (bytes beyond LDS)
+        d_.rho_nz = device_alloc<unsigned char>(m);
+        RELP_HIP(hipMemsetAsync(d_.rho_nz, 0, m, stream_));
+    }
+    RELP_HIP(hipStreamSynchronize(stream_));
+}
+
+// The dense block in the form the plan chose (DenseStorage).
+void Solver::upload_dense_block() {
+    const int n_art = path_.n_art, n_dense = path_.n_dense;
+    const std::vector<int>&col_start = host_.col_start, &row_index = host_.row_index;
+    const std::vector<double>& value = host_.value;
+    const auto put = [&](auto*& dst, const auto& block) {  // (synchronised: `block` is a temporary of the caller)
+        dst = device_alloc<typename std::decay_t<decltype(block)>::value_type>(block.size());
+        upload_vec(dst, block, stream_);
+        RELP_HIP(hipStreamSynchronize(stream_));
+    };
+    std::vector<double> dense;  // plain column-major
+    if (path_.dense_storage == DenseStorage::F32_ROWS || path_.dense_storage == DenseStorage::F64_ROWS) {
+        dense.assign((size_t)n_dense * d_.dense_ld, 0.0);
+        for (int jd = 0; jd < n_dense; ++jd)
+            for (int e = col_start[n_art + jd]; e < col_start[n_art + jd + 1]; ++e) dense[(size_t)jd * d_.dense_ld + row_index[e]] = value[e];
+    }
+    switch (path_.dense_storage) {
+    case DenseStorage::NONE: return;
+    case DenseStorage::I8_LANE: put(d_.dense_val8, pack_dense_lanes<signed char>(host_, n_art, n_dense, path_.dense_blocks, d_.dense_ld)); break;
+    case DenseStorage::F32_LANE: put(d_.dense_val32, pack_dense_lanes<float>(host_, n_art, n_dense, path_.dense_blocks, d_.dense_ld)); break;
+    case DenseStorage::F64_LANE: put(d_.dense_val, pack_dense_lanes<double>(host_, n_art, n_dense, path_.dense_blocks, d_.dense_ld)); break;
+    case DenseStorage::I8_PERMUTED: {
+        std::vector<signed char> bytes((size_t)n_dense * d_.dense_ld, 0);
+        for (int jd = 0; jd < n_dense; ++jd)
+            for (int e = col_start[n_art + jd]; e < col_start[n_art + jd + 1]; ++e) {
+                const int row = row_index[e], chunk = row / 1024, within = row % 1024;
+                const int pair = within / 128, lane = (within % 128) / 2, t = 2 * pair + (within & 1);  // see price_dense_kernel
+                bytes[(size_t)jd * d_.dense_ld + (size_t)chunk * 1024 + lane * 16 + t] = (signed char)value[e];
+            }
+        put(d_.dense_val8, bytes);
+        break;
+    }
+    case DenseStorage::F32_ROWS: put(d_.dense_val32, std::vector<float>(dense.begin(), dense.end())); break;
+    case DenseStorage::F64_ROWS: put(d_.dense_val, dense); break;
+    }
+    if (!path_.dense_lane) configure_dense_lds((size_t)3 * d_.dense_ld * sizeof(double));  // (one wave per column: the vectors are in LDS)
+}
+
+// Everything a pivot reads and writes: the vectors, the inverse, the candidate slots of the pricing passes, the buffers of the
+// pivot form the plan chose, the bounds of an LP with implicit bounds, and the control block.
+void Solver::allocate_pivot_state() {
+    const int m = path_.m, n = path_.n, vector_len = path_.vector_len, slots = path_.slots();
     d_.xB = device_alloc<double>(m);
     d_.minus_pi = device_alloc<double>(vector_len);
     RELP_HIP(hipMemsetAsync(d_.minus_pi, 0, (size_t)vector_len * sizeof(double), stream_));
     d_.basis = device_alloc<int>(m);
     d_.pos = device_alloc<int>(n);
     d_.gamma = device_alloc<double>(n);
+    RELP_HIP(hipMemsetAsync(d_.gamma, 0, n * sizeof(double), stream_));
     d_.cb = device_alloc<double>(m);
     d_.cb_idx = device_alloc<int>(m + 1);
-    tick("sparse arrays");
-    if (!lu_mode_ && !network_) d_.Binv = device_alloc<double>((size_t)m * d_.ld);  // the LU and the forest carries have no m x m array at all
     // The second copy of the inverse and the residual matrix are only needed once a polish finds something to correct
     // (Solver::ensure_polish_buffers): at m = 65 534 each is 34 GB and about a second of hipMalloc, and the max-flow LP of
     // config 5, whose bases are unimodular, never needs them.
-    tick("inverse buffers (hipMalloc)");
+    if (!path_.lu_mode && !path_.network) d_.Binv = device_alloc<double>((size_t)m * d_.ld);  // the LU and the forest carries have no m x m array at all
     d_.alpha = device_alloc<double>(m);
+    RELP_HIP(hipMemsetAsync(d_.alpha, 0, m * sizeof(double), stream_));
     d_.rho = device_alloc<double>(vector_len);
     RELP_HIP(hipMemsetAsync(d_.rho, 0, (size_t)vector_len * sizeof(double), stream_));
     d_.nz_index = device_alloc<int>(m);
     d_.nz_alpha = device_alloc<double>(m);
     d_.w = device_alloc<double>(vector_len);
     RELP_HIP(hipMemsetAsync(d_.w, 0, (size_t)vector_len * sizeof(double), stream_));
-    d_.cand_key = device_alloc<double>(price_blocks_ + dense_blocks_);
-    d_.cand_j = device_alloc<int>(price_blocks_ + dense_blocks_);
-    d_.cand_cbar = device_alloc<double>(price_blocks_ + dense_blocks_);
-    d_.cand_rows = device_alloc<int>((size_t)(price_blocks_ + dense_blocks_) * ELL_W);
-    d_.cand_vals = device_alloc<double>((size_t)(price_blocks_ + dense_blocks_) * ELL_W);
-    d_.cand_len = device_alloc<int>(price_blocks_ + dense_blocks_);
-    RELP_HIP(hipMemsetAsync(d_.cand_rows, 0, (size_t)(price_blocks_ + dense_blocks_) * ELL_W * sizeof(int), stream_));  // width-2 pricing writes two of the ELL_W slots
-    RELP_HIP(hipMemsetAsync(d_.cand_vals, 0, (size_t)(price_blocks_ + dense_blocks_) * ELL_W * sizeof(double), stream_));
-    {
-        const int width = d_.ell_w;
-        std::vector<int> er((size_t)n * width, 0);
-        std::vector<double> ev((size_t)n * width, 0.0);
-        for (int j = 0; j < n; ++j)
-            for (int e = col_start[j], k = 0; e < col_start[j + 1] && k < width; ++e, ++k) {
-                er[(size_t)j * width + k] = row_index[e];
-                ev[(size_t)j * width + k] = value[e];
-            }
-        if (unit) {  // (generated incidence columns: decided where the pricing grid was sized)
-            for (int j = 0; j < n; ++j)
-                for (int k = 0; k < width; ++k) {
-                    const int len = col_start[j + 1] - col_start[j];
-                    er[(size_t)j * width + k] = k < len ? (int)((unsigned)row_index[col_start[j] + k] | (value[col_start[j] + k] < 0.0 ? 0x80000000u : 0u))
-                                                        : 0x7fffffff;
-                }
-            std::vector<signed char> c8(n);
-            for (int j = 0; j < n; ++j) c8[j] = (signed char)cost2[j];
-            d_.cost8 = device_alloc<signed char>(n);
-            d_.cost8_2 = device_alloc<signed char>(n);
-            upload_vec(d_.cost8_2, c8, stream_);
-        } else {
-            d_.ell_vals = device_alloc<double>(ev.size());
-            upload_vec(d_.ell_vals, ev, stream_);
-        }
-        d_.ell_rows = device_alloc<int>(er.size());
-        upload_vec(d_.ell_rows, er, stream_);
-        RELP_HIP(hipStreamSynchronize(stream_));
-    }
-    d_.alpha_part = device_alloc<double>((size_t)std::max(1, ftran_slices_) * m);
+    d_.cand_key = device_alloc<double>(slots);
+    d_.cand_j = device_alloc<int>(slots);
+    d_.cand_cbar = device_alloc<double>(slots);
+    d_.cand_rows = device_alloc<int>((size_t)slots * ELL_W);
+    d_.cand_vals = device_alloc<double>((size_t)slots * ELL_W);
+    d_.cand_len = device_alloc<int>(slots);
+    RELP_HIP(hipMemsetAsync(d_.cand_rows, 0, (size_t)slots * ELL_W * sizeof(int), stream_));  // width-2 pricing writes two of the ELL_W slots
+    RELP_HIP(hipMemsetAsync(d_.cand_vals, 0, (size_t)slots * ELL_W * sizeof(double), stream_));
+    d_.alpha_part = device_alloc<double>((size_t)std::max(1, path_.ftran_slices) * m);
     d_.alpha_in = device_alloc<double>(m);
-    // deferred product form of the inverse: the dense pipeline (multi-block FTRAN), m even and <= 4096 (alpha_reduce_kernel, btran_pass_kernel)
-    // (relp_options.product_form = 1 / RELP_ETA=0 keeps the per-pivot rank-one update: A/B measurements)
-    eta_mode_ = n_dense > 0 && ftran_slices_ > 0 && m % 2 == 0 && m <= 4096 && !product_form_off;
-    d_.eta_cap = eta_mode_ ? eta_max() : 0;
-    slack_in_btran_ = eta_mode_ && !slack_of_row.empty();
-    if (slack_in_btran_) {
+    if (path_.slack_in_btran) {
         d_.slack_of_row = device_alloc<int>(m);
-        upload_vec(d_.slack_of_row, slack_of_row, stream_);
-        RELP_HIP(hipStreamSynchronize(stream_));
+        upload_vec(d_.slack_of_row, path_.slack_of_row, stream_);
     }
-    // unit columns of the inverse are tracked where skipping them pays: the dense pipeline and the larger sparse LPs
-    // (below that the update kernel is latency bound and the extra indirection would cost a round trip)
-    d_.track_touched = (eta_mode_ || m > 2048) && !lu_mode_ && !network_ && !sw(RELP_SW_NO_TOUCHED) ? 1 : 0;
     d_.touched = device_alloc<int>(m);
     d_.tlist = device_alloc<int>(m);
     RELP_HIP(hipMemsetAsync(d_.touched, 0, m * sizeof(int), stream_));
-    if (eta_mode_) {
+    if (path_.eta_mode) {  // deferred product form of the inverse (alpha_reduce_kernel, btran_pass_kernel)
         d_.eta_cols = device_alloc<double>((size_t)2 * d_.eta_cap * d_.ld);
         d_.eta_dot_part = device_alloc<double>((size_t)d_.eta_cap * ((m + 63) / 64));
         d_.eta_rows = device_alloc<int>(d_.eta_cap);
@@ -366,90 +330,21 @@ void Solver::upload() {
         RELP_HIP(hipMemsetAsync(d_.eta_slot, 0xff, m * sizeof(int), stream_));
         configure_btran_lds((size_t)2 * ((m + 1) & ~1) * sizeof(double));
     }
-    if (dense_bytes && d_.dense_lane) {
-        const std::vector<signed char> bytes = pack_dense_lanes<signed char>(host_, n_art, n_dense, dense_blocks_, d_.dense_ld);
-        d_.dense_val8 = device_alloc<signed char>(bytes.size());
-        upload_vec(d_.dense_val8, bytes, stream_);
-        dense_entry_bytes_ = 1;
-        RELP_HIP(hipStreamSynchronize(stream_));
-    } else if (dense_bytes && (size_t)3 * ((m + 1023) & ~1023) * sizeof(double) > 160 * 1024 - 4096) {
-        dense_bytes = false;  // (the row-permuted form keeps the padded vectors in LDS)
-    }
-    if (dense_floats && d_.dense_lane) {
-        const std::vector<float> floats = pack_dense_lanes<float>(host_, n_art, n_dense, dense_blocks_, d_.dense_ld);
-        d_.dense_val32 = device_alloc<float>(floats.size());
-        upload_vec(d_.dense_val32, floats, stream_);
-        dense_entry_bytes_ = 4;
-        RELP_HIP(hipStreamSynchronize(stream_));
-    } else if (dense_bytes && d_.dense_lane) {
-    } else if (d_.dense_lane) {
-        const std::vector<double> doubles = pack_dense_lanes<double>(host_, n_art, n_dense, dense_blocks_, d_.dense_ld);
-        d_.dense_val = device_alloc<double>(doubles.size());
-        upload_vec(d_.dense_val, doubles, stream_);
-        dense_entry_bytes_ = 8;
-        RELP_HIP(hipStreamSynchronize(stream_));
-    } else if (dense_bytes) {
-        d_.dense_ld = (m + 1023) & ~1023;
-        std::vector<signed char> bytes((size_t)n_dense * d_.dense_ld, 0);
-        for (int jd = 0; jd < n_dense; ++jd)
-            for (int e = col_start[n_art + jd]; e < col_start[n_art + jd + 1]; ++e) {
-                const int row = row_index[e], chunk = row / 1024, within = row % 1024;
-                const int pair = within / 128, lane = (within % 128) / 2, t = 2 * pair + (within & 1);  // see price_dense_kernel
-                bytes[(size_t)jd * d_.dense_ld + (size_t)chunk * 1024 + lane * 16 + t] = (signed char)value[e];
-            }
-        d_.dense_val8 = device_alloc<signed char>(bytes.size());
-        upload_vec(d_.dense_val8, bytes, stream_);
-        dense_entry_bytes_ = 1;
-        RELP_HIP(hipStreamSynchronize(stream_));
-        configure_dense_lds((size_t)3 * d_.dense_ld * sizeof(double));
-    } else if (n_dense > 0) {
-        std::vector<double> dense((size_t)n_dense * d_.dense_ld, 0.0);
-        for (int jd = 0; jd < n_dense; ++jd)
-            for (int e = col_start[n_art + jd]; e < col_start[n_art + jd + 1]; ++e) dense[(size_t)jd * d_.dense_ld + row_index[e]] = value[e];
-        bool exact_in_float = !want_f64_block;  // relp_options.dense_storage = RELP_DENSE_DOUBLE keeps the f64 block
-        for (size_t k = 0; exact_in_float && k < dense.size(); ++k) exact_in_float = (double)(float)dense[k] == dense[k];
-        if (exact_in_float) {
-            std::vector<float> dense32(dense.begin(), dense.end());
-            d_.dense_val32 = device_alloc<float>(dense32.size());
-            upload_vec(d_.dense_val32, dense32, stream_);
-        } else {
-            d_.dense_val = device_alloc<double>(dense.size());
-            upload_vec(d_.dense_val, dense, stream_);
-        }
-        dense_entry_bytes_ = exact_in_float ? 4 : 8;
-        RELP_HIP(hipStreamSynchronize(stream_));
-        configure_dense_lds((size_t)3 * d_.dense_ld * sizeof(double));
-    }
-    d_.rhs0 = device_alloc<double>(m);
-    if (bounded_) {
-        const std::vector<double> ub = implicit_upper_bounds(md, cols_);
+    if (path_.bounded) {
+        const std::vector<double> ub = implicit_upper_bounds(form_.data, cols_);
         zero_width_.assign(n, 0);
         for (int j = 0; j < n; ++j) zero_width_[j] = ub[j] == 0.0 ? 1 : 0;
         d_.ub = device_alloc<double>(n);
         d_.xub = device_alloc<double>(m);
         d_.flipped = device_alloc<int>(n);
         upload_vec(d_.ub, ub, stream_);
-        RELP_HIP(hipStreamSynchronize(stream_));
+        RELP_HIP(hipStreamSynchronize(stream_));  // (`ub` is read until the copy has been made)
     }
-    if (!fast_k2_available(d_, price_blocks_ + dense_blocks_) && (!sw(RELP_SW_K2_SINGLE) || network_)) {  // m > 8192: multi-workgroup ratio test
+    if (path_.multi_workgroup_ratio) {  // m > 8192
         d_.k2_partd = device_alloc<double>((size_t)8 * ((m + 1023) / 1024));
         d_.k2_parti = device_alloc<int>((size_t)4 * ((m + 1023) / 1024));
     }
-    // `Tableau::select_primal_pivot_row` (tableau/mod.rs:287-313): which ratio test runs.  The reference's rule is implemented by the
-    // register-resident ratio test (m <= 8192), the fused pivot kernel and the LU pivot kernel; the multi-workgroup test beyond 8192 rows
-    // and the one-workgroup fallback implement the two-pass rule only.  AUTO (the default): the reference's rule where the data are
-    // small integers, Harris on decimal data.
-    {
-        // (the forest carry has the reference's rule at every size: alpha is +-1 on its path, see net_enqueue_pivot)
-        const bool kernels_have_it = lu_mode_ || network_ || fast_k2_available(d_, price_blocks_ + dense_blocks_);
-        if (opt_.ratio_rule == RELP_RATIO_TEXTBOOK && !kernels_have_it)
-            throw std::invalid_argument("RELP_RATIO_TEXTBOOK: the reference's ratio test is implemented up to 8192 rows (the multi-workgroup ratio test has the two-pass rule only)");
-        ratio_textbook_ = opt_.ratio_rule == RELP_RATIO_TEXTBOOK || (opt_.ratio_rule == RELP_RATIO_AUTO && host_.small_integer_data() && kernels_have_it);
-    }
-    // small LPs: ratio test and inverse update in one launch (pivot_fused_kernel; RELP_NO_FUSED=1 keeps the three-kernel pivot)
-    fused_ = !lu_mode_ && !network_ && !bounded_ && !eta_mode_ && n_dense == 0 && ftran_slices_ == 0 && !d_.track_touched && d_.ell_w == ELL_W &&
-             fused_pivot_available(d_, price_blocks_) && opt_.pivot_kernels != 1;
-    if (fused_) {
+    if (path_.fused) {  // x_B, the basis and the control block twice (pivot_fused_kernel)
         for (int k = 0; k < 2; ++k) {
             d_.state[k].ctl = device_alloc<Ctl>(1);
             d_.state[k].xB = device_alloc<double>(m);
@@ -461,52 +356,7 @@ void Solver::upload() {
     d_.ctl = device_alloc<Ctl>(1);
     d_.dbg = device_alloc<unsigned long long>(64);
     RELP_HIP(hipMemsetAsync(d_.dbg, 0, 64 * sizeof(unsigned long long), stream_));
-
-    upload_vec(d_.col_start, col_start, stream_);
-    upload_vec(d_.row_index, row_index, stream_);
-    upload_vec(d_.value, value, stream_);
-    upload_vec(d_.row_start, row_start, stream_);
-    upload_vec(d_.col_index, col_index, stream_);
-    upload_vec(d_.row_value, row_value, stream_);
-    upload_vec(d_.cost1, cost1, stream_);
-    upload_vec(d_.cost2, cost2, stream_);
-    upload_vec(d_.rhs, rhs, stream_);
-    upload_vec(d_.rhs0, rhs, stream_);
-    if (d_.ell_w == 2 && !d_.cost8) {  // columns with values: the packed records of price_kernel<.., 2>
-        d_.prw = device_alloc<double>((size_t)4 * m);
-        RELP_HIP(hipMemsetAsync(d_.prw, 0, (size_t)4 * m * sizeof(double), stream_));
-    } else if (d_.ell_w == 2) {  // generated columns: -pi from its own vector, rho_p's non-zero rows as bits (bytes beyond LDS)
-        d_.price_unit_pairs = sw(RELP_SW_PRICE_UNIT_PAIRS);
-        d_.rho_words = ((m + 127) / 128) * 4;
-        if ((size_t)d_.rho_words * 4 > 64 * 1024 || sw(RELP_SW_NO_RHO_BITS) || d_.price_unit_pairs) d_.rho_words = 0;
-        if (d_.rho_words) {
-            d_.rho_bits = device_alloc<unsigned>((size_t)2 * d_.rho_words);
-            RELP_HIP(hipMemsetAsync(d_.rho_bits, 0, (size_t)2 * d_.rho_words * sizeof(unsigned), stream_));
-        } else {
-            d_.rho_nz = device_alloc<unsigned char>(m);
-            RELP_HIP(hipMemsetAsync(d_.rho_nz, 0, m, stream_));
-        }
-    }
-    RELP_HIP(hipMemsetAsync(d_.rho, 0, m * sizeof(double), stream_));
-    RELP_HIP(hipMemsetAsync(d_.w, 0, m * sizeof(double), stream_));
-    RELP_HIP(hipMemsetAsync(d_.alpha, 0, m * sizeof(double), stream_));
-    RELP_HIP(hipMemsetAsync(d_.gamma, 0, n * sizeof(double), stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
-    configure_lds(std::min<size_t>(price_lds_, 160 * 1024 - 1024));
-    tick("uploads");
-
-    stats_.price_bytes = (long long)(col_start[n] - col_start[sparse_first_]) * 12 + (long long)(n - n_art) * 24 +
-                         (long long)n_dense * m * dense_entry_bytes_;  // upper bound: every dense column non-basic
-    if (d_.cost8) stats_.price_bytes = (long long)(n - n_art) * (8 + 1 + 4);  // endpoints, cost byte, pos (+ the weight of the few columns that need it)
-    stats_.update_bytes = network_ ? 0 : (long long)2 * m * m * 8;
-    if (network_) net_allocate();
-    h_basis_.assign(m, -1);
-    h_solution_.assign(md.nr_columns(), 0.0);
-    if (opt_.crash) {  // the rows by columns too (the crash walks them)
-        h_row_start_ = row_start;
-        h_col_index_ = col_index;
-    }
-    if (!(lu_mode_ || network_ || opt_.crash)) host_ = DeviceMatrix{};  // (nothing on the host reads it after the upload)
 }
 
 Ctl Solver::read_ctl() {
@@ -548,21 +398,21 @@ void Solver::begin_phase_one() {
     const int m = d_.m, n = d_.n, n_art = d_.n_art;
     const std::vector<int>& basis = cols_.basis0;
     std::vector<int> pos = cols_.pos0();
-    if (bounded_)  // a variable whose two bounds coincide can never move: it is not priced (pos -3; see DeviceLP::pos)
+    if (path_.bounded)  // a variable whose two bounds coincide can never move: it is not priced (pos -3; see DeviceLP::pos)
         for (int j = n_art; j < n; ++j)
             if (zero_width_[j] && pos[j] < 0) pos[j] = -3;
     upload_vec(d_.basis, basis, stream_);
     upload_vec(d_.pos, pos, stream_);
     RELP_HIP(hipMemcpyAsync(d_.rhs, d_.rhs0, m * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-    if (bounded_) {  // nothing is complemented; the initial basic variables (artificials, <= slacks) have no upper bound
+    if (path_.bounded) {  // nothing is complemented; the initial basic variables (artificials, <= slacks) have no upper bound
         std::vector<double> xub(m, std::numeric_limits<double>::infinity());
         upload_vec(d_.xub, xub, stream_);
         RELP_HIP(hipMemsetAsync(d_.flipped, 0, n * sizeof(int), stream_));
         RELP_HIP(hipStreamSynchronize(stream_));
     }
     RELP_HIP(hipMemcpyAsync(d_.xB, d_.rhs, m * sizeof(double), hipMemcpyDeviceToDevice, stream_));
-    if (lu_mode_) lu_identity();
-    else if (network_) {
+    if (path_.lu_mode) lu_identity();
+    else if (path_.network) {
         net_upload(net_build(basis, std::vector<int>()));  // every row its own root (unit columns)
         if (net_.stats) RELP_HIP(hipMemsetAsync(net_.stats, 0, NS_WORDS * sizeof(unsigned long long), stream_));
     }
@@ -598,7 +448,7 @@ void Solver::begin_phase_one() {
 // gamma_j = 1 + |B^-1 a_j|^2 (pivot_rule.rs:202-219) are computed from the same sparse columns.  The crash is only kept when
 // it is primal feasible; phase one then starts from it (with zero artificials left it ends without a pivot).
 bool Solver::crash_basis() {
-    if (lu_mode_ || eta_mode_ || d_.n_dense > 0 || host_.col_start.empty() || h_row_start_.empty()) return false;
+    if (path_.lu_mode || path_.eta_mode || d_.n_dense > 0 || host_.col_start.empty() || h_row_start_.empty()) return false;
     const int m = d_.m, n = d_.n, n_art = d_.n_art;
     const bool timing = diagnostic("RELP_TIME_SOLVE");
     double t_last = now_seconds();
@@ -627,7 +477,7 @@ bool Solver::crash_basis() {
     std::vector<char> is_basic(n, 0);
     for (int i = 0; i < m; ++i) is_basic[basis[i]] = 1;
     for (int j = n_art; j < n; ++j)
-        if (count[j] == 1 && !is_basic[j] && !(bounded_ && zero_width_[j])) queue.push_back(j);
+        if (count[j] == 1 && !is_basic[j] && !(path_.bounded && zero_width_[j])) queue.push_back(j);
     std::vector<int> order_of_row(m, -1), crash_rows;  // order in which the rows were covered
     std::vector<double> diagonal(m, 1.0);
     for (size_t head = 0; head < queue.size(); ++head) {
@@ -650,13 +500,13 @@ bool Solver::crash_basis() {
         for (int e = row_start[r]; e < row_start[r + 1]; ++e) {
             const int j2 = row_cols[e];
             if (j2 < n_art) continue;
-            if (--count[j2] == 1 && !is_basic[j2] && !(bounded_ && zero_width_[j2])) queue.push_back(j2);
+            if (--count[j2] == 1 && !is_basic[j2] && !(path_.bounded && zero_width_[j2])) queue.push_back(j2);
         }
     }
     const int covered = (int)crash_rows.size();
     tick("rows by columns, BFS");
     if (covered == 0) return false;
-    if (network_) {  // the forest carry takes the crash columns as they are: no inverse on the host
+    if (path_.network) {  // the forest carry takes the crash columns as they are: no inverse on the host
         if (!net_crash(basis)) return false;
         crash_rows_covered_ = covered;
         tick("forest, x_B, weights");
@@ -715,7 +565,7 @@ bool Solver::crash_basis() {
         for (size_t e = inv_start[k]; e < inv_start[k + 1]; ++e) xb[inv_pos[e]] += inv_val[e] * b;
     }
     std::vector<double> ub;
-    if (bounded_) {
+    if (path_.bounded) {
         ub.resize(n);
         RELP_HIP(hipMemcpyAsync(ub.data(), d_.ub, n * sizeof(double), hipMemcpyDeviceToHost, stream_));
         RELP_HIP(hipStreamSynchronize(stream_));
@@ -724,7 +574,7 @@ bool Solver::crash_basis() {
     for (int i = 0; i < m; ++i) scale = std::max(scale, std::fabs(host_.rhs[i]));
     for (int i = 0; i < m; ++i) {
         if (xb[i] < -1e-9 * scale) return false;
-        if (bounded_ && xb[i] > ub[basis[i]] + 1e-9 * scale) return false;
+        if (path_.bounded && xb[i] > ub[basis[i]] + 1e-9 * scale) return false;
         if (xb[i] < 0.0) xb[i] = 0.0;
     }
     // steepest-edge weights of the non-basic columns from the sparse inverse columns
@@ -784,7 +634,7 @@ bool Solver::crash_basis() {
     RELP_HIP(hipMemcpyAsync(d_value, inv_val.data(), inv_val.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
     launch_scatter(d_.Binv, d_index, d_value, (long long)inv_val.size(), stream_);
     std::vector<int> pos(n, -1), touched(m, 0);
-    if (bounded_)
+    if (path_.bounded)
         for (int j = n_art; j < n; ++j)
             if (zero_width_[j]) pos[j] = -3;
     for (int i = 0; i < m; ++i) pos[basis[i]] = i;
@@ -795,7 +645,7 @@ bool Solver::crash_basis() {
     upload_vec(d_.gamma, gamma, stream_);
     upload_vec(d_.touched, touched, stream_);
     upload_vec(d_.tlist, crash_rows, stream_);
-    if (bounded_) {
+    if (path_.bounded) {
         std::vector<double> xub(m);
         for (int i = 0; i < m; ++i) xub[i] = ub[basis[i]];
         upload_vec(d_.xub, xub, stream_);
@@ -824,8 +674,8 @@ void Solver::set_phase(int phase) {
         if (phase == 1) RELP_HIP(hipMemsetAsync(d_.cost8, 0, d_.n, stream_));
         else RELP_HIP(hipMemcpyAsync(d_.cost8, d_.cost8_2, d_.n, hipMemcpyDeviceToDevice, stream_));
     }
-    if (lu_mode_) launch_lu_pi(d_, lu().device(), stream_);
-    else if (network_) net_refresh(false, true);
+    if (path_.lu_mode) launch_lu_pi(d_, lu().device(), stream_);
+    else if (path_.network) net_refresh(false, true);
     else launch_pi(d_, stream_);
     // Steepest-edge weights gamma_j = 1 + |B^-1 a_j|^2 do not depend on the costs, and the recurrences that maintain them
     // are exact: what phase one leaves is what `SteepestDescentAlongObjective::new` (pivot_rule.rs:202-219) would recompute
@@ -834,7 +684,7 @@ void Solver::set_phase(int phase) {
     const double carry_threshold = opt_.carry_weights_min > 0.0 ? opt_.carry_weights_min : 4e9;  // (test hook)
     // (the LU carry always keeps them: recomputing is one FTRAN per non-basic column)
     const bool carry_weights = phase == 2 && phase_before == 1 && !binv_identity_ &&
-                               (lu_mode_ || (double)(d_.n - d_.n_art) * (double)d_.m > carry_threshold);
+                               (path_.lu_mode || (double)(d_.n - d_.n_art) * (double)d_.m > carry_threshold);
     if (opt_.pivot_rule == RELP_PIVOT_STEEPEST_EDGE) {
         if (carry_weights) {
             Ctl pending = read_ctl();
@@ -847,9 +697,9 @@ void Solver::set_phase(int phase) {
             }
         } else if (gamma_ready_) {
             gamma_ready_ = false;  // the crash computed them on the host from its sparse inverse
-        } else if (lu_mode_ && !binv_identity_) {
+        } else if (path_.lu_mode && !binv_identity_) {
             launch_lu_gamma(d_, lu().device(), stream_);
-        } else if (network_ && !binv_identity_) {
+        } else if (path_.network && !binv_identity_) {
             net_set_gamma();
         } else {
             launch_gamma_init(d_, binv_identity_ ? 1 : 0, stream_);
@@ -871,7 +721,7 @@ void Solver::set_phase(int phase) {
 
 // One batch of `count` iterations of the loop of phase_one.rs:134-178 / phase_two.rs:36-58.
 void Solver::launch_pivots(int count, bool forced) {
-    if (fused_ && !forced) {  // two kernels per pivot; x_B, basis and control block alternate between their two copies (kernels.hip, K23)
+    if (path_.fused && !forced) {  // two kernels per pivot; x_B, basis and control block alternate between their two copies (kernels.hip, K23)
         launch_begin_batch(d_, count, stream_);
         for (int it = 0; it < count; ++it) {
             enqueue_price_fused(it & 1);
@@ -883,7 +733,7 @@ void Solver::launch_pivots(int count, bool forced) {
         return;
     }
     launch_budget(d_, count, stream_);
-    if (network_) {  // pricing, entering column + tree path, ratio test, forest update: a linear chain of launches
+    if (path_.network) {  // pricing, entering column + tree path, ratio test, forest update: a linear chain of launches
         for (int it = 0; it < count; ++it) {
             enqueue_price(0);
             net_enqueue_pivot(0);
@@ -892,7 +742,7 @@ void Solver::launch_pivots(int count, bool forced) {
         stats_.price_launches += count;
         return;
     }
-    if (lu_mode_) {  // two kernels per pivot: the pricing pass and the single-workgroup LU kernel
+    if (path_.lu_mode) {  // two kernels per pivot: the pricing pass and the single-workgroup LU kernel
         for (int it = 0; it < count; ++it) {
             enqueue_price(0);
             enqueue_ftran_ratio(0);
@@ -905,9 +755,9 @@ void Solver::launch_pivots(int count, bool forced) {
         enqueue_price(0, it == 0);
         enqueue_ftran_ratio(0);
         enqueue_update();
-        if (eta_mode_ && ((it + 1) % d_.eta_cap == 0 || it + 1 == count)) enqueue_consolidate();
+        if (path_.eta_mode && ((it + 1) % d_.eta_cap == 0 || it + 1 == count)) enqueue_consolidate();
     }
-    stats_.launches += 1 + (3LL + (dense_blocks_ > 0) + 2 * (ftran_slices_ > 0)) * count;
+    stats_.launches += 1 + (3LL + (path_.dense_blocks > 0) + 2 * (path_.ftran_slices > 0)) * count;
     stats_.price_launches += count;
 }
 
@@ -920,57 +770,57 @@ void Solver::enqueue_price(int skip_weights, bool first_of_batch) {
     // (80BAU3B, m = 5746: 486 workgroups x 138 KB = 67 MB of staging against 1.5 MB of gathers; 53.8 -> 45.7 us per pivot without).
     // Between 2000 and 2800 rows the two forms are within the run-to-run noise (BNL2, CYCLE, GREENBEA).  RELP_PRICE_LDS_MAX: A/B hook.
     const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
-    const bool use_lds = price_lds_ <= lds_max && dense_blocks_ == 0;
-    // slack_in_btran_: the BTRAN pass of the previous pivot has priced the slack columns (weights included); only the first
+    const bool use_lds = path_.price_lds <= lds_max && path_.dense_blocks == 0;
+    // path_.slack_in_btran: the BTRAN pass of the previous pivot has priced the slack columns (weights included); only the first
     // pivot of a batch has no predecessor in the batch, and its pass must not apply the weight update a second time
-    if (price_blocks_ > 0 && (!slack_in_btran_ || first_of_batch))
-        launch_price(d_, opt_.pivot_rule, price_blocks_, use_lds ? price_lds_ : 0, use_lds, slack_in_btran_ ? 1 : skip_weights, opt_.tol_dual,
-                     sparse_first_, d_.n, 0, stream_);
-    if (dense_blocks_ > 0) launch_price_dense(d_, dense_blocks_, skip_weights, opt_.tol_dual, price_blocks_, stream_);
+    if (path_.price_blocks > 0 && (!path_.slack_in_btran || first_of_batch))
+        launch_price(d_, opt_.pivot_rule, path_.price_blocks, use_lds ? path_.price_lds : 0, use_lds, path_.slack_in_btran ? 1 : skip_weights, opt_.tol_dual,
+                     path_.sparse_first, d_.n, 0, stream_);
+    if (path_.dense_blocks > 0) launch_price_dense(d_, path_.dense_blocks, skip_weights, opt_.tol_dual, path_.price_blocks, stream_);
 }
 
 // Fused mode: the pricing pass before pivot k reads the control block of copy k & 1 (it writes nothing of the twin state).
 void Solver::enqueue_price_fused(int parity) {
     DeviceLP d = d_;
     d.ctl = d_.state[parity].ctl;
-    const bool use_lds = price_lds_ <= 160 * 1024 - 1024;
-    launch_price(d, opt_.pivot_rule, price_blocks_, use_lds ? price_lds_ : 0, use_lds, 0, opt_.tol_dual, sparse_first_, d_.n, 0, stream_);
+    const bool use_lds = path_.price_lds <= 160 * 1024 - 1024;
+    launch_price(d, opt_.pivot_rule, path_.price_blocks, use_lds ? path_.price_lds : 0, use_lds, 0, opt_.tol_dual, path_.sparse_first, d_.n, 0, stream_);
 }
 void Solver::enqueue_pivot_fused(int parity) {
-    launch_pivot_fused(d_, opt_.pivot_rule, parity, price_blocks_, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, stream_);
+    launch_pivot_fused(d_, opt_.pivot_rule, parity, path_.price_blocks, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, stream_);
 }
 
 // The basis update: rank-one update of the explicit inverse (K3), or -- deferred product form -- the eta bookkeeping plus
 // one read-only pass for rho_p, w and -pi.
 void Solver::enqueue_update() {
-    if (eta_mode_) launch_eta_update(d_, opt_.tol_dual, stream_);
+    if (path_.eta_mode) launch_eta_update(d_, opt_.tol_dual, stream_);
     else launch_update(d_, stream_);
 }
 // Fold the pending etas into the stored inverse (no-op kernels when there are none; runs whatever the status is, so that
 // everything outside the pivot loop sees the plain explicit inverse).
 void Solver::enqueue_consolidate() {
-    if (eta_mode_) launch_eta_consolidate(d_, stream_);
+    if (path_.eta_mode) launch_eta_consolidate(d_, stream_);
 }
 
 // Entering column + FTRAN + ratio test (+ updates in mode 0).  Long (dense) columns take the multi-block FTRAN.
 void Solver::enqueue_ftran_ratio(int mode) {
     const int skip_art = phase_ == 2 ? 1 : 0;
-    const int slots = price_blocks_ + dense_blocks_;
-    if (network_) {
+    const int slots = path_.price_blocks + path_.dense_blocks;
+    if (path_.network) {
         net_enqueue_pivot(mode);
         return;
     }
-    if (lu_mode_) {
+    if (path_.lu_mode) {
         hipEvent_t start = nullptr, stop = nullptr;
         take_launch_timer(1, &start, &stop);
-        launch_lu_pivot(d_, lu().device(), opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, refactor_period_, stream_, start, stop);
+        launch_lu_pivot(d_, lu().device(), opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, path_.refactor_period, stream_, start, stop);
         return;
     }
-    if (ftran_slices_ > 0) {
-        launch_ftran_partial(d_, ftran_slices_, slots, opt_.pivot_rule, stream_);
-        launch_alpha_reduce(d_, ftran_slices_, stream_);
+    if (path_.ftran_slices > 0) {
+        launch_ftran_partial(d_, path_.ftran_slices, slots, opt_.pivot_rule, stream_);
+        launch_alpha_reduce(d_, path_.ftran_slices, stream_);
     }
-    launch_ftran_ratio(d_, opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, ftran_slices_ > 0 ? 1 : 0, stream_);
+    launch_ftran_ratio(d_, opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, path_.ftran_slices > 0 ? 1 : 0, stream_);
 }
 
 void Solver::destroy_graphs() {
@@ -998,11 +848,11 @@ void Solver::build_graph(int count) {
 
 // Newton-Schulz polish (see kernels.hip).  Two iterations at most; the residual before the polish is recorded.
 void Solver::polish(bool refresh_vectors, bool force) {
-    if (lu_mode_) {  // the LU carry's refresh is a refactorisation
+    if (path_.lu_mode) {  // the LU carry's refresh is a refactorisation
         refactor_lu(refresh_vectors);
         return;
     }
-    if (network_) {  // the forest is exact: x_B, -pi and the objective recomputed from it
+    if (path_.network) {  // the forest is exact: x_B, -pi and the objective recomputed from it
         if (since_polish_ == 0 && !force && !(opt_.switches & RELP_SW_POLISH_ALWAYS)) return;
         if (refresh_vectors) net_refresh(true, true);
         polish_scale_ = std::min(256, polish_scale_ * 4);
@@ -1071,11 +921,11 @@ void Solver::ensure_polish_buffers() {
 }
 
 void Solver::invert_from_scratch() {
-    if (lu_mode_) {
+    if (path_.lu_mode) {
         refactor_lu(false);
         return;
     }
-    if (network_) {  // the forest of the basis on the device, built on the host in O(m)
+    if (path_.network) {  // the forest of the basis on the device, built on the host in O(m)
         net_upload(net_download());
         return;
     }
@@ -1126,7 +976,7 @@ void Solver::set_basis(const int* basis_columns) {
     RELP_HIP(hipSetDevice(opt_.device));
     const int m = d_.m, n = d_.n;
     std::vector<int> basis(m), pos(n, -1);
-    if (!bounded_) {
+    if (!path_.bounded) {
         for (int i = 0; i < m; ++i) {
             int c = basis_columns[i];
             int dev = cols_.to_device(c);
@@ -1209,8 +1059,8 @@ void Solver::set_basis(const int* basis_columns) {
     c.scan_column = std::numeric_limits<int>::max();
     write_ctl(c);
     invert_from_scratch();
-    if (lu_mode_) launch_lu_xb(d_, lu().device(), stream_);
-    else if (network_) net_refresh(true, false);
+    if (path_.lu_mode) launch_lu_xb(d_, lu().device(), stream_);
+    else if (path_.network) net_refresh(true, false);
     else launch_xb(d_, stream_);
     binv_identity_ = false;
     refactors_ = 0;
@@ -1232,16 +1082,16 @@ long long Solver::iterate(long long count, int* stop_reason) {
     long long iters_before = read_ctl().iters;  // one control-word read per batch: the next batch starts where this one ended
     // LU carry: a batch is one refactorisation cycle (period updates + the pivot that asks for the refactorisation)
     // (the refactorisation beside the pivots needs the host's attention more often than once per cycle: batches of 16 pivots)
-    const int full_batch = async_refactor_ ? (opt_.pivots_per_launch > 0 && opt_.pivots_per_launch < 64 ? opt_.pivots_per_launch : 16) : lu_mode_ ? refactor_period_ + 1 : std::max(1, opt_.pivots_per_launch);
+    const int full_batch = path_.async_refactor ? (opt_.pivots_per_launch > 0 && opt_.pivots_per_launch < 64 ? opt_.pivots_per_launch : 16) : path_.lu_mode ? path_.refactor_period + 1 : std::max(1, opt_.pivots_per_launch);
     while (done < count) {
         if (async_in_flight_ && hipEventQuery(ev_refactored_) == hipSuccess) finish_async_refactor(iters_before);
-        long long room = (!lu_mode_ && opt_.polish_period > 0) ? (long long)opt_.polish_period * polish_scale_ - since_polish_ : count;
+        long long room = (!path_.lu_mode && opt_.polish_period > 0) ? (long long)opt_.polish_period * polish_scale_ - since_polish_ : count;
         if (room <= 0) { polish(true); continue; }  // (a polish does not touch the iteration counter)
         int batch = (int)std::min<long long>({count - done, room, (long long)full_batch});
         if (opt_.use_graph && batch == full_batch) {
             build_graph(batch);
             RELP_HIP(hipGraphLaunch(graph_exec_[graph_index()], stream_));
-            stats_.launches += 1 + (network_ ? (long long)net_launches_per_pivot() : lu_mode_ ? 2LL : 3LL) * batch;
+            stats_.launches += 1 + (path_.network ? (long long)net_launches_per_pivot() : path_.lu_mode ? 2LL : 3LL) * batch;
             stats_.price_launches += batch;
         } else {
             launch_pivots(batch);
@@ -1263,8 +1113,8 @@ long long Solver::iterate(long long count, int* stop_reason) {
             continue;
         }
         // the next factors are started early enough that the pivots made meanwhile fit the log of their etas
-        if (async_refactor_ && !async_in_flight_ && after.status == ST_RUNNING && lu().device().inverse_factors == 4 &&
-            since_polish_ + LU_LOG_CAPACITY + full_batch > refactor_period_)
+        if (path_.async_refactor && !async_in_flight_ && after.status == ST_RUNNING && lu().device().inverse_factors == 4 &&
+            since_polish_ + LU_LOG_CAPACITY + full_batch > path_.refactor_period)
             start_async_refactor(after.iters);
         if (made == 0 && after.status == ST_RUNNING && !fell_back) break;  // defensive: nothing happened
     }
@@ -1284,7 +1134,7 @@ int Solver::drive_out_artificials() {
         Ctl c = read_ctl();
         c.scan_column = std::numeric_limits<int>::max();
         write_ctl(c);
-        if (lu_mode_) {  // row r of the inverse by one BTRAN, then the scan of rho_r a_j over the non-basic columns
+        if (path_.lu_mode) {  // row r of the inverse by one BTRAN, then the scan of rho_r a_j over the non-basic columns
             double* rowvec = d_.scratch + (d_.m + 1) / 2 + 1 + d_.m;
             int* d_slot = reinterpret_cast<int*>(d_.scratch);
             double* d_one = d_.scratch + (d_.m + 1) / 2 + 1;
@@ -1293,7 +1143,7 @@ int Solver::drive_out_artificials() {
             RELP_HIP(hipMemcpyAsync(d_one, &one, sizeof(double), hipMemcpyHostToDevice, stream_));
             launch_lu_btran(lu().device(), d_slot, d_one, 1, rowvec, stream_);
             launch_lu_row_scan(d_, rowvec, 1e-7, stream_);
-        } else if (network_) {  // row r of the inverse from the forest, then the same scan
+        } else if (path_.network) {  // row r of the inverse from the forest, then the same scan
             double* rowvec = d_.scratch + (d_.m + 1) / 2 + 1 + d_.m;
             launch_net_row(d_, net_, r, rowvec, stream_);
             launch_lu_row_scan(d_, rowvec, 1e-7, stream_);
@@ -1394,7 +1244,7 @@ void Solver::solve(relp_result* result) {
     for (int i = 0; i < m; ++i)  // never index host arrays with an unchecked device value
         if (basis[i] < 0 || basis[i] >= d_.n) throw std::runtime_error("the device returned an invalid basis (row " + std::to_string(i) + ")");
     std::fill(h_solution_.begin(), h_solution_.end(), 0.0);
-    if (!bounded_) {
+    if (!path_.bounded) {
         for (int i = 0; i < m; ++i) {
             h_basis_[i] = cols_.to_provider(basis[i]);
             if (basis[i] >= d_.n_art) h_solution_[basis[i] - d_.n_art] = xb[i];
@@ -1433,7 +1283,7 @@ void Solver::solve(relp_result* result) {
     // The exact certificate: optimality of the final basis; for the two other verdicts of `OptimizationResult`
     // (algorithm/mod.rs:43-47), which the reference decides exactly, a Farkas certificate / an unbounded ray.
     unbounded_column_ = kind == RELP_RESULT_UNBOUNDED ? c.q - d_.n_art : -1;
-    if (opt_.certify && !bounded_ &&
+    if (opt_.certify && !path_.bounded &&
         (kind == RELP_RESULT_FINITE_OPTIMUM || kind == RELP_RESULT_INFEASIBLE || kind == RELP_RESULT_UNBOUNDED)) certify(&res);
     else if (opt_.certify && kind == RELP_RESULT_FINITE_OPTIMUM) certify(&res);
     last_result = res;
@@ -1460,7 +1310,7 @@ std::vector<int> Solver::explicit_basis(const std::vector<int>& basis, const std
 }
 
 void Solver::certify(relp_result* result) {
-    if (network_) {  // from the forest, O(m + n) (certify_basis needs m^2 words); the other verdicts stay uncertified here
+    if (path_.network) {  // from the forest, O(m + n) (certify_basis needs m^2 words); the other verdicts stay uncertified here
         if (result->kind == RELP_RESULT_FINITE_OPTIMUM) net_certify(result);
         else last_error = "RELP_CARRY_NETWORK certifies finite optima only";
         return;
@@ -1504,15 +1354,15 @@ void Solver::lu_identity() {
     f.u_start.assign(m + 1, 0);
     f.diag.assign(m, 1.0);
     // (device refactorisation: every array sized by bounds first, so that the layout -- and the captured graphs -- stay put)
-    if (device_refactor_ && lu().prepare_device(m, refactor_period_ + 1, true, (size_t)host_.col_start.back())) destroy_graphs();
-    if (lu().upload(f, refactor_period_ + 1, stream_, lu_inverse_)) destroy_graphs();  // the captured batches hold the old addresses
+    if (path_.device_refactor && lu().prepare_device(m, path_.refactor_period + 1, true, (size_t)host_.col_start.back())) destroy_graphs();
+    if (lu().upload(f, path_.refactor_period + 1, stream_, path_.lu_inverse)) destroy_graphs();  // the captured batches hold the old addresses
 }
 // `BasisInverse::invert(basis columns)` (lower_upper/mod.rs:78-92; called by `Carry::change_basis` when `should_refactor`,
 // carry/mod.rs:584-591): Markowitz factorisation of the current basis on the host, one upload, and -- `refresh_vectors` -- x_B,
 // -pi and the objective recomputed from the fresh factors (what the explicit carry's polish does too).
 void Solver::refactor_lu(bool refresh_vectors, bool settle) {
     abandon_async_flight();  // (factors on their way on the other stream belong to a basis this call supersedes: never swapped in)
-    if (!device_refactor_) {
+    if (!path_.device_refactor) {
         refactor_lu_host(refresh_vectors);
         return;
     }
@@ -1525,7 +1375,7 @@ void Solver::refactor_lu(bool refresh_vectors, bool settle) {
     src.row_index = d_.row_index;
     src.value = d_.value;
     src.basis = d_.basis;
-    src.flipped = bounded_ ? d_.flipped : nullptr;
+    src.flipped = path_.bounded ? d_.flipped : nullptr;
     const double threshold = opt_.lu_pivot_threshold > 0.0 ? opt_.lu_pivot_threshold : 0.1;
     // (dense tail: the last rows through a dense LU out of LDS.  It saves the factorisation its slowest rounds but makes the ends of both
     //  triangles dense, and the INVERTED triangles pay for that -- more entries per product and a serial chain in the inversion)
@@ -1558,11 +1408,11 @@ void Solver::start_async_refactor(long long iters_now) {
         RELP_HIP(hipMalloc(&d_basis_snapshot_, (size_t)m * sizeof(int)));
         RELP_HIP(hipMalloc(&d_probe_, ((size_t)2 * m + 2) * sizeof(double)));  // the guard's probe v, B^-1 v and the residual
         launch_lu_probe_fill(d_probe_, m, stream_);
-        if (bounded_) RELP_HIP(hipMalloc(&d_flipped_snapshot_, (size_t)d_.n * sizeof(*d_.flipped)));
+        if (path_.bounded) RELP_HIP(hipMalloc(&d_flipped_snapshot_, (size_t)d_.n * sizeof(*d_.flipped)));
     }
-    if (!next.device_prepared()) next.prepare_device(m, refactor_period_ + 1, true, (size_t)host_.col_start.back());
+    if (!next.device_prepared()) next.prepare_device(m, path_.refactor_period + 1, true, (size_t)host_.col_start.back());
     RELP_HIP(hipMemcpyAsync(d_basis_snapshot_, d_.basis, (size_t)m * sizeof(int), hipMemcpyDeviceToDevice, stream_));
-    if (bounded_) RELP_HIP(hipMemcpyAsync(d_flipped_snapshot_, d_.flipped, (size_t)d_.n * sizeof(*d_.flipped), hipMemcpyDeviceToDevice, stream_));
+    if (path_.bounded) RELP_HIP(hipMemcpyAsync(d_flipped_snapshot_, d_.flipped, (size_t)d_.n * sizeof(*d_.flipped), hipMemcpyDeviceToDevice, stream_));
     lu().start_log(stream_);
     RELP_HIP(hipEventRecord(ev_snapshot_, stream_));
     RELP_HIP(hipStreamWaitEvent(refactor_stream_, ev_snapshot_, 0));
@@ -1571,7 +1421,7 @@ void Solver::start_async_refactor(long long iters_now) {
     src.row_index = d_.row_index;
     src.value = d_.value;
     src.basis = d_basis_snapshot_;
-    src.flipped = bounded_ ? reinterpret_cast<decltype(src.flipped)>(d_flipped_snapshot_) : nullptr;
+    src.flipped = path_.bounded ? reinterpret_cast<decltype(src.flipped)>(d_flipped_snapshot_) : nullptr;
     const double threshold = opt_.lu_pivot_threshold > 0.0 ? opt_.lu_pivot_threshold : 0.1;
     const int dense_tail = opt_.luf_dense_tail > 0 ? opt_.luf_dense_tail : (opt_.luf_dense_tail < 0 ? 0 : 8);
     next.refactor_device(src, threshold, 0, dense_tail, nullptr, ST_REFACTOR_FAILED, refactor_stream_);  // (a failure stays in its info words)
@@ -1608,7 +1458,7 @@ bool Solver::finish_async_refactor(long long iters_now) {
     next.replay_log_of(lu(), stream_);
     // the guard (see lu_basis_residual_kernel): x = B^-1 v through the new factors and the replayed etas, |B x - v| over the basis now
     launch_lu_ftran_dense(next.device(), d_probe_, d_probe_ + d_.m, stream_);
-    launch_lu_basis_residual(d_.col_start, d_.row_index, d_.value, d_.basis, bounded_ ? d_.flipped : nullptr, d_probe_ + d_.m, d_probe_, d_.m, d_probe_ + 2 * (size_t)d_.m, stream_);
+    launch_lu_basis_residual(d_.col_start, d_.row_index, d_.value, d_.basis, path_.bounded ? d_.flipped : nullptr, d_probe_ + d_.m, d_probe_, d_.m, d_probe_ + 2 * (size_t)d_.m, stream_);
     double residual = 0.0;
     RELP_HIP(hipMemcpyAsync(&residual, d_probe_ + 2 * (size_t)d_.m, sizeof(double), hipMemcpyDeviceToHost, stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
@@ -1645,7 +1495,7 @@ void Solver::refactor_lu_host(bool refresh_vectors) {
     std::vector<int> rows(total);
     std::vector<double> vals(total);
     std::vector<int> flipped;
-    if (bounded_) {  // implicit bounds: a complemented column sits in the basis with the opposite sign
+    if (path_.bounded) {  // implicit bounds: a complemented column sits in the basis with the opposite sign
         flipped.resize(d_.n);
         RELP_HIP(hipMemcpyAsync(flipped.data(), d_.flipped, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
         RELP_HIP(hipStreamSynchronize(stream_));
@@ -1654,7 +1504,7 @@ void Solver::refactor_lu_host(bool refresh_vectors) {
         const int a = host_.col_start[basis[k]], len = host_.col_start[basis[k] + 1] - a;
         std::copy(host_.row_index.begin() + a, host_.row_index.begin() + a + len, rows.begin() + cs[k]);
         std::copy(host_.value.begin() + a, host_.value.begin() + a + len, vals.begin() + cs[k]);
-        if (bounded_ && flipped[basis[k]])
+        if (path_.bounded && flipped[basis[k]])
             for (int e = cs[k]; e < cs[k] + len; ++e) vals[e] = -vals[e];
     }
     LuOptions lo;
@@ -1665,7 +1515,7 @@ void Solver::refactor_lu_host(bool refresh_vectors) {
     HostLU f = lu_factor(m, cs.data(), rows.data(), vals.data(), lo);
     if (f.singular) throw std::runtime_error("singular basis in the LU refactorisation");
     const double t2 = now_seconds();
-    if (lu().upload(f, refactor_period_ + 1, stream_, lu_inverse_)) destroy_graphs();
+    if (lu().upload(f, path_.refactor_period + 1, stream_, path_.lu_inverse)) destroy_graphs();
     if (time_parts) {
         part_seconds[0] += t1 - t0;
         part_seconds[1] += t2 - t1;
@@ -1696,7 +1546,7 @@ void Solver::ftran(int nnz, const int* rows, const double* values, double* out) 
     double* d_out = d_vals + d_.m;
     check_sparse(nnz, rows, values, d_.m);
     RELP_HIP(hipSetDevice(opt_.device));
-    if (network_) {
+    if (path_.network) {
         std::vector<double> v(d_.m, 0.0);
         for (int e = 0; e < nnz; ++e) v[rows[e]] += values[e];
         const std::vector<double> x = net_host_solve(net_download(), false, v);
@@ -1705,7 +1555,7 @@ void Solver::ftran(int nnz, const int* rows, const double* values, double* out) 
     }
     RELP_HIP(hipMemcpyAsync(d_rows, rows, nnz * sizeof(int), hipMemcpyHostToDevice, stream_));
     RELP_HIP(hipMemcpyAsync(d_vals, values, nnz * sizeof(double), hipMemcpyHostToDevice, stream_));
-    if (lu_mode_) launch_lu_ftran(lu().device(), d_rows, d_vals, nnz, d_out, 0, stream_);
+    if (path_.lu_mode) launch_lu_ftran(lu().device(), d_rows, d_vals, nnz, d_out, 0, stream_);
     else launch_ftran_vec(d_, d_rows, d_vals, nnz, d_out, stream_);
     RELP_HIP(hipMemcpyAsync(out, d_out, d_.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
@@ -1716,7 +1566,7 @@ void Solver::btran(int nnz, const int* rows, const double* values, double* out) 
     double* d_out = d_vals + d_.m;
     check_sparse(nnz, rows, values, d_.m);
     RELP_HIP(hipSetDevice(opt_.device));
-    if (network_) {
+    if (path_.network) {
         std::vector<double> v(d_.m, 0.0);
         for (int e = 0; e < nnz; ++e) v[rows[e]] += values[e];
         const std::vector<double> x = net_host_solve(net_download(), true, v);
@@ -1725,7 +1575,7 @@ void Solver::btran(int nnz, const int* rows, const double* values, double* out) 
     }
     RELP_HIP(hipMemcpyAsync(d_rows, rows, nnz * sizeof(int), hipMemcpyHostToDevice, stream_));
     RELP_HIP(hipMemcpyAsync(d_vals, values, nnz * sizeof(double), hipMemcpyHostToDevice, stream_));
-    if (lu_mode_) launch_lu_btran(lu().device(), d_rows, d_vals, nnz, d_out, stream_);
+    if (path_.lu_mode) launch_lu_btran(lu().device(), d_rows, d_vals, nnz, d_out, stream_);
     else launch_btran_vec(d_, d_rows, d_vals, nnz, d_out, stream_);
     RELP_HIP(hipMemcpyAsync(out, d_out, d_.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
@@ -1763,8 +1613,8 @@ void Solver::price(int* column, double* cbar) {
     c.forced_q = c.forced_p = -1;
     write_ctl(c);
     enqueue_price(0);
-    if (lu_mode_) enqueue_ftran_ratio(1);
-    else launch_ftran_ratio(d_, opt_.pivot_rule, price_blocks_ + dense_blocks_, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, 1, 0, stream_);
+    if (path_.lu_mode) enqueue_ftran_ratio(1);
+    else launch_ftran_ratio(d_, opt_.pivot_rule, path_.price_blocks + path_.dense_blocks, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, 1, 0, stream_);
     c = read_ctl();
     *column = c.q;
     *cbar = c.q >= 0 ? c.cbar_q : 0.0;
@@ -1785,7 +1635,7 @@ void Solver::ratio(int column, int* row, double* alpha_out) {
     c.forced_p = -1;
     // the multi-block FTRAN (ftran_partial_kernel) has no mode: it computes nothing once the budget of the last batch is used up,
     // and the ratio test would then read the alpha of an earlier column
-    if (ftran_slices_ > 0) c.budget = c.iters + 1;
+    if (path_.ftran_slices > 0) c.budget = c.iters + 1;
     write_ctl(c);
     enqueue_ftran_ratio(2);
     c = read_ctl();
@@ -1876,8 +1726,8 @@ double Solver::refactor() {
 // bracketed by its own start/stop event pair (hipExtLaunchKernelGGL) on this handle's stream.  The solve advances.
 double Solver::profile_kernel(int which, int repetitions) {
     if (phase_ == 0) throw std::runtime_error("no phase started");
-    if (lu_mode_ && which == 2) throw std::invalid_argument("the LU carry has no separate update kernel (which = 1 covers it)");
-    if (fused_ && which == 2) throw std::invalid_argument("the update is part of kernel 1 (fused pivot kernel): which = 1 covers it");
+    if (path_.lu_mode && which == 2) throw std::invalid_argument("the LU carry has no separate update kernel (which = 1 covers it)");
+    if (path_.fused && which == 2) throw std::invalid_argument("the update is part of kernel 1 (fused pivot kernel): which = 1 covers it");
     RELP_HIP(hipSetDevice(opt_.device));
     const int m = d_.m;
     if (which == 0) {
@@ -1894,7 +1744,7 @@ double Solver::profile_kernel(int which, int repetitions) {
                 continue;
             }
             const bool dense_col = j >= d_.dense_first && j < d_.dense_first + d_.n_dense;
-            bytes += dense_col ? (long long)m * dense_entry_bytes_ : (long long)(cs[j + 1] - cs[j]) * 12;
+            bytes += dense_col ? (long long)m * path_.dense_entry_bytes() : (long long)(cs[j + 1] - cs[j]) * 12;
             bytes += 24;  // cost, gamma read + gamma write
         }
         stats_.price_bytes = bytes;
@@ -1905,7 +1755,7 @@ double Solver::profile_kernel(int which, int repetitions) {
         RELP_HIP(hipEventCreate(&stops[k]));
     }
     Ctl before = read_ctl();
-    if (network_) {  // (the forest's kernels are bracketed by events of their own: 0 pricing, 1 path + ratio test, 2 forest update)
+    if (path_.network) {  // (the forest's kernels are bracketed by events of their own: 0 pricing, 1 path + ratio test, 2 forest update)
         launch_budget(d_, repetitions, stream_);
         for (int k = 0; k < repetitions; ++k) {
             if (which == 0) RELP_HIP(hipEventRecord(starts[k], stream_));
@@ -1918,7 +1768,7 @@ double Solver::profile_kernel(int which, int repetitions) {
             net_enqueue_pivot(0, 2);
             if (which == 2) RELP_HIP(hipEventRecord(stops[k], stream_));
         }
-    } else if (fused_) {
+    } else if (path_.fused) {
         launch_begin_batch(d_, repetitions, stream_);
         for (int k = 0; k < repetitions; ++k) {
             if (which == 0) arm_launch_timer(0, starts[k], stops[k]);
@@ -1935,15 +1785,15 @@ double Solver::profile_kernel(int which, int repetitions) {
         if (which == 1) arm_launch_timer(1, starts[k], stops[k]);
         enqueue_ftran_ratio(0);
         if (which == 2) arm_launch_timer(2, starts[k], stops[k]);
-        if (!lu_mode_) enqueue_update();
-        if (eta_mode_ && ((k + 1) % d_.eta_cap == 0 || k + 1 == repetitions)) enqueue_consolidate();
+        if (!path_.lu_mode) enqueue_update();
+        if (path_.eta_mode && ((k + 1) % d_.eta_cap == 0 || k + 1 == repetitions)) enqueue_consolidate();
     }
     }
     arm_launch_timer(-1, nullptr, nullptr);
     Ctl after = read_ctl();
     // K3's algorithmic bytes at the profiled state when unit columns are skipped: read + write of (non-zero rows of alpha) x
     // (columns of the stored inverse that carry information)
-    if (d_.track_touched && !eta_mode_) stats_.update_bytes = 16LL * std::max(1, after.nz_count) * std::max(1, after.touched_count);
+    if (d_.track_touched && !path_.eta_mode) stats_.update_bytes = 16LL * std::max(1, after.nz_count) * std::max(1, after.touched_count);
     if (after.status == ST_REFACTOR) refactor_lu(true);
     const long long made = after.iters - before.iters;
     pivots_[phase_ - 1] += made;
@@ -1975,7 +1825,7 @@ void Solver::get_b(double* out) {
 }
 double Solver::objective() { return -read_ctl().minus_obj; }
 long long Solver::bound_flips() {
-    if (!bounded_ || phase_ == 0) return 0;
+    if (!path_.bounded || phase_ == 0) return 0;
     RELP_HIP(hipSetDevice(opt_.device));
     return read_ctl().bound_flips;
 }
@@ -1984,7 +1834,7 @@ void Solver::get_basis(int* out) {
     std::vector<int> basis(d_.m);
     RELP_HIP(hipMemcpyAsync(basis.data(), d_.basis, d_.m * sizeof(int), hipMemcpyDeviceToHost, stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
-    if (bounded_) {  // in the reference's formulation: one entry per row of MatrixData, bound rows included
+    if (path_.bounded) {  // in the reference's formulation: one entry per row of MatrixData, bound rows included
         std::vector<int> pos(d_.n);
         RELP_HIP(hipMemcpyAsync(pos.data(), d_.pos, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
         RELP_HIP(hipStreamSynchronize(stream_));

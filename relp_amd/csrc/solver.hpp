@@ -18,6 +18,7 @@
 
 #include "../../include/relp_amd.h"
 #include "device_columns.hpp"
+#include "kernel_path.hpp"
 #include "device_memory.hpp"
 #include "model.hpp"
 #include "lu.hpp"
@@ -95,8 +96,6 @@ struct Ctl {
     int eta_new;       // ... and whether the last pivot added a kept column (its row had none) -- both written by K2
     int rho_buf;       // generated columns: which half of DeviceLP::rho_bits the writers of rho_p mark (flipped by the kernel that decides a pivot)
 };
-
-constexpr int ELL_W = 8;  // padded entries per column = lanes per column in the pricing kernel
 
 enum : int { ST_RUNNING = 0, ST_NO_ENTERING = 1, ST_UNBOUNDED = 2, ST_BUDGET = 3, ST_REFACTOR = 4, ST_REFACTOR_FAILED = 5 };  // 4: LU carry, refactorise now;
 // 5: the refactorisation kernels gave up (a capacity, a row too long for the eliminating wave): the pivots behind them are no-ops, the host factorises
@@ -313,7 +312,7 @@ public:
 
     void load(StandardForm&& form);
     bool loaded() const { return loaded_; }
-    bool ratio_textbook() const { return ratio_textbook_; }
+    bool ratio_textbook() const { return path_.ratio_textbook; }
 
     void solve(relp_result* result);
     void begin_phase_one();
@@ -335,7 +334,7 @@ public:
                      long long* p2, std::vector<int>* trace, std::string* objective, std::vector<int>* basis,
                      std::vector<std::pair<int, long long>>* survived, int* redundant_rows = nullptr);
     size_t device_bytes() const { return device_memory_.bytes(); }  // bytes this handle has allocated on the device
-    bool network_carry() const { return network_; }
+    bool network_carry() const { return path_.network; }
     const std::vector<unsigned long long>& network_stats() const { return net_stats_; }  // RELP_SW_NETWORK_STATS: NS_* of the last solve
     const std::vector<ExactWidthRecord>& exact_records() const { return exact_records_; }  // of the last solve_exact, one per width tried
     void last_pivot(int* phase, int* column, int* row, int* leaving);
@@ -353,9 +352,9 @@ public:
     const relp_stats& stats() const { return stats_; }
     void reset_stats();
     int n_art() const { return d_.n_art; }
-    bool refactors_on_device() const { return device_refactor_; }
+    bool refactors_on_device() const { return path_.device_refactor; }
     long long device_refactor_fallbacks() const { return device_refactor_failures_; }
-    bool refactors_asynchronously() const { return async_refactor_; }
+    bool refactors_asynchronously() const { return path_.async_refactor; }
     long long async_refactors() const { return async_refactors_; }
     long long async_refactors_abandoned() const { return async_abandoned_; }
     double async_worst_residual() const { return async_worst_residual_; }
@@ -368,15 +367,20 @@ public:
     relp_result last_result{};
 
 private:
-    void upload();
+    // The constants of the loaded LP: which kernels it runs and how its arrays are sized (kernel_path.hpp).  Assigned once per load(),
+    // at the top of upload(), before anything is allocated.
+    KernelPath path_;
+    void upload();                // plan, then one function per group of arrays (none of them decides anything)
+    void upload_matrix();         // CSC / CSR, costs, right-hand side
+    void upload_pricing_copy();   // ELL copy, generated columns, prw / rho_bits / rho_nz
+    void upload_dense_block();    // one form per DenseStorage
+    void allocate_pivot_state();  // vectors, candidate slots, eta buffers, touched lists, K2 partials, fused twin state, bounds, ctl
     void free_device();
     void set_phase(int phase);
     void launch_pivots(int count, bool forced = false);
     void enqueue_price_fused(int parity);
     void enqueue_pivot_fused(int parity);  // forced: the caller set forced_q / forced_p (three-kernel pivot)
-    bool fused_ = false;          // ratio test + inverse update in one launch (pivot_fused_kernel: m <= 2048, explicit carry, no implicit bounds)
     void enqueue_price(int skip_weights, bool first_of_batch = true);
-    bool slack_in_btran_ = false; // the slack columns of the dense pipeline are priced by the BTRAN pass of the previous pivot
     void enqueue_ftran_ratio(int mode);
     void enqueue_update();
     void enqueue_consolidate();
@@ -394,7 +398,6 @@ private:
     std::vector<double> net_host_solve(const HostTree& t, bool transposed, const std::vector<double>& v) const;  // B^-1 v or v' B^-1
     CertifyScratch certify_scratch_;
     // spanning-forest carry (network_carry.hip)
-    bool network_ = false;
     NetTree net_;
     void net_allocate();
     HostTree net_build(const std::vector<int>& basis, const std::vector<int>& flipped) const;  // throws unless the basis is a forest
@@ -415,7 +418,6 @@ private:
     void refactor_lu(bool refresh_vectors, bool settle = true);  // BasisInverse::invert of the current basis: kernels on the device (lu_factor.hip), or ...
     void refactor_lu_host(bool refresh_vectors);  // ... host Markowitz + upload (relp_options.lu_refactor; the LU + Forrest-Tomlin carry; the fallback)
     std::vector<ExactWidthRecord> exact_records_;
-    bool device_refactor_ = false;
     long long device_refactor_failures_ = 0;
     void lu_identity();                      // BasisInverse::identity
     LuFactors lu_sets_[2];  // (two sets of factor arrays: the asynchronous refactorisation builds the next factors in the other one)
@@ -423,7 +425,7 @@ private:
     LuFactors& lu() { return lu_sets_[lu_cur_]; }
     const LuFactors& lu() const { return lu_sets_[lu_cur_]; }
     // the refactorisation beside the pivots (relp_options.lu_refactor = RELP_REFACTOR_DEVICE_ASYNC; solver.hip: start_async_refactor)
-    bool async_refactor_ = false, async_in_flight_ = false;
+    bool async_in_flight_ = false;
     hipStream_t refactor_stream_ = nullptr;
     hipEvent_t ev_snapshot_ = nullptr, ev_refactored_ = nullptr;
     long long async_iters_at_snapshot_ = 0;
@@ -435,13 +437,9 @@ private:
     void start_async_refactor(long long iters_now);
     void abandon_async_flight();
     bool finish_async_refactor(long long iters_now);  // true: the handle now runs on the new factors
-    bool lu_mode_ = false;
-    bool lu_inverse_ = false;  // ... in its inverse-factor form (lu.hpp: L^-1, U^-1 and product-form updates)
     bool lu_is_identity_ = true;
-    int refactor_period_ = 64;
     // (a negative slack selects the reference's ratio test in the kernels that implement it: the fused kernel for m <= 8192 and the LU kernel)
-    double ratio_delta() const { return ratio_textbook_ ? -1.0 : opt_.harris_delta; }
-    bool ratio_textbook_ = false;  // the reference's ratio test runs (relp_options.ratio_rule resolved against the data and the kernels at upload)
+    double ratio_delta() const { return path_.ratio_textbook ? -1.0 : opt_.harris_delta; }
     int unbounded_column_ = -1;  // provider column of the ray when the result is UNBOUNDED
     long long refactors_ = 0;
     double refactor_seconds_ = 0.0;
@@ -458,14 +456,6 @@ private:
     bool loaded_ = false;
     bool binv_identity_ = true;
     int phase_ = 0;
-    int price_blocks_ = 0;        // sparse pricing workgroups
-    int dense_blocks_ = 0;        // dense pricing workgroups (candidate slots follow the sparse ones)
-    int ftran_slices_ = 0;        // > 0: multi-block FTRAN pipeline (select -> partial FTRAN -> fused kernel)
-    int sparse_first_ = 0;        // device columns priced by the CSC kernel: [sparse_first_, n)
-    int dense_entry_bytes_ = 8;   // 4 when the dense block is held as float (exactly representable entries)
-    bool bounded_ = false;        // implicit upper bounds are active for the loaded LP
-    bool eta_mode_ = false;       // deferred product form of the inverse (DeviceLP::eta_cap > 0)
-    size_t price_lds_ = 0;
     hipStream_t stream_ = nullptr;
     // one captured batch of pivots per phase (the phases differ in a kernel argument); both survive across solves of the
     // same LP, so a solve pays for no capture or instantiation after the first
@@ -484,8 +474,6 @@ private:
     double max_residual_ = 0.0;
     long long since_polish_ = 0;
     int polish_scale_ = 1;        // multiplier of polish_period, adapted to the drift measured at each polish
-
-    friend struct SolverAccess;
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) acts on the CURRENT device's copy of a kernel, and a batch (relp_batch_create) may

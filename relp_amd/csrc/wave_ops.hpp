@@ -6,8 +6,6 @@
 
 namespace relp {
 
-constexpr int WAVE = 64;
-
 #ifdef RELP_STAMPS
 #define STAMP(k) do { if (threadIdx.x == 0) { unsigned long long t__ = clock64(); lp.dbg[(k)] += t__ - t_prev__; t_prev__ = t__; } } while (0)
 #define STAMP_INIT unsigned long long t_prev__ = clock64(); if (threadIdx.x == 0) lp.dbg[63] += 1

@@ -1,0 +1,59 @@
+// plan_kernel_path under the host sanitizers, without a device: plans AFIRO and a dense 64 x 128 LP under a few options each and prints
+// the plans.  kernel_path.cpp is compiled here, instrumented (its limits are inline in kernel_limits.hpp); the library only parses
+// the models:
+//   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Irelp_amd/csrc tools/kernel_path_sanitize.cpp
+//       relp_amd/csrc/kernel_path.cpp -Lrelp_amd -lrelp_amd -Wl,-rpath,$PWD/relp_amd -o kernel_path_sanitize && ./kernel_path_sanitize
+#include <cstdio>
+#include <vector>
+
+#include "kernel_path.hpp"
+
+using namespace relp;
+
+static void plan(const relp_model* model, relp_options o, const char* what) {
+    const MatrixData& md = model->form.data;
+    const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
+    try {
+        std::printf("%s: %s\n", what, kernel_path_json(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names)).c_str());
+    } catch (const std::exception& e) {
+        std::printf("%s: refused: %s\n", what, e.what());
+    }
+}
+
+int main() {
+    relp_options o;
+    relp_options_default(&o);
+    char error[512];
+    relp_model* afiro = nullptr;
+    if (relp_model_from_mps_ex("data/netlib/AFIRO.SIF", 1, 0, &afiro, error, 512) != RELP_OK) return std::printf("%s\n", error), 1;
+    plan(afiro, o, "afiro");
+    relp_options lu = o;
+    lu.carry = RELP_CARRY_LU_INVERSE, lu.lu_refactor = RELP_REFACTOR_DEVICE;
+    plan(afiro, lu, "afiro, inverse-factor carry");
+    relp_options net = o;
+    net.carry = RELP_CARRY_NETWORK;
+    plan(afiro, net, "afiro, network carry");
+    // dense_lp(64, 128): A[i][j] = 1 + (i * 131 + j * 17) % 100 stands in for the generator's draws (same shape, same value range)
+    const int m = 64, n = 128;
+    std::vector<int64_t> start(n + 1), num, den, b(m, 100000), one(n > m ? n : m, 1), cost(n, -1), zero(n, 0);
+    std::vector<int32_t> rows, kind(m, 2);
+    std::vector<uint8_t> has_l(n, 1), has_u(n, 0);
+    for (int j = 0; j < n; ++j) {
+        for (int i = 0; i < m; ++i) rows.push_back(i), num.push_back(1 + (i * 131 + j * 17) % 100), den.push_back(1);
+        start[j + 1] = (int64_t)rows.size();
+    }
+    relp_model* dense = nullptr;
+    if (relp_model_from_general_form(0, m, n, start.data(), rows.data(), num.data(), den.data(), kind.data(), zero.data(), one.data(), b.data(), one.data(),
+                                     cost.data(), one.data(), has_l.data(), zero.data(), one.data(), has_u.data(), zero.data(), one.data(), 0, 1, 0, &dense, error, 512) != RELP_OK)
+        return std::printf("%s\n", error), 1;
+    plan(dense, o, "dense 64 x 128");
+    relp_options eta = o;
+    eta.ftran_min_nnz = 16;
+    plan(dense, eta, "dense 64 x 128, multi-block FTRAN");
+    relp_options rows_form = o;
+    rows_form.switches = RELP_SW_NO_DENSE_LANE, rows_form.dense_storage = RELP_DENSE_FLOAT;
+    plan(dense, rows_form, "dense 64 x 128, float rows");
+    relp_model_free(afiro);
+    relp_model_free(dense);
+    return 0;
+}
