@@ -385,6 +385,7 @@ struct DeviceBuffers {  // device memory of one certificate, drawn from and retu
     CertifyScratch* scratch = nullptr;
     std::mutex* guard = nullptr;  // (the dual lifting allocates from a second host thread)
     std::vector<void*> ptrs;
+    std::vector<void*> pinned_ptrs;  // staging in pinned host memory, from the same scratch; held as long as the device buffers
     template <class T>
     T* alloc(size_t count) {
         const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
@@ -398,14 +399,109 @@ struct DeviceBuffers {  // device memory of one certificate, drawn from and retu
         ptrs.push_back(p);
         return reinterpret_cast<T*>(p);
     }
+    template <class T>
+    T* pinned(size_t count) {
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        void* p = nullptr;
+        if (scratch) {
+            std::lock_guard<std::mutex> lock(*guard);
+            p = scratch->take_pinned(bytes);
+        } else {
+            RELP_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+        }
+        pinned_ptrs.push_back(p);
+        return reinterpret_cast<T*>(p);
+    }
     ~DeviceBuffers() {
         if (scratch) {
             std::lock_guard<std::mutex> lock(*guard);
             for (void* p : ptrs) scratch->give_back(p);
+            for (void* p : pinned_ptrs) scratch->give_back_pinned(p);
         } else {
             for (void* p : ptrs) (void)hipFree(p);
+            for (void* p : pinned_ptrs) (void)hipHostFree(p);
         }
     }
+};
+
+// Several host arrays as ONE upload: packed into one pinned block, copied with one hipMemcpyAsync into one device block; the
+// device arrays are offsets into that block (16-byte aligned).  The sources are read by send() and not afterwards.
+struct PackedUpload {
+    struct Part {
+        const void* src;
+        size_t bytes, offset;
+    };
+    std::vector<Part> parts;
+    size_t total = 0;
+    template <class T>
+    size_t add(const std::vector<T>& v) {
+        const size_t offset = total;
+        parts.push_back(Part{v.data(), v.size() * sizeof(T), offset});
+        total += (v.size() * sizeof(T) + 15) & ~(size_t)15;
+        return offset;
+    }
+    char* send(DeviceBuffers& buf, hipStream_t stream) {
+        char* host = buf.pinned<char>(total);
+        char* device = buf.alloc<char>(total);
+        for (const Part& part : parts)
+            if (part.bytes) std::memcpy(host + part.offset, part.src, part.bytes);
+        if (total) RELP_HIP(hipMemcpyAsync(device, host, total, hipMemcpyHostToDevice, stream));
+        return device;
+    }
+};
+
+// The host thread that drives the dual lifting, kept by the handle (CertifyScratch::worker) instead of being created by every
+// certificate.  One task at a time: start() hands it over and returns, wait() returns when it has run.  A task does not throw.
+class CertifyWorker {
+public:
+    CertifyWorker() : thread_([this] { loop(); }) {}
+    CertifyWorker(const CertifyWorker&) = delete;
+    CertifyWorker& operator=(const CertifyWorker&) = delete;
+    ~CertifyWorker() {
+        {
+            std::lock_guard<std::mutex> lock(mutex_);
+            stop_ = true;
+        }
+        wake_.notify_all();
+        thread_.join();
+    }
+    void start(std::function<void()> task) {
+        {
+            std::lock_guard<std::mutex> lock(mutex_);
+            task_ = std::move(task);
+            busy_ = true;
+        }
+        wake_.notify_all();
+    }
+    void wait() {
+        std::unique_lock<std::mutex> lock(mutex_);
+        done_.wait(lock, [&] { return !busy_; });
+    }
+
+private:
+    void loop() {
+        while (true) {
+            std::function<void()> task;
+            {
+                std::unique_lock<std::mutex> lock(mutex_);
+                wake_.wait(lock, [&] { return stop_ || task_; });
+                if (!task_) return;  // (stopped, and nothing handed over)
+                task = std::move(task_);
+                task_ = nullptr;
+            }
+            task();
+            {
+                std::lock_guard<std::mutex> lock(mutex_);
+                busy_ = false;
+            }
+            done_.notify_all();
+        }
+    }
+    std::mutex mutex_;
+    std::condition_variable wake_, done_;
+    std::function<void()> task_;
+    bool busy_ = false, stop_ = false;
+    std::thread thread_;  // (last: it starts in the constructor, after the members it uses)
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -616,14 +712,17 @@ bool dixon_solve(const IntegerBasis& B, const std::vector<i64>& rhs, int transpo
     i64* d_r = buf.alloc<i64>(m);
     int* d_info = buf.alloc<int>(4);
     RELP_HIP(hipMemsetAsync(d_info, 0, 4 * sizeof(int), stream));
-    RELP_HIP(hipMemcpyAsync(d_r, rhs.data(), m * sizeof(i64), hipMemcpyHostToDevice, stream));
+    i64* h_r = buf.pinned<i64>(m);  // (held by `buf`: not handed out again before the stream has read it)
+    std::memcpy(h_r, rhs.data(), m * sizeof(i64));
+    int* info = buf.pinned<int>(4);
+    RELP_HIP(hipMemcpyAsync(d_r, h_r, m * sizeof(i64), hipMemcpyHostToDevice, stream));
     bool all_zero = std::all_of(rhs.begin(), rhs.end(), [](i64 v) { return v == 0; });
     out->numer.assign(m, BigInt(0));
     out->denom = BigInt(1);
     if (all_zero) return true;
 
-    std::vector<const u32*> digits;             // digits[step][i]: rows of the downloaded blocks below (no copy)
-    std::vector<std::vector<u32>> blocks;       // one block of digit steps per round of the doubling
+    std::vector<const u32*> digits;             // digits[step][i]: rows of the downloaded blocks (no copy): one block of digit steps per
+                                                // round of the doubling, in the pinned staging arena, held by `buf`
     int steps_done = 0;
     int target = std::max(8, first_target);
     const int max_steps = 1 << 15;
@@ -645,11 +744,10 @@ bool dixon_solve(const IntegerBasis& B, const std::vector<i64>& rhs, int transpo
             hipLaunchKernelGGL(dixon_residual_kernel, dim3((m + 3) / 4), dim3(256), 0, stream, m, d_row_start, d_col_index,
                                d_row_value, xs, d_r, p, d_info);
         }
-        blocks.emplace_back((size_t)(target - steps_done) * m);
-        std::vector<u32>& flat = blocks.back();
-        int info[4];
-        RELP_HIP(hipMemcpyAsync(flat.data(), d_digits + (size_t)steps_done * m, flat.size() * sizeof(u32), hipMemcpyDeviceToHost, stream));
-        RELP_HIP(hipMemcpyAsync(info, d_info, sizeof(info), hipMemcpyDeviceToHost, stream));
+        const size_t flat_size = (size_t)(target - steps_done) * m;
+        const u32* flat = buf.pinned<u32>(flat_size);
+        RELP_HIP(hipMemcpyAsync(const_cast<u32*>(flat), d_digits + (size_t)steps_done * m, flat_size * sizeof(u32), hipMemcpyDeviceToHost, stream));
+        RELP_HIP(hipMemcpyAsync(info, d_info, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
         RELP_HIP(hipStreamSynchronize(stream));
         times.device_digits += wall_now() - t_digits;
         const double t_host = wall_now();
@@ -662,7 +760,7 @@ bool dixon_solve(const IntegerBasis& B, const std::vector<i64>& rhs, int transpo
             *message = info[2] ? "Dixon residual overflow (coefficients too large for the 128-bit path)" : "Dixon residual not divisible by p";
             return false;
         }
-        for (int s = steps_done; s < target; ++s) digits.push_back(flat.data() + (size_t)(s - steps_done) * m);
+        for (int s = steps_done; s < target; ++s) digits.push_back(flat + (size_t)(s - steps_done) * m);
         steps_done = target;
 
         // ---- assemble, reconstruct with a common denominator, verify (dixon_reconstruct, above) ------------
@@ -716,9 +814,29 @@ void CertifyScratch::give_back(void* ptr) {
     for (Block& b : blocks)
         if (b.ptr == ptr) b.busy = false;
 }
+void* CertifyScratch::take_pinned(size_t bytes) {
+    Block* best = nullptr;
+    for (Block& b : pinned)
+        if (!b.busy && b.bytes >= bytes && (!best || b.bytes < best->bytes)) best = &b;
+    if (best && best->bytes <= 4 * bytes + 4096) {
+        best->busy = true;
+        return best->ptr;
+    }
+    void* p = nullptr;
+    RELP_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    pinned.push_back(Block{p, bytes, true});
+    return p;
+}
+void CertifyScratch::give_back_pinned(void* ptr) {
+    for (Block& b : pinned)
+        if (b.ptr == ptr) b.busy = false;
+}
 void CertifyScratch::release() {
+    worker.reset();  // (joins the thread of the dual lifting: it is idle between certificates)
     for (Block& b : blocks) (void)hipFree(b.ptr);
     blocks.clear();
+    for (Block& b : pinned) (void)hipHostFree(b.ptr);
+    pinned.clear();
     if (second) (void)hipStreamDestroy(second);
     second = nullptr;
 }
@@ -758,16 +876,26 @@ int exact_witness_mode(const ExactWitnesses& witnesses) { return witnesses.mode;
 
 std::vector<std::pair<int, std::string>> exact_witness_values(const ExactWitnesses& w, int which) {
     std::vector<std::pair<int, std::string>> out;
+    {
+        // the first call folds the multipliers of the integer scaling into y (make_exact_witnesses only kept them)
+        std::lock_guard<std::mutex> lock(w.finish_guard);
+        if (!w.finished) {
+            for (size_t i = 0; i < w.y.numer.size(); ++i) w.y.numer[i] = w.y.numer[i] * big_from_i128(w.row_mult[i]);
+            if (w.mode != 1) w.y.denom = w.y.denom * big_from_i128(w.cost_mult);
+            w.finished = true;
+        }
+    }
     if (which == RELP_WITNESS_DUAL) {  // by row, already ascending
         for (size_t i = 0; i < w.y.numer.size(); ++i)
             if (w.y.numer[i].sign() != 0) out.push_back({(int)i, reduced_text(w.y.numer[i], w.y.denom)});
         return out;
     }
     const bool ray = which == RELP_WITNESS_RAY;
-    const ExactVector& v = ray ? w.alpha : w.x;
-    for (size_t k = 0; k < w.basis.size() && k < v.numer.size(); ++k) {
-        if (w.basis[k] < 0 || v.numer[k].sign() == 0) continue;  // (an artificial: 0, checked by the certificate)
-        out.push_back({w.basis[k], reduced_text(ray ? -v.numer[k] : v.numer[k], v.denom)});
+    const std::vector<BigInt>& numer = ray ? w.alpha.numer : w.shared_x ? w.shared_x->numer : w.x.numer;
+    const BigInt& denom = ray ? w.alpha.denom : w.shared_x ? w.shared_x->denom : w.x.denom;
+    for (size_t k = 0; k < w.basis.size() && k < numer.size(); ++k) {
+        if (w.basis[k] < 0 || numer[k].sign() == 0) continue;  // (an artificial: 0, checked by the certificate)
+        out.push_back({w.basis[k], reduced_text(ray ? -numer[k] : numer[k], denom)});
     }
     if (ray) out.push_back({w.entering, "1/1"});
     std::sort(out.begin(), out.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
@@ -775,15 +903,17 @@ std::vector<std::pair<int, std::string>> exact_witness_values(const ExactWitness
 }
 
 std::shared_ptr<const ExactWitnesses> make_exact_witnesses(const CertifyStatic& statics, int mode, const std::vector<int>& basis, int entering,
-                                                          ExactVector& x, ExactVector& y, ExactVector& alpha) {
+                                                          ExactVector& x, ExactVector& y, ExactVector& alpha,
+                                                          std::shared_ptr<const ExactPrimal> shared_x) {
     auto kept = std::make_shared<ExactWitnesses>();
     kept->mode = mode;
     kept->basis = basis;
     kept->entering = entering;
-    kept->x = std::move(x);
-    kept->y.numer.resize(y.numer.size());
-    for (size_t i = 0; i < y.numer.size(); ++i) kept->y.numer[i] = y.numer[i] * big_from_i128(statics.row_mult[i]);
-    kept->y.denom = mode == 1 ? y.denom : y.denom * big_from_i128(statics.cost_mult);
+    if (shared_x) kept->shared_x = std::move(shared_x);
+    else kept->x = std::move(x);
+    kept->y = std::move(y);  // (scaled by the first exact_witness_values)
+    kept->row_mult.assign(statics.row_mult.begin(), statics.row_mult.begin() + kept->y.numer.size());
+    kept->cost_mult = statics.cost_mult;
     if (mode == 2) kept->alpha = std::move(alpha);
     return kept;
 }
@@ -1079,18 +1209,17 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         u32* dC = buf.alloc<u32>((size_t)m * m);
         u32* dCT = buf.alloc<u32>((size_t)m * m);
         u32* dX = buf.alloc<u32>((size_t)m * m);
-        int* d_col_start = buf.alloc<int>(m + 1);
-        int* d_row_index = buf.alloc<int>(nnz);
-        i64* d_value = buf.alloc<i64>(nnz);
-        int* d_row_start = buf.alloc<int>(m + 1);
-        int* d_col_index = buf.alloc<int>(nnz);
-        i64* d_row_value = buf.alloc<i64>(nnz);
-        RELP_HIP(hipMemcpyAsync(d_col_start, B.col_start.data(), (m + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-        RELP_HIP(hipMemcpyAsync(d_row_index, B.row_index.data(), nnz * sizeof(int), hipMemcpyHostToDevice, stream));
-        RELP_HIP(hipMemcpyAsync(d_value, B.value.data(), nnz * sizeof(i64), hipMemcpyHostToDevice, stream));
-        RELP_HIP(hipMemcpyAsync(d_row_start, B.row_start.data(), (m + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-        RELP_HIP(hipMemcpyAsync(d_col_index, B.col_index.data(), nnz * sizeof(int), hipMemcpyHostToDevice, stream));
-        RELP_HIP(hipMemcpyAsync(d_row_value, B.row_value.data(), nnz * sizeof(i64), hipMemcpyHostToDevice, stream));
+        // both orientations of the integer basis: packed in the pinned arena, one copy, one device block
+        PackedUpload basis_upload;
+        const size_t o_col_start = basis_upload.add(B.col_start), o_row_index = basis_upload.add(B.row_index), o_value = basis_upload.add(B.value);
+        const size_t o_row_start = basis_upload.add(B.row_start), o_col_index = basis_upload.add(B.col_index), o_row_value = basis_upload.add(B.row_value);
+        char* d_basis = basis_upload.send(buf, stream);
+        int* d_col_start = reinterpret_cast<int*>(d_basis + o_col_start);
+        int* d_row_index = reinterpret_cast<int*>(d_basis + o_row_index);
+        i64* d_value = reinterpret_cast<i64*>(d_basis + o_value);
+        int* d_row_start = reinterpret_cast<int*>(d_basis + o_row_start);
+        int* d_col_index = reinterpret_cast<int*>(d_basis + o_col_index);
+        i64* d_row_value = reinterpret_cast<i64*>(d_basis + o_row_value);
         stamp("device buffers allocated, uploads enqueued");
         u32 p = 0;
         for (u32 candidate : primes) {
@@ -1111,38 +1240,37 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
             std::vector<u32> dinv(m);
             for (int i = 0; i < m; ++i) dinv[i] = ops.inverse(f.diag[i]);
             const size_t nl = f.l_col.size(), nu = f.u_col.size();
-            int* d_rowpos = buf.alloc<int>(m);
-            int* d_colpos = buf.alloc<int>(m);
-            int* d_ls = buf.alloc<int>(m + 1);
-            int* d_us = buf.alloc<int>(m + 1);
-            int* d_lc = buf.alloc<int>(nl);
-            int* d_uc = buf.alloc<int>(nu);
-            u32* d_lv = buf.alloc<u32>(nl);
-            u32* d_uv = buf.alloc<u32>(nu);
-            u32* d_dinv = buf.alloc<u32>(m);
-            RELP_HIP(hipMemcpyAsync(d_rowpos, f.rowpos.data(), m * sizeof(int), hipMemcpyHostToDevice, stream));
-            RELP_HIP(hipMemcpyAsync(d_colpos, f.colpos.data(), m * sizeof(int), hipMemcpyHostToDevice, stream));
-            RELP_HIP(hipMemcpyAsync(d_ls, f.l_start.data(), (m + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-            RELP_HIP(hipMemcpyAsync(d_us, f.u_start.data(), (m + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-            if (nl) RELP_HIP(hipMemcpyAsync(d_lc, f.l_col.data(), nl * sizeof(int), hipMemcpyHostToDevice, stream));
-            if (nl) RELP_HIP(hipMemcpyAsync(d_lv, f.l_val.data(), nl * sizeof(u32), hipMemcpyHostToDevice, stream));
-            if (nu) RELP_HIP(hipMemcpyAsync(d_uc, f.u_col.data(), nu * sizeof(int), hipMemcpyHostToDevice, stream));
-            if (nu) RELP_HIP(hipMemcpyAsync(d_uv, f.u_val.data(), nu * sizeof(u32), hipMemcpyHostToDevice, stream));
-            RELP_HIP(hipMemcpyAsync(d_dinv, dinv.data(), m * sizeof(u32), hipMemcpyHostToDevice, stream));
             HostLUT<u32> fs = f;
             lu_schedules(fs);
             const int levels_l = (int)fs.lev_start[0].size() - 1, levels_u = (int)fs.lev_start[1].size() - 1;
             const size_t level_lds = ((size_t)2 * (m + 1) + 2 * nl + 2 * nu + m + (levels_l + 1) + m + (levels_u + 1) + m + m + (size_t)4 * m) * sizeof(u32);
-            if (level_lds <= 150 * 1024 && !thread_tuning().has(RELP_SW_CERTIFY_NO_LEVELS)) {
+            const bool by_levels = level_lds <= 150 * 1024 && !thread_tuning().has(RELP_SW_CERTIFY_NO_LEVELS);
+            // the factors, and the level schedules of the kernel that walks them by levels: packed in the pinned arena, one copy
+            PackedUpload factor_upload;
+            const size_t o_rowpos = factor_upload.add(f.rowpos), o_colpos = factor_upload.add(f.colpos), o_ls = factor_upload.add(f.l_start),
+                         o_us = factor_upload.add(f.u_start), o_lc = factor_upload.add(f.l_col), o_uc = factor_upload.add(f.u_col),
+                         o_lv = factor_upload.add(f.l_val), o_uv = factor_upload.add(f.u_val), o_dinv = factor_upload.add(dinv);
+            size_t o_levl = 0, o_rowl = 0, o_levu = 0, o_rowu = 0;
+            if (by_levels) {
+                o_levl = factor_upload.add(fs.lev_start[0]), o_rowl = factor_upload.add(fs.lev_row[0]);
+                o_levu = factor_upload.add(fs.lev_start[1]), o_rowu = factor_upload.add(fs.lev_row[1]);
+            }
+            char* d_factors = factor_upload.send(buf, stream);
+            int* d_rowpos = reinterpret_cast<int*>(d_factors + o_rowpos);
+            int* d_colpos = reinterpret_cast<int*>(d_factors + o_colpos);
+            int* d_ls = reinterpret_cast<int*>(d_factors + o_ls);
+            int* d_us = reinterpret_cast<int*>(d_factors + o_us);
+            int* d_lc = reinterpret_cast<int*>(d_factors + o_lc);
+            int* d_uc = reinterpret_cast<int*>(d_factors + o_uc);
+            u32* d_lv = reinterpret_cast<u32*>(d_factors + o_lv);
+            u32* d_uv = reinterpret_cast<u32*>(d_factors + o_uv);
+            u32* d_dinv = reinterpret_cast<u32*>(d_factors + o_dinv);
+            if (by_levels) {
                 // one wave per column, level by level (modular_inverse_levels_kernel)
-                int* d_levl = buf.alloc<int>(levels_l + 1);
-                int* d_rowl = buf.alloc<int>(m);
-                int* d_levu = buf.alloc<int>(levels_u + 1);
-                int* d_rowu = buf.alloc<int>(m);
-                RELP_HIP(hipMemcpyAsync(d_levl, fs.lev_start[0].data(), (levels_l + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-                RELP_HIP(hipMemcpyAsync(d_rowl, fs.lev_row[0].data(), m * sizeof(int), hipMemcpyHostToDevice, stream));
-                RELP_HIP(hipMemcpyAsync(d_levu, fs.lev_start[1].data(), (levels_u + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-                RELP_HIP(hipMemcpyAsync(d_rowu, fs.lev_row[1].data(), m * sizeof(int), hipMemcpyHostToDevice, stream));
+                int* d_levl = reinterpret_cast<int*>(d_factors + o_levl);
+                int* d_rowl = reinterpret_cast<int*>(d_factors + o_rowl);
+                int* d_levu = reinterpret_cast<int*>(d_factors + o_levu);
+                int* d_rowu = reinterpret_cast<int*>(d_factors + o_rowu);
                 static PerDeviceOnce configured_levels;  // (certificates run from the worker threads of a batch, possibly on several devices)
                 configured_levels.run([] {
                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modular_inverse_levels_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1171,7 +1299,7 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
                                    d_rowpos, d_colpos, d_ls, d_lc, d_lv, d_us, d_uc, d_uv, d_dinv, dX, dC, dCT, in_lds ? 1 : 0, columns, staged ? 1 : 0);
             }
             const double t_sync = wall_now();
-            RELP_HIP(hipStreamSynchronize(stream));  // (the staging vectors above go out of scope)
+            RELP_HIP(hipStreamSynchronize(stream));
             if (timeline) fprintf(stderr, "[certify]   waited %.2f ms for the uploads and the inverse kernel\n", (wall_now() - t_sync) * 1e3);
             p = candidate;
             break;
@@ -1229,7 +1357,12 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
             std::string dual_message;
             std::exception_ptr dual_error;
             CertifyTimes dual_times;
-            std::thread dual([&] {
+            std::shared_ptr<CertifyWorker> worker = scratch ? std::static_pointer_cast<CertifyWorker>(scratch->worker) : nullptr;
+            if (scratch && !worker) {  // the handle's first certificate: the thread stays with the handle
+                worker = std::make_shared<CertifyWorker>();
+                scratch->worker = worker;
+            }
+            const auto dual_lifting = [&] {
                 try {
                     RELP_HIP(hipSetDevice(device));
                     hipStream_t second = scratch ? scratch->second : nullptr;
@@ -1254,7 +1387,10 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
                 } catch (...) {
                     dual_error = std::current_exception();
                 }
-            });
+            };
+            std::thread dual;
+            if (worker) worker->start(dual_lifting);
+            else dual = std::thread(dual_lifting);
             bool primal_ok = false;
             std::exception_ptr primal_error;
             try {
@@ -1263,7 +1399,8 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
                 primal_error = std::current_exception();
             }
             stamp("primal solve done");
-            dual.join();
+            if (worker) worker->wait();
+            else dual.join();
             stamp("dual solve joined");
             if (timeline)
                 fprintf(stderr, "[certify]   unpack %.2f / %.2f; primal: device %.2f host %.2f (Horner %.2f combine %.2f numerators %.2f verify %.2f gcd %.2f, %d reconstructions %.2f); "
@@ -1331,12 +1468,13 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
             if (primal) {  // OptimizationResult::FiniteOptimum(x) in exact form (algorithm/mod.rs:43-47), kept as integers over one denominator
                 auto kept = std::make_shared<ExactPrimal>();
                 kept->basis = basis;
-                kept->numer = witnesses ? x.numer : std::move(x.numer);
+                kept->numer = std::move(x.numer);
                 kept->denom = x.denom;
                 *primal = kept;
             }
             ExactVector no_ray;
-            if (witnesses) *witnesses = make_exact_witnesses(*statics, mode, basis, -1, x, y, no_ray);  // (of the basis after the repair pivots)
+            // (of the basis after the repair pivots; x is the kept primal solution's where there is one)
+            if (witnesses) *witnesses = make_exact_witnesses(*statics, mode, basis, -1, x, y, no_ray, primal ? *primal : nullptr);
             return;
         }
         if (round == max_repairs) break;

@@ -5,6 +5,7 @@
 // functions; what differs between them is only who produced the digits.
 #pragma once
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -47,16 +48,23 @@ struct ExactVector {           // numer[i] / denom
     BigInt denom = BigInt(1);
 };
 
-// The exact vectors a certificate proved its verdict with (declared in solver.hpp), in the terms of the caller's LP: the row and
-// cost multipliers of the integer scaling are folded in by make_exact_witnesses.  Big integers over one denominator per vector;
-// the "num/den" texts are made on demand (exact_witness_values).
+// The exact vectors a certificate proved its verdict with (declared in solver.hpp), in the terms of the caller's LP.  Big integers
+// over one denominator per vector; the "num/den" texts are made on demand (exact_witness_values).  A certificate only KEEPS what
+// the witnesses are made of -- most results are never asked for theirs: the row and cost multipliers of the integer scaling are
+// folded into y by the first exact_witness_values (under `finish_guard`: accessors may come from several threads), and x is
+// shared with the kept exact primal solution where there is one, not copied.
 struct ExactWitnesses {
     int mode = 0;               // as certify_basis: 0 FINITE_OPTIMUM, 1 INFEASIBLE, 2 UNBOUNDED
     std::vector<int> basis;     // the basis that was finally proved: provider column per row (-1-k: artificial k)
     int entering = -1;          // mode 2: the provider column q of the ray
-    ExactVector x;              // x_B[k] = x.numer[k] / x.denom
-    ExactVector y;              // y_i = y.numer[i] / y.denom per row: the dual solution (mode 1: the Farkas vector)
+    ExactVector x;              // x_B[k] = x.numer[k] / x.denom ...
+    std::shared_ptr<const ExactPrimal> shared_x;  // ... unless this is set: then x is the kept primal solution's (same basis, same values)
+    mutable ExactVector y;      // once finished: y_i = y.numer[i] / y.denom per row: the dual solution (mode 1: the Farkas vector)
     ExactVector alpha;          // mode 2: alpha = B^-1 a_q, d_{basis[k]} = -alpha_k
+    mutable std::mutex finish_guard;
+    mutable bool finished = false;      // false: y is still the solution of the scaled system, and these wait to be folded in:
+    std::vector<i128> row_mult;
+    i128 cost_mult = 1;
 };
 
 // What depends on the loaded LP only (kept by the handle between certificates, CertifyScratch::statics).
@@ -118,7 +126,9 @@ bool certify_unbounded_ray(const std::vector<int>& basis, const ExactVector& alp
 // `x` as the checks saw it (x.denom holds rhs_den already); `y` is the solution of the SCALED system (diag(r) B)' y^ = mu c_B with the
 // row multipliers r and the cost multiplier mu (mode 1: the phase-one costs, mu = 1), so the dual solution of the caller's LP is
 // y_i = r_i y^_i / mu: B' (r . y^) = mu c_B.  x and alpha do not see the row scaling.  The vectors are moved from.
+// `shared_x` (may be null): the kept exact primal solution of the same basis; x is then taken from there (and may have been moved from).
 std::shared_ptr<const ExactWitnesses> make_exact_witnesses(const CertifyStatic& statics, int mode, const std::vector<int>& basis, int entering,
-                                                          ExactVector& x, ExactVector& y, ExactVector& alpha);
+                                                          ExactVector& x, ExactVector& y, ExactVector& alpha,
+                                                          std::shared_ptr<const ExactPrimal> shared_x = nullptr);
 
 }  // namespace relp

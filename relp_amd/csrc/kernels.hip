@@ -2652,6 +2652,10 @@ __global__ void __launch_bounds__(256) commit_kernel(DeviceLP lp, int parity) {
             Ctl c = *last.ctl;
             c.t_buf = 0;
             *lp.ctl = c;
+            if (lp.ctl_mirror) {  // the host reads the end of the batch from its pinned mirror, after synchronising the stream
+                *lp.ctl_mirror = c;
+                __threadfence_system();
+            }
         }
     }
 }

@@ -77,6 +77,10 @@ Solver::~Solver() {
 
 void Solver::free_device() {
     device_memory_.free_all();
+    pinned_memory_.free_all();
+    h_ctl_ = h_ctl_out_ = nullptr;
+    h_rb_basis_ = h_rb_flipped_ = h_rb_pos_ = nullptr;
+    h_rb_xb_ = h_rb_ub_ = nullptr;
     d_ = DeviceLP{};
     net_ = NetTree{};
 }
@@ -354,6 +358,18 @@ void Solver::allocate_pivot_state() {
     }
     d_.scratch = device_alloc<double>((size_t)std::max(m, n) * 3 + 16);  // fine-grained ops carve m ints + 2 m doubles out of it
     d_.ctl = device_alloc<Ctl>(1);
+    // what the host and the device hand each other around the kernels lives in pinned host memory (no device bytes)
+    h_ctl_ = pinned_memory_.alloc<Ctl>(1);
+    h_ctl_out_ = pinned_memory_.alloc<Ctl>(1);
+    *h_ctl_ = Ctl{};
+    if (path_.fused) d_.ctl_mirror = PinnedAllocations::device_pointer(h_ctl_);  // (before any graph is captured: a graph keeps its kernels' arguments)
+    h_rb_basis_ = pinned_memory_.alloc<int>(m);
+    h_rb_xb_ = pinned_memory_.alloc<double>(m);
+    if (path_.bounded) {
+        h_rb_flipped_ = pinned_memory_.alloc<int>(n);
+        h_rb_pos_ = pinned_memory_.alloc<int>(n);
+        h_rb_ub_ = pinned_memory_.alloc<double>(n);
+    }
     d_.dbg = device_alloc<unsigned long long>(64);
     RELP_HIP(hipMemsetAsync(d_.dbg, 0, 64 * sizeof(unsigned long long), stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
@@ -362,10 +378,11 @@ void Solver::allocate_pivot_state() {
 Ctl Solver::read_ctl() {
     // Every batch of launches ends in a read of the control block (never inside a stream capture): the place where a
     // rejected launch -- a grid or an LDS request the device refuses -- surfaces instead of leaving stale device state behind.
+    // The copy lands in the handle's pinned mirror: a copy into pageable memory is staged through a copy kernel of the runtime.
     RELP_HIP(hipGetLastError());
-    Ctl c;
-    RELP_HIP(hipMemcpyAsync(&c, d_.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, stream_));
+    RELP_HIP(hipMemcpyAsync(h_ctl_, d_.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
+    Ctl c = *h_ctl_;
     if (c.status == ST_REFACTOR_FAILED) {
         // the refactorisation kernels gave up (a capacity, a row too long for the eliminating wave): nothing has pivoted since, the
         // basis on the device is the one they were given -- factorise it on the host (which also grows what was too small)
@@ -376,17 +393,27 @@ Ctl Solver::read_ctl() {
             fprintf(stderr, "[lu] the device refactorisation gave up with status %d (m %d): host fallback\n", info[LUF_STATUS], d_.m);
         }
         c.status = ST_REFACTOR;
-        RELP_HIP(hipMemcpyAsync(d_.ctl, &c, sizeof(Ctl), hipMemcpyHostToDevice, stream_));
-        RELP_HIP(hipStreamSynchronize(stream_));
+        write_ctl(c);
         refactor_lu_host(true);
         refactors_--;  // (counted once, by the attempt on the device)
-        RELP_HIP(hipMemcpyAsync(&c, d_.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, stream_));
+        RELP_HIP(hipMemcpyAsync(h_ctl_, d_.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, stream_));
         RELP_HIP(hipStreamSynchronize(stream_));
+        c = *h_ctl_;
     }
     return c;
 }
+// The end of a batch of pivots (Solver::iterate).  Fused path: commit_kernel, the last kernel of every batch, has stored the
+// committed block into the mirror as well (DeviceLP::ctl_mirror), so nothing is enqueued -- the host waits for the stream and reads.
+// The mirror is never read while a kernel may still be running.
+Ctl Solver::read_ctl_after_batch() {
+    if (!d_.ctl_mirror) return read_ctl();
+    RELP_HIP(hipGetLastError());
+    RELP_HIP(hipStreamSynchronize(stream_));
+    return *h_ctl_;
+}
 void Solver::write_ctl(const Ctl& c) {
-    RELP_HIP(hipMemcpyAsync(d_.ctl, &c, sizeof(Ctl), hipMemcpyHostToDevice, stream_));
+    *h_ctl_out_ = c;  // (the wait below: the pinned block is free again when this returns)
+    RELP_HIP(hipMemcpyAsync(d_.ctl, h_ctl_out_, sizeof(Ctl), hipMemcpyHostToDevice, stream_));
     RELP_HIP(hipStreamSynchronize(stream_));
 }
 
@@ -1097,7 +1124,7 @@ long long Solver::iterate(long long count, int* stop_reason) {
             launch_pivots(batch);
         }
         const long long fallbacks_before = device_refactor_failures_;
-        Ctl after = read_ctl();  // (a refactorisation the kernels gave up on is redone by the host in here: nothing pivoted, go on)
+        Ctl after = read_ctl_after_batch();  // (a refactorisation the kernels gave up on is redone by the host in here: nothing pivoted, go on)
         const bool fell_back = device_refactor_failures_ != fallbacks_before;
         long long made = after.iters - iters_before;
         iters_before = after.iters;
@@ -1206,12 +1233,10 @@ void Solver::solve(relp_result* result) {
         if (kind == RELP_RESULT_NONE) {
             polish(true);
             tick("polish");
-            Ctl c = read_ctl();
-            std::vector<double> xb(d_.m);
-            RELP_HIP(hipMemcpyAsync(xb.data(), d_.xB, d_.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
-            RELP_HIP(hipStreamSynchronize(stream_));
+            RELP_HIP(hipMemcpyAsync(h_rb_xb_, d_.xB, d_.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
+            Ctl c = read_ctl();  // (waits for x_B too)
             double scale = 1.0;
-            for (double v : xb) scale += std::fabs(v);
+            for (int i = 0; i < d_.m; ++i) scale += std::fabs(h_rb_xb_[i]);
             if (-c.minus_obj > opt_.tol_feasible * scale) {
                 kind = RELP_RESULT_INFEASIBLE;  // phase_one.rs:171-173
             } else {
@@ -1236,11 +1261,17 @@ void Solver::solve(relp_result* result) {
     }
     // results: Carry::current_bfs (carry/mod.rs:636-645) + reconstruct_solution (matrix_data.rs:402-411)
     const int m = d_.m;
-    std::vector<int> basis(m);
-    std::vector<double> xb(m);
-    RELP_HIP(hipMemcpyAsync(basis.data(), d_.basis, m * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    RELP_HIP(hipMemcpyAsync(xb.data(), d_.xB, m * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    // (into the handle's pinned buffers, all behind the one wait of read_ctl)
+    RELP_HIP(hipMemcpyAsync(h_rb_basis_, d_.basis, m * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    RELP_HIP(hipMemcpyAsync(h_rb_xb_, d_.xB, m * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    if (path_.bounded) {
+        RELP_HIP(hipMemcpyAsync(h_rb_flipped_, d_.flipped, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        RELP_HIP(hipMemcpyAsync(h_rb_pos_, d_.pos, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        RELP_HIP(hipMemcpyAsync(h_rb_ub_, d_.ub, d_.n * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    }
     Ctl c = read_ctl();
+    const std::vector<int> basis(h_rb_basis_, h_rb_basis_ + m);
+    const double* xb = h_rb_xb_;
     for (int i = 0; i < m; ++i)  // never index host arrays with an unchecked device value
         if (basis[i] < 0 || basis[i] >= d_.n) throw std::runtime_error("the device returned an invalid basis (row " + std::to_string(i) + ")");
     std::fill(h_solution_.begin(), h_solution_.end(), 0.0);
@@ -1254,15 +1285,12 @@ void Solver::solve(relp_result* result) {
         // variable sits at its upper bound, and the basis of the full MatrixData has, on every bound row, the bound slack
         // (variable below its bound) or the variable itself (variable at its bound).
         const MatrixData& md = form_.data;
-        std::vector<int> flipped(d_.n), pos(d_.n);
-        std::vector<double> ub(d_.n);
-        RELP_HIP(hipMemcpyAsync(flipped.data(), d_.flipped, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
-        RELP_HIP(hipMemcpyAsync(pos.data(), d_.pos, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
-        RELP_HIP(hipMemcpyAsync(ub.data(), d_.ub, d_.n * sizeof(double), hipMemcpyDeviceToHost, stream_));
-        RELP_HIP(hipStreamSynchronize(stream_));
+        const std::vector<int> flipped(h_rb_flipped_, h_rb_flipped_ + d_.n);
+        std::vector<int> pos(h_rb_pos_, h_rb_pos_ + d_.n);
+        const std::vector<double> ub(h_rb_ub_, h_rb_ub_ + d_.n);
         resolve_fixed_columns(pos);
         h_basis_ = explicit_basis(basis, pos);
-        explicit_solution(md, cols_, basis, xb.data(), flipped, pos, ub, h_solution_);
+        explicit_solution(md, cols_, basis, xb, flipped, pos, ub, h_solution_);
     }
     if (net_.stats) {
         net_stats_.assign(NS_WORDS, 0);

@@ -31,16 +31,22 @@ struct ExactPrimal;
 // Farkas vector of an INFEASIBLE verdict) and alpha = B^-1 a_q of an UNBOUNDED one.
 struct ExactWitnesses;
 // What a handle keeps between its certificates (certify.hip): the second stream of the dual lifting (creating and destroying a
-// stream costs 4 + 2 ms, as much as the rest of a certificate), the device buffers (returned to the handle, not to the driver) and
-// the p-adic digit counts the last certificate of the loaded LP needed.
+// stream costs 4 + 2 ms, as much as the rest of a certificate), the host thread that drives it (creating one costs 0.1 ms), the
+// device buffers (returned to the handle, not to the driver), the pinned staging arena the uploads are packed into and the digits
+// are downloaded into (a copy from or to pageable memory goes through a copy kernel of the runtime and blocks), and the p-adic digit
+// counts the last certificate of the loaded LP needed.  Nothing of it is shared between handles.
 struct CertifyScratch {
     hipStream_t second = nullptr;
+    std::shared_ptr<void> worker;  // certify.hip: CertifyWorker, made by the first certificate; joined by release() or with the scratch
     struct Block {
         void* ptr;
         size_t bytes;
         bool busy;
     };
     std::vector<Block> blocks;
+    std::vector<Block> pinned;    // the staging arena: pinned host blocks, handed out and taken back like the device blocks
+    void* take_pinned(size_t bytes);
+    void give_back_pinned(void* ptr);
     int digit_hints[2] = {0, 0};  // (primal, dual); 0: unknown.  Reset when another LP is loaded.
     std::shared_ptr<const void> statics;  // the LP's integer scaling (certify.hip: CertifyStatic); reset when another LP is loaded
     void* take(size_t bytes);     // smallest free block that fits, else a new allocation
@@ -191,6 +197,8 @@ struct DeviceLP {
     int* k2_parti = nullptr;     //   ... candidate rows, their basic columns, non-zero counts and list offsets
     double* scratch = nullptr;   // m or n doubles for the fine-grained ops
     Ctl* ctl = nullptr;
+    Ctl* ctl_mirror = nullptr;   // fused pivot kernel: the handle's pinned host copy of the control block, as the device addresses it; commit_kernel
+                                 // writes the committed block there too, so that the host reads the end of a batch without a copy
     // fused pivot kernel (pivot_fused_kernel, small LPs): x_B, basis and control block exist twice; pivot k of a batch reads copy
     // k & 1 and writes the other (kernels.hip, K23)
     struct State {
@@ -391,8 +399,20 @@ private:
     void resolve_fixed_columns(std::vector<int>& pos);
     std::vector<char> zero_width_;  // implicit bounds: device columns with upper bound 0 (fixed variables)
     void ensure_polish_buffers();  // second inverse + residual matrix, allocated when a polish first has something to correct
-    Ctl read_ctl();
+    Ctl read_ctl();                // an explicit copy of the device's control block into the pinned mirror, behind a stream synchronise
+    Ctl read_ctl_after_batch();    // the same after a batch of pivots: the fused path's commit_kernel has written the mirror itself
     void write_ctl(const Ctl& c);
+    // Pinned, host-mapped memory of the loaded LP (sized at load, freed with the device buffers): the mirror of the control block,
+    // the block write_ctl copies out of (every write_ctl waits for the stream, so it is never reused before it has been consumed), and
+    // the read-backs of a solve.  Read only behind a hipStreamSynchronize of stream_.
+    PinnedAllocations pinned_memory_;
+    Ctl* h_ctl_ = nullptr;
+    Ctl* h_ctl_out_ = nullptr;
+    int* h_rb_basis_ = nullptr;     // [m]
+    double* h_rb_xb_ = nullptr;     // [m]
+    int* h_rb_flipped_ = nullptr;   // [n] implicit bounds only, like the next two
+    int* h_rb_pos_ = nullptr;       // [n]
+    double* h_rb_ub_ = nullptr;     // [n]
     int drive_out_artificials();
     void certify(relp_result* result);
     std::vector<double> net_host_solve(const HostTree& t, bool transposed, const std::vector<double>& v) const;  // B^-1 v or v' B^-1
