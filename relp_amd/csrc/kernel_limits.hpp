@@ -8,6 +8,7 @@ namespace relp {
 constexpr int WAVE = 64;
 constexpr int ELL_W = 8;            // padded entries per column = lanes per column in the pricing kernel
 constexpr int PRICE_UNIT_ARCS = 4;  // arcs per lane of price_unit_kernel
+constexpr size_t PRICE_LDS_CONFIGURED = 160 * 1024 - 1024;  // the dynamic LDS a pricing workgroup may ask for (configure_lds)
 inline int price_columns_per_block(int ell_w, bool generated) { return generated ? 256 * PRICE_UNIT_ARCS : 256 / ell_w; }
 
 // column-per-lane pricing of the dense block (price_dense_lane_kernel)

@@ -158,7 +158,16 @@ KernelPath plan_kernel_path(const relp_options& opt_, const MatrixData& md, cons
             p.dense_storage = exact_in_float ? DenseStorage::F32_ROWS : DenseStorage::F64_ROWS;
         }
     }
-    p.multi_workgroup_ratio = !fast_k2 && (!sw(RELP_SW_K2_SINGLE) || p.network);  // m > 8192
+    // The ratio test: rows in registers where they fit (the smallest R with m <= R * K2F_THREADS), beyond that across workgroups for
+    // a full iteration (RELP_SW_K2_SINGLE: A/B; the forest carry has no other form there) and in one workgroup for the calls that
+    // make no basis change.
+    p.ratio_kernel_no_change = !fast_k2 ? RatioKernel::ONE_WORKGROUP
+                               : m <= 2 * K2F_THREADS ? RatioKernel::REGISTERS_2
+                               : m <= 4 * K2F_THREADS ? RatioKernel::REGISTERS_4
+                               : m <= 8 * K2F_THREADS ? RatioKernel::REGISTERS_8
+                                                      : RatioKernel::REGISTERS_16;
+    p.ratio_kernel = !fast_k2 && (!sw(RELP_SW_K2_SINGLE) || p.network) ? RatioKernel::MULTI_WORKGROUP : p.ratio_kernel_no_change;  // m > 8192
+    p.multi_workgroup_ratio = p.ratio_kernel == RatioKernel::MULTI_WORKGROUP;
     // The reference's ratio rule is implemented by the register-resident ratio test (m <= 8192), the fused pivot kernel and the LU
     // pivot kernel; the multi-workgroup test beyond 8192 rows and the one-workgroup fallback implement the two-pass rule only.
     {
@@ -171,16 +180,43 @@ KernelPath plan_kernel_path(const relp_options& opt_, const MatrixData& md, cons
     // small LPs: ratio test and inverse update in one launch (pivot_fused_kernel; relp_options.pivot_kernels = 1 keeps the three-kernel pivot)
     p.fused = !p.lu_mode && !p.network && !p.bounded && !p.eta_mode && n_dense == 0 && p.ftran_slices == 0 && !p.track_touched && p.ell_w == ELL_W &&
               fused_pivot_available(m, p.price_blocks) && opt_.pivot_kernels != 1;
+    p.fused_rows = !p.fused ? 0 : m <= 2 * K2F_THREADS ? 2 : KF_MAX_R;
     if (p.generated_columns) {  // -pi from its own vector, rho_p's non-zero rows as bits (bytes beyond LDS)
         p.price_unit_pairs = sw(RELP_SW_PRICE_UNIT_PAIRS);
         p.rho_words = ((m + 127) / 128) * 4;
         if ((size_t)p.rho_words * 4 > 64 * 1024 || sw(RELP_SW_NO_RHO_BITS) || p.price_unit_pairs) p.rho_words = 0;
     }
+    // The CSC pricing kernel.  At width 8 it stages -pi, rho_p and w in LDS (3 m doubles per workgroup) where that pays.  Not beside a
+    // dense block: the CSC kernel then only sees the short slack columns, and staging would cost more than the gathers it saves.
+    // (Running it on a second stream beside the dense pass was measured too: the fork/join edges of the captured graph cost 15 us per
+    // pivot against the 8 us they hide.)  Not beyond 4096 rows (96 KB): a workgroup prices 32 columns and would stage 3 m doubles for
+    // them, one workgroup per CU (80BAU3B, m = 5746: 486 workgroups x 138 KB = 67 MB of staging against 1.5 MB of gathers; 53.8 ->
+    // 45.7 us per pivot without).  Between 2000 and 2800 rows the two forms are within the run-to-run noise (BNL2, CYCLE, GREENBEA).
+    // relp_options.price_lds_max: A/B hook.  The fused pivot's batches stage whatever the CU holds.
+    const auto price_kernel = [&](bool stage_in_lds) {
+        if (p.ell_w == 2 && p.generated_columns && p.price_unit_pairs) return PriceKernel::UNIT_PAIRS;
+        if (p.ell_w == 2 && p.generated_columns) return PriceKernel::GENERATED;
+        if (p.ell_w == 2) return PriceKernel::WIDTH_2;
+        return stage_in_lds ? PriceKernel::LDS : PriceKernel::GATHER;
+    };
+    const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
+    p.price_kernel = price_kernel(p.price_lds <= lds_max && p.dense_blocks == 0);
+    p.price_kernel_fused = price_kernel(p.price_lds <= PRICE_LDS_CONFIGURED);
+    // The rank-one update of the explicit inverse.  Up to 2048 rows it is latency bound and reads whole columns; beyond, its loads
+    // are predicated on alpha_i != 0, and a full sweep runs one workgroup per column pair where the touched columns are listed (the
+    // list-driven modes use the first quarter of that grid; beyond 16384 rows they dominate -- graph LPs -- and 4x the workgroups
+    // only cost launch time).
+    p.update_kernel = m <= 2048 ? UpdateKernel::EAGER : (p.track_touched && m <= 16384) ? UpdateKernel::PREDICATED_SPLIT_GRID : UpdateKernel::PREDICATED;
+    p.polish_gemm = sw(RELP_SW_GEMM_VECTOR) ? PolishGemm::VECTOR : PolishGemm::MFMA;  // (the switch: A/B measurements)
     return p;
 }
 
 std::string kernel_path_json(const KernelPath& p) {
     static const char* storage[] = {"NONE", "I8_LANE", "F32_LANE", "F64_LANE", "I8_PERMUTED", "F32_ROWS", "F64_ROWS"};
+    static const char* price[] = {"UNIT_PAIRS", "GENERATED", "WIDTH_2", "LDS", "GATHER"};
+    static const char* ratio[] = {"REGISTERS_2", "REGISTERS_4", "REGISTERS_8", "REGISTERS_16", "MULTI_WORKGROUP", "ONE_WORKGROUP"};
+    static const char* update[] = {"EAGER", "PREDICATED", "PREDICATED_SPLIT_GRID"};
+    static const char* gemm[] = {"MFMA", "VECTOR"};
     std::ostringstream out;
 #define RELP_FIELD(x) << ", \"" #x "\": " << p.x
     out << std::boolalpha << "{\"m\": " << p.m RELP_FIELD(n) RELP_FIELD(n_art) RELP_FIELD(n_p) RELP_FIELD(bounded) RELP_FIELD(network) RELP_FIELD(lu_mode)
@@ -189,7 +225,12 @@ std::string kernel_path_json(const KernelPath& p) {
         << ", \"dense_storage\": \"" << storage[(int)p.dense_storage] << "\", \"dense_entry_bytes\": " << p.dense_entry_bytes() RELP_FIELD(ell_w) RELP_FIELD(generated_columns)
         RELP_FIELD(price_blocks) RELP_FIELD(dense_blocks) RELP_FIELD(vector_len) RELP_FIELD(price_lds) RELP_FIELD(ftran_slices) RELP_FIELD(eta_mode)
         RELP_FIELD(eta_cap) RELP_FIELD(slack_in_btran) << ", \"slack_of_row_length\": " << p.slack_of_row.size() RELP_FIELD(track_touched)
-        RELP_FIELD(multi_workgroup_ratio) RELP_FIELD(ratio_textbook) RELP_FIELD(fused) RELP_FIELD(rho_words) RELP_FIELD(price_unit_pairs) << "}";
+        RELP_FIELD(multi_workgroup_ratio) RELP_FIELD(ratio_textbook) RELP_FIELD(fused) RELP_FIELD(rho_words) RELP_FIELD(price_unit_pairs)
+        << ", \"price_kernel\": \"" << price[(int)p.price_kernel] << "\", \"price_kernel_fused\": \"" << price[(int)p.price_kernel_fused]
+        << "\", \"ratio_kernel\": \"" << ratio[(int)p.ratio_kernel] << "\", \"ratio_kernel_no_change\": \"" << ratio[(int)p.ratio_kernel_no_change] << "\""
+        RELP_FIELD(fused_rows) << ", \"update_kernel\": \"" << update[(int)p.update_kernel] << "\", \"polish_gemm\": \"" << gemm[(int)p.polish_gemm]
+        << "\", \"launches_per_batch\": " << p.launches_per_batch(false, false) << ", \"launches_per_pivot\": " << p.launches_per_pivot(false, false)
+        << ", \"launches_per_pivot_forced\": " << p.launches_per_pivot(true, false) << ", \"launches_per_pivot_replayed\": " << p.launches_per_pivot(false, true) << "}";
 #undef RELP_FIELD
     return out.str();
 }

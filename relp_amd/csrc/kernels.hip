@@ -3327,41 +3327,42 @@ void take_launch_timer(int which, hipEvent_t* start, hipEvent_t* stop) {
 constexpr int PRICE_LPC = 8;  // lanes per sparse column in the pricing kernel
 
 template <int RULE>
-static void launch_price_rule(const DeviceLP& d, int blocks, size_t lds, bool use_lds, int skip_weights, double tol,
-                              int first, int last, int cand_offset, hipStream_t s) {
-    const bool timed_elsewhere = d.n_dense > 0;  // with a dense block the dense kernel is the one that is timed
-    if (d.ell_w == 2 && d.cost8 && d.price_unit_pairs)  // (the round-2 form, two lanes per arc: A/B)
-        RELP_LAUNCH(timed_elsewhere ? -2 : 0, (price_kernel<RULE, false, 2, true>), dim3(blocks), dim3(256), 0, s, d, skip_weights, tol, first, last, cand_offset);
-    else if (d.ell_w == 2 && d.cost8)  // incidence columns generated from the arcs' endpoints (8 B per arc)
-        RELP_LAUNCH(timed_elsewhere ? -2 : 0, (price_unit_kernel<RULE>), dim3(blocks), dim3(256), (size_t)d.rho_words * sizeof(unsigned), s, d, skip_weights, tol, first, last, cand_offset);
-    else if (d.ell_w == 2)  // graph LPs: two entries per column, 128 columns per workgroup pass (large m: vectors gathered from L2)
-        RELP_LAUNCH(timed_elsewhere ? -2 : 0, (price_kernel<RULE, false, 2>), dim3(blocks), dim3(256), 0, s, d, skip_weights, tol, first, last, cand_offset);
-    else if (use_lds)
-        RELP_LAUNCH(timed_elsewhere ? -2 : 0, (price_kernel<RULE, true, PRICE_LPC>), dim3(blocks), dim3(256), lds, s, d, skip_weights, tol, first, last, cand_offset);
-    else
-        RELP_LAUNCH(timed_elsewhere ? -2 : 0, (price_kernel<RULE, false, PRICE_LPC>), dim3(blocks), dim3(256), 0, s, d, skip_weights, tol, first, last, cand_offset);
-}
-
-// sparse (CSC) pricing over the device columns [first, last)
-void launch_price(const DeviceLP& d, int rule, int blocks, size_t lds, bool use_lds, int skip_weights, double tol,
-                  int first, int last, int cand_offset, hipStream_t s) {
-    switch (rule) {
-        case RELP_PIVOT_DANTZIG: launch_price_rule<RELP_PIVOT_DANTZIG>(d, blocks, lds, use_lds, skip_weights, tol, first, last, cand_offset, s); break;
-        case RELP_PIVOT_FIRST_PROFITABLE: launch_price_rule<RELP_PIVOT_FIRST_PROFITABLE>(d, blocks, lds, use_lds, skip_weights, tol, first, last, cand_offset, s); break;
-        case RELP_PIVOT_FIRST_PROFITABLE_MEMORY: launch_price_rule<RELP_PIVOT_FIRST_PROFITABLE_MEMORY>(d, blocks, lds, use_lds, skip_weights, tol, first, last, cand_offset, s); break;
-        default: launch_price_rule<RELP_PIVOT_STEEPEST_EDGE>(d, blocks, lds, use_lds, skip_weights, tol, first, last, cand_offset, s); break;
+static void launch_price_rule(const DeviceLP& d, const KernelPath& path, PriceKernel kernel, int skip_weights, double tol, hipStream_t s) {
+    const int which = d.n_dense > 0 ? -2 : 0;  // with a dense block the dense kernel is the one that is timed
+    const dim3 grid(path.price_blocks), block(256);
+    const int first = path.sparse_first, last = d.n, cand_offset = 0;
+    switch (kernel) {
+    case PriceKernel::UNIT_PAIRS: RELP_LAUNCH(which, (price_kernel<RULE, false, 2, true>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
+    case PriceKernel::GENERATED: RELP_LAUNCH(which, (price_unit_kernel<RULE>), grid, block, (size_t)d.rho_words * sizeof(unsigned), s, d, skip_weights, tol, first, last, cand_offset); break;
+    case PriceKernel::WIDTH_2: RELP_LAUNCH(which, (price_kernel<RULE, false, 2>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
+    case PriceKernel::LDS: RELP_LAUNCH(which, (price_kernel<RULE, true, PRICE_LPC>), grid, block, path.price_lds, s, d, skip_weights, tol, first, last, cand_offset); break;
+    case PriceKernel::GATHER: RELP_LAUNCH(which, (price_kernel<RULE, false, PRICE_LPC>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
     }
 }
 
-void launch_price_dense(const DeviceLP& d, int blocks, int skip_weights, double tol, int cand_offset, hipStream_t s) {
+// sparse (CSC) pricing over the device columns [path.sparse_first, n): `kernel` is path.price_kernel or path.price_kernel_fused
+void launch_price(const DeviceLP& d, const KernelPath& path, PriceKernel kernel, int rule, int skip_weights, double tol, hipStream_t s) {
+    switch (rule) {
+        case RELP_PIVOT_DANTZIG: launch_price_rule<RELP_PIVOT_DANTZIG>(d, path, kernel, skip_weights, tol, s); break;
+        case RELP_PIVOT_FIRST_PROFITABLE: launch_price_rule<RELP_PIVOT_FIRST_PROFITABLE>(d, path, kernel, skip_weights, tol, s); break;
+        case RELP_PIVOT_FIRST_PROFITABLE_MEMORY: launch_price_rule<RELP_PIVOT_FIRST_PROFITABLE_MEMORY>(d, path, kernel, skip_weights, tol, s); break;
+        default: launch_price_rule<RELP_PIVOT_STEEPEST_EDGE>(d, path, kernel, skip_weights, tol, s); break;
+    }
+}
+
+void launch_price_dense(const DeviceLP& d, const KernelPath& path, int skip_weights, double tol, hipStream_t s) {
     const size_t lds = (size_t)3 * d.dense_ld * sizeof(double);
-    if (d.dense_lane) {
-        if (d.dense_val) RELP_LAUNCH(0, price_dense_lane_kernel<8>, dim3(blocks), dim3(dense_lane_threads(d.m)), 0, s, d, skip_weights, tol, cand_offset);
-        else if (d.dense_val32) RELP_LAUNCH(0, price_dense_lane_kernel<4>, dim3(blocks), dim3(dense_lane_threads(d.m)), 0, s, d, skip_weights, tol, cand_offset);
-        else RELP_LAUNCH(0, price_dense_lane_kernel<1>, dim3(blocks), dim3(dense_lane_threads(d.m)), 0, s, d, skip_weights, tol, cand_offset);
-    } else if (d.dense_val8) RELP_LAUNCH(0, (price_dense_kernel<false, true>), dim3(blocks), dim3(K1D_THREADS), lds, s, d, skip_weights, tol, cand_offset);
-    else if (d.dense_val32) RELP_LAUNCH(0, price_dense_kernel<true>, dim3(blocks), dim3(K1D_THREADS), lds, s, d, skip_weights, tol, cand_offset);
-    else RELP_LAUNCH(0, price_dense_kernel<false>, dim3(blocks), dim3(K1D_THREADS), lds, s, d, skip_weights, tol, cand_offset);
+    const dim3 grid(path.dense_blocks), lane_block(dense_lane_threads(d.m)), row_block(K1D_THREADS);
+    const int cand_offset = path.price_blocks;
+    switch (path.dense_storage) {
+    case DenseStorage::NONE: throw std::logic_error("launch_price_dense: no dense block");
+    case DenseStorage::F64_LANE: RELP_LAUNCH(0, price_dense_lane_kernel<8>, grid, lane_block, 0, s, d, skip_weights, tol, cand_offset); break;
+    case DenseStorage::F32_LANE: RELP_LAUNCH(0, price_dense_lane_kernel<4>, grid, lane_block, 0, s, d, skip_weights, tol, cand_offset); break;
+    case DenseStorage::I8_LANE: RELP_LAUNCH(0, price_dense_lane_kernel<1>, grid, lane_block, 0, s, d, skip_weights, tol, cand_offset); break;
+    case DenseStorage::I8_PERMUTED: RELP_LAUNCH(0, (price_dense_kernel<false, true>), grid, row_block, lds, s, d, skip_weights, tol, cand_offset); break;
+    case DenseStorage::F32_ROWS: RELP_LAUNCH(0, price_dense_kernel<true>, grid, row_block, lds, s, d, skip_weights, tol, cand_offset); break;
+    case DenseStorage::F64_ROWS: RELP_LAUNCH(0, price_dense_kernel<false>, grid, row_block, lds, s, d, skip_weights, tol, cand_offset); break;
+    }
 }
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel on the CURRENT device: setting it to the current LP's size would
 // let the last loaded handle decide for every other one.  It is set once per device (PerDeviceOnce, solver.hpp), to what the CU has
@@ -3372,7 +3373,7 @@ static void allow_full_lds(const void* kernel) {
     if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) fixed = attr.sharedSizeBytes;
     if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - fixed)) != hipSuccess) (void)hipGetLastError();
 }
-void configure_dense_lds(size_t) {
+void configure_dense_lds() {
     static PerDeviceOnce once;
     once.run([] {
         allow_full_lds(reinterpret_cast<const void*>(&price_dense_kernel<false>));
@@ -3384,7 +3385,7 @@ void launch_ftran_partial(const DeviceLP& d, int n_slices, int n_price_blocks, i
     hipLaunchKernelGGL(ftran_partial_kernel, dim3((d.m + 255) / 256, n_slices), dim3(256), 0, s, d, n_slices, n_price_blocks, rule);
 }
 
-void configure_lds(size_t) {
+void configure_lds() {
     // opt in to > 64 KB of dynamic LDS (160 KB per CU on gfx950), once per device
     static PerDeviceOnce once;
     once.run([] {
@@ -3395,48 +3396,58 @@ void configure_lds(size_t) {
     });
 }
 
+// mode 0 runs path.ratio_kernel, modes 1 and 2 path.ratio_kernel_no_change; n_alpha_slices > 0 (alpha given in alpha_in) is read
+// by the register-resident kernel only
 template <int RULE>
-static void launch_ftran_ratio_rule(const DeviceLP& d, int n_price_blocks, double tol_pivot, double harris_delta,
-                                    int skip_artificial_rows, int mode, int n_alpha_slices, hipStream_t s) {
-    const bool fits = n_price_blocks <= K2F_MAX_BLOCKS;
-    if (fits && d.m <= 2 * K2F_THREADS)
-        RELP_LAUNCH(1, (ftran_ratio_fast_kernel<RULE, 2>), dim3(1), dim3(K2F_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices);
-    else if (fits && d.m <= 4 * K2F_THREADS)
-        RELP_LAUNCH(1, (ftran_ratio_fast_kernel<RULE, 4>), dim3(1), dim3(K2F_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices);
-    else if (fits && d.m <= 8 * K2F_THREADS)
-        RELP_LAUNCH(1, (ftran_ratio_fast_kernel<RULE, 8>), dim3(1), dim3(K2F_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices);
-    else if (fits && d.m <= 16 * K2F_THREADS)
-        RELP_LAUNCH(1, (ftran_ratio_fast_kernel<RULE, 16>), dim3(1), dim3(K2F_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices);
-    else if (mode == 0 && d.k2_partd != nullptr) {
+static void launch_ftran_ratio_rule(const DeviceLP& d, const KernelPath& path, double tol_pivot, double harris_delta, int skip_artificial_rows,
+                                    int mode, int n_alpha_slices, hipStream_t s) {
+    const RatioKernel kernel = mode == 0 ? path.ratio_kernel : path.ratio_kernel_no_change;
+    const int n_price_blocks = path.slots();
+    if (n_alpha_slices > 0 && ratio_rows_per_thread(kernel) == 0) throw std::logic_error("launch_ftran_ratio: a preselected alpha needs the register-resident ratio test");
+#define RELP_RATIO_REGISTERS(R) \
+    RELP_LAUNCH(1, (ftran_ratio_fast_kernel<RULE, R>), dim3(1), dim3(K2F_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices)
+    switch (kernel) {
+    case RatioKernel::REGISTERS_2: RELP_RATIO_REGISTERS(2); break;
+    case RatioKernel::REGISTERS_4: RELP_RATIO_REGISTERS(4); break;
+    case RatioKernel::REGISTERS_8: RELP_RATIO_REGISTERS(8); break;
+    case RatioKernel::REGISTERS_16: RELP_RATIO_REGISTERS(16); break;
+    case RatioKernel::MULTI_WORKGROUP: {
         const int blocks = (d.m + K2L_THREADS - 1) / K2L_THREADS;
         RELP_LAUNCH(1, (k2l_ftran_kernel<RULE>), dim3(blocks), dim3(K2L_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows);
         hipLaunchKernelGGL(k2l_harris_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks, tol_pivot, skip_artificial_rows);
         hipLaunchKernelGGL(k2l_apply_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks);
-    } else
-        RELP_LAUNCH(1, (ftran_ratio_kernel<RULE>), dim3(1), dim3(K2_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode);
-}
-
-// n_alpha_slices > 0 requires the register-resident kernel (m <= 8192 and <= 2048 pricing workgroups)
-
-void launch_ftran_ratio(const DeviceLP& d, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
-                        int skip_artificial_rows, int mode, int n_alpha_slices, hipStream_t s) {
-    if (rule == RELP_PIVOT_STEEPEST_EDGE)
-        launch_ftran_ratio_rule<RELP_PIVOT_STEEPEST_EDGE>(d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices, s);
-    else
-        launch_ftran_ratio_rule<RELP_PIVOT_DANTZIG>(d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices, s);
-}
-
-void launch_pivot_fused(const DeviceLP& d, int rule, int parity, int n_price_blocks, double tol_pivot, double harris_delta,
-                        int skip_artificial_rows, hipStream_t s) {
-    const dim3 grid((d.m + KF_NW - 1) / KF_NW);
-    const bool small = d.m <= 2 * KF_THREADS;
-    if (rule == RELP_PIVOT_STEEPEST_EDGE) {
-        if (small) RELP_LAUNCH(1, (pivot_fused_kernel<RELP_PIVOT_STEEPEST_EDGE, 2>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows);
-        else RELP_LAUNCH(1, (pivot_fused_kernel<RELP_PIVOT_STEEPEST_EDGE, 4>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows);
-    } else {
-        if (small) RELP_LAUNCH(1, (pivot_fused_kernel<RELP_PIVOT_DANTZIG, 2>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows);
-        else RELP_LAUNCH(1, (pivot_fused_kernel<RELP_PIVOT_DANTZIG, 4>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows);
+        break;
     }
+    case RatioKernel::ONE_WORKGROUP:
+        RELP_LAUNCH(1, (ftran_ratio_kernel<RULE>), dim3(1), dim3(K2_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode);
+        break;
+    }
+#undef RELP_RATIO_REGISTERS
+}
+
+void launch_ftran_ratio(const DeviceLP& d, const KernelPath& path, int rule, double tol_pivot, double harris_delta, int skip_artificial_rows,
+                        int mode, int n_alpha_slices, hipStream_t s) {
+    if (rule == RELP_PIVOT_STEEPEST_EDGE)
+        launch_ftran_ratio_rule<RELP_PIVOT_STEEPEST_EDGE>(d, path, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices, s);
+    else
+        launch_ftran_ratio_rule<RELP_PIVOT_DANTZIG>(d, path, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices, s);
+}
+
+template <int RULE>
+static void launch_pivot_fused_rule(const DeviceLP& d, const KernelPath& path, int parity, double tol_pivot, double harris_delta,
+                                    int skip_artificial_rows, hipStream_t s) {
+    const dim3 grid((d.m + KF_NW - 1) / KF_NW);
+    const int n_price_blocks = path.price_blocks;
+    switch (path.fused_rows) {
+    case 2: RELP_LAUNCH(1, (pivot_fused_kernel<RULE, 2>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows); break;
+    case 4: RELP_LAUNCH(1, (pivot_fused_kernel<RULE, 4>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows); break;
+    default: throw std::logic_error("launch_pivot_fused: the path has no fused pivot");
+    }
+}
+void launch_pivot_fused(const DeviceLP& d, const KernelPath& path, int rule, int parity, double tol_pivot, double harris_delta,
+                        int skip_artificial_rows, hipStream_t s) {
+    if (rule == RELP_PIVOT_STEEPEST_EDGE) launch_pivot_fused_rule<RELP_PIVOT_STEEPEST_EDGE>(d, path, parity, tol_pivot, harris_delta, skip_artificial_rows, s);
+    else launch_pivot_fused_rule<RELP_PIVOT_DANTZIG>(d, path, parity, tol_pivot, harris_delta, skip_artificial_rows, s);
 }
 void launch_begin_batch(const DeviceLP& d, long long add, hipStream_t s) {
     hipLaunchKernelGGL(begin_batch_kernel, dim3(1), dim3(256), 0, s, d, add);
@@ -3445,13 +3456,14 @@ void launch_commit(const DeviceLP& d, int parity, hipStream_t s) {
     hipLaunchKernelGGL(commit_kernel, dim3(std::min(256, (d.m + 3) / 4)), dim3(256), 0, s, d, parity);
 }
 
-void launch_update(const DeviceLP& d, hipStream_t s) {
+void launch_update(const DeviceLP& d, const KernelPath& path, hipStream_t s) {
     const int cols_per_block = (K3_THREADS / WAVE) * K3_CPW;
-    const dim3 grid((d.m + cols_per_block - 1) / cols_per_block);
-    // m > 2048: a full sweep runs one workgroup per column pair (the list-driven modes use the first quarter of the grid)
-    const dim3 grid_split((d.m + K3_CPW - 1) / K3_CPW);
-    if (d.m <= 2048) RELP_LAUNCH(2, (update_kernel<true>), grid, dim3(K3_THREADS), 0, s, d);
-    else RELP_LAUNCH(2, (update_kernel<false>), (d.track_touched && d.m <= 16384) ? grid_split : grid, dim3(K3_THREADS), 0, s, d);  // larger m: the list-driven modes dominate (graph LPs) and 4x the workgroups only cost launch time
+    const dim3 grid((d.m + cols_per_block - 1) / cols_per_block), grid_split((d.m + K3_CPW - 1) / K3_CPW);
+    switch (path.update_kernel) {
+    case UpdateKernel::EAGER: RELP_LAUNCH(2, (update_kernel<true>), grid, dim3(K3_THREADS), 0, s, d); break;
+    case UpdateKernel::PREDICATED: RELP_LAUNCH(2, (update_kernel<false>), grid, dim3(K3_THREADS), 0, s, d); break;
+    case UpdateKernel::PREDICATED_SPLIT_GRID: RELP_LAUNCH(2, (update_kernel<false>), grid_split, dim3(K3_THREADS), 0, s, d); break;
+    }
 }
 
 void launch_budget(const DeviceLP& d, long long add, hipStream_t s) {
@@ -3491,7 +3503,6 @@ void launch_scatter(double* X, const long long* index, const double* value, long
 void launch_residual(const DeviceLP& d, const double* T, double* S, hipStream_t s) {
     hipLaunchKernelGGL(residual_kernel, dim3(d.m), dim3(256), 0, s, d, T, S);
 }
-static bool use_mfma_gemm() { return !thread_tuning().has(RELP_SW_GEMM_VECTOR); }  // (the switch selects the plain-FMA kernel: A/B measurements)
 __global__ void __launch_bounds__(256) copy_rows_kernel(const double* src, double* dst, int m, int ld, const int* row_list, int n_rows) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
@@ -3500,31 +3511,30 @@ __global__ void __launch_bounds__(256) copy_rows_kernel(const double* src, doubl
         dst[row + i] = src[row + i];
     }
 }
-bool gemm_row_lists_supported() { return use_mfma_gemm(); }  // the plain-FMA fallback kernels compute every row
 void launch_copy_rows(const double* src, double* dst, int m, int ld, const int* row_list, int n_rows, hipStream_t s) {
     if (n_rows > 0) hipLaunchKernelGGL(copy_rows_kernel, dim3((m + 255) / 256, std::min(n_rows, 65535)), dim3(256), 0, s, src, dst, m, ld, row_list, n_rows);
 }
-// row_list (device, n_rows entries) restricts the computed storage rows; nullptr = all m
-void launch_gemm_polish(const double* X, const double* R, double* C, int m, int ld, const int* row_list, int n_rows, hipStream_t s) {
+// row_list (device, n_rows entries) restricts the computed storage rows; nullptr = all m (PolishGemm::VECTOR computes every row: no list)
+void launch_gemm_polish(PolishGemm gemm, const double* X, const double* R, double* C, int m, int ld, const int* row_list, int n_rows, hipStream_t s) {
     const int rows = row_list ? n_rows : m;
     if (rows <= 0) return;
     dim3 grid((m + GT - 1) / GT, (rows + GT - 1) / GT);
-    if (use_mfma_gemm()) hipLaunchKernelGGL((gemm_mfma_kernel<0>), grid, dim3(256), 0, s, X, R, C, m, ld, (double*)nullptr, row_list, n_rows);
+    if (gemm == PolishGemm::MFMA) hipLaunchKernelGGL((gemm_mfma_kernel<0>), grid, dim3(256), 0, s, X, R, C, m, ld, (double*)nullptr, row_list, n_rows);
     else hipLaunchKernelGGL((gemm_polish_kernel<0>), grid, dim3(256), 0, s, X, R, C, m, ld, (double*)nullptr);
 }
 // S = I - B' T for a dense basis: gather B' into `Bd`, then one GEMM (also records max |S|)
-void launch_residual_dense(const DeviceLP& d, double* Bd, const double* T, double* S, const int* row_list, int n_rows, hipStream_t s) {
+void launch_residual_dense(const DeviceLP& d, PolishGemm gemm, double* Bd, const double* T, double* S, const int* row_list, int n_rows, hipStream_t s) {
     hipLaunchKernelGGL(gather_basis_kernel, dim3(d.m), dim3(256), 0, s, d, Bd);
     const int rows = row_list ? n_rows : d.m;
     if (rows <= 0) return;
     dim3 grid((d.m + GT - 1) / GT, (rows + GT - 1) / GT);
-    if (use_mfma_gemm()) hipLaunchKernelGGL((gemm_mfma_kernel<1>), grid, dim3(256), 0, s, Bd, T, S, d.m, d.ld, &d.ctl->residual, row_list, n_rows);
+    if (gemm == PolishGemm::MFMA) hipLaunchKernelGGL((gemm_mfma_kernel<1>), grid, dim3(256), 0, s, Bd, T, S, d.m, d.ld, &d.ctl->residual, row_list, n_rows);
     else hipLaunchKernelGGL((gemm_polish_kernel<1>), grid, dim3(256), 0, s, Bd, T, S, d.m, d.ld, &d.ctl->residual);
 }
 void launch_alpha_reduce(const DeviceLP& d, int n_slices, hipStream_t s) {
     hipLaunchKernelGGL(alpha_reduce_kernel, dim3((d.m + AR_ROWS - 1) / AR_ROWS), dim3(AR_ROWS * AR_GROUPS), 0, s, d, n_slices);
 }
-void configure_btran_lds(size_t) {
+void configure_btran_lds() {
     static PerDeviceOnce once;
     once.run([] { allow_full_lds(reinterpret_cast<const void*>(&btran_pass_kernel)); });
 }

@@ -468,19 +468,17 @@ void launch_net_row(const DeviceLP& d, const NetTree& t, int r, double* out, hip
     hipLaunchKernelGGL(net_row_kernel, dim3(net_grid(d.m)), dim3(NET_THREADS), 0, s, d, t, r, out);
 }
 
-int Solver::net_launches_per_pivot() const { return fast_k2_available(d_.m, path_.price_blocks + path_.dense_blocks) ? 5 : 7; }
-
 // parts: 1 entering column, path and ratio test; 2 the forest update (mode 0)
 void Solver::net_enqueue_pivot(int mode, int parts) {
-    const int slots = path_.price_blocks + path_.dense_blocks;
+    const int slots = path_.slots();
     const int skip_art = phase_ == 2 ? 1 : 0;
     if (parts & 1) {
         if (opt_.pivot_rule == RELP_PIVOT_STEEPEST_EDGE)
             hipLaunchKernelGGL(net_ftran_kernel<RELP_PIVOT_STEEPEST_EDGE>, dim3(1), dim3(NET_THREADS), 0, stream_, d_, net_, slots, mode);
         else
             hipLaunchKernelGGL(net_ftran_kernel<RELP_PIVOT_DANTZIG>, dim3(1), dim3(NET_THREADS), 0, stream_, d_, net_, slots, mode);
-        if (fast_k2_available(d_.m, slots)) {
-            launch_ftran_ratio(d_, opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, 1, stream_);
+        if (!path_.multi_workgroup_ratio) {
+            launch_ftran_ratio(d_, path_, opt_.pivot_rule, opt_.tol_pivot, ratio_delta(), skip_art, mode, 1, stream_);
         } else {
             if (mode != 0) throw std::invalid_argument("RELP_CARRY_NETWORK: the ratio test without a basis change is implemented up to 8192 rows");
             // Every non-zero of alpha is +-1 on a network basis, so the two-pass test with a slack of 0 IS the reference's rule: pass 1

@@ -139,7 +139,7 @@ void Solver::upload() {
     upload_dense_block();
     tick("dense block");
     allocate_pivot_state();
-    configure_lds(std::min<size_t>(path_.price_lds, 160 * 1024 - 1024));
+    configure_lds();
     tick("pivot state");
 
     stats_.price_bytes = (long long)(host_.col_start[n] - host_.col_start[path_.sparse_first]) * 12 + (long long)(n - n_art) * 24 +
@@ -280,7 +280,7 @@ void Solver::upload_dense_block() {
     case DenseStorage::F32_ROWS: put(d_.dense_val32, std::vector<float>(dense.begin(), dense.end())); break;
     case DenseStorage::F64_ROWS: put(d_.dense_val, dense); break;
     }
-    if (!path_.dense_lane) configure_dense_lds((size_t)3 * d_.dense_ld * sizeof(double));  // (one wave per column: the vectors are in LDS)
+    if (!path_.dense_lane) configure_dense_lds();  // (one wave per column: the vectors are in LDS)
 }
 
 // Everything a pivot reads and writes: the vectors, the inverse, the candidate slots of the pricing passes, the buffers of the
@@ -332,7 +332,7 @@ void Solver::allocate_pivot_state() {
         d_.eta_slot = device_alloc<int>(m);
         d_.eta_gather = device_alloc<double>((size_t)d_.eta_cap * m);
         RELP_HIP(hipMemsetAsync(d_.eta_slot, 0xff, m * sizeof(int), stream_));
-        configure_btran_lds((size_t)2 * ((m + 1) & ~1) * sizeof(double));
+        configure_btran_lds();
     }
     if (path_.bounded) {
         const std::vector<double> ub = implicit_upper_bounds(form_.data, cols_);
@@ -748,6 +748,8 @@ void Solver::set_phase(int phase) {
 
 // One batch of `count` iterations of the loop of phase_one.rs:134-178 / phase_two.rs:36-58.
 void Solver::launch_pivots(int count, bool forced) {
+    stats_.launches += path_.launches(count, forced, false);
+    stats_.price_launches += count;
     if (path_.fused && !forced) {  // two kernels per pivot; x_B, basis and control block alternate between their two copies (kernels.hip, K23)
         launch_begin_batch(d_, count, stream_);
         for (int it = 0; it < count; ++it) {
@@ -755,73 +757,42 @@ void Solver::launch_pivots(int count, bool forced) {
             enqueue_pivot_fused(it & 1);
         }
         launch_commit(d_, count & 1, stream_);
-        stats_.launches += 2 + 2LL * count;
-        stats_.price_launches += count;
         return;
     }
     launch_budget(d_, count, stream_);
-    if (path_.network) {  // pricing, entering column + tree path, ratio test, forest update: a linear chain of launches
-        for (int it = 0; it < count; ++it) {
-            enqueue_price(0);
-            net_enqueue_pivot(0);
-        }
-        stats_.launches += 1 + (long long)net_launches_per_pivot() * count;
-        stats_.price_launches += count;
-        return;
-    }
-    if (path_.lu_mode) {  // two kernels per pivot: the pricing pass and the single-workgroup LU kernel
-        for (int it = 0; it < count; ++it) {
-            enqueue_price(0);
-            enqueue_ftran_ratio(0);
-        }
-        stats_.launches += 1 + 2LL * count;
-        stats_.price_launches += count;
-        return;
-    }
     for (int it = 0; it < count; ++it) {
         enqueue_price(0, it == 0);
-        enqueue_ftran_ratio(0);
+        enqueue_ftran_ratio(0);  // (the forest carry: its whole pivot, a linear chain of launches; the LU carry: its single-workgroup kernel)
+        if (path_.network || path_.lu_mode) continue;
         enqueue_update();
         if (path_.eta_mode && ((it + 1) % d_.eta_cap == 0 || it + 1 == count)) enqueue_consolidate();
     }
-    stats_.launches += 1 + (3LL + (path_.dense_blocks > 0) + 2 * (path_.ftran_slices > 0)) * count;
-    stats_.price_launches += count;
 }
 
 // Pricing pass: the dense block (if any) streams through price_dense_kernel, every other column through the CSC kernel.
 void Solver::enqueue_price(int skip_weights, bool first_of_batch) {
-    // beside a dense block the CSC kernel only sees the short slack columns: staging -pi, rho_p, w in LDS (3 m doubles per
-    // workgroup) would cost more than the gathers it saves.  (Running it on a second stream beside the dense pass was
-    // measured too: the fork/join edges of the captured graph cost 15 us per pivot against the 8 us they hide.)
-    // ... and beyond 4096 rows as well: a workgroup prices 32 columns and would stage 3 m doubles for them, one workgroup per CU
-    // (80BAU3B, m = 5746: 486 workgroups x 138 KB = 67 MB of staging against 1.5 MB of gathers; 53.8 -> 45.7 us per pivot without).
-    // Between 2000 and 2800 rows the two forms are within the run-to-run noise (BNL2, CYCLE, GREENBEA).  RELP_PRICE_LDS_MAX: A/B hook.
-    const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
-    const bool use_lds = path_.price_lds <= lds_max && path_.dense_blocks == 0;
     // path_.slack_in_btran: the BTRAN pass of the previous pivot has priced the slack columns (weights included); only the first
     // pivot of a batch has no predecessor in the batch, and its pass must not apply the weight update a second time
     if (path_.price_blocks > 0 && (!path_.slack_in_btran || first_of_batch))
-        launch_price(d_, opt_.pivot_rule, path_.price_blocks, use_lds ? path_.price_lds : 0, use_lds, path_.slack_in_btran ? 1 : skip_weights, opt_.tol_dual,
-                     path_.sparse_first, d_.n, 0, stream_);
-    if (path_.dense_blocks > 0) launch_price_dense(d_, path_.dense_blocks, skip_weights, opt_.tol_dual, path_.price_blocks, stream_);
+        launch_price(d_, path_, path_.price_kernel, opt_.pivot_rule, path_.slack_in_btran ? 1 : skip_weights, opt_.tol_dual, stream_);
+    if (path_.dense_blocks > 0) launch_price_dense(d_, path_, skip_weights, opt_.tol_dual, stream_);
 }
 
 // Fused mode: the pricing pass before pivot k reads the control block of copy k & 1 (it writes nothing of the twin state).
 void Solver::enqueue_price_fused(int parity) {
     DeviceLP d = d_;
     d.ctl = d_.state[parity].ctl;
-    const bool use_lds = path_.price_lds <= 160 * 1024 - 1024;
-    launch_price(d, opt_.pivot_rule, path_.price_blocks, use_lds ? path_.price_lds : 0, use_lds, 0, opt_.tol_dual, path_.sparse_first, d_.n, 0, stream_);
+    launch_price(d, path_, path_.price_kernel_fused, opt_.pivot_rule, 0, opt_.tol_dual, stream_);
 }
 void Solver::enqueue_pivot_fused(int parity) {
-    launch_pivot_fused(d_, opt_.pivot_rule, parity, path_.price_blocks, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, stream_);
+    launch_pivot_fused(d_, path_, opt_.pivot_rule, parity, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, stream_);
 }
 
 // The basis update: rank-one update of the explicit inverse (K3), or -- deferred product form -- the eta bookkeeping plus
 // one read-only pass for rho_p, w and -pi.
 void Solver::enqueue_update() {
     if (path_.eta_mode) launch_eta_update(d_, opt_.tol_dual, stream_);
-    else launch_update(d_, stream_);
+    else launch_update(d_, path_, stream_);
 }
 // Fold the pending etas into the stored inverse (no-op kernels when there are none; runs whatever the status is, so that
 // everything outside the pivot loop sees the plain explicit inverse).
@@ -832,7 +803,7 @@ void Solver::enqueue_consolidate() {
 // Entering column + FTRAN + ratio test (+ updates in mode 0).  Long (dense) columns take the multi-block FTRAN.
 void Solver::enqueue_ftran_ratio(int mode) {
     const int skip_art = phase_ == 2 ? 1 : 0;
-    const int slots = path_.price_blocks + path_.dense_blocks;
+    const int slots = path_.slots();
     if (path_.network) {
         net_enqueue_pivot(mode);
         return;
@@ -847,7 +818,7 @@ void Solver::enqueue_ftran_ratio(int mode) {
         launch_ftran_partial(d_, path_.ftran_slices, slots, opt_.pivot_rule, stream_);
         launch_alpha_reduce(d_, path_.ftran_slices, stream_);
     }
-    launch_ftran_ratio(d_, opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, path_.ftran_slices > 0 ? 1 : 0, stream_);
+    launch_ftran_ratio(d_, path_, opt_.pivot_rule, opt_.tol_pivot, ratio_delta(), skip_art, mode, path_.ftran_slices > 0 ? 1 : 0, stream_);
 }
 
 void Solver::destroy_graphs() {
@@ -893,7 +864,7 @@ void Solver::polish(bool refresh_vectors, bool force) {
     const int m = d_.m;
     // dense pipeline: only the columns of the stored inverse that are not unit vectors take part (the corresponding
     // rows of S are zero and those columns of the polished inverse do not change): both GEMMs shrink by m / touched
-    const bool by_rows = d_.track_touched && gemm_row_lists_supported();
+    const bool by_rows = path_.track_touched && path_.polish_gemm == PolishGemm::MFMA;  // (the plain-FMA kernels compute every row)
     const int* rows = by_rows ? d_.tlist : nullptr;
     int n_rows = m;
     if (by_rows) n_rows = read_ctl().touched_count;
@@ -901,7 +872,7 @@ void Solver::polish(bool refresh_vectors, bool force) {
     for (int it = 0; it < 2; ++it) {
         RELP_HIP(hipMemsetAsync(&d_.ctl->residual, 0, sizeof(double), stream_));
         if (by_rows && d_.R) RELP_HIP(hipMemsetAsync(d_.R, 0, (size_t)m * d_.ld * sizeof(double), stream_));
-        if (d_.n_dense > 0) launch_residual_dense(d_, d_.Binv2, d_.Binv, d_.R, rows, n_rows, stream_);
+        if (d_.n_dense > 0) launch_residual_dense(d_, path_.polish_gemm, d_.Binv2, d_.Binv, d_.R, rows, n_rows, stream_);
         else launch_residual(d_, d_.Binv, d_.R, stream_);  // R == nullptr: norm only
         Ctl c = read_ctl();  // max |I - B' T|
         if (d_.R == nullptr && c.residual >= 1e-12 && c.residual < 0.5) {  // something to correct: now S itself is needed
@@ -926,7 +897,7 @@ void Solver::polish(bool refresh_vectors, bool force) {
             invert_from_scratch();
             break;
         }
-        launch_gemm_polish(d_.Binv, d_.R, d_.Binv2, m, d_.ld, rows, n_rows, stream_);
+        launch_gemm_polish(path_.polish_gemm, d_.Binv, d_.R, d_.Binv2, m, d_.ld, rows, n_rows, stream_);
         if (by_rows) launch_copy_rows(d_.Binv2, d_.Binv, m, d_.ld, rows, n_rows, stream_);
         else RELP_HIP(hipMemcpyAsync(d_.Binv, d_.Binv2, (size_t)m * d_.ld * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         if (c.residual < 1e-8) break;  // one quadratic step takes it to ~residual^2
@@ -986,7 +957,7 @@ void Solver::invert_from_scratch() {
     for (int it = 0; it < 200; ++it) {
         RELP_HIP(hipMemsetAsync(&d_.ctl->residual, 0, sizeof(double), stream_));
         launch_residual(d_, d_.Binv, d_.R, stream_);
-        launch_gemm_polish(d_.Binv, d_.R, d_.Binv2, m, d_.ld, nullptr, m, stream_);
+        launch_gemm_polish(path_.polish_gemm, d_.Binv, d_.R, d_.Binv2, m, d_.ld, nullptr, m, stream_);
         RELP_HIP(hipMemcpyAsync(d_.Binv, d_.Binv2, (size_t)m * d_.ld * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         Ctl c = read_ctl();
         if (c.residual < 1e-11) break;
@@ -1118,7 +1089,7 @@ long long Solver::iterate(long long count, int* stop_reason) {
         if (opt_.use_graph && batch == full_batch) {
             build_graph(batch);
             RELP_HIP(hipGraphLaunch(graph_exec_[graph_index()], stream_));
-            stats_.launches += 1 + (path_.network ? (long long)net_launches_per_pivot() : path_.lu_mode ? 2LL : 3LL) * batch;
+            stats_.launches += path_.launches(batch, false, true);
             stats_.price_launches += batch;
         } else {
             launch_pivots(batch);
@@ -1642,7 +1613,7 @@ void Solver::price(int* column, double* cbar) {
     write_ctl(c);
     enqueue_price(0);
     if (path_.lu_mode) enqueue_ftran_ratio(1);
-    else launch_ftran_ratio(d_, opt_.pivot_rule, path_.price_blocks + path_.dense_blocks, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, 1, 0, stream_);
+    else launch_ftran_ratio(d_, path_, opt_.pivot_rule, opt_.tol_pivot, ratio_delta(), phase_ == 2 ? 1 : 0, 1, 0, stream_);
     c = read_ctl();
     *column = c.q;
     *cbar = c.q >= 0 ? c.cbar_q : 0.0;

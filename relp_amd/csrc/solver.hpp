@@ -428,7 +428,6 @@ private:
     void net_set_gamma();                     // ... of every non-basic column, uploaded
     bool net_crash(const std::vector<int>& basis);
     void net_certify(relp_result* result);
-    int net_launches_per_pivot() const;      // pricing, path, ratio test (one kernel, or three across workgroups), update, re-hang
     void net_enqueue_pivot(int mode, int parts = 3);  // entering column + tree path, ratio test (+ forest update in mode 0)
     std::vector<unsigned long long> net_stats_;
     DeviceAllocations device_memory_;  // every buffer of the loaded LP: d_, net_ (free_device)

@@ -1,5 +1,5 @@
-// plan_kernel_path under the host sanitizers, without a device: plans AFIRO and a dense 64 x 128 LP under a few options each and prints
-// the plans.  kernel_path.cpp is compiled here, instrumented (its limits are inline in kernel_limits.hpp); the library only parses
+// plan_kernel_path under the host sanitizers, without a device: plans AFIRO, a dense 64 x 128 LP and the diagonal LP on each side of
+// every row count at which the plan takes another kernel instantiation, under a few options each, and prints the plans.  kernel_path.cpp is compiled here, instrumented (its limits are inline in kernel_limits.hpp); the library only parses
 // the models:
 //   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Irelp_amd/csrc tools/kernel_path_sanitize.cpp
 //       relp_amd/csrc/kernel_path.cpp -Lrelp_amd -lrelp_amd -Wl,-rpath,$PWD/relp_amd -o kernel_path_sanitize && ./kernel_path_sanitize
@@ -53,6 +53,36 @@ int main() {
     relp_options rows_form = o;
     rows_form.switches = RELP_SW_NO_DENSE_LANE, rows_form.dense_storage = RELP_DENSE_FLOAT;
     plan(dense, rows_form, "dense 64 x 128, float rows");
+    // the diagonal LP of tools/record_kernel_paths.py (row i: x_i - z_i = b_i, min sum x) around 1024, 2048, 4096 and 8192 rows
+    for (const int rows_d : {1024, 1025, 2048, 2049, 4096, 4097, 8192, 8193}) {
+        const int cols_d = 2 * rows_d;
+        std::vector<int64_t> d_start(cols_d + 1), d_num(cols_d), d_den(cols_d, 1), d_b(rows_d), d_cost(cols_d), d_one(cols_d, 1), d_zero(cols_d, 0);
+        std::vector<int32_t> d_rows(cols_d), d_kind(rows_d, 0);
+        std::vector<uint8_t> d_has_l(cols_d, 1), d_has_u(cols_d, 0);
+        for (int j = 0; j < cols_d; ++j) d_start[j + 1] = j + 1, d_rows[j] = j % rows_d, d_num[j] = j < rows_d ? 1 : -1, d_cost[j] = j < rows_d ? 1 : 0;
+        for (int i = 0; i < rows_d; ++i) d_b[i] = i % 100 == 0 ? 1 : 0;
+        relp_model* diagonal = nullptr;
+        if (relp_model_from_general_form(0, rows_d, cols_d, d_start.data(), d_rows.data(), d_num.data(), d_den.data(), d_kind.data(), d_zero.data(), d_one.data(),
+                                         d_b.data(), d_one.data(), d_cost.data(), d_one.data(), d_has_l.data(), d_zero.data(), d_one.data(), d_has_u.data(),
+                                         d_zero.data(), d_one.data(), 0, 1, 0, &diagonal, error, 512) != RELP_OK)
+            return std::printf("%s\n", error), 1;
+        char what[96];
+        std::snprintf(what, sizeof what, "diagonal %d", rows_d);
+        plan(diagonal, o, what);
+        if (rows_d <= 2048) {
+            relp_options three = o;
+            three.pivot_kernels = 1;
+            std::snprintf(what, sizeof what, "diagonal %d, three-kernel pivot", rows_d);
+            plan(diagonal, three, what);
+        }
+        if (rows_d == 8193) {
+            relp_options single = o;
+            single.switches = RELP_SW_K2_SINGLE;
+            plan(diagonal, single, "diagonal 8193, one-workgroup ratio test");
+            plan(diagonal, net, "diagonal 8193, network carry");
+        }
+        relp_model_free(diagonal);
+    }
     relp_model_free(afiro);
     relp_model_free(dense);
     return 0;

@@ -65,6 +65,7 @@ _BUILDERS = {
     "kb2": lambda: relp_amd.Model(os.path.join(ROOT, "data", "netlib", "KB2.SIF")),  # variable bounds (tests/test_gpu_bounded.py)
     "dense64": lambda: _dense(64, 128),
     "dense65": lambda: _dense(65, 130),
+    "diag1100": lambda: _diagonal(1100),
     "diag2100": lambda: _diagonal(2100),
     "diag7000": lambda: _diagonal(7000),
     "diag8400": lambda: _diagonal(8400),
@@ -126,6 +127,13 @@ CASES = [
     _case("reload-dense64-then-afiro", "dense64", run="reload"),
 ]
 CASE_BY_NAME = {case["name"]: case for case in CASES}
+# The kernel instantiations the plan names that no case above reaches (tests/golden/kernel_choice_fingerprints.json, recorded with the
+# library of the commit before the plan named them; replayed by tests/test_gpu_kernel_choice.py).  They are in the table of plans too.
+CHOICE_CASES = [
+    _case("afiro-gemm-vector", "afiro", switches=api.SW_GEMM_VECTOR),  # (the polish GEMM on plain FMAs)
+    _case("diag1100", "diag1100", run="iterate"),  # (between 1024 and 2048 rows: four rows per thread in the fused pivot and the ratio test)
+    _case("diag2100-no-touched", "diag2100", run="iterate", switches=api.SW_NO_TOUCHED),  # (the predicated update on its plain grid)
+]
 REFUSED = [case for case in CASES if case["run"] == "refused"]
 
 
@@ -231,7 +239,7 @@ def merge(path_a, path_b, path_out):
 
 def table(path):
     """The plan of every case that loads (tests/golden/kernel_path_table.json); needs no device."""
-    _write(path, {case["name"]: model(case["model"]).kernel_path(**case["options"]) for case in CASES if case["run"] != "refused"})
+    _write(path, {case["name"]: model(case["model"]).kernel_path(**case["options"]) for case in CASES + CHOICE_CASES if case["run"] != "refused"})
 
 
 if __name__ == "__main__":
