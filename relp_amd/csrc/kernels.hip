@@ -46,6 +46,9 @@ __global__ void budget_kernel(Ctl* ctl, long long add) {
 // LPC lanes share one sparse column (entries strided over the lanes, shuffle-reduced), so that the dependent
 // index -> LDS gather chain is 1-3 steps long whatever the column length; -pi, rho_p and w are staged in LDS once
 // per workgroup.  Traffic is the column data itself: nnz*(8+4) + 3*8 bytes per column.
+// Round trips, as compiled (tools/isa_round_trips.py, profiles/round_trips_isa.txt): ONE before the barrier -- column, control word and
+// the first 1024 rows of the three vectors are issued before the first wait; entries 8 .. 23 of a long column follow when its extent is
+// back, still ahead of the barrier -- and one per further eight entries of a column longer than 24.
 // The reference makes TWO passes over A per pivot (pricing, weight update) and clones every column twice.
 // ---------------------------------------------------------------------------------------------------
 typedef double f64x2_t __attribute__((ext_vector_type(2)));
@@ -63,49 +66,93 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
     Ctl* ctl = lp.ctl;
     const int m = lp.m;
     const int g = threadIdx.x / LPC, sub = threadIdx.x % LPC;
-    // ---- ONE memory round trip: control word, this workgroup's first columns, and the three vectors ----------
+    // ---- ONE memory round trip: this workgroup's first columns, the control word and the three vectors -------------------
+    // Every load below is issued before the first wait on any of them; the CSC entries 8 .. 23 of a long column follow as soon as
+    // its extent has arrived, ahead of the LDS stores and the barrier.  Loads are unconditional, from clamped addresses, and what
+    // an absent column loaded is dropped by selects in accept_column: a branch around a load would end in a wait of its own.
+    // The compiler orders loads and waits as it sees fit, so the claim is checked on the ISA (tools/isa_round_trips.py,
+    // profiles/round_trips_isa.txt), not here.
+    int base = col_first + blockIdx.x * CPB;
+    int a = 0, b = 0, r0 = 0;
+    double v0 = 0.0, cost_j = 0.0, g_j = 1.0;
+    bool nonbasic = false;
+    double sgn_j = 1.0;  // -1: the column is held in complemented form (implicit upper bounds)
+    // the words of the column in flight (`_n`): loaded by issue_column / issue_extension, taken over by accept_column
+    bool in_n = false, has1_n = false, has2_n = false;
+    int pos_n = 0, a_n = 0, b_n = 0, r0_n = 0, cost8_n = 0;
+    double v0_n = 0.0, cost_n = 0.0, g_n = 1.0;
+    int xr1_n = 0, xr2_n = 0;  // entries a + 8 + sub and a + 16 + sub of a column longer than the padded width
+    double xv1_n = 0.0, xv2_n = 0.0;
+    bool has1 = false, has2 = false;
+    int xr1 = 0, xr2 = 0;
+    double xv1 = 0.0, xv2 = 0.0;
+    auto issue_column = [&](int j) {
+        in_n = j < col_last;
+        const int jc = in_n ? j : max(col_last - 1, 0);
+        pos_n = lp.pos[jc];
+        if (LPC != 2) {  // width 2: no column is longer than the padded copy, the CSC is not needed
+            a_n = lp.col_start[jc];
+            b_n = lp.col_start[jc + 1];
+        }
+        r0_n = lp.ell_rows[(size_t)jc * LPC + sub];  // (non-temporal loads of the three streams: measured, no gain)
+        if (UNIT) {
+            cost8_n = lp.cost8[jc];
+        } else {
+            v0_n = lp.ell_vals[(size_t)jc * LPC + sub];
+            cost_n = lp.cost[jc];
+        }
+        // (generated columns: the weight is fetched only by the columns that need it -- candidates and columns with an
+        //  entry in the pivot row -- 16 of the 29 bytes per arc otherwise)
+        if (RULE == RELP_PIVOT_STEEPEST_EDGE && !UNIT) g_n = lp.gamma[jc];
+    };
+    auto issue_extension = [&]() {  // (waits for the column's position and extent, nothing else)
+        if constexpr (LPC == ELL_W) {
+            const bool priced = in_n && column_priced(pos_n);
+            const int e1 = a_n + LPC + sub, e2 = a_n + 2 * LPC + sub;
+            has1_n = priced && e1 < b_n;
+            has2_n = priced && e2 < b_n;
+            if (has1_n) {
+                xr1_n = lp.row_index[e1];
+                xv1_n = lp.value[e1];
+            }
+            if (has2_n) {
+                xr2_n = lp.row_index[e2];
+                xv2_n = lp.value[e2];
+            }
+        }
+    };
+    auto accept_column = [&]() {
+        nonbasic = in_n && column_priced(pos_n);
+        sgn_j = in_n ? column_sign(pos_n) : 1.0;
+        a = in_n ? a_n : 0;
+        b = in_n ? b_n : 0;
+        if (UNIT) {
+            const unsigned code = (unsigned)r0_n;
+            const bool absent = !in_n || code == 0x7fffffffu;
+            r0 = absent ? 0 : (int)(code & 0x7fffffffu);
+            v0 = absent ? 0.0 : ((code >> 31) ? -1.0 : 1.0);
+            cost_j = in_n ? (double)cost8_n : 0.0;
+        } else {
+            r0 = in_n ? r0_n : 0;
+            v0 = in_n ? v0_n : 0.0;
+            cost_j = in_n ? cost_n : 0.0;
+        }
+        g_j = (RULE == RELP_PIVOT_STEEPEST_EDGE && !UNIT && in_n) ? g_n : 1.0;
+        has1 = has1_n;
+        has2 = has2_n;
+        xr1 = xr1_n;
+        xv1 = xv1_n;
+        xr2 = xr2_n;
+        xv2 = xv2_n;
+    };
     const int status = ctl->status;
     const int pending = (RULE == RELP_PIVOT_STEEPEST_EDGE) ? (ctl->pending && !skip_weights) : 0;
     const double gamma_q = ctl->gamma_q;
     const double alpha_pq = ctl->alpha_pq;
     const int leaving = ctl->leaving;
     const int last = ctl->last_selected;
-    int base = col_first + blockIdx.x * CPB;
-    int a = 0, b = 0, r0 = 0;
-    double v0 = 0.0, cost_j = 0.0, g_j = 1.0;
-    bool nonbasic = false;
-    double sgn_j = 1.0;  // -1: the column is held in complemented form (implicit upper bounds)
-    auto load_column = [&](int j) {
-        a = b = r0 = 0;
-        v0 = cost_j = 0.0;
-        g_j = 1.0;
-        nonbasic = false;
-        sgn_j = 1.0;
-        if (j < col_last) {
-            const int pos_j = lp.pos[j];
-            nonbasic = column_priced(pos_j);
-            sgn_j = column_sign(pos_j);
-            if (LPC != 2) {  // width 2: no column is longer than the padded copy, the CSC is not needed
-                a = lp.col_start[j];
-                b = lp.col_start[j + 1];
-            }
-            if (UNIT) {
-                const unsigned code = (unsigned)lp.ell_rows[(size_t)j * LPC + sub];  // (non-temporal loads of the three streams: measured, no gain)
-                const bool absent = code == 0x7fffffffu;
-                r0 = absent ? 0 : (int)(code & 0x7fffffffu);
-                v0 = absent ? 0.0 : ((code >> 31) ? -1.0 : 1.0);
-                cost_j = (double)lp.cost8[j];
-            } else {
-                r0 = lp.ell_rows[(size_t)j * LPC + sub];
-                v0 = lp.ell_vals[(size_t)j * LPC + sub];
-                cost_j = lp.cost[j];
-            }
-            // (generated columns: the weight is fetched only by the columns that need it -- candidates and columns with an
-            //  entry in the pivot row -- 16 of the 29 bytes per arc otherwise)
-            if (RULE == RELP_PIVOT_STEEPEST_EDGE && !UNIT) g_j = lp.gamma[j];
-        }
-    };
-    load_column(base + g);
+    RELP_LOADS_PINNED();  // (scalar loads: left alone they are sunk to their first use, behind the waits of the column)
+    issue_column(base + g);
     const double* v_pi = lp.minus_pi;
     const double* v_rho = lp.rho;
     const double* v_w = lp.w;
@@ -113,8 +160,28 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
         double* s_pi = smem;
         double* s_rho = smem + m;
         double* s_w = smem + 2 * m;
-        for (int i0 = threadIdx.x; i0 < m; i0 += 4 * 256) {
-            double t_pi[4], t_rho[4], t_w[4];
+        // the first 1024 rows travel with the column: twelve loads from clamped addresses, no branch
+        double t_pi[4], t_rho[4], t_w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = threadIdx.x + u * 256;
+            const int ic = i < m ? i : 0;
+            t_pi[u] = lp.minus_pi[ic];
+            t_rho[u] = lp.rho[ic];
+            t_w[u] = lp.w[ic];
+        }
+        issue_extension();
+        RELP_LOADS_ISSUED();
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = threadIdx.x + u * 256;
+            if (i < m) {
+                s_pi[i] = t_pi[u];
+                s_rho[i] = t_rho[u];
+                s_w[i] = t_w[u];
+            }
+        }
+        for (int i0 = threadIdx.x + 4 * 256; i0 < m; i0 += 4 * 256) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int i = i0 + u * 256;
@@ -135,7 +202,11 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
         v_pi = s_pi;
         v_rho = s_rho;
         v_w = s_w;
+    } else {
+        issue_extension();
+        RELP_LOADS_ISSUED();
     }
+    accept_column();
     if (status != ST_RUNNING) return;  // uniform: every thread read the same word
     if (USE_LDS) __syncthreads();
 
@@ -179,7 +250,23 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
                 d_w = v0 * v_w[r0];
             }
         }
-        for (int e = a + LPC + sub; e < b; e += LPC) {  // columns longer than the padded width (rare)
+        if constexpr (LPC == ELL_W) {  // columns longer than the padded width: entries 8 .. 23 came with the column
+            if (has1) {
+                d_pi += xv1 * v_pi[xr1];
+                if (pending) {
+                    d_rho += xv1 * v_rho[xr1];
+                    d_w += xv1 * v_w[xr1];
+                }
+            }
+            if (has2) {
+                d_pi += xv2 * v_pi[xr2];
+                if (pending) {
+                    d_rho += xv2 * v_rho[xr2];
+                    d_w += xv2 * v_w[xr2];
+                }
+            }
+        }
+        for (int e = a + 3 * LPC + sub; e < b; e += LPC) {  // ... and the rest of it (rare; never at width 2)
             const int r = lp.row_index[e];
             const double v = lp.value[e];
             d_pi += v * v_pi[r];
@@ -226,7 +313,13 @@ __global__ void __launch_bounds__(256) price_kernel(DeviceLP lp, int skip_weight
             best_len = LPC == 2 ? 2 : b - a;
         }
         base += gridDim.x * CPB;
-        if (base < col_last) load_column(base + g);
+        if (base < col_last) {
+            issue_column(base + g);
+            RELP_LOADS_ISSUED();
+            issue_extension();
+            RELP_LOADS_ISSUED();
+            accept_column();
+        }
     }
     const Cand blk = block_best_candidate<RULE>(best, s_cand);
     const int slot = cand_offset + blockIdx.x;
@@ -1985,21 +2078,59 @@ struct K2fShared {
 };
 // The candidates of the pricing workgroups: this thread's best (key, rank), every reduced cost into LDS and -- when there are few
 // enough -- the padded entries of every candidate column, so that the FTRAN starts without another fetch.
-template <int RULE>
-__device__ __forceinline__ void k2f_candidates(const DeviceLP& lp, int n_price_blocks, K2fShared& sm, double& ckey, unsigned long long& crank) {
+// It comes in two halves so that the caller can put its own loads of the same round trip beside these: k2f_candidates_issue only
+// loads -- slot tid and, with inline columns, entries tid and tid + 512 and the slot's length, from clamped addresses: no branch
+// stands around a load and nothing is waited for -- the caller ends the group (RELP_LOADS_ISSUED), and k2f_candidates_fold stores
+// and folds what arrived.  Slots past the first 512 go through a loop of their own, each pass issued whole before its first wait.
+static_assert(K2F_INLINE_BLOCKS * ELL_W <= 2 * K2F_THREADS, "the inline entries are two loads per thread");
+struct K2fCandidateLoads {
+    int j, len;
+    double key, cbar;
+    int row[2];
+    double val[2];
+};
+__device__ __forceinline__ void k2f_candidates_issue(const DeviceLP& lp, int n_price_blocks, K2fCandidateLoads& c) {
     const int tid = threadIdx.x;
-    for (int b = tid; b < n_price_blocks; b += K2F_THREADS) {
-        const int j = lp.cand_j[b];
-        const double k = lp.cand_key[b];
-        sm.cbarv[b] = lp.cand_cbar[b];
-        offer_entering<RULE>(k, j, b, ckey, crank);
+    const int bc = tid < n_price_blocks ? tid : 0;
+    c.j = lp.cand_j[bc];
+    c.key = lp.cand_key[bc];
+    c.cbar = lp.cand_cbar[bc];
+    // (loaded with more than K2F_INLINE_BLOCKS slots too, where nothing reads them: a branch here, even a uniform one, splits the group)
+    c.len = lp.cand_len[bc];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int e = tid + t * K2F_THREADS;
+        const int ec = e < n_price_blocks * ELL_W ? e : 0;
+        c.row[t] = lp.cand_rows[ec];
+        c.val[t] = lp.cand_vals[ec];
+    }
+}
+template <int RULE>
+__device__ __forceinline__ void k2f_candidates_fold(const DeviceLP& lp, int n_price_blocks, K2fShared& sm, const K2fCandidateLoads& c,
+                                                    double& ckey, unsigned long long& crank) {
+    const int tid = threadIdx.x;
+    if (tid < n_price_blocks) {
+        sm.cbarv[tid] = c.cbar;
+        offer_entering<RULE>(c.key, c.j, tid, ckey, crank);
     }
     if (n_price_blocks <= K2F_INLINE_BLOCKS) {
-        for (int e = tid; e < n_price_blocks * ELL_W; e += K2F_THREADS) {
-            sm.crows[e] = lp.cand_rows[e];
-            sm.cvals[e] = lp.cand_vals[e];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int e = tid + t * K2F_THREADS;
+            if (e < n_price_blocks * ELL_W) {
+                sm.crows[e] = c.row[t];
+                sm.cvals[e] = c.val[t];
+            }
         }
-        for (int b = tid; b < n_price_blocks; b += K2F_THREADS) sm.clen[b] = lp.cand_len[b];
+        if (tid < n_price_blocks) sm.clen[tid] = c.len;
+    }
+    for (int b = tid + K2F_THREADS; b < n_price_blocks; b += K2F_THREADS) {  // more than 512 pricing workgroups
+        const int j = lp.cand_j[b];
+        const double k = lp.cand_key[b];
+        const double cb = lp.cand_cbar[b];
+        RELP_LOADS_ISSUED();
+        sm.cbarv[b] = cb;
+        offer_entering<RULE>(k, j, b, ckey, crank);
     }
 }
 // The winner among them: q (-1: none), its reduced cost and the pricing workgroup that offered it.
@@ -2016,18 +2147,29 @@ __device__ __forceinline__ void k2f_ftran_inline(const DeviceLP& lp, const doubl
                                                  double (&al)[R], int& ca, int& cb_) {
     const int tid = threadIdx.x, m = lp.m, ld = lp.ld;
     const int len = sm.clen[winner_block];
+    if (len >= 0) {  // (uniform)
+        // the eight gathers of up to four rows are ONE group of loads (all R rows in the fused kernel); a row past m reads row 0 and
+        // its sum is dropped
+        constexpr int G = R <= 4 ? R : 4;
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = tid + r * K2F_THREADS;
-        if (i >= m || len < 0) continue;
-        const double* col = T + i;
-        double t[ELL_W];
+        for (int rg = 0; rg < R; rg += G) {
+            double t[G][ELL_W];
 #pragma unroll
-        for (int e = 0; e < ELL_W; ++e) t[e] = col[(size_t)sm.crows[winner_block * ELL_W + e] * ld];  // padding: row 0, value 0
-        double a0 = 0.0;
+            for (int g = 0; g < G; ++g) {
+                const int i = tid + (rg + g) * K2F_THREADS;
+                const double* col = T + (i < m ? i : 0);
 #pragma unroll
-        for (int e = 0; e < ELL_W; ++e) a0 += t[e] * sm.cvals[winner_block * ELL_W + e];
-        al[r] = a0;
+                for (int e = 0; e < ELL_W; ++e) t[g][e] = col[(size_t)sm.crows[winner_block * ELL_W + e] * ld];  // padding: row 0, value 0
+            }
+            RELP_LOADS_ISSUED();
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                double a0 = 0.0;
+#pragma unroll
+                for (int e = 0; e < ELL_W; ++e) a0 += t[g][e] * sm.cvals[winner_block * ELL_W + e];
+                if (tid + (rg + g) * K2F_THREADS < m) al[rg + g] = a0;
+            }
+        }
     }
     if (len > ELL_W || len < 0) {
         ca = lp.col_start[q] + (len < 0 ? 0 : ELL_W);
@@ -2187,7 +2329,8 @@ __device__ __forceinline__ void k2f_broadcast_row(int p, const double (&al)[R], 
 // K2, register-resident variant for m <= R*K2F_THREADS (the common case).  Same contract as ftran_ratio_kernel, but
 // the dependent chain of global-memory round trips (~1.2 k cycles each when the data was produced by the previous
 // kernel on another XCD) is cut to four: {control word, candidates, own x_B/basis rows} -> {column extent} ->
-// {column entries} -> {inverse columns}.  alpha_i, x_B,i and basis_i of the rows a thread owns stay in registers;
+// {column entries} -> {inverse columns}, and to two with inline candidate columns ({first phase} -> {the 8 gathers of four rows at a
+// time}).  The first phase is ONE group of loads in the compiled code too (tools/isa_round_trips.py, profiles/round_trips_isa.txt).  alpha_i, x_B,i and basis_i of the rows a thread owns stay in registers;
 // scalars are exchanged through LDS.
 // ---------------------------------------------------------------------------------------------------
 template <int RULE, int R>
@@ -2201,34 +2344,52 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
     const int tid = threadIdx.x;
     const int m = lp.m;
     // ---- round trip 1: everything that does not depend on q -----------------------------------------
+    kernel_args_ready(ctl, lp.xB, lp.basis, lp.alpha_in, lp.cand_j, lp.cand_key, lp.cand_cbar, lp.cand_len, lp.cand_rows, lp.cand_vals, m, n_price_blocks,
+                      n_alpha_slices);
+    // (rows past m load row 0 and are overwritten below: no branch around a load.  How many trips the compiled kernel makes is
+    //  checked with tools/isa_round_trips.py, profiles/round_trips_isa.txt)
+    double xb[R];
+    int bas[R];
+    double ain[R];
+    const bool preselected = n_alpha_slices > 0;
+    const double* ain_from = preselected ? lp.alpha_in : lp.xB;  // (alpha_in exists in the dense pipeline only)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = tid + r * K2F_THREADS;
+        const int ic = i < m ? i : 0;
+        xb[r] = lp.xB[ic];
+        bas[r] = lp.basis[ic];
+        ain[r] = ain_from[ic];
+    }
+    double ckey = 0.0;
+    unsigned long long crank = RANK_NONE;
+    // NOT conditional on forced_q (a value still in flight): that would put these loads a round trip later
+    K2fCandidateLoads cand;
+    k2f_candidates_issue(lp, n_price_blocks, cand);
+    RELP_LOADS_PINNED();
+    // the control block's words LAST: loads come back in order, so whatever waits for one of them finds the whole group issued
     const int status = ctl->status;
     const long long iters = ctl->iters;
     const long long budget = ctl->budget;
     const int forced_q = ctl->forced_q;
     const int forced_p = ctl->forced_p;
     const double minus_obj = ctl->minus_obj;
-    double xb[R];
-    int bas[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int i = tid + r * K2F_THREADS;
-        xb[r] = i < m ? lp.xB[i] : 0.0;
-        bas[r] = i < m ? lp.basis[i] : 0x7fffffff;
-    }
-    double ckey = 0.0;
-    unsigned long long crank = RANK_NONE;
-    const bool preselected = n_alpha_slices > 0;
     // preselected: q, its reduced cost and the whole column alpha_in were left by earlier kernels -- requested in this round trip too
-    const int q_pre = preselected ? ctl->q : -1;
-    const double cbar_pre = preselected ? ctl->cbar_q : 0.0;
-    double ain[R];
+    // (loaded either way and dropped by a select below: a branch here, even a uniform one, splits the group of loads)
+    const int q_loaded = ctl->q;
+    const double cbar_loaded = ctl->cbar_q;
+    RELP_LOADS_ISSUED();
+    const int q_pre = preselected ? q_loaded : -1;
+    const double cbar_pre = preselected ? cbar_loaded : 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int i = tid + r * K2F_THREADS;
-        ain[r] = (preselected && i < m) ? lp.alpha_in[i] : 0.0;
+        if (tid + r * K2F_THREADS >= m) {
+            xb[r] = 0.0;
+            bas[r] = 0x7fffffff;
+        }
+        if (!preselected || tid + r * K2F_THREADS >= m) ain[r] = 0.0;
     }
-    // NOT conditional on forced_q (a value still in flight): that would put these loads a round trip later
-    if (!preselected) k2f_candidates<RULE>(lp, n_price_blocks, sm, ckey, crank);
+    if (!preselected) k2f_candidates_fold<RULE>(lp, n_price_blocks, sm, cand, ckey, crank);
     const bool inline_column = forced_q < 0 && !preselected && n_price_blocks <= K2F_INLINE_BLOCKS;
     if (status != ST_RUNNING) return;
     STAMP(0);
@@ -2441,6 +2602,10 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
 // The front half IS that of ftran_ratio_fast_kernel<RULE, R> (the k2f_* templates above) and the column update keeps the arithmetic
 // of update_kernel<true> in the same order: the pivot sequence and every number are bit-identical with the three-kernel pivot
 // (tests/test_gpu_fused.py).
+// Round trips, as compiled (tools/isa_round_trips.py, profiles/round_trips_isa.txt -- the source order alone does not bind the
+// compiler): ONE for the first phase (x_B, basis, candidate slot, inline entries, control block: a single group of loads, then the
+// first wait), ONE for the wave's own column, -pi_j and the 8 R gathers of the FTRAN (the own column goes out ahead of the entering
+// column's reduction), plus the CSC path's two for a column longer than its slot.  No scratch: Ctl is handed on field by field.
 // Measured and dropped: one wave per workgroup with all rows in registers (a wave cannot keep enough loads in
 // flight: 25 us), wave-local decisions out of LDS (16 rows and 32 divisions per lane: 14 us), and ONE launch per pivot with
 // every workgroup pricing all columns (360 KB of conflicting LDS gathers per workgroup: 21 us).
@@ -2468,22 +2633,38 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
     const int m = lp.m, ld = lp.ld;
     const bool writer = blockIdx.x == 0;
     // ---- round trip 1: everything that does not depend on q -----------------------------------------
-    const int status = ctl->status;
-    const long long iters = ctl->iters;
-    const long long budget = ctl->budget;
-    const double minus_obj = ctl->minus_obj;
-    const int t_buf = ctl->t_buf;
+    kernel_args_ready(ctl, in.xB, in.basis, lp.cand_j, lp.cand_key, lp.cand_cbar, lp.cand_len, lp.cand_rows, lp.cand_vals, m, n_price_blocks);
+    // (rows past m load row 0 and are overwritten below: no branch around a load.  The trips of the compiled kernel are counted with
+    //  tools/isa_round_trips.py, profiles/round_trips_isa.txt)
     double xb[R];
     int bas[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int i = tid + r * KF_THREADS;
-        xb[r] = i < m ? in.xB[i] : 0.0;
-        bas[r] = i < m ? in.basis[i] : 0x7fffffff;
+        const int ic = i < m ? i : 0;
+        xb[r] = in.xB[ic];
+        bas[r] = in.basis[ic];
     }
     double ckey = 0.0;
     unsigned long long crank = RANK_NONE;
-    k2f_candidates<RULE>(lp, n_price_blocks, sm, ckey, crank);
+    K2fCandidateLoads cand;
+    k2f_candidates_issue(lp, n_price_blocks, cand);
+    RELP_LOADS_PINNED();
+    // the control block's words LAST: loads come back in order, so whatever waits for one of them finds the whole group issued
+    const int status = ctl->status;
+    const long long iters = ctl->iters;
+    const long long budget = ctl->budget;
+    const double minus_obj = ctl->minus_obj;
+    const int t_buf = ctl->t_buf;
+    RELP_LOADS_ISSUED();
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (tid + r * KF_THREADS >= m) {
+            xb[r] = 0.0;
+            bas[r] = 0x7fffffff;
+        }
+    }
+    k2f_candidates_fold<RULE>(lp, n_price_blocks, sm, cand, ckey, crank);
     const bool inline_column = n_price_blocks <= K2F_INLINE_BLOCKS;
     // workgroup 0 hands the state on when no pivot is made: x_B and the basis unchanged, the control block edited by `verdict`
     auto hand_on = [&](auto verdict) {
@@ -2497,11 +2678,12 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
             }
         }
         if (tid == 0) {
-            Ctl c = *ctl;  // (read again by one thread: preloading the whole block in round trip 1 was measured slower)
+            Ctl c;  // (read again by one thread: preloading the whole block in round trip 1 was measured slower)
+            ctl_copy(c, *ctl);
             verdict(c);
             c.forced_q = -1;
             c.forced_p = -1;
-            *out.ctl = c;
+            ctl_copy(*out.ctl, c);
         }
     };
     if (status != ST_RUNNING) {
@@ -2513,16 +2695,9 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
         hand_on([](Ctl& c) { ctl_budget(c); });
         return;
     }
-    // ---- entering column --------------------------------------------------------------------------
-    double cbar_q;
-    int winner_block = 0;
-    const int q = k2f_entering<RULE>(ckey, crank, sm, cbar_q, winner_block);
-    if (q < 0) {
-        hand_on([](Ctl& c) { ctl_no_entering(c, 0); });
-        return;
-    }
-    FSTAMP(1);
-    // ---- this wave's column of the inverse: issued together with the FTRAN loads (both only needed round trip 1) ---
+    // ---- this wave's column of the inverse and its -pi: they depend on t_buf only, so they go out here, ahead of the entering
+    //      column's reduction, and are in flight with the FTRAN loads.  Clamped addresses; what a wave without a column or a lane
+    //      past m loaded is dropped below, behind the FTRAN loads.
     const int j_own = blockIdx.x * KF_NW + wave;
     const bool own = j_own < m;
     const double* t_old = (t_buf ? lp.Binv2 : lp.Binv);
@@ -2532,9 +2707,19 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
 #pragma unroll
     for (int u = 0; u < KF_U; ++u) {
         const int i = lane + u * WAVE;
-        o[u] = (own && i < m) ? c_old[i] : 0.0;
+        o[u] = c_old[i < m ? i : 0];
     }
-    const double pi_old = (own && lane == LAST) ? lp.minus_pi[j_own] : 0.0;
+    double pi_old = lp.minus_pi[own ? j_own : 0];
+    RELP_LOADS_PINNED();
+    // ---- entering column --------------------------------------------------------------------------
+    double cbar_q;
+    int winner_block = 0;
+    const int q = k2f_entering<RULE>(ckey, crank, sm, cbar_q, winner_block);
+    if (q < 0) {
+        hand_on([](Ctl& c) { ctl_no_entering(c, 0); });
+        return;
+    }
+    FSTAMP(1);
     // ---- FTRAN -------------------------------------------------------------------------------------
     double al[R];
 #pragma unroll
@@ -2546,6 +2731,11 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
         ca = lp.col_start[q];
         cb_ = lp.col_start[q + 1];
     }
+#pragma unroll
+    for (int u = 0; u < KF_U; ++u) {
+        if (!own || lane + u * WAVE >= m) o[u] = 0.0;
+    }
+    if (!own || lane != LAST) pi_old = 0.0;
     k2f_ftran_csc<R>(lp, t_old, sm, ca, cb_, al);
     FSTAMP(2);
     // ---- gamma_q and Harris pass 1 (never bounded here); alpha into LDS for the column updates ---------------------
@@ -2583,10 +2773,11 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
             }
         }
         if (tid == 0) {
-            Ctl c = *ctl;  // (read again by one thread: preloading the whole block in round trip 1 was measured slower)
+            Ctl c;  // (read again by one thread: preloading the whole block in round trip 1 was measured slower)
+            ctl_copy(c, *ctl);
             ctl_basis_change(lp, c, false, q, p, leaving, 0, step, INFINITY, cbar_q, alpha_pq, gamma_q, 0, minus_obj, iters);
             c.t_buf = t_buf ^ 1;
-            *out.ctl = c;
+            ctl_copy(*out.ctl, c);
         }
     }
     FSTAMP(5);
@@ -2599,10 +2790,14 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
     const double r_j = __shfl(o_p, lane_p) / alpha_pq;  // row p of the new inverse
     double* c_new = t_new + (size_t)j_own * ld;
     double w_j = 0.0;
+    double a_u[KF_U];  // the lane's rows of alpha, all read before the first store
+#pragma unroll
+    for (int u = 0; u < KF_U; ++u) a_u[u] = s_alpha[lane + u * WAVE];
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < KF_U; ++u) {
         const int i = lane + u * WAVE;
-        const double a = s_alpha[i];
+        const double a = a_u[u];
         w_j += a * o[u];
         if (i < m) c_new[i] = (i == p) ? r_j : ((a != 0.0) ? o[u] - a * r_j : o[u]);
     }

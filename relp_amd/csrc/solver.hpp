@@ -103,6 +103,21 @@ struct Ctl {
     int rho_buf;       // generated columns: which half of DeviceLP::rho_bits the writers of rho_p mark (flipped by the kernel that decides a pivot)
 };
 
+// The control block field by field: a kernel that reads it, edits it and writes it elsewhere keeps it in registers this way (the
+// struct assignment `Ctl c = *src` is made of overlapping 16-byte pieces that the compiler keeps on the stack: 176 bytes of scratch
+// per lane of the fused pivot kernel).
+#if defined(__HIPCC__)
+#define RELP_CTL_FIELDS(X) X(status) X(q) X(p) X(leaving) X(pending) X(forced_q) X(forced_p) X(last_selected) X(iters) X(budget) X(cbar_q) \
+    X(alpha_pq) X(gamma_q) X(xp) X(minus_obj) X(residual) X(scan_value) X(scan_column) X(nz_count) X(eta_count) X(touched_count) \
+    X(flip_cost) X(bound_flips) X(k2_forced) X(t_buf) X(eta_version) X(eta_new) X(rho_buf)
+__device__ __forceinline__ void ctl_copy(Ctl& dst, const Ctl& src) {
+    static_assert(sizeof(Ctl) == 8 * 4 + 2 * 8 + 7 * 8 + 4 * 4 + 2 * 8 + 5 * 4 + 4, "a field of Ctl is missing from RELP_CTL_FIELDS");
+#define RELP_CTL_COPY(f) dst.f = src.f;
+    RELP_CTL_FIELDS(RELP_CTL_COPY)
+#undef RELP_CTL_COPY
+}
+#endif
+
 enum : int { ST_RUNNING = 0, ST_NO_ENTERING = 1, ST_UNBOUNDED = 2, ST_BUDGET = 3, ST_REFACTOR = 4, ST_REFACTOR_FAILED = 5 };  // 4: LU carry, refactorise now;
 // 5: the refactorisation kernels gave up (a capacity, a row too long for the eliminating wave): the pivots behind them are no-ops, the host factorises
 

@@ -14,6 +14,18 @@ namespace relp {
 #define STAMP_INIT do {} while (0)
 #endif
 
+// End of a group of loads that make ONE memory round trip: no memory access moves across this line in either direction, in the
+// optimiser (the empty statement may touch memory as far as it knows) or in the instruction scheduler.  It takes no operand, so it
+// waits for nothing itself: the first wait comes where a loaded value is first used, and that use is below the whole group.
+// The kernel arguments a group of loads needs, fetched and waited for BEFORE the group: scalar loads come back out of order, so a
+// wait for an argument fetched in the middle of the group would wait for the control block's words as well.
+template <class A>
+__device__ __forceinline__ void kernel_arg_ready(A a) { asm volatile("" ::"s"(a)); }
+template <class... A>
+__device__ __forceinline__ void kernel_args_ready(A... a) { (kernel_arg_ready(a), ...); }
+#define RELP_LOADS_PINNED() asm volatile("" ::: "memory")  // the optimiser's half alone: inside a group, keeps its loads where they are
+#define RELP_LOADS_ISSUED() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+
 // ---------------------------------------------------------------------------------------------------
 // reductions: wave64 DPP (data-parallel primitives) moves instead of ds_bpermute shuffles.  A __shfl_down chain is
 // six DEPENDENT LDS-crossbar round trips per value (measured: 3-4 k cycles per struct arg-max); the DPP sequence
