@@ -2136,7 +2136,8 @@ __device__ __forceinline__ void k2f_candidates_fold(const DeviceLP& lp, int n_pr
 // The winner among them: q (-1: none), its reduced cost and the pricing workgroup that offered it.
 template <int RULE>
 __device__ __forceinline__ int k2f_entering(double ckey, unsigned long long crank, K2fShared& sm, double& cbar_q, int& winner_block) {
-    const int q = entering_winner<RULE>(ckey, crank, sm.akey, sm.arank, winner_block);
+    // (no opening barrier: this is the first use of sm.akey / sm.arank in both kernels -- no thread can be reading them)
+    const int q = entering_winner<RULE, true>(ckey, crank, sm.akey, sm.arank, winner_block);
     cbar_q = q >= 0 ? sm.cbarv[winner_block] : 0.0;
     return q;
 }
@@ -2270,7 +2271,16 @@ __device__ __forceinline__ void k2f_pass1(const DeviceLP& lp, bool bounded, cons
         if (row.eligible) theta = fmin(theta, harris_pass1(row.room, slack, a));
     }
 }
-// gamma_q = 1 + |alpha_q|^2 (pivot_rule.rs:258) and theta_max in ONE combined block reduction.
+// gamma_q = 1 + |alpha_q|^2 (pivot_rule.rs:258) and theta_max in ONE combined block reduction: the wave partials go to LDS, ONE
+// barrier, and every thread folds the eight of them itself (as block_argbest scans its slots).
+// The sum keeps the bits of the second ladder it replaces -- wave_sum over s0..s7 in lanes 0..7 of wave 0 and +0.0 in lanes 8..63.
+// Step by step through wave_ladder: quad_perm [1,0,3,2] leaves s0+s1 in lanes 0-1, s2+s3 in 2-3, s4+s5 in 4-5, s6+s7 in 6-7 (a + b
+// and b + a are the same double); quad_perm [2,3,0,1] leaves A = (s0+s1)+(s2+s3) in lanes 0-3 and B = (s4+s5)+(s6+s7) in 4-7;
+// row_ror:4 and row_ror:8 bring A and B together once, in the order A + B or B + A, every other operand being +0.0; the two row
+// broadcasts carry lane 15's A + B to lane 63 through rows that hold +0.0.  The partials are sums of squares, so they are +0.0 or
+// positive (never -0.0), and x + (+0.0) is x exactly: lane 63 held (A + B) bit for bit.  The minimum has no rounding to keep.
+// The slots' next writer is the next launch (or, for red / red2, nobody): no barrier is needed behind the fold.
+static_assert(K2F_NW == 8, "k2f_reduce spells out the ladder's tree over eight wave partials");
 __device__ __forceinline__ void k2f_reduce(K2fShared& sm, double sumsq, double theta, double& gamma_q, double& theta_max) {
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     sumsq = wave_sum(sumsq);
@@ -2280,19 +2290,11 @@ __device__ __forceinline__ void k2f_reduce(K2fShared& sm, double sumsq, double t
         sm.red2[wave] = theta;
     }
     __syncthreads();
-    if (wave == 0) {
-        double t1 = lane < K2F_NW ? sm.red[lane] : 0.0;
-        double t2 = lane < K2F_NW ? sm.red2[lane] : INFINITY;
-        t1 = wave_sum(t1);
-        t2 = wave_min(t2);
-        if (lane == LAST) {
-            sm.red[K2F_NW] = t1;
-            sm.red2[K2F_NW] = t2;
-        }
-    }
-    __syncthreads();
-    gamma_q = 1.0 + sm.red[K2F_NW];
-    theta_max = sm.red2[K2F_NW];
+    const double a = (sm.red[0] + sm.red[1]) + (sm.red[2] + sm.red[3]);
+    const double b = (sm.red[4] + sm.red[5]) + (sm.red[6] + sm.red[7]);
+    gamma_q = 1.0 + (a + b);
+    theta_max = fmin(fmin(fmin(sm.red2[0], sm.red2[1]), fmin(sm.red2[2], sm.red2[3])),
+                     fmin(fmin(sm.red2[4], sm.red2[5]), fmin(sm.red2[6], sm.red2[7])));
 }
 // Harris pass 2: the pivot row, or -1.
 template <int R>
@@ -2306,7 +2308,9 @@ __device__ __forceinline__ int k2f_pass2(bool textbook, const double (&al)[R], c
         if (eligible[r] && harris_accepts(room[r], mag, theta_max))
             keep_better(harris_key(textbook, mag), leaving_rank(bas[r], threadIdx.x + r * K2F_THREADS), hkey, hrank);
     }
-    block_argbest(hkey, hrank, sm.akey, sm.arank);
+    // (no opening barrier: the slots' previous readers are the scan of k2f_entering, and the barrier of k2f_reduce, which every
+    //  caller runs between the two, lies behind that scan)
+    block_argbest<true>(hkey, hrank, sm.akey, sm.arank);
     return leaving_row(hrank);
 }
 // The pivot row's scalars from the registers of its owner to every thread (sm.bcast[1..3], sm.ibcast[0]).
@@ -2588,24 +2592,34 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
 // ---------------------------------------------------------------------------------------------------
 // K23: ratio test AND inverse update in ONE launch (m <= 2048, explicit carry, no implicit bounds, no forced pivot): two
 // kernels per pivot instead of three.  Every workgroup repeats the whole of K2 -- entering column, FTRAN, ratio test: 60 KB
-// of L2 reads and three block reductions, identical bits in every workgroup -- and then its eight waves update one column of
-// the inverse each, so the kernel boundary between K2 and K3 (a cold start on data written by another XCD, 1.5-2 us) and
-// K3's own first round trip disappear.  Workgroups are not synchronised, so nothing a workgroup reads at its start may be
-// written by another one before its end:
+// of L2 reads and three block reductions, identical bits in every workgroup -- and then the eight waves of a column-owning
+// workgroup update one column of the inverse each, so the kernel boundary between K2 and K3 (a cold start on data written by
+// another XCD, 1.5-2 us) and K3's own first round trip disappear.
+// Who writes what (grid: ceil(m / KF_NW) + 1 workgroups):
+//   * workgroup 0 is the WRITER and owns no column.  Behind the shared front half it takes the pivot row's scalars through LDS,
+//     decides the step and stores lp.alpha, out.xB, out.basis, the column positions and the control block; it alone hands the state
+//     on when no pivot is made (status not running, budget used up, no entering column, unbounded); then it returns;
+//   * workgroup b >= 1 owns the columns (b - 1) * KF_NW + wave.  It goes from pass 2 straight to them -- alpha_pq = s_alpha[p], no
+//     broadcast, no step decision -- and writes its column of T_new, w_j, rho_j and -pi_j, nothing else.
+//   A kernel ends with its last wave: the bookkeeping (a dependent re-read of the control block by one thread) runs beside the column
+//   updates, not in front of one of them.
+// Workgroups are not synchronised, so nothing a workgroup reads at its start may be written by another one before its end:
 //   * x_B, the basis and the control block exist twice (`lp.state[2]`); pivot k of a batch reads copy k & 1 (the pricing pass
-//     before it too) and workgroup 0 writes copy (k + 1) & 1 -- also when nothing happens (status != running: copied through);
+//     before it too) and the writer writes copy (k + 1) & 1 -- also when nothing happens (status != running: copied through);
 //   * the inverse is updated OUT OF PLACE (T_old = buffer ctl->t_buf, T_new = the other one; every entry is written);
-//   * -pi_j, rho_j, w_j are touched by the owner of column j only; column positions are written by workgroup 0 and read by the
+//   * -pi_j, rho_j, w_j are touched by the owner of column j only; column positions are written by the writer and read by the
 //     next pricing pass;
 //   * `begin_batch_kernel` / `commit_kernel` move the canonical arrays into copy 0 and the last copy (and the inverse) back, so
 //     everything outside a batch of pivots sees the canonical arrays only.
 // The front half IS that of ftran_ratio_fast_kernel<RULE, R> (the k2f_* templates above) and the column update keeps the arithmetic
 // of update_kernel<true> in the same order: the pivot sequence and every number are bit-identical with the three-kernel pivot
 // (tests/test_gpu_fused.py).
-// Round trips, as compiled (tools/isa_round_trips.py, profiles/round_trips_isa.txt -- the source order alone does not bind the
+// Round trips, as compiled (tools/isa_round_trips.py, profiles/pivot_tail_isa.txt -- the source order alone does not bind the
 // compiler): ONE for the first phase (x_B, basis, candidate slot, inline entries, control block: a single group of loads, then the
 // first wait), ONE for the wave's own column, -pi_j and the 8 R gathers of the FTRAN (the own column goes out ahead of the entering
-// column's reduction), plus the CSC path's two for a column longer than its slot.  No scratch: Ctl is handed on field by field.
+// column's reduction; the writer's waves load column 0 and drop it, so the group is the same in every workgroup), plus the CSC
+// path's two for a column longer than its slot.  Barriers on a pivot's path: the entering column's arg-max (one), k2f_reduce (one),
+// pass 2 (one); the writer's broadcast adds one.  No scratch: Ctl is handed on field by field.
 // Measured and dropped: one wave per workgroup with all rows in registers (a wave cannot keep enough loads in
 // flight: 25 us), wave-local decisions out of LDS (16 rows and 32 divisions per lane: 14 us), and ONE launch per pivot with
 // every workgroup pricing all columns (360 KB of conflicting LDS gathers per workgroup: 21 us).
@@ -2626,7 +2640,8 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
 #ifdef RELP_STAMPS
     unsigned long long t_prev__ = clock64();
     if (tid == 0 && blockIdx.x == 0) lp.dbg[63] += 1;
-#define FSTAMP(k) do { if (tid == 0 && blockIdx.x == 0) { unsigned long long t__ = clock64(); lp.dbg[(k)] += t__ - t_prev__; t_prev__ = t__; } } while (0)
+    // the writer (workgroup 0) in dbg[0..], the first column-owning workgroup in dbg[16..] (tools/stamps_fused.py)
+#define FSTAMP(k) do { if (tid == 0 && blockIdx.x <= 1) { unsigned long long t__ = clock64(); lp.dbg[(k) + 16 * blockIdx.x] += t__ - t_prev__; t_prev__ = t__; } } while (0)
 #else
 #define FSTAMP(k) do {} while (0)
 #endif
@@ -2666,7 +2681,7 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
     }
     k2f_candidates_fold<RULE>(lp, n_price_blocks, sm, cand, ckey, crank);
     const bool inline_column = n_price_blocks <= K2F_INLINE_BLOCKS;
-    // workgroup 0 hands the state on when no pivot is made: x_B and the basis unchanged, the control block edited by `verdict`
+    // the writer hands the state on when no pivot is made: x_B and the basis unchanged, the control block edited by `verdict`
     auto hand_on = [&](auto verdict) {
         if (!writer) return;
 #pragma unroll
@@ -2696,10 +2711,10 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
         return;
     }
     // ---- this wave's column of the inverse and its -pi: they depend on t_buf only, so they go out here, ahead of the entering
-    //      column's reduction, and are in flight with the FTRAN loads.  Clamped addresses; what a wave without a column or a lane
-    //      past m loaded is dropped below, behind the FTRAN loads.
-    const int j_own = blockIdx.x * KF_NW + wave;
-    const bool own = j_own < m;
+    //      column's reduction, and are in flight with the FTRAN loads.  Clamped addresses; what a wave without a column (the writer's
+    //      eight among them: they load column 0) or a lane past m loaded is dropped below, behind the FTRAN loads.
+    const int j_own = ((int)blockIdx.x - 1) * KF_NW + wave;
+    const bool own = !writer && j_own < m;
     const double* t_old = (t_buf ? lp.Binv2 : lp.Binv);
     double* t_new = (t_buf ? lp.Binv : lp.Binv2);
     const double* c_old = t_old + (size_t)(own ? j_own : 0) * ld;
@@ -2756,13 +2771,14 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
         return;
     }
     FSTAMP(4);
-    k2f_broadcast_row<R>(p, al, xb, room, bas, sm);
-    const double alpha_pq = sm.bcast[1];
-    const int leaving = sm.ibcast[0];
-    const Step step = step_decision(false, false, p, alpha_pq, sm.bcast[2], sm.bcast[3], INFINITY);
-    const double xp = step.xp;
-    // ---- workgroup 0: x_B update (carry/mod.rs:295-325), basis bookkeeping, control block -----------------------
+    // ---- the writer: the pivot row's scalars, the step, x_B update (carry/mod.rs:295-325), basis bookkeeping, control block ------
     if (writer) {
+        k2f_broadcast_row<R>(p, al, xb, room, bas, sm);
+        const double alpha_pq = sm.bcast[1];
+        const int leaving = sm.ibcast[0];
+        const Step step = step_decision(false, false, p, alpha_pq, sm.bcast[2], sm.bcast[3], INFINITY);
+        const double xp = step.xp;
+        FSTAMP(5);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int i = tid + r * KF_THREADS;
@@ -2779,10 +2795,18 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
             c.t_buf = t_buf ^ 1;
             ctl_copy(*out.ctl, c);
         }
+        FSTAMP(6);
+        return;
     }
-    FSTAMP(5);
     // ---- this wave's column: rho_p[j], w_j, -pi_j and the rank-one update, written to the other buffer ------------
+    // Straight from pass 2: alpha_pq is the double the writer's broadcast carries -- s_alpha was stored ahead of k2f_reduce, whose
+    // barrier made it visible -- and x_B,p, the room, the leaving column and the step are the writer's business alone.
     if (!own) return;
+    const double alpha_pq = s_alpha[p];
+    // (the lane number anew, opaque to the optimiser: the KF_U row numbers lane + u * WAVE are formed again here, an add each,
+    //  and do not occupy KF_U registers from the own-column loads to this point: 142 VGPRs instead of 127 at R = 2)
+    int lane_again = lane;
+    asm volatile("" : "+v"(lane_again));
     const int u_p = p >> 6, lane_p = p & (WAVE - 1);
     double o_p = 0.0;
 #pragma unroll
@@ -2792,11 +2816,11 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
     double w_j = 0.0;
     double a_u[KF_U];  // the lane's rows of alpha, all read before the first store
 #pragma unroll
-    for (int u = 0; u < KF_U; ++u) a_u[u] = s_alpha[lane + u * WAVE];
+    for (int u = 0; u < KF_U; ++u) a_u[u] = s_alpha[lane_again + u * WAVE];
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < KF_U; ++u) {
-        const int i = lane + u * WAVE;
+        const int i = lane_again + u * WAVE;
         const double a = a_u[u];
         w_j += a * o[u];
         if (i < m) c_new[i] = (i == p) ? r_j : ((a != 0.0) ? o[u] - a * r_j : o[u]);
@@ -2807,7 +2831,7 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
         lp.rho[j_own] = r_j;
         lp.minus_pi[j_own] = pi_old - cbar_q * r_j;
     }
-    FSTAMP(6);
+    FSTAMP(7);
 }
 #undef FSTAMP
 // Batch start in the fused mode: the budget, and copy 0 of the state made equal to the canonical arrays.
@@ -3631,7 +3655,7 @@ void launch_ftran_ratio(const DeviceLP& d, const KernelPath& path, int rule, dou
 template <int RULE>
 static void launch_pivot_fused_rule(const DeviceLP& d, const KernelPath& path, int parity, double tol_pivot, double harris_delta,
                                     int skip_artificial_rows, hipStream_t s) {
-    const dim3 grid((d.m + KF_NW - 1) / KF_NW);
+    const dim3 grid((d.m + KF_NW - 1) / KF_NW + 1);  // the writer, then a workgroup per KF_NW columns of the inverse
     const int n_price_blocks = path.price_blocks;
     switch (path.fused_rows) {
     case 2: RELP_LAUNCH(1, (pivot_fused_kernel<RULE, 2>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows); break;

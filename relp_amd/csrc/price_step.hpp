@@ -107,10 +107,11 @@ __device__ __forceinline__ void fold_candidates(const int* cand_j, const double*
                                                 double& key, unsigned long long& rank) {
     for (int b = tid; b < n_blocks; b += n_threads) offer_entering<RULE>(cand_key[b], cand_j[b], b, key, rank);
 }
-// s_key / s_rank: one slot per wave (block_argbest).  Returns q for every thread, -1: none; `block`: the slot that offered it.
-template <int RULE>
+// s_key / s_rank: one slot per wave (block_argbest, whose SLOTS_FREE this passes on).  Returns q for every thread, -1: none; `block`:
+// the slot that offered it.
+template <int RULE, bool SLOTS_FREE = false>
 __device__ __forceinline__ int entering_winner(double key, unsigned long long rank, double* s_key, unsigned long long* s_rank, int& block) {
-    block_argbest(key, rank, s_key, s_rank);
+    block_argbest<SLOTS_FREE>(key, rank, s_key, s_rank);
     if (rank == RANK_NONE) return -1;
     block = entering_block(rank);
     return entering_column<RULE>(rank);

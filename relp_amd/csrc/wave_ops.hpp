@@ -130,6 +130,10 @@ __device__ __forceinline__ unsigned long long lane63_u64(unsigned long long v) {
 }
 constexpr unsigned long long RANK_NONE = ~0ull;
 // s_key / s_rank: one slot per wave.  Returns the winner in (key, rank) for every thread; rank == RANK_NONE: none.
+// SLOTS_FREE: the caller vouches that no thread of the workgroup can still be reading the slots from an earlier call -- there was
+// none, or a barrier of the caller's own lies between that call's scan and this one -- and the opening barrier is left out.  Each such
+// call names the barrier it relies on; everything else keeps the guarded form.
+template <bool SLOTS_FREE = false>
 __device__ __forceinline__ void block_argbest(double& key, unsigned long long& rank, double* s_key, unsigned long long* s_rank) {
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int nwaves = (blockDim.x + WAVE - 1) / WAVE;
@@ -137,7 +141,7 @@ __device__ __forceinline__ void block_argbest(double& key, unsigned long long& r
     const double wmax = lane63_f64(wave_max(k0));
     const unsigned long long tie = (rank != RANK_NONE && k0 == wmax) ? rank : RANK_NONE;
     const unsigned long long wmin = lane63_u64(wave_min_u64(tie));
-    __syncthreads();  // previous users of the slots are done
+    if (!SLOTS_FREE) __syncthreads();  // previous users of the slots are done
     if (lane == 0) {
         s_key[wave] = wmax;
         s_rank[wave] = wmin;
