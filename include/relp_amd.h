@@ -467,7 +467,8 @@ int32_t relp_get_basis(const relp_handle* handle, int32_t* basis);
 int32_t relp_set_basis(relp_handle* handle, const int32_t* basis_columns);
 /* Phase-one start: `Tableau::<_, Partially<_>>::new` (kind/artificial/partially.rs:125-205). */
 int32_t relp_begin_phase_one(relp_handle* handle);
-/* `Tableau::from_artificial` hand-over (kind/non_artificial.rs:99-120, carry/mod.rs:499-525). */
+/* `Tableau::from_artificial` hand-over (kind/non_artificial.rs:99-120, carry/mod.rs:499-525).  Needs a basis: RELP_ERR_STATE unless
+ * relp_begin_phase_one or relp_set_basis has run on this LP (an LP without artificials starts phase two in relp_begin_phase_one). */
 int32_t relp_begin_phase_two(relp_handle* handle);
 /* `BasisInverse::left_multiply_by_basis_inverse` (carry/mod.rs:98-107; lower_upper/mod.rs:180-210): FTRAN. */
 int32_t relp_bi_ftran(relp_handle* handle, int32_t nnz, const int32_t* row_index, const double* value, double* out_m);

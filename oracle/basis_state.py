@@ -16,6 +16,10 @@ first, so the elimination runs on the Schur block of the other columns only.  Ea
 f64 arrays ``hi = float(q)``, ``lo = float(q - hi)``; products with the columns of ``A`` are then formed in ``np.longdouble``
 from ``hi + lo``.  Where ``longdouble`` is no wider than f64 (``EXTENDED`` false) the per-column quantities are exact integer dot
 products instead, on the sample of columns that ``columns_to_check`` returns.
+
+``BasisState`` holds dense (m, m) and (m, n) arrays: fine for the dense pipeline's few hundred rows.  ``SparseBasisState`` yields the
+same numbers from the structure of that elimination alone -- the k x k Schur block and the sparse rows of the non-unit basic columns
+-- for sparse LPs of thousands of rows (tests/test_gpu_sparse_state.py: 8193 rows, k = 100, well under a second and 22 MB).
 """
 from fractions import Fraction
 from math import lcm
@@ -294,6 +298,275 @@ class BasisState:
             for i in np.flatnonzero(self.num[int(r), :] != 0):
                 total[i] += int(v) * Fraction(self.num[int(r), i], self.den[int(r)])
         return long_double(*zip(*[split_fraction(t) for t in total]))
+
+
+class SparseBasisState(BasisState):
+    """The same state for a sparse LP of thousands of rows, held in the structure ``_invert`` finds and never as an (m, m) or (m, n)
+    array.  With ``B' = B diag(scale)`` (integer; single-entry columns become unit vectors), ``unit`` the positions of those columns,
+    ``other`` the k remaining ones, ``rest`` the k rows no unit column takes, ``S = B'[rest, other]`` and ``U = B'[unit rows, other]``:
+
+        x = B'^-1 y:   x_other = S^-1 y_rest,                         x_u = y_row(u) - U[u, :] x_other
+        z = w' B'^-1:  z_rest = (w_other - w_unit' U) S^-1,           z_row(u) = w_u
+
+    so a row of the inverse has entries in ``rest`` and, for a unit position, at its own row.  Stored: ``S^-1 = block / det`` in Python
+    integers and as ``longdouble``, ``U`` as coordinate lists, the scales, and all n columns in compressed form.  The per-column
+    quantities cost O(k nnz_j + nnz(U)) each.  Index spaces, ``den``, ``x_exact``, ``objective_exact``, ``reduced_cost_exact``,
+    ``alpha_exact`` and ``gamma_exact`` are those of ``BasisState``; ``num`` is read a row at a time (``row_exact``)."""
+
+    # ---- B^-1 --------------------------------------------------------------------------------------
+    def _invert(self):
+        m = self.m
+        columns = [self.column(j) for j in self.basis]
+        scale = []
+        for entries in columns:
+            if not entries:
+                raise ZeroDivisionError("singular basis")
+            scale.append(1 / entries[0][1] if len(entries) == 1 else Fraction(lcm(*[v.denominator for _, v in entries])))
+        unit = [k for k in range(m) if len(columns[k]) == 1]
+        unit_row = [columns[k][0][0] for k in unit]
+        if len(set(unit_row)) != len(unit_row):
+            raise ZeroDivisionError("singular basis")
+        other = [k for k in range(m) if len(columns[k]) != 1]
+        taken = set(unit_row)
+        rest = [i for i in range(m) if i not in taken]
+        k = len(other)
+        rest_at = -np.ones(m, dtype=np.int64)  # row -> its place in `rest`, or -1
+        rest_at[rest] = np.arange(k)
+        unit_at = -np.ones(m, dtype=np.int64)  # row -> the place in `unit` of the unit column that takes it, or -1
+        unit_at[unit_row] = np.arange(len(unit))
+        schur = np.zeros((k, k), dtype=object)
+        coo = []  # U: (place in `unit`, place in `other`, integer)
+        for a, position in enumerate(other):
+            for i, v in columns[position]:
+                value = int(v * scale[position])
+                if rest_at[i] >= 0:
+                    schur[rest_at[i], a] = value
+                else:
+                    coo.append((int(unit_at[i]), a, value))
+        self.block, self.det = fraction_free_inverse(schur)
+        self.k, self.scale = k, scale
+        self.unit, self.unit_row, self.other, self.rest = (np.array(v, dtype=np.int64) for v in (unit, unit_row, other, rest))
+        self.rest_at, self.unit_at = rest_at, unit_at
+        coo.sort()
+        self.coo_unit = np.array([c[0] for c in coo], dtype=np.int64)
+        self.coo_other = np.array([c[1] for c in coo], dtype=np.int64)
+        self.coo_value = [c[2] for c in coo]
+        self.coo_long = np.array(self.coo_value, dtype=np.longdouble)  # (entries of B times an lcm of a few denominators: far below 2^64)
+        self.coo_of_unit = {}  # place in `unit` -> [(place in `other`, integer)]
+        for u, a, value in coo:
+            self.coo_of_unit.setdefault(u, []).append((a, value))
+        self.place = np.zeros(m, dtype=np.int64)  # position -> its place in `unit` or in `other`
+        self.place[self.unit] = np.arange(len(unit))
+        self.place[self.other] = np.arange(k)
+        self.in_other = np.zeros(m, dtype=bool)
+        self.in_other[self.other] = True
+        self.den, self.factor = [], []  # row `position` of B^-1 = factor * (row of det B'^-1) / den, den > 0 as in BasisState
+        for position in range(m):
+            d = self.det * scale[position].denominator
+            self.den.append(abs(d))
+            self.factor.append(scale[position].numerator * (-1 if d < 0 else 1))
+        self.scale_long = long_double(*zip(*[split_fraction(s) for s in scale]))
+        hi, lo = np.zeros((k, k)), np.zeros((k, k))
+        for a in range(k):
+            for i in range(k):
+                hi[a, i], lo[a, i] = split(self.block[a, i], self.det)
+        self.block_long = long_double(hi, lo)
+        self._csc = None
+
+    def row_exact(self, position):
+        """Row ``position`` of ``B^-1`` as ``(columns, numerators)`` over ``den[position]``; zeros left out, columns ascending."""
+        position = int(position)
+        factor = self.factor[position]
+        if self.in_other[position]:
+            where, values = self.rest, self.block[self.place[position], :] * factor
+        else:
+            u = int(self.place[position])
+            entries = self.coo_of_unit.get(u)
+            if entries is None:
+                return np.array([self.unit_row[u]]), np.array([self.det * factor], dtype=object)
+            spread = np.zeros(self.k, dtype=object)
+            for a, value in entries:
+                spread = spread - value * self.block[a, :]
+            where = np.concatenate([self.rest, [self.unit_row[u]]])
+            values = np.concatenate([spread, np.array([self.det], dtype=object)]) * factor
+        keep = np.flatnonzero(values != 0)
+        order = keep[np.argsort(where[keep], kind="stable")]
+        return where[order], values[order]
+
+    def inverse_exact(self, k, i):
+        where, values = self.row_exact(k)
+        at = np.flatnonzero(where == i)
+        return Fraction(int(values[at[0]]), self.den[k]) if len(at) else Fraction(0)
+
+    def inverse_row(self, k):
+        hi, lo = np.zeros(self.m), np.zeros(self.m)
+        where, values = self.row_exact(k)
+        for i, value in zip(where, values):
+            hi[i], lo[i] = split(int(value), self.den[k])
+        return hi, lo
+
+    def inverse_long(self):
+        raise NotImplementedError("the structured state holds no (m, m) array: read inverse_row(k)")
+
+    def matrix(self):
+        raise NotImplementedError("the structured state holds no (m, n) array")
+
+    def rows_that_may_not_be_unit(self):
+        """Positions whose row of the inverse can have more than one entry (every other row is a multiple of a unit vector)."""
+        return np.array(sorted(set(self.other.tolist()) | {int(self.unit[u]) for u in self.coo_of_unit}), dtype=np.int64)
+
+    # ---- the two solves, exact --------------------------------------------------------------------------
+    def _solve(self, rows, values):
+        """``B^-1 y`` for the sparse ``y`` (Fractions) as ``{position: Fraction}``, zeros left out."""
+        common = lcm(*[v.denominator for v in values]) if len(values) else 1
+        ints = [int(v * common) for v in values]
+        den = self.det * common
+        product = np.zeros(self.k, dtype=object)  # det S^-1 y_rest
+        top = {}  # place in `unit` -> common y_row(u)
+        for i, v in zip(rows, ints):
+            if self.rest_at[i] >= 0:
+                product = product + v * self.block[:, self.rest_at[i]]
+            else:
+                top[int(self.unit_at[i])] = v * self.det
+        out = {}
+        for a in np.flatnonzero(product != 0):
+            out[int(self.other[a])] = self.scale[self.other[a]] * Fraction(int(product[a]), den)
+        if len(out):
+            for u, a, value in zip(self.coo_unit.tolist(), self.coo_other.tolist(), self.coo_value):
+                if product[a] != 0:
+                    top[u] = top.get(u, 0) - value * product[a]
+        for u, value in top.items():
+            if value != 0:
+                out[int(self.unit[u])] = self.scale[self.unit[u]] * Fraction(int(value), den)
+        return out
+
+    def _combine(self, weights):
+        """``w' B^-1`` for ``{position: Fraction}`` as ``{row: Fraction}``, zeros left out."""
+        scaled = {position: w * self.scale[position] for position, w in weights.items() if w != 0}
+        out = {}
+        reduced = [Fraction(0)] * self.k  # w_other - w_unit' U
+        by_unit = {}
+        for position, w in scaled.items():
+            if self.in_other[position]:
+                reduced[self.place[position]] += w
+            else:
+                by_unit[int(self.place[position])] = w
+                out[int(self.unit_row[self.place[position]])] = w
+        for u in by_unit.keys() & self.coo_of_unit.keys():
+            for a, value in self.coo_of_unit[u]:
+                reduced[a] -= by_unit[u] * value
+        common = lcm(*[v.denominator for v in reduced]) if self.k else 1
+        product = np.array([int(v * common) for v in reduced], dtype=object).dot(self.block) if self.k else []
+        for i, value in zip(self.rest.tolist(), product):
+            if value != 0:
+                out[i] = Fraction(int(value), self.det * common)
+        return out
+
+    def _vectors(self):
+        m = self.m
+        x = self._solve(range(m), self.b)
+        self.x_exact = [x.get(k, Fraction(0)) for k in range(m)]
+        self.x_hi, self.x_lo = (np.array(v) for v in zip(*[split_fraction(v) for v in self.x_exact]))
+        c_basic = [self.cost[j] for j in self.basis]
+        self.objective_exact = sum((c * v for c, v in zip(c_basic, self.x_exact) if c != 0), Fraction(0))
+        pi = self._combine({k: c for k, c in enumerate(c_basic)})
+        self.pi_exact = [pi.get(i, Fraction(0)) for i in range(m)]  # pi' = c_B' B^-1
+        self.pi_hi, self.pi_lo = (np.array(v) for v in zip(*[split_fraction(v) for v in self.pi_exact]))
+
+    # ---- per-column quantities, exact ---------------------------------------------------------------
+    def alpha_sparse_exact(self, j):
+        entries = self.column(j)
+        return self._solve([i for i, _ in entries], [v for _, v in entries])
+
+    def alpha_exact(self, j):
+        alpha = self.alpha_sparse_exact(j)
+        return [alpha.get(k, Fraction(0)) for k in range(self.m)]
+
+    def alpha_nnz(self, j):
+        """The number of non-zeros of ``B^-1 a_j``, counted on the exact values."""
+        return len(self.alpha_sparse_exact(j))
+
+    def gamma_exact(self, j):
+        return 1 + sum((v * v for v in self.alpha_sparse_exact(j).values()), Fraction(0))
+
+    def reduced_cost_exact(self, j):
+        return self.cost[j] - sum((self.pi_exact[i] * v for i, v in self.column(j)), Fraction(0))
+
+    # ---- per-column quantities in longdouble from hi + lo --------------------------------------------------
+    def compressed(self):
+        """All n columns: ``(start, rows, longdouble values)``."""
+        if self._csc is None:
+            start, rows, hi, lo = [0], [], [], []
+            for j in range(self.n):
+                for i, v in self.column(j):
+                    rows.append(i)
+                    h, l = split(v.numerator, v.denominator)
+                    hi.append(h)
+                    lo.append(l)
+                start.append(len(rows))
+            self._csc = np.array(start, dtype=np.int64), np.array(rows, dtype=np.int64), long_double(hi, lo)
+        return self._csc
+
+    def _alpha_long(self, rows, values):
+        """``(positions, longdouble values)`` of ``B^-1 a`` for a column given by rows and ``longdouble`` values."""
+        at = self.rest_at[rows]
+        inside = at >= 0
+        if not inside.any():  # every entry lies in a row that a unit column takes: alpha is the column, scaled
+            positions = self.unit[self.unit_at[rows]]
+            return positions, self.scale_long[positions] * values
+        out = np.zeros(self.m, dtype=np.longdouble)
+        solved = self.block_long[:, at[inside]] @ values[inside]
+        out[self.other] = solved
+        top = np.zeros(len(self.unit), dtype=np.longdouble)
+        top[self.unit_at[rows[~inside]]] = values[~inside]
+        np.subtract.at(top, self.coo_unit, self.coo_long * solved[self.coo_other])
+        out[self.unit] = top
+        return np.arange(self.m), out * self.scale_long
+
+    def alpha(self, j):
+        if not self.extended:
+            return np.array([float(v) for v in self.alpha_exact(j)], dtype=np.longdouble)
+        start, rows, values = self.compressed()
+        out = np.zeros(self.m, dtype=np.longdouble)
+        positions, alpha = self._alpha_long(rows[start[j]:start[j + 1]], values[start[j]:start[j + 1]])
+        out[positions] = alpha
+        return out
+
+    def alpha_nnz_estimates(self, columns):
+        """Per column, how many entries of the ``longdouble`` alpha exceed 2^-40 of its largest: a guide to which columns have long
+        and short alphas (``alpha_nnz`` is the exact count)."""
+        start, rows, values = self.compressed()
+        out = np.zeros(len(columns), dtype=np.int64)
+        for at, j in enumerate(columns):
+            _, alpha = self._alpha_long(rows[start[j]:start[j + 1]], values[start[j]:start[j + 1]])
+            size = np.abs(alpha)
+            out[at] = int((size > 2.0 ** -40 * size.max()).sum()) if len(size) else 0
+        return out
+
+    def gammas(self, columns):
+        if not self.extended:
+            return np.array([float(self.gamma_exact(int(j))) for j in columns], dtype=np.longdouble)
+        start, rows, values = self.compressed()
+        out = np.zeros(len(columns), dtype=np.longdouble)
+        for at, j in enumerate(columns):
+            _, alpha = self._alpha_long(rows[start[j]:start[j + 1]], values[start[j]:start[j + 1]])
+            out[at] = 1 + (alpha * alpha).sum()
+        return out
+
+    def reduced_costs(self, columns):
+        if not self.extended:
+            return np.array([float(self.reduced_cost_exact(int(j))) for j in columns], dtype=np.longdouble)
+        start, rows, values = self.compressed()
+        out = long_double(*zip(*[split_fraction(c) for c in self.cost]))
+        np.subtract.at(out, np.repeat(np.arange(self.n), np.diff(start)), long_double(self.pi_hi, self.pi_lo)[rows] * values)
+        return out[np.asarray(columns)]
+
+    def right_multiply(self, rows, values):
+        weights = {}
+        for r, v in zip(rows, values):
+            weights[int(r)] = weights.get(int(r), Fraction(0)) + Fraction(int(v))
+        total = self._combine(weights)
+        return long_double(*zip(*[split_fraction(total.get(i, Fraction(0))) for i in range(self.m)]))
 
 
 # ---- the f64 restatement of the Newton-Schulz inversion and polish (the yardstick for the device's error after either) ----------

@@ -2483,6 +2483,13 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
     const Step step = step_decision(bounded, forced_p >= 0, p, alpha_pq, sm.bcast[2], sm.bcast[3], ub_q);
     const double xp = step.xp;
     if (p < 0 && !step.flip) {
+        if (mode == 2) {  // `generate_column` without a pivot row: the caller reads the column all the same (ftran_ratio_kernel has stored it)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = tid + r * K2F_THREADS;
+                if (i < m) lp.alpha[i] = al[r];
+            }
+        }
         if (tid == 0) ctl_unbounded(*ctl, q, mode);
         return;
     }

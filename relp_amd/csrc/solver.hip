@@ -691,7 +691,12 @@ bool Solver::crash_basis() {
 
 // `Tableau::from_artificial` (non_artificial.rs:99-120): same basis, provider costs; -pi, -obj and the weights are
 // recomputed from the resident inverse (carry/mod.rs:499-525; pivot_rule.rs:202-219).
-void Solver::begin_phase_two() { set_phase(2); }
+void Solver::begin_phase_two() {
+    // (set_phase reads the basis, its positions and the inverse: before begin_phase_one or set_basis has written them the kernels would
+    //  index with whatever the arrays hold.  An LP without artificials starts phase two in begin_phase_one)
+    if (phase_ == 0) throw std::runtime_error("begin_phase_two: no basis yet (begin_phase_one or set_basis comes first)");
+    set_phase(2);
+}
 
 void Solver::set_phase(int phase) {
     const int phase_before = phase_;

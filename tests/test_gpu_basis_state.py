@@ -18,23 +18,11 @@ import pytest
 import relp_amd
 from relp_amd.api import SW_NO_DENSE_LANE
 from relp_amd.workloads import dense_lp
-from basis_state import BasisState, DenseLE, long_double, newton_schulz_polish, polished_tolerance
+import state_checks
+from basis_state import BasisState, DenseLE
+from state_checks import EVERYTHING, assert_state, close, device_inverse
 
 pytestmark = pytest.mark.gpu
-
-EVERYTHING = ("inverse", "vertex", "costs", "weights", "alpha", "btran", "selection")
-
-
-def close(got, want):
-    """``close()`` of tests/test_gpu_parity.py against a ``longdouble`` vector."""
-    want = np.asarray(want, dtype=np.longdouble)
-    scale = max(1.0, float(np.abs(want).max()))
-    error = np.abs(np.asarray(got, dtype=np.longdouble) - want)
-    return bool((error <= 1e-9 * scale + 1e-8 * np.abs(want)).all())
-
-
-def device_inverse(solver):
-    return np.stack([solver.basis_inverse_row(i) for i in range(solver.m)])
 
 
 def exact_state(solver, lp):
@@ -42,78 +30,9 @@ def exact_state(solver, lp):
     return BasisState(DenseLE(a), b, c, solver.basis())
 
 
-def assert_state(solver, exact, parts=EVERYTHING, inverse=None):
-    """``exact``: the ``BasisState`` of ``solver.basis()``.  ``inverse``: what ``device_inverse`` has just read, if the caller holds it."""
-    m, n = solver.m, solver.n
-    assert (n, solver.n_art) == (exact.n, exact.n_art)
-    n_dense = exact.columns.n
-    free = np.flatnonzero(~exact.is_basic)
-    free = free[free >= exact.n_art]
-    checked = exact.columns_to_check(n_grouped=n_dense)  # every column, unless longdouble is f64 here: then the sample of the exact path
-    checked_free = np.intersect1d(checked, free)
-    selected = solver.select_primal_pivot_column()  # (applies the pending weight update, as the next pricing pass would)
-    want_cost = exact.reduced_costs(checked)
-    if "inverse" in parts:
-        got = device_inverse(solver) if inverse is None else inverse
-        want = exact.inverse_long()
-        for i in range(m):
-            assert close(got[i], want[i]), ("row of the inverse", i, float(np.abs(got[i] - want[i]).max()))
-    if "vertex" in parts:
-        assert close(solver.b(), long_double(*exact.x_basic())), "b"
-        assert solver.objective_function_value() == pytest.approx(float(exact.objective_exact), rel=1e-9, abs=1e-10)
-    if "costs" in parts:
-        got = solver.relative_costs()[checked]
-        assert np.allclose(got, np.asarray(want_cost, dtype=np.float64), rtol=1e-9, atol=1e-9), \
-            ("relative cost", int(checked[np.argmax(np.abs(got - np.asarray(want_cost, dtype=np.float64)))]))
-    want_gamma = exact.gammas(checked_free)
-    if "weights" in parts:
-        got = solver.gamma()
-        assert np.isnan(got[exact.is_basic]).all()
-        relative = np.abs(np.asarray(got[checked_free], dtype=np.longdouble) / want_gamma - 1)
-        assert relative.max() <= 1e-8, ("gamma", int(checked_free[np.argmax(relative)]), float(relative.max()))
-    if "alpha" in parts:
-        slack = next((int(j) for j in free if j >= n_dense), n_dense)
-        dense_free = free[free < n_dense]
-        for q in sorted({int(free[0]), int(dense_free[len(dense_free) // 3]), n_dense - 1, slack}):
-            _, alpha = solver.select_primal_pivot_row(q)  # the multi-block FTRAN where the pipeline is in force
-            assert close(alpha, exact.alpha(q)), ("alpha", q)
-    if "btran" in parts:
-        rows = np.array([1, m // 2, m - 1], dtype=np.int32)
-        values = np.array([3.0, 5.0, 7.0])
-        assert close(solver.right_multiply_by_basis_inverse(rows, values), exact.right_multiply(rows, values)), "btran"
-    if "selection" in parts:
-        position = {int(j): at for at, j in enumerate(checked)}
-        cost_free = np.array([want_cost[position[int(j)]] for j in checked_free], dtype=np.longdouble)
-        key = np.where(cost_free < 0, cost_free * cost_free / want_gamma, 0)
-        if selected is None:
-            # the device's costs are within 1e-9 of the exact ones (asserted above) and tol_dual is 1e-9: nothing is 3e-9 below zero
-            assert float(cost_free.min()) >= -3e-9
-        else:
-            q, cost_q = selected
-            exact_q = exact.reduced_cost_exact(q)
-            assert cost_q == pytest.approx(float(exact_q), rel=1e-9, abs=1e-12)
-            key_q = float(exact_q * exact_q / exact.gamma_exact(q))
-            if len(checked) == n:
-                assert key_q == pytest.approx(float(key.max()), rel=1e-9)  # same maximum (ties may pick another column)
-            else:
-                assert key_q >= float(key.max()) * (1 - 1e-9)  # (a sample: the choice is at least as good as every column in it)
-
-
 def assert_polished(solver, lp, inverse_before, parts=EVERYTHING):
     """After ``refactor()``: the resident inverse and b within the post-polish tolerance (module docstring) of the exact state."""
-    exact = exact_state(solver, lp)
-    B = exact.basis_matrix()
-    reference = newton_schulz_polish(B, inverse_before)
-    got = device_inverse(solver)
-    bound, error = polished_tolerance(reference, exact.inverse_long())
-    device_error = float(np.abs(got - exact.inverse_long()).max())
-    print("polish: device error %.3e, restatement %.3e, bound %.3e" % (device_error, error, bound))
-    assert device_error <= bound, ("polished inverse", device_error, error, bound)
-    bound, error = polished_tolerance(reference @ np.asarray(lp[1], dtype=np.float64), long_double(*exact.x_basic()))
-    device_error = float(np.abs(solver.b() - long_double(*exact.x_basic())).max())
-    print("polish: b: device error %.3e, restatement %.3e, bound %.3e" % (device_error, error, bound))
-    assert device_error <= bound, ("polished b", device_error, error, bound)
-    assert_state(solver, exact, parts=parts, inverse=got)  # ... and everything else still at the tolerance of the unpolished state
+    state_checks.assert_polished(solver, exact_state(solver, lp), inverse_before, np.asarray(lp[1], dtype=np.float64), parts=parts)
 
 
 def pipeline_solver(lp, **options):

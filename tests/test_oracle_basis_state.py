@@ -145,3 +145,124 @@ def test_newton_schulz_restatements_reach_the_exact_inverse():
     drifted = state.inverse_hi * (1 + 1e-7 * np.cos(np.arange(64 * 64)).reshape(64, 64))
     assert np.abs(drifted - state.inverse_hi).max() > 1e-9 * scale
     assert np.abs(newton_schulz_polish(B, drifted) - state.inverse_hi).max() <= 1e-11 * scale
+
+
+# ---- the structured form for sparse LPs of thousands of rows: the same numbers as the dense class ---------------------------------
+def assert_same_state(dense, sparse, columns):
+    """``SparseBasisState`` against ``BasisState`` of the same basis: exactly equal where both are exact; where both sum ``longdouble`` products of ``hi + lo``
+    in their own order, within 2^-56 of the largest entry (up to 40 products of a column entry <= 3 with an entry rounded to a 64-bit
+    significand, 40 * 3 * 2^-64 < 2^-57 each way, and the exact value may cancel to zero)."""
+    m = dense.m
+    assert sparse.den == dense.den
+    for k in range(m):
+        where, numerators = sparse.row_exact(k)
+        filled = np.flatnonzero(dense.num[k] != 0)
+        assert where.tolist() == filled.tolist() and [int(v) for v in numerators] == [int(v) for v in dense.num[k, filled]], k
+        assert np.array_equal(sparse.inverse_row(k)[0], dense.inverse_row(k)[0]) and np.array_equal(sparse.inverse_row(k)[1], dense.inverse_row(k)[1])
+    assert sparse.x_exact == dense.x_exact and sparse.objective_exact == dense.objective_exact
+    assert np.array_equal(sparse.x_hi, dense.x_hi) and np.array_equal(sparse.x_lo, dense.x_lo)
+    assert np.array_equal(sparse.pi_hi, dense.pi_hi) and np.array_equal(sparse.pi_lo, dense.pi_lo)
+    for j in columns:
+        assert sparse.reduced_cost_exact(j) == dense.reduced_cost_exact(j), j
+        assert sparse.gamma_exact(j) == dense.gamma_exact(j), j
+        assert sparse.alpha_nnz(j) == sum(1 for v in dense.alpha_exact(j) if v != 0), j
+    if not (sparse.extended and dense.extended):
+        return
+
+    def same(got, want):
+        return float(np.abs(got - want).max()) <= 2.0 ** -56 * max(1.0, float(np.abs(want).max()))
+    columns = np.asarray(columns)
+    assert same(sparse.gammas(columns), dense.gammas(columns))
+    assert same(sparse.reduced_costs(columns), dense.reduced_costs(columns))
+    for j in columns[:12]:
+        assert same(sparse.alpha(int(j)), dense.alpha(int(j))), j
+    every_row = np.arange(m)
+    assert same(sparse.right_multiply(every_row, 1 + every_row % 7), dense.right_multiply(every_row, 1 + every_row % 7))
+
+
+def test_structured_state_equals_the_dense_one_on_afiro(afiro):
+    from basis_state import SparseBasisState
+    data, columns = afiro
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "AFIRO.json")))
+    arguments = (columns, data.right_hand_side(), [data.cost_value(j) for j in range(len(columns))], golden["basis"])
+    assert_same_state(BasisState(*arguments), SparseBasisState(*arguments), range(len(columns)))
+
+
+@pytest.mark.parametrize("family, mix, m, pivots", [("equality", "mixed", 65, 40), ("equality", "short", 65, 40), ("less", "mixed", 65, 40),
+                                                    ("equality", "mixed", 513, 100), ("less", "mixed", 513, 100)])
+def test_structured_state_equals_the_dense_one_on_walked_bases(family, mix, m, pivots):
+    """Bases reached by the f64 model of the device's loop on the two LP families of tests/sparse_lps.py.  The equality family is still
+    in phase one after the walk, so artificials are basic.  Every basis is compared under the phase-one AND the phase-two costs: with
+    artificials basic the phase-two cost vector is offset by n_art and c_B mixes zeros with real costs."""
+    import sparse_lps
+    _, provider, phase = sparse_lps.case(family, mix, m)
+    walked = sparse_lps.walk(provider, phase, pivots)
+    basis = sparse_lps.basis_of(walked)
+    assert (min(basis) < 0) == (family == "equality")  # artificials are present in the equality family's basis
+    n = walked.n
+    columns = range(n) if m == 65 else sorted(set(range(0, n, 29)) | set(range(n - 8, n)))  # (every length of the mix: 29 is prime to 5 and 8)
+    for costs in (1, 2):
+        dense = provider.state(basis, costs, cls=BasisState)
+        sparse = provider.state(basis, costs)
+        assert sparse.k <= pivots and sparse.n_art == walked.n_art
+        assert_same_state(dense, sparse, columns)
+        if costs == phase:
+            assert float(sparse.objective_exact) == pytest.approx(walked.objective(), rel=1e-9)
+    # the fallback where longdouble is f64: exact integers on the sample, the same numbers
+    dense = provider.state(basis, phase, cls=BasisState)
+    sample = provider.state(basis, phase, extended=False)
+    checked = sample.columns_to_check(minimum=24)[:40]
+    assert np.allclose(np.asarray(sample.gammas(checked), dtype=np.float64), [float(dense.gamma_exact(int(j))) for j in checked], rtol=4e-16, atol=0)
+    assert np.allclose(np.asarray(sample.reduced_costs(checked), dtype=np.float64), [float(dense.reduced_cost_exact(int(j))) for j in checked],
+                       rtol=4e-16, atol=1e-18)
+    assert np.allclose(np.asarray(sample.alpha(int(checked[-1])), dtype=np.float64), [float(v) for v in dense.alpha_exact(int(checked[-1]))],
+                       rtol=4e-16, atol=1e-18)
+
+
+@pytest.mark.slow
+def test_structured_state_at_8193_rows_and_the_f64_model():
+    """100 pivots of the mixed family at m = 8193, walked by ``f64_model.Model`` without a polish (about half a minute in numpy, most of
+    it the model's own dense (m, m) inverse and its first (m, n) product).  The state builds in seconds from k x k integers, and the
+    model's inverse and x_B are within ``close()`` of it (measured: 1e-14)."""
+    import time
+    import tracemalloc
+    import sparse_lps
+    from state_checks import close
+    _, provider, phase = sparse_lps.case("equality", "mixed", 8193)
+    walked = sparse_lps.walk(provider, phase, 100)
+    basis = sparse_lps.basis_of(walked)
+
+    def build():
+        state = provider.state(basis, phase)
+        free = np.flatnonzero(~state.is_basic)
+        free = free[free >= state.n_art]
+        return state, free, state.gammas(free), state.reduced_costs(np.arange(state.n))
+    started = time.perf_counter()
+    state, free, gammas, costs = build()
+    seconds = time.perf_counter() - started
+    tracemalloc.start()  # (numpy's buffers are traced too; tracing slows the build, so it is timed above without)
+    build()
+    grown = tracemalloc.get_traced_memory()[1] / 2.0 ** 20
+    tracemalloc.stop()
+    print("state, every weight and every relative cost at m = 8193: %.1f s, k = %d, %.0f MB at the peak" % (seconds, state.k, grown))
+    # measured 1.3 s and 22 MB; one (m, k) array of Python integers or one (m, m) array of f64 would be 100 MB and more
+    assert seconds < 5 and grown < 100 and state.k <= 100
+    assert not hasattr(state, "num") and not hasattr(state, "inverse_hi")  # no (m, m) array
+    for k in state.rows_that_may_not_be_unit().tolist() + list(range(0, 8193, 64)) + [8192]:
+        assert close(walked.Binv[k], long_double(*state.inverse_row(k))), k
+    assert close(walked.xB, long_double(*state.x_basic()))
+    assert np.abs(walked.gamma[free] / np.asarray(gammas, dtype=np.float64) - 1).max() <= 1e-8
+    assert np.allclose(walked.cost + walked.AT @ walked.minus_pi, np.asarray(costs, dtype=np.float64), rtol=1e-9, atol=1e-9)
+
+
+@pytest.mark.parametrize("family, mix, m", [pytest.param(*key, marks=pytest.mark.slow) if key[2] > 2049 else key for key in sorted(__import__("sparse_lps").SEEDS)])
+def test_replaced_seeds_meet_the_preconditions_of_the_gpu_cases(family, mix, m):
+    """Every LP whose seed is not 1000 + m (``sparse_lps.SEEDS``), walked 100 pivots by the f64 model under the reference's ratio rule --
+    the one the device takes on these LPs up to 8192 rows -- meets what tests/test_gpu_sparse_state.py asserts before it compares."""
+    import sparse_lps
+    _, provider, phase = sparse_lps.case(family, mix, m)
+    walked = sparse_lps.walk(provider, phase, sparse_lps.PIVOTS, textbook=True)
+    state = provider.state(sparse_lps.basis_of(walked), phase)
+    not_unit, columns, nnz, entered = sparse_lps.preconditions(state, provider, mix)
+    print("%s %s %d: %d entered columns in the basis, k = %d, nnz(alpha) of the checked columns %r" % (family, mix, m, entered, state.k, nnz))
+    assert m - 1 in not_unit and len(columns) >= 3
