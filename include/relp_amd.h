@@ -865,6 +865,31 @@ int32_t relp_many_get_witness_exact(const relp_many* many, int32_t model, int32_
 int32_t relp_many_get_solution_exact(const relp_many* many, int32_t model, int32_t original, int32_t capacity, int32_t* count,
                                      int32_t* index, char* buffer, int64_t buffer_capacity, int64_t* length);
 
+/* ---- dual simplex: re-solve from a basis after cuts or tightened bounds (relp_amd/csrc/dual.hip) ------------------------------------
+ * The optimal basis of an LP is still dual feasible after rows are appended or a right-hand side is tightened, and primal infeasible
+ * exactly where the change bites.  The caller builds the changed LP as a new model, loads it, and passes the old basis extended by
+ * the slack column of each new row (relp_model_initial_pivots names it); nothing mutates a loaded LP.  `basis_columns`: m provider
+ * columns, as relp_set_basis takes them.
+ * RELP_ERR_ARGUMENT, before anything is launched, with the reason in relp_last_error: a plan the dual kernels do not take
+ * (relp_debug_dual_refusal), an artificial column (a negative code) in the basis, and -- after the inverse of the basis has been
+ * built -- a basis that is not dual feasible (the first column with a relative cost below -tol_dual is named).
+ * relp_solve_dual: dual pivots until no row is infeasible, then the primal loop from that basis (it normally makes no pivot) and
+ * the result as relp_solve_relaxation reports it: the primal pivots in pivots_phase_two, the dual ones through relp_get_dual_pivots
+ * and as "dual_pivots" in relp_get_record_json ("dual_device_seconds": the device time of their batches).  A finite optimum is
+ * certified as options.certify asks.  RELP_RESULT_INFEASIBLE (the dual is unbounded) comes back with certified = 0 and
+ * relp_last_error saying so: the dual loop does not prove infeasibility yet.  A pivot element that is unusable even after a
+ * polish of the inverse (an ill-conditioned basis) ends the call with RELP_ERR_STATE.
+ * relp_begin_dual / relp_iterate_dual: the same loop in steps.  Stop reasons: 1 no infeasible row is left (the basis is primal
+ * feasible), 2 the dual is unbounded (the LP is infeasible), 3 `count` pivots were made.  relp_get_last_pivot reports phase 3 after a
+ * dual pivot.  The steepest-edge weights are not maintained by the dual loop: relp_begin_phase_two recomputes them. */
+int32_t relp_solve_dual(relp_handle* handle, const int32_t* basis_columns, relp_result* result);
+int32_t relp_begin_dual(relp_handle* handle, const int32_t* basis_columns);
+int32_t relp_iterate_dual(relp_handle* handle, int64_t count, int64_t* done, int32_t* stop_reason);
+int32_t relp_get_dual_pivots(const relp_handle* handle, int64_t* dual_pivots);
+/* Host only: the empty string if the plan of (model, options) takes the dual loop, else the reason (the protocol of
+ * relp_debug_kernel_path; a load that would itself be refused returns its status and message). */
+int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length);
+
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);
 

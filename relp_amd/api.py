@@ -193,6 +193,8 @@ SYMBOLS = [
     # the exact vectors behind a certified result (x, y / Farkas, ray), and the exact model data a caller checks them against
     "relp_get_witness_exact", "relp_many_keep_witnesses", "relp_many_get_witness_exact", "relp_many_get_solution_exact",
     "relp_model_cost_exact", "relp_model_right_hand_side_exact", "relp_model_fixed_cost_exact",
+    # dual simplex from a dual-feasible basis (relp_amd/csrc/dual.hip)
+    "relp_solve_dual", "relp_begin_dual", "relp_iterate_dual", "relp_get_dual_pivots", "relp_debug_dual_refusal",
 ]
 
 
@@ -491,6 +493,18 @@ class Model:
             raise RelpError(status, buf.value.decode())
         return json.loads(buf.value.decode())
 
+    def dual_refusal(self, **options):
+        """Why ``Solver(**options).solve_dual`` would refuse this model's plan, in words; ``""`` if it takes it
+        (``relp_debug_dual_refusal``).  Host only.  Raises ``RelpError`` with the load's message where the load itself would be refused."""
+        opts = default_options(**options)
+        length = C.c_int32()
+        lib().relp_debug_dual_refusal(self._h, C.byref(opts), None, 0, C.byref(length))
+        buf = C.create_string_buffer(length.value + 1)
+        status = lib().relp_debug_dual_refusal(self._h, C.byref(opts), buf, length.value + 1, C.byref(length))
+        if status != OK:
+            raise RelpError(status, buf.value.decode())
+        return buf.value.decode()
+
     def pivot_element_indices(self):
         count = C.c_int32()
         rows = np.zeros(self.nr_rows, dtype=np.int32)
@@ -694,6 +708,34 @@ class Solver:
     def set_basis(self, basis):
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_set_basis(self._h, _ptr(arr, C.c_int32)))
+
+    # ---- dual simplex from a dual-feasible basis ----------------------------------------------------
+    def solve_dual(self, basis):
+        """Re-solve the loaded LP from ``basis`` (as ``set_basis`` takes it: the optimal basis of the LP before rows were appended
+        or a right-hand side tightened, extended by the slack of each new row) by dual pivots; returns ``Result``
+        (``relp_solve_dual``).  ``RelpError`` where the plan, or the basis, is refused."""
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        result = Result()
+        self._check(lib().relp_solve_dual(self._h, _ptr(arr, C.c_int32), C.byref(result)))
+        return result
+
+    def begin_dual(self, basis):
+        """``set_basis`` and the checks of ``solve_dual``, no pivot (``relp_begin_dual``)."""
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        self._check(lib().relp_begin_dual(self._h, _ptr(arr, C.c_int32)))
+
+    def iterate_dual(self, count):
+        """Up to ``count`` dual pivots: ``(done, reason)``; ``STOP_NO_ENTERING``: no infeasible row is left, ``STOP_UNBOUNDED``: the
+        dual is unbounded (the LP is infeasible), ``STOP_BUDGET``."""
+        done, reason = C.c_int64(), C.c_int32()
+        self._check(lib().relp_iterate_dual(self._h, int(count), C.byref(done), C.byref(reason)))
+        return done.value, reason.value
+
+    def dual_pivots(self):
+        """Dual pivots of the last ``solve_dual`` / since ``begin_dual``."""
+        count = C.c_int64()
+        self._check(lib().relp_get_dual_pivots(self._h, C.byref(count)))
+        return count.value
 
     # ---- fine-grained trait ops -------------------------------------------------------------------
     def begin_phase_one(self):

@@ -768,7 +768,7 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     out << "{\"name\": \"" << json_escaped(sv.form().name) << "\", \"presolve\": \"" << presolve_states[sv.form().presolve_state & 3] << "\", \"m\": " << md.nr_rows() << ", \"n\": " << md.nr_columns() << ", \"nnz\": " << nnz
         << ", \"device_rows\": " << d.m << ", \"artificials\": " << d.n_art << ", \"result\": \"" << kinds[r.kind >= 0 && r.kind <= 4 ? r.kind : 0]
         << "\", \"carry\": \"" << (h->options.carry == RELP_CARRY_LU ? "lu" : h->options.carry == RELP_CARRY_LU_INVERSE ? "lu_inverse" : sv.network_carry() ? "network" : "explicit") << "\", \"pivots_phase_one\": " << r.pivots_phase_one
-        << ", \"pivots_phase_two\": " << r.pivots_phase_two << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
+        << ", \"pivots_phase_two\": " << r.pivots_phase_two << ", \"dual_pivots\": " << sv.dual_pivots() << ", \"dual_device_seconds\": " << sv.dual_device_seconds() << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
         << "\", \"device_refactor_fallbacks\": " << sv.device_refactor_fallbacks()
         << ", \"async_refactors\": " << sv.async_refactors() << ", \"async_refactors_abandoned\": " << sv.async_refactors_abandoned() << ", \"async_worst_residual\": " << sv.async_worst_residual()
@@ -873,6 +873,36 @@ int32_t relp_set_basis(relp_handle* h, const int32_t* basis_columns) {
     REQUIRE_LOADED(h);
     if (!basis_columns) return RELP_ERR_ARGUMENT;
     return guarded(h, [&] { h->solver->set_basis(basis_columns); });
+}
+
+int32_t relp_solve_dual(relp_handle* h, const int32_t* basis_columns, relp_result* result) {
+    REQUIRE_LOADED(h);
+    if (!basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] {
+        h->solver->last_error.clear();
+        h->solver->solve_dual(basis_columns, result);
+        if (!h->solver->last_error.empty()) h->error = h->solver->last_error;  // e.g. that INFEASIBLE comes back uncertified
+    });
+}
+int32_t relp_begin_dual(relp_handle* h, const int32_t* basis_columns) {
+    REQUIRE_LOADED(h);
+    if (!basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] { h->solver->begin_dual(basis_columns); });
+}
+int32_t relp_iterate_dual(relp_handle* h, int64_t count, int64_t* done, int32_t* stop_reason) {
+    REQUIRE_LOADED(h);
+    return guarded(h, [&] {
+        int reason = 0;
+        long long d = h->solver->iterate_dual(count, &reason);
+        if (done) *done = d;
+        if (stop_reason) *stop_reason = reason;
+    });
+}
+int32_t relp_get_dual_pivots(const relp_handle* h, int64_t* dual_pivots) {
+    REQUIRE_LOADED(h);
+    if (!dual_pivots) return RELP_ERR_ARGUMENT;
+    *dual_pivots = h->solver->dual_pivots();
+    return RELP_OK;
 }
 
 int32_t relp_begin_phase_one(relp_handle* h) {
@@ -1046,6 +1076,30 @@ int32_t relp_debug_kernel_path(const relp_model* model, const relp_options* opti
         const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
         text = kernel_path_json(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
     } catch (const std::invalid_argument& e) {
+        text = e.what();
+        status = RELP_ERR_ARGUMENT;
+    } catch (const std::exception& e) {
+        text = e.what();
+        status = RELP_ERR_STATE;
+    }
+    if (length) *length = (int32_t)text.size();
+    if (buffer && capacity > 0) {
+        const int32_t nbytes = std::min<int32_t>((int32_t)text.size(), capacity - 1);
+        std::memcpy(buffer, text.data(), nbytes);
+        buffer[nbytes] = 0;
+    }
+    return status;
+}
+int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+    relp_options o;
+    if (!model || adopt_options(options, &o) != RELP_OK) return RELP_ERR_ARGUMENT;
+    int32_t status = RELP_OK;
+    std::string text;
+    try {
+        const MatrixData& md = model->form.data;
+        const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
+        text = dual_refusal(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
+    } catch (const std::invalid_argument& e) {  // (the load itself would be refused: its message)
         text = e.what();
         status = RELP_ERR_ARGUMENT;
     } catch (const std::exception& e) {

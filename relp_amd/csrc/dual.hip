@@ -1,0 +1,334 @@
+// Dual simplex from a given dual-feasible basis: the five kernels of one dual pivot (gfx950, wave64) and their launch helpers.
+//
+// The primal kernels cannot leave a primal-infeasible basis (step_decision clamps the leaving value at zero), and the rules of
+// pivot_step.hpp are shared with the fused pivot, so the dual loop is a set of kernels of its own over the same device state
+// (dual.hpp).  The textbook method: the leaving row is the most infeasible one, the entering column the one whose relative cost
+// reaches zero first along row p of the tableau, found by a two-pass ratio test of the same shape as the primal Harris test
+// (pass 1: the largest dual step that keeps every relative cost above -tol_dual; pass 2: the largest |alpha_pj| within it).
+// Candidates go through per-workgroup slots that one workgroup folds, as in the primal loop; no floating-point atomics, every
+// reduction in a fixed order.
+#include <hip/hip_runtime.h>
+
+#include "pivot_step.hpp"
+#include "solver.hpp"
+#include "wave_ops.hpp"
+
+namespace relp {
+
+namespace {
+
+constexpr int DL_THREADS = 1024;      // the two single-workgroup kernels
+constexpr int DL_U = 8;               // rows per thread in flight together (K2_U of ftran_ratio_kernel)
+constexpr int DL_COL_CHUNK = 1024;    // entries of the entering column staged per pass
+constexpr int DU_THREADS = 256;       // dual_update_kernel: four waves, a column pair each
+constexpr int DU_CPW = 2;
+
+// ---------------------------------------------------------------------------------------------------
+// 1. The leaving row: key = -x_B[i] among the rows with x_B[i] < -delta, ties to the lowest basic column, then the lowest row.
+//    Then rho = row p of the inverse (m strided loads of the column-major inverse, as btran_vec_kernel does for a unit vector).
+//    Also the budget check of the chain: the four kernels behind this one only look at the status.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, double delta) {
+    __shared__ double s_key[DL_THREADS / WAVE];
+    __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
+    Ctl* ctl = lp.ctl;
+    if (ctl->status != ST_RUNNING) return;
+    if (ctl->iters >= ctl->budget) {
+        if (threadIdx.x == 0) ctl_budget(*ctl);
+        return;
+    }
+    const int m = lp.m, ld = lp.ld;
+    double key = 0.0;
+    unsigned long long rank = RANK_NONE;
+    for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
+        double xbv[DL_U];
+        int basv[DL_U];
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int i = i0 + u * DL_THREADS;
+            xbv[u] = i < m ? lp.xB[i] : 0.0;
+            basv[u] = i < m ? lp.basis[i] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int i = i0 + u * DL_THREADS;
+            if (i < m && xbv[u] < -delta) keep_better(-xbv[u], leaving_rank(basv[u], i), key, rank);
+        }
+    }
+    block_argbest<true>(key, rank, s_key, s_rank);  // (the first use of the slots)
+    const int p = leaving_row(rank);
+    if (p < 0) {  // primal feasible
+        if (threadIdx.x == 0) {
+            ctl->status = ST_NO_ENTERING;
+            ctl->pending = 0;
+        }
+        return;
+    }
+    for (int j0 = threadIdx.x; j0 < m; j0 += DL_U * DL_THREADS) {
+        double v[DL_U];
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int j = j0 + u * DL_THREADS;
+            v[u] = j < m ? lp.Binv[(size_t)j * ld + p] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int j = j0 + u * DL_THREADS;
+            if (j < m) lp.rho[j] = v[u];
+        }
+    }
+    if (threadIdx.x == 0) ctl->p = p;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// 2. Row p of the tableau and the relative costs over the provider columns, one lane per column, in one pass over its entries:
+//    alpha_pj = sum v rho[r], d_j = c_j + sum v (-pi)[r] (the sum of reduced_cost_of, in its order).  A basic column stores
+//    alpha_pj = 0 and is never eligible.  Pass 1 of the ratio test over the columns with alpha_pj < -tol_pivot: the workgroup's
+//    minimum of (max(d_j, 0) + slack) / |alpha_pj|.  LDS: rho and -pi staged in 2 m doubles of dynamic LDS.
+// ---------------------------------------------------------------------------------------------------
+template <bool LDS>
+__global__ void __launch_bounds__(DUAL_COLUMNS_PER_BLOCK) dual_row_kernel(DeviceLP lp, DualBuffers b, double tol_pivot, double slack) {
+    extern __shared__ __attribute__((aligned(16))) double s_vectors[];
+    __shared__ __attribute__((aligned(16))) double s_red[DUAL_COLUMNS_PER_BLOCK / WAVE + 2];
+    if (lp.ctl->status != ST_RUNNING) return;
+    const int m = lp.m;
+    const double* rho = lp.rho;
+    const double* minus_pi = lp.minus_pi;
+    if (LDS) {
+        for (int i = threadIdx.x; i < m; i += DUAL_COLUMNS_PER_BLOCK) {
+            s_vectors[i] = lp.rho[i];
+            s_vectors[m + i] = lp.minus_pi[i];
+        }
+        __syncthreads();
+        rho = s_vectors;
+        minus_pi = s_vectors + m;
+    }
+    const int j = lp.n_art + blockIdx.x * DUAL_COLUMNS_PER_BLOCK + threadIdx.x;
+    double theta = INFINITY;
+    if (j < lp.n) {
+        double a = 0.0, dj = 0.0;
+        if (lp.pos[j] < 0) {
+            dj = lp.cost[j];
+            const int first = lp.col_start[j], last = lp.col_start[j + 1];
+            for (int e = first; e < last; ++e) {
+                const int r = lp.row_index[e];
+                const double v = lp.value[e];
+                dj += v * minus_pi[r];
+                a += v * rho[r];
+            }
+            if (a < -tol_pivot) theta = (fmax(dj, 0.0) + slack) / fabs(a);
+        }
+        b.alpha_row[j] = a;
+        b.d[j] = dj;
+    }
+    theta = block_reduce<1>(theta, s_red);
+    if (threadIdx.x == 0) b.part_theta[blockIdx.x] = theta;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// 3. theta_max = the minimum of the partial minima (every workgroup folds them itself, in the same order), then pass 2: among the
+//    eligible columns with max(d_j, 0) / |alpha_pj| <= theta_max the largest |alpha_pj| (key 1 under the textbook rule), ties to the
+//    lowest column.  One candidate per workgroup.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DUAL_COLUMNS_PER_BLOCK) dual_choose_kernel(DeviceLP lp, DualBuffers b, double tol_pivot, int textbook) {
+    __shared__ double s_red[DUAL_COLUMNS_PER_BLOCK / WAVE + 2];
+    __shared__ double s_key[DUAL_COLUMNS_PER_BLOCK / WAVE];
+    __shared__ unsigned long long s_rank[DUAL_COLUMNS_PER_BLOCK / WAVE];
+    if (lp.ctl->status != ST_RUNNING) return;
+    double theta = INFINITY;
+    for (int k = threadIdx.x; k < b.blocks; k += DUAL_COLUMNS_PER_BLOCK) theta = fmin(theta, b.part_theta[k]);
+    const double theta_max = block_reduce<1>(theta, s_red);
+    const int j = lp.n_art + blockIdx.x * DUAL_COLUMNS_PER_BLOCK + threadIdx.x;
+    double key = 0.0;
+    unsigned long long rank = RANK_NONE;
+    if (j < lp.n) {
+        const double a = b.alpha_row[j];
+        if (a < -tol_pivot) {
+            const double mag = fabs(a);
+            if (fmax(b.d[j], 0.0) / mag <= theta_max) {
+                key = textbook ? 1.0 : mag;
+                rank = (unsigned long long)(unsigned)j;
+            }
+        }
+    }
+    block_argbest<true>(key, rank, s_key, s_rank);  // (the slots' first use; block_reduce has its own)
+    if (threadIdx.x == 0) {
+        b.cand_j[blockIdx.x] = rank == RANK_NONE ? -1 : (int)rank;
+        b.cand_key[blockIdx.x] = key;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// 4. The entering column q from the candidates (none: the dual is unbounded, the LP infeasible), alpha_q = Binv a_q with the column
+//    staged through LDS as in ftran_ratio_kernel, the check that alpha_q[p] agrees with the row's value (ST_REFACTOR otherwise),
+//    then the step theta = x_B[p] / alpha_q[p] -- the FTRAN value of the pivot, used
+//    below and by the update of the inverse alike --, x_B, basis, pos and the control block.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, DualBuffers b, double tol_pivot) {
+    __shared__ double s_key[DL_THREADS / WAVE];
+    __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
+    __shared__ int s_rows[DL_COL_CHUNK];
+    __shared__ double s_vals[DL_COL_CHUNK];
+    __shared__ double s_pivot[2];  // alpha_q[p], x_B[p]
+    Ctl* ctl = lp.ctl;
+    if (ctl->status != ST_RUNNING) return;
+    const int m = lp.m, ld = lp.ld;
+    const int p = ctl->p;
+    double key = 0.0;
+    unsigned long long rank = RANK_NONE;
+    for (int k = threadIdx.x; k < b.blocks; k += DL_THREADS) {
+        const int j = b.cand_j[k];
+        if (j >= 0) keep_better(b.cand_key[k], (unsigned long long)(unsigned)j, key, rank);
+    }
+    block_argbest<true>(key, rank, s_key, s_rank);  // (the first use of the slots)
+    if (rank == RANK_NONE) {
+        if (threadIdx.x == 0) {
+            ctl->status = ST_UNBOUNDED;
+            ctl->q = -1;
+            ctl->p = -1;
+            ctl->pending = 0;
+        }
+        return;
+    }
+    const int q = (int)rank;
+    const int ca = lp.col_start[q], cb = lp.col_start[q + 1];
+    const bool single = (cb - ca) <= DL_COL_CHUNK;
+    if (!single)
+        for (int i = threadIdx.x; i < m; i += DL_THREADS) lp.alpha[i] = 0.0;
+    for (int c0 = ca; c0 < cb; c0 += DL_COL_CHUNK) {
+        const int cnt = min(DL_COL_CHUNK, cb - c0);
+        __syncthreads();
+        for (int e = threadIdx.x; e < cnt; e += DL_THREADS) {
+            s_rows[e] = lp.row_index[c0 + e];
+            s_vals[e] = lp.value[c0 + e];
+        }
+        __syncthreads();
+        for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
+            double acc[DL_U];
+#pragma unroll
+            for (int u = 0; u < DL_U; ++u) {
+                const int i = i0 + u * DL_THREADS;
+                acc[u] = (!single && i < m) ? lp.alpha[i] : 0.0;
+            }
+            for (int e = 0; e < cnt; ++e) {
+                const size_t off = (size_t)s_rows[e] * ld;
+                const double v = s_vals[e];
+#pragma unroll
+                for (int u = 0; u < DL_U; ++u) {
+                    const int i = i0 + u * DL_THREADS;
+                    if (i < m) acc[u] += lp.Binv[off + i] * v;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < DL_U; ++u) {
+                const int i = i0 + u * DL_THREADS;
+                if (i < m) lp.alpha[i] = acc[u];  // (read again below by the thread that wrote it)
+            }
+        }
+    }
+    if ((p % DL_THREADS) == (int)threadIdx.x) {  // the thread that owns row p
+        s_pivot[0] = lp.alpha[p];
+        s_pivot[1] = lp.xB[p];
+    }
+    __syncthreads();
+    const double alpha_pq = s_pivot[0];
+    // The column was chosen on rho_p . a_q < -tol_pivot; the FTRAN value is the same number through the other side of the inverse.
+    // Where the two disagree -- the FTRAN value is no usable pivot of that sign -- the inverse has drifted: x_B, the basis and the inverse
+    // are still untouched, the chain stops with ST_REFACTOR and the host polishes the inverse and asks again (Solver::iterate_dual).
+    if (!(alpha_pq < -tol_pivot)) {
+        if (threadIdx.x == 0) {
+            ctl->status = ST_REFACTOR;
+            ctl->pending = 0;
+        }
+        return;
+    }
+    const double theta = s_pivot[1] / alpha_pq;
+    for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
+        double av[DL_U], xbv[DL_U];
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int i = i0 + u * DL_THREADS;
+            av[u] = i < m ? lp.alpha[i] : 0.0;
+            xbv[u] = i < m ? lp.xB[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int i = i0 + u * DL_THREADS;
+            if (i < m) lp.xB[i] = i == p ? theta : xbv[u] - theta * av[u];
+        }
+    }
+    if (threadIdx.x == 0) {
+        const int leaving = lp.basis[p];
+        const double d_q = b.d[q];
+        lp.basis[p] = q;
+        lp.pos[q] = p;
+        lp.pos[leaving] = -1;
+        ctl->q = q;
+        ctl->leaving = leaving;
+        ctl->alpha_pq = alpha_pq;
+        ctl->cbar_q = d_q;
+        ctl->xp = theta;
+        ctl->minus_obj = ctl->minus_obj - d_q * theta;
+        ctl->iters = ctl->iters + 1;
+        ctl->pending = 0;  // the steepest-edge weights are not maintained here: set_phase(2) recomputes them
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// 5. The inverse and -pi, a wave per pair of columns, rows coalesced: with r = c[p] / alpha_pq (row p of the new inverse),
+//    c[i] -= alpha_q[i] r for i != p, c[p] = r, (-pi)[j] -= d_q r.  A column with c[p] == 0 exactly does not change.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DU_THREADS) dual_update_kernel(DeviceLP lp) {
+    const Ctl* ctl = lp.ctl;
+    if (ctl->status != ST_RUNNING) return;  // (still running behind dual_pivot_kernel: it has pivoted)
+    const int m = lp.m, ld = lp.ld;
+    const int p = ctl->p;
+    const double alpha_pq = ctl->alpha_pq, d_q = ctl->cbar_q;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int j0 = (blockIdx.x * (DU_THREADS / WAVE) + threadIdx.x / WAVE) * DU_CPW;
+    double r[DU_CPW];
+#pragma unroll
+    for (int c = 0; c < DU_CPW; ++c) r[c] = j0 + c < m ? lp.Binv[(size_t)(j0 + c) * ld + p] / alpha_pq : 0.0;
+    if (r[0] == 0.0 && r[1] == 0.0) return;
+    for (int i = lane; i < m; i += WAVE) {
+        const double a = lp.alpha[i];
+#pragma unroll
+        for (int c = 0; c < DU_CPW; ++c) {
+            if (r[c] == 0.0) continue;
+            double* column = lp.Binv + (size_t)(j0 + c) * ld;
+            column[i] = i == p ? r[c] : column[i] - a * r[c];
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < DU_CPW; ++c)
+            if (r[c] != 0.0) lp.minus_pi[j0 + c] -= d_q * r[c];
+    }
+}
+
+}  // namespace
+
+void launch_dual_leave(const DeviceLP& d, double harris_delta, hipStream_t s) {
+    hipLaunchKernelGGL(dual_leave_kernel, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta);
+}
+void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, double tol_pivot, double slack, hipStream_t s) {
+    static PerDeviceOnce once;  // more than 64 KB of dynamic LDS is an opt-in, per device
+    once.run([] {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dual_row_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8192 * 8) != hipSuccess)
+            (void)hipGetLastError();
+    });
+    if (lds) hipLaunchKernelGGL(dual_row_kernel<true>, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 2 * (size_t)d.m * sizeof(double), s, d, b, tol_pivot, slack);
+    else hipLaunchKernelGGL(dual_row_kernel<false>, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 0, s, d, b, tol_pivot, slack);
+}
+void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivot, bool textbook, hipStream_t s) {
+    hipLaunchKernelGGL(dual_choose_kernel, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 0, s, d, b, tol_pivot, textbook ? 1 : 0);
+}
+void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, double tol_pivot, hipStream_t s) {
+    hipLaunchKernelGGL(dual_pivot_kernel, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
+}
+void launch_dual_update(const DeviceLP& d, hipStream_t s) {
+    const int waves = (d.m + DU_CPW - 1) / DU_CPW, per_block = DU_THREADS / WAVE;
+    hipLaunchKernelGGL(dual_update_kernel, dim3((waves + per_block - 1) / per_block), dim3(DU_THREADS), 0, s, d);
+}
+
+}  // namespace relp

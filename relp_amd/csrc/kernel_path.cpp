@@ -211,6 +211,19 @@ KernelPath plan_kernel_path(const relp_options& opt_, const MatrixData& md, cons
     return p;
 }
 
+std::string dual_refusal(const KernelPath& p) {
+    if (p.lu_mode) return "the dual simplex needs the explicit inverse: the LU carries (carry = 1, 2) are not supported";
+    if (p.network) return "the dual simplex needs the explicit inverse: the spanning-forest carry (carry = 3) is not supported";
+    if (p.bounded) return "the dual simplex does not know implicit upper bounds (implicit_bounds = 1 on an LP with a bound)";
+    if (p.eta_mode) return "the dual simplex does not read the deferred product form of the inverse (the dense pipeline)";
+    if (p.n_dense > 0) return "the dual simplex does not price a dense block (" + std::to_string(p.n_dense) + " dense columns)";
+    if (p.ftran_slices > 0) return "the dual simplex does not run beside the multi-block FTRAN";
+    if (p.generated_columns) return "the dual simplex reads the columns from the CSC: generated incidence columns are not supported";
+    if (p.ell_w == 2) return "the dual simplex does not take the two-entry column layout of graph LPs";
+    if (p.m > DUAL_MAX_ROWS) return "the dual simplex takes at most " + std::to_string(DUAL_MAX_ROWS) + " rows (this LP has " + std::to_string(p.m) + ")";
+    return std::string();
+}
+
 std::string kernel_path_json(const KernelPath& p) {
     static const char* storage[] = {"NONE", "I8_LANE", "F32_LANE", "F64_LANE", "I8_PERMUTED", "F32_ROWS", "F64_ROWS"};
     static const char* price[] = {"UNIT_PAIRS", "GENERATED", "WIDTH_2", "LDS", "GATHER"};

@@ -125,6 +125,12 @@ inline bool resolves_to_textbook(const relp_options& o, const DeviceMatrix& data
 KernelPath plan_kernel_path(const relp_options& o, const MatrixData& md, const DeviceColumns& cols, const DeviceMatrix& a,
                             const std::vector<std::string>* column_names = nullptr);
 
+// Why the dual simplex (dual.hip) does not take this plan, in words; empty: it does.  Its kernels read and write the explicit inverse
+// as it stands outside a batch, one column-major buffer with every column present, and know neither bounds nor generated columns:
+// they take the explicit carry without the dense pipeline, up to the row count of the single-workgroup kernels.
+constexpr int DUAL_MAX_ROWS = 8192;
+std::string dual_refusal(const KernelPath& p);
+
 // The plan as one JSON object (relp_debug_kernel_path); slack_of_row by its length only.
 std::string kernel_path_json(const KernelPath& p);
 

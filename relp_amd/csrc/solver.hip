@@ -83,6 +83,8 @@ void Solver::free_device() {
     h_rb_xb_ = h_rb_ub_ = nullptr;
     d_ = DeviceLP{};
     net_ = NetTree{};
+    dual_ = DualBuffers{};
+    dual_ready_ = false;
 }
 
 void Solver::reset_stats() { stats_ = relp_stats{}; }
@@ -422,6 +424,7 @@ void Solver::write_ctl(const Ctl& c) {
 void Solver::begin_phase_one() {
     if (!loaded_) throw std::runtime_error("no LP loaded");
     RELP_HIP(hipSetDevice(opt_.device));
+    dual_ready_ = false;
     const int m = d_.m, n = d_.n, n_art = d_.n_art;
     const std::vector<int>& basis = cols_.basis0;
     std::vector<int> pos = cols_.pos0();
@@ -701,6 +704,7 @@ void Solver::begin_phase_two() {
 void Solver::set_phase(int phase) {
     const int phase_before = phase_;
     phase_ = phase;
+    last_pivot_dual_ = false;
     RELP_HIP(hipMemcpyAsync(d_.cost, phase == 1 ? d_.cost1 : d_.cost2, d_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
     if (d_.cost8) {  // generated columns: the priced columns (never the artificials) cost 0 in phase one
         if (phase == 1) RELP_HIP(hipMemsetAsync(d_.cost8, 0, d_.n, stream_));
@@ -977,6 +981,7 @@ void Solver::invert_from_scratch() {
 void Solver::set_basis(const int* basis_columns) {
     if (!loaded_) throw std::runtime_error("no LP loaded");
     RELP_HIP(hipSetDevice(opt_.device));
+    dual_ready_ = false;
     const int m = d_.m, n = d_.n;
     std::vector<int> basis(m), pos(n, -1);
     if (!path_.bounded) {
@@ -1108,6 +1113,7 @@ long long Solver::iterate(long long count, int* stop_reason) {
         since_polish_ += made;
         pivots_[phase_ - 1] += made;
         if (made > 0) binv_identity_ = false;  // (the phase hand-over must not take the weights of the identity basis)
+        if (made > 0) last_pivot_dual_ = false;
         if (after.status == ST_NO_ENTERING || after.status == ST_UNBOUNDED) { reason = after.status; break; }
         if (after.status == ST_REFACTOR) {  // LU carry: should_refactor (or an unstable update) -- BasisInverse::invert
             // (the new factors may be on their way on the other stream: wait for them, replay, go on; else factorise now)
@@ -1180,7 +1186,6 @@ void Solver::solve(relp_result* result) {
     if (!loaded_) throw std::runtime_error("no LP loaded");
     RELP_HIP(hipSetDevice(opt_.device));
     const double t0 = now_seconds();
-    relp_result res{};
     exact_objective.clear();
     exact_primal.reset();
     exact_witnesses.reset();
@@ -1235,6 +1240,12 @@ void Solver::solve(relp_result* result) {
             tick("final polish");
         } else kind = RELP_RESULT_ITERATION_LIMIT;
     }
+    collect_result(kind, t0, true, tick, result);
+}
+
+// The tail of a solve (`solve`, `solve_dual`): the basis and the vertex read back, the result struct, the exact certificate.
+void Solver::collect_result(int kind, double t0, bool certify_verdicts, const std::function<void(const char*)>& tick, relp_result* result) {
+    relp_result res{};
     // results: Carry::current_bfs (carry/mod.rs:636-645) + reconstruct_solution (matrix_data.rs:402-411)
     const int m = d_.m;
     // (into the handle's pinned buffers, all behind the one wait of read_ctl)
@@ -1287,8 +1298,8 @@ void Solver::solve(relp_result* result) {
     // The exact certificate: optimality of the final basis; for the two other verdicts of `OptimizationResult`
     // (algorithm/mod.rs:43-47), which the reference decides exactly, a Farkas certificate / an unbounded ray.
     unbounded_column_ = kind == RELP_RESULT_UNBOUNDED ? c.q - d_.n_art : -1;
-    if (opt_.certify && !path_.bounded &&
-        (kind == RELP_RESULT_FINITE_OPTIMUM || kind == RELP_RESULT_INFEASIBLE || kind == RELP_RESULT_UNBOUNDED)) certify(&res);
+    if (opt_.certify && !path_.bounded && (kind == RELP_RESULT_FINITE_OPTIMUM || (certify_verdicts && (kind == RELP_RESULT_INFEASIBLE || kind == RELP_RESULT_UNBOUNDED))))
+        certify(&res);
     else if (opt_.certify && kind == RELP_RESULT_FINITE_OPTIMUM) certify(&res);
     last_result = res;
     if (result) *result = res;
@@ -1335,6 +1346,147 @@ void Solver::certify(relp_result* result) {
     result->exact_repair_pivots = repairs;
     result->certify_seconds = now_seconds() - t0;
     if (!ok) last_error = message;
+}
+
+// ---- dual simplex from a given basis (dual.hip) -------------------------------------------------------
+// The optimal basis of an LP stays dual feasible when rows are appended or a right-hand side is tightened, and is primal infeasible
+// where the change bites: the caller loads the changed LP and passes the old basis, extended by the slack of each new row.
+void Solver::begin_dual(const int* basis_columns) {
+    if (!loaded_) throw std::runtime_error("no LP loaded");
+    RELP_HIP(hipSetDevice(opt_.device));
+    const std::string refusal = dual_refusal(path_);
+    if (!refusal.empty()) throw std::invalid_argument(refusal);
+    const int m = d_.m, n = d_.n, n_art = d_.n_art;
+    for (int i = 0; i < m; ++i)
+        if (basis_columns[i] < 0)
+            throw std::invalid_argument("begin_dual: the basis holds an artificial column (code " + std::to_string(basis_columns[i]) + " on row " + std::to_string(i) +
+                                        "): the dual simplex starts from a basis of the LP's own columns");
+    set_basis(basis_columns);  // inverse from scratch, x_B, the costs of phase two, -pi; every column of the inverse marked touched
+    if (!dual_.alpha_row) {
+        dual_.blocks = dual_blocks(n_art, n);
+        dual_.alpha_row = device_alloc<double>(n);
+        dual_.d = device_alloc<double>(n);
+        dual_.part_theta = device_alloc<double>(dual_.blocks);
+        dual_.cand_key = device_alloc<double>(dual_.blocks);
+        dual_.cand_j = device_alloc<int>(dual_.blocks);
+    }
+    const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
+    dual_lds_ = 2 * (size_t)m * sizeof(double) <= lds_max;
+    std::vector<double> cbar(n);
+    relative_costs(cbar.data());
+    for (int i = 0; i < m; ++i) cbar[cols_.to_device(basis_columns[i])] = 0.0;  // (a basic column's is zero up to rounding)
+    for (int j = n_art; j < n; ++j)
+        if (cbar[j] < -opt_.tol_dual) {
+            char value[32];
+            snprintf(value, sizeof(value), "%.6g", cbar[j]);
+            throw std::invalid_argument("begin_dual: the basis is not dual feasible: column " + std::to_string(j - n_art) + " has the relative cost " + value +
+                                        " (a primal clean-up from such a basis is not part of the dual simplex)");
+        }
+    dual_pivots_ = 0;
+    dual_device_seconds_ = 0.0;
+    dual_ready_ = true;
+}
+
+// One batch: the budget, then five launches per pivot (dual.hpp).  The chain is a run of no-ops from the first kernel that stops it.
+void Solver::launch_dual_pivots(int count) {
+    stats_.launches += 1 + 5LL * count;
+    launch_budget(d_, count, stream_);
+    const bool textbook = path_.ratio_textbook;
+    for (int it = 0; it < count; ++it) {
+        launch_dual_leave(d_, opt_.harris_delta, stream_);
+        launch_dual_row(d_, dual_, dual_lds_, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, stream_);
+        launch_dual_choose(d_, dual_, opt_.tol_pivot, textbook, stream_);
+        launch_dual_pivot(d_, dual_, opt_.tol_pivot, stream_);
+        launch_dual_update(d_, stream_);
+    }
+}
+
+long long Solver::iterate_dual(long long count, int* stop_reason) {
+    if (!dual_ready_) throw std::runtime_error("iterate_dual: no dual loop started (begin_dual comes first)");
+    RELP_HIP(hipSetDevice(opt_.device));
+    long long done = 0;
+    int reason = ST_BUDGET;
+    Ctl c = read_ctl();
+    if (c.status != ST_RUNNING) {  // an earlier loop stopped here: whether a row is infeasible now is for the kernels to say
+        c.status = ST_RUNNING;
+        write_ctl(c);
+    }
+    long long iters_before = c.iters;
+    const int full_batch = std::max(1, opt_.pivots_per_launch);
+    bool polished_for_pivot = false;
+    while (done < count) {
+        const long long room = opt_.polish_period > 0 ? (long long)opt_.polish_period * polish_scale_ - since_polish_ : count;
+        if (room <= 0) { polish(true); continue; }
+        const int batch = (int)std::min<long long>({count - done, room, (long long)full_batch});
+        RELP_HIP(hipEventRecord(ev_a_, stream_));  // the device time of the batch, for relp_get_record_json ("dual_device_seconds")
+        launch_dual_pivots(batch);
+        RELP_HIP(hipEventRecord(ev_b_, stream_));
+        Ctl after = read_ctl();
+        float batch_ms = 0.0f;
+        RELP_HIP(hipEventElapsedTime(&batch_ms, ev_a_, ev_b_));
+        dual_device_seconds_ += 1e-3 * batch_ms;
+        const long long made = after.iters - iters_before;
+        iters_before = after.iters;
+        done += made;
+        since_polish_ += made;
+        dual_pivots_ += made;
+        if (made > 0) {
+            binv_identity_ = false;
+            last_pivot_dual_ = true;
+        }
+        if (after.status == ST_NO_ENTERING || after.status == ST_UNBOUNDED) { reason = after.status; break; }
+        if (after.status == ST_REFACTOR) {
+            // dual_pivot_kernel found the FTRAN value of its pivot unusable where the row's value was usable: the inverse has drifted.
+            // Nothing of that pivot was written.  A forced polish, and the loop asks again; twice in a row at one basis is an error.
+            if (made == 0 && polished_for_pivot) throw std::runtime_error("iterate_dual: the pivot element of row " + std::to_string(after.p) +
+                                                                          " is not usable after a polish of the inverse (an ill-conditioned basis)");
+            polish(true, true);
+            polished_for_pivot = true;
+            after.status = ST_RUNNING;
+            write_ctl(after);
+            continue;
+        }
+        polished_for_pivot = false;
+        if (made == 0) break;  // defensive: nothing happened
+    }
+    if (stop_reason) *stop_reason = reason;
+    return done;
+}
+
+void Solver::solve_dual(const int* basis_columns, relp_result* result) {
+    if (!loaded_) throw std::runtime_error("no LP loaded");
+    RELP_HIP(hipSetDevice(opt_.device));
+    const double t0 = now_seconds();
+    exact_objective.clear();
+    exact_primal.reset();
+    exact_witnesses.reset();
+    begin_dual(basis_columns);
+    const long long cap = opt_.max_pivots > 0 ? opt_.max_pivots : 200LL * (d_.m + d_.n) + 100000;
+    int kind = RELP_RESULT_NONE;
+    int reason = 0;
+    iterate_dual(cap, &reason);
+    // primal feasible in f64: the same question again on the polished state, while that still finds an infeasible row
+    for (int round = 0; round < 3 && reason == ST_NO_ENTERING; ++round) {
+        polish(true, true);
+        if (iterate_dual(cap - dual_pivots_, &reason) == 0) break;
+    }
+    if (reason == ST_UNBOUNDED) kind = RELP_RESULT_INFEASIBLE;
+    else if (reason != ST_NO_ENTERING) kind = RELP_RESULT_ITERATION_LIMIT;
+    if (kind == RELP_RESULT_NONE) {
+        // the primal loop from the primal-feasible basis: the weights recomputed, the control block reset (minus_obj kept); it
+        // removes relative costs that drifted below -tol_dual and normally makes no pivot
+        set_phase(2);
+        iterate(cap - dual_pivots_, &reason);
+        if (reason == ST_UNBOUNDED) kind = RELP_RESULT_UNBOUNDED;
+        else if (reason == ST_NO_ENTERING) {
+            kind = RELP_RESULT_FINITE_OPTIMUM;
+            polish(true);
+        } else kind = RELP_RESULT_ITERATION_LIMIT;
+    }
+    const bool dual_unbounded = kind == RELP_RESULT_INFEASIBLE;
+    collect_result(kind, t0, !dual_unbounded, [](const char*) {}, result);
+    if (dual_unbounded)  // (reported with certified = 0 whatever the options ask for)
+        last_error ="the dual simplex does not certify infeasibility yet (the Farkas vector is the row of the inverse at which the dual is unbounded)";
 }
 
 // ---- LU carry ---------------------------------------------------------------------------------------
@@ -1671,7 +1823,7 @@ void Solver::solve_exact(int first_limbs, int max_limbs, long long max_pivots, i
 void Solver::last_pivot(int* phase, int* column, int* row, int* leaving) {
     const Ctl c = read_ctl();
     const bool any = c.iters > 0 && c.p >= 0;
-    *phase = phase_;
+    *phase = last_pivot_dual_ ? 3 : phase_;
     *column = any ? c.q : -1;
     *row = any ? c.p : -1;
     *leaving = any ? c.leaving : -1;
@@ -1712,6 +1864,7 @@ void Solver::bring_into_basis(int column, int row) {
     pivots_[phase_ - 1] += 1;
     since_polish_ += 1;
     binv_identity_ = false;
+    last_pivot_dual_ = false;
     if (c.status == ST_REFACTOR) refactor_lu(true);  // LU carry: `should_refactor` was true for this pivot
 }
 // `BasisInverse::should_refactor` + `invert` (lower_upper/mod.rs:78-92, 249-252) on demand: the Newton-Schulz polish of the

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -22,6 +23,7 @@
 #include "device_memory.hpp"
 #include "model.hpp"
 #include "lu.hpp"
+#include "dual.hpp"
 
 namespace relp {
 
@@ -342,6 +344,16 @@ public:
     void begin_phase_two();
     void set_basis(const int* basis_columns);
     long long iterate(long long count, int* stop_reason);
+    // Dual simplex from a dual-feasible basis of the loaded LP, given as set_basis takes it (dual.hpp; DESIGN.md "Dual simplex from a
+    // given basis").  begin_dual: the refusals (std::invalid_argument: a plan the dual kernels do not take, an artificial in the basis,
+    // a basis that is not dual feasible), set_basis, the loop's buffers; no pivot.  iterate_dual: up to `count` dual pivots; the stop
+    // reasons are ST_NO_ENTERING (no infeasible row is left), ST_UNBOUNDED (the LP is infeasible) and ST_BUDGET.  solve_dual: both,
+    // then the primal loop from the primal-feasible basis (it normally makes no pivot) and the result as `solve` reports it.
+    void begin_dual(const int* basis_columns);
+    long long iterate_dual(long long count, int* stop_reason);
+    void solve_dual(const int* basis_columns, relp_result* result);
+    long long dual_pivots() const { return dual_pivots_; }  // of the last solve_dual / since begin_dual
+    double dual_device_seconds() const { return dual_device_seconds_; }  // ... and the device time of their batches (stream events)
 
     // fine-grained ops (trait parity)
     void ftran(int nnz, const int* rows, const double* values, double* out);
@@ -429,7 +441,18 @@ private:
     int* h_rb_pos_ = nullptr;       // [n]
     double* h_rb_ub_ = nullptr;     // [n]
     int drive_out_artificials();
+    // The tail of a solve: read-backs, h_basis_, h_solution_, the objective and the exact certificate (`certify_verdicts`: of the
+    // INFEASIBLE and UNBOUNDED verdicts too, where the options ask for one) into last_result and *result.
+    void collect_result(int kind, double t0, bool certify_verdicts, const std::function<void(const char*)>& tick, relp_result* result);
     void certify(relp_result* result);
+    // the dual loop (dual.hip)
+    DualBuffers dual_;
+    bool dual_lds_ = false;         // its row kernel stages rho and -pi in LDS (2 m doubles within relp_options.price_lds_max)
+    bool dual_ready_ = false;       // begin_dual has run on the loaded LP
+    bool last_pivot_dual_ = false;  // the last pivot was a dual one: last_pivot reports phase 3
+    long long dual_pivots_ = 0;
+    double dual_device_seconds_ = 0.0;
+    void launch_dual_pivots(int count);
     std::vector<double> net_host_solve(const HostTree& t, bool transposed, const std::vector<double>& v) const;  // B^-1 v or v' B^-1
     CertifyScratch certify_scratch_;
     // spanning-forest carry (network_carry.hip)

@@ -1,0 +1,117 @@
+"""What the dual simplex saves on a re-solve after cuts, and what one of its pivots costs (a real MI355X; not a test).
+
+For the cut cases of tests/dual_lps.py at m = 1025 and m = 2049 (the parent solved cold and certified, 24 cuts its vertex violates):
+  cold       a cold certified solve of the child: ms, pivots
+  dual       ``solve_dual`` from the parent's basis, certified: ms, dual pivots, primal clean-up pivots
+  per pivot  wall time of ``iterate_dual(256)`` over the pivots it made, beside ``iterate(256)`` of the primal loop from the slack
+             basis on the same handle -- as the handle runs it (fused pivot or three kernels, replayed from a graph) and as three
+             kernels in plain launches, which is the form the dual loop has (five plain launches).  Every call ends in a stream
+             synchronise, so these are times a caller sees, launch overhead included.
+  device     the same without the host: the dual batch between two events on the handle's stream (``dual_device_seconds`` of
+             ``record()``: five kernels per pivot and the gaps between them), and the kernels of a primal pivot one by one inside
+             the running loop (``relp_profile_kernel``: pricing + ratio test / fused pivot + update, their sum, no gaps).
+``--decimal`` divides every matrix value by 10: the Harris rule runs instead of the reference's.
+Every figure is the median of 5 runs after one warm-up, in one process.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for path in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, path)
+import relp_amd  # noqa: E402
+import dual_lps  # noqa: E402
+
+RUNS = 5
+
+
+def median_of(run):
+    run()  # warm-up
+    samples = [run() for _ in range(RUNS)]
+    return [statistics.median(column) for column in zip(*samples)]
+
+
+def probe(m, decimal, n_cuts):
+    seed, default_cuts = dual_lps.STATE_CASES[m]
+    case = dual_lps.cut_case(m, dual_lps.MIXED, seed, n_cuts or default_cuts, decimal=decimal)
+    parent = relp_amd.Solver(certify=1).load_model(case.parent)
+    assert parent.solve_relaxation().certified
+    child, basis, _ = case.child(parent.basis(), parent.solution_exact())
+    parent.close()
+    solver = relp_amd.Solver(certify=1).load_model(child)
+    plain = relp_amd.Solver(certify=0, pivot_kernels=1, use_graph=0).load_model(child)
+
+    def cold():
+        result = solver.solve_relaxation()
+        assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+        return 1e3 * (result.solve_seconds + result.certify_seconds), result.pivots_phase_one + result.pivots_phase_two, solver.objective_exact()
+
+    def dual():
+        result = solver.solve_dual(basis)
+        assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+        return 1e3 * (result.solve_seconds + result.certify_seconds), solver.dual_pivots(), result.pivots_phase_two, solver.objective_exact()
+
+    def dual_pivot():
+        solver.begin_dual(basis)
+        started = time.perf_counter()
+        done, _ = solver.iterate_dual(256)
+        return (1e6 * (time.perf_counter() - started) / max(1, done), done)
+
+    def dual_device():
+        solver.begin_dual(basis)
+        done, _ = solver.iterate_dual(256)
+        return (1e6 * solver.record()["dual_device_seconds"] / max(1, done),)
+
+    def primal_kernels(handle, kernels):
+        def run():
+            handle.begin_phase_one()
+            handle.iterate(64)
+            return tuple(1e6 * handle.profile_kernel(which, 64) for which in kernels)
+        return run
+
+    def primal_pivot(handle):
+        def run():
+            handle.begin_phase_one()
+            started = time.perf_counter()
+            done, _ = handle.iterate(256)
+            return (1e6 * (time.perf_counter() - started) / max(1, done), done)
+        return run
+
+    exact = {cold()[2], dual()[3]}
+    assert len(exact) == 1, exact
+    cold_ms, cold_pivots = median_of(lambda: cold()[:2])
+    dual_ms, dual_pivots, clean_up = median_of(lambda: dual()[:3])
+    dual_us, dual_done = median_of(dual_pivot)
+    primal_us, _ = median_of(primal_pivot(solver))
+    plain_us, _ = median_of(primal_pivot(plain))
+    plan = child.kernel_path()
+    (dual_device_us,) = median_of(dual_device)
+    own_kernels = median_of(primal_kernels(solver, (0, 1) if plan["fused"] else (0, 1, 2)))
+    plain_kernels = median_of(primal_kernels(plain, (0, 1, 2)))
+    print("m = %d + %d cuts (%s, %s): cold %.1f ms, %d pivots | solve_dual %.1f ms, %d dual + %d primal pivots | per pivot: dual %.1f us "
+          "(%d pivots), primal %.1f us as the handle runs it, %.1f us as three kernels in plain launches | device time per pivot: dual %.1f us, "
+          "primal kernels %s = %.1f us as the handle runs it, %s = %.1f us as three kernels" % (
+              m, child.nr_rows - m, "decimal" if decimal else "integer", "fused pivot" if plan["fused"] else "three-kernel pivot", cold_ms, cold_pivots,
+              dual_ms, dual_pivots, clean_up, dual_us, dual_done, primal_us, plain_us, dual_device_us,
+              " + ".join("%.1f" % v for v in own_kernels), sum(own_kernels), " + ".join("%.1f" % v for v in plain_kernels), sum(plain_kernels)))
+    solver.close()
+    plain.close()
+
+
+def main():
+    parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
+    parser.add_argument("--decimal", action="store_true")
+    parser.add_argument("--cuts", type=int, default=0, help="cuts per child (default: those of tests/dual_lps.py)")
+    args = parser.parse_args()
+    for m in args.sizes:
+        probe(m, args.decimal, args.cuts)
+
+
+if __name__ == "__main__":
+    main()
