@@ -6,7 +6,7 @@
 // schedule[t], tickets are drawn by an atomic fetch-add -- or by the caller's `next_ticket`, so that several processes (one
 // rank per GPU under torch.distributed) can share ONE queue.  No collective and no data exchange between workers.
 // Built on the public C ABI only (relp_create / relp_load_model / relp_solve_relaxation): what a caller could write itself.
-#include "solver.hpp"
+#include "options.hpp"
 #include <atomic>
 #include <chrono>
 #include <cstring>

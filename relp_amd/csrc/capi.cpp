@@ -9,6 +9,7 @@
 #include "network.hpp"
 #include "presolve.hpp"
 #include "exact_values.hpp"
+#include "options.hpp"
 #include "solver.hpp"
 
 using namespace relp;

@@ -5,7 +5,8 @@
 
 #include "lu.hpp"
 #include "lu_factor.hpp"
-#include "solver.hpp"
+#include "device_memory.hpp"
+#include "options.hpp"
 
 using namespace relp;
 

@@ -29,7 +29,8 @@
 #include "certify_parts.hpp"
 #include "rational_reconstruct.hpp"
 #include "lu_host.hpp"
-#include "solver.hpp"
+#include "launch.hpp"
+#include "options.hpp"
 
 namespace relp {
 
@@ -849,7 +850,7 @@ void CertifyScratch::release() {
 //         phase_one.rs:123-179) with a POSITIVE optimum -- the dual solution y is a Farkas certificate (y'A <= 0, y'b > 0).
 // mode 2: the LP is UNBOUNDED along provider column `entering`: x_B >= 0, cbar_q < 0 and B^-1 a_q <= 0 exactly
 //         (phase_two.rs:53; zero on the rows whose basic variable is a zero-level artificial).
-struct ExactPrimal {  // (declared in solver.hpp)
+struct ExactPrimal {  // (declared in certify.hpp)
     std::vector<int> basis;     // provider column per row (-1-k: artificial k, value 0)
     std::vector<BigInt> numer;  // x_B[k] = numer[k] / denom
     BigInt denom;
@@ -1272,9 +1273,7 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
                 int* d_levu = reinterpret_cast<int*>(d_factors + o_levu);
                 int* d_rowu = reinterpret_cast<int*>(d_factors + o_rowu);
                 static PerDeviceOnce configured_levels;  // (certificates run from the worker threads of a batch, possibly on several devices)
-                configured_levels.run([] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modular_inverse_levels_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                });
+                allow_full_lds_once(configured_levels, &modular_inverse_levels_kernel);
                 ModularFactors mf{d_rowpos, d_colpos, d_ls, d_lc, d_lv, d_us, d_uc, d_uv, d_dinv, d_levl, d_rowl, levels_l, d_levu, d_rowu, levels_u};
                 hipLaunchKernelGGL(modular_inverse_levels_kernel, dim3((m + 3) / 4), dim3(256), level_lds, stream, m, candidate, mf, dCT);
                 hipLaunchKernelGGL(transpose_u32_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(256), 0, stream, m, dCT, dC);
@@ -1290,9 +1289,7 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
                 const bool in_lds = (size_t)columns * m * sizeof(u32) <= room;
                 if (!in_lds) staged = false;
                 static PerDeviceOnce configured;
-                configured.run([] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&modular_inverse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                });
+                allow_full_lds_once(configured, &modular_inverse_kernel);
                 if (!in_lds) columns = 64;
                 const size_t lds = in_lds ? (size_t)columns * m * sizeof(u32) + (staged ? factor_bytes : 0) : 0;
                 hipLaunchKernelGGL(modular_inverse_kernel, dim3((m + columns - 1) / columns), dim3(staged ? 256 : columns), lds, stream, m, candidate,

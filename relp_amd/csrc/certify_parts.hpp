@@ -10,7 +10,8 @@
 #include <vector>
 
 #include "bigint.hpp"
-#include "solver.hpp"
+#include "certify.hpp"
+#include "device_columns.hpp"
 
 namespace relp {
 
@@ -48,7 +49,7 @@ struct ExactVector {           // numer[i] / denom
     BigInt denom = BigInt(1);
 };
 
-// The exact vectors a certificate proved its verdict with (declared in solver.hpp), in the terms of the caller's LP.  Big integers
+// The exact vectors a certificate proved its verdict with (declared in certify.hpp), in the terms of the caller's LP.  Big integers
 // over one denominator per vector; the "num/den" texts are made on demand (exact_witness_values).  A certificate only KEEPS what
 // the witnesses are made of -- most results are never asked for theirs: the row and cost multipliers of the integer scaling are
 // folded into y by the first exact_witness_values (under `finish_guard`: accessors may come from several threads), and x is

@@ -11,6 +11,7 @@
 #include <limits>
 #include <vector>
 
+#include "../../include/relp_amd.h"
 #include "model.hpp"
 
 namespace relp {
@@ -87,6 +88,19 @@ struct DeviceMatrix {
         return small_integers;
     }
 };
+
+// Implicit upper bounds apply to an LP that has a finite bound (relp_options.implicit_bounds); the device LP then has the
+// constraint rows and the first four column groups only.
+inline bool implicit_bounds_apply(const relp_options& o, const MatrixData& md) { return o.implicit_bounds != 0 && md.nr_variable_bounds() > 0; }
+inline DeviceColumns device_columns(const MatrixData& md, bool bounded) {
+    return bounded ? DeviceColumns(md, md.nr_constraints(), md.col_end[3]) : DeviceColumns(md);
+}
+
+// `Tableau::select_primal_pivot_row` (tableau/mod.rs:287-313): which ratio test runs.  TEXTBOOK asks for the reference's rule; AUTO
+// (the default) takes it where the data are small integers and the kernels of the path implement it, Harris on decimal data.
+inline bool resolves_to_textbook(const relp_options& o, const DeviceMatrix& data, bool kernels_have_it) {
+    return o.ratio_rule == RELP_RATIO_TEXTBOOK || (o.ratio_rule == RELP_RATIO_AUTO && data.small_integer_data() && kernels_have_it);
+}
 
 // ---- implicit upper bounds: between the device LP (constraint rows, the first four column groups) and the reference's formulation
 // (every row of MatrixData, the VariableBound / SlackBound rows and their slack columns of matrix_data.rs:104-145 included) ----------

@@ -9,6 +9,7 @@
 // reduction in a fixed order.
 #include <hip/hip_runtime.h>
 
+#include "launch.hpp"
 #include "pivot_step.hpp"
 #include "solver.hpp"
 #include "wave_ops.hpp"
@@ -313,10 +314,7 @@ void launch_dual_leave(const DeviceLP& d, double harris_delta, hipStream_t s) {
 }
 void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, double tol_pivot, double slack, hipStream_t s) {
     static PerDeviceOnce once;  // more than 64 KB of dynamic LDS is an opt-in, per device
-    once.run([] {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dual_row_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8192 * 8) != hipSuccess)
-            (void)hipGetLastError();
-    });
+    allow_full_lds_once(once, &dual_row_kernel<true>);
     if (lds) hipLaunchKernelGGL(dual_row_kernel<true>, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 2 * (size_t)d.m * sizeof(double), s, d, b, tol_pivot, slack);
     else hipLaunchKernelGGL(dual_row_kernel<false>, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 0, s, d, b, tol_pivot, slack);
 }

@@ -9,7 +9,7 @@
 
 namespace relp {
 
-struct DeviceLP;  // solver.hpp, which includes this file for the handle's DualBuffers
+struct DeviceLP;  // device_lp.hpp; solver.hpp includes this file for the handle's DualBuffers
 
 // Allocated by the first begin_dual of a loaded LP, freed with the LP's other device buffers.
 struct DualBuffers {

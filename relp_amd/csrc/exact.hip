@@ -30,7 +30,9 @@
 #include <vector>
 
 #include "bigint.hpp"
-#include "solver.hpp"
+#include "device_columns.hpp"
+#include "exact.hpp"
+#include "launch.hpp"
 #include <hip/hip_cooperative_groups.h>
 
 #include "grid_barrier.hpp"
@@ -3946,13 +3948,6 @@ void exact_simplex(const StandardForm& form, int device, hipStream_t stream, int
     int* d_row_list = dalloc<int>((size_t)2 * m, owned);
     int* d_col_heavy = dalloc<int>((size_t)m + 1, owned);
     int* d_col_light = dalloc<int>((size_t)m + 1, owned);
-#ifdef RELP_REPRO_R5_LIST_RACE
-    // (diagnostic build, tools/repro_16_limb_hang.py: the column classes of the update in the tournaments' arrays again, as they were when the
-    //  16-limb matrix-core run hung on ISRAEL in round 5 -- the splitter workgroup overwrites bracket[0] / cand[..] while a workgroup late
-    //  out of the ratio test's last barrier still reads the winner through them)
-    d_col_heavy = d_bracket;
-    d_col_light = d_cand;
-#endif
     RELP_HIP(hipMemcpyAsync(d_col_start, col_start.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
     RELP_HIP(hipMemcpyAsync(d_row_index, row_index.data(), row_index.size() * sizeof(int), hipMemcpyHostToDevice, stream));
     RELP_HIP(hipMemcpyAsync(d_value, value.data(), value.size() * sizeof(i64), hipMemcpyHostToDevice, stream));
@@ -4100,7 +4095,7 @@ void exact_simplex(const StandardForm& form, int device, hipStream_t stream, int
         }
         void* args[] = {(void*)&lp};
         RELP_HIP(hipLaunchCooperativeKernel(kernel, dim3(grid), dim3(EX_THREADS), args, 0, stream));
-        RELP_HIP(hipGetLastError());
+        check_launch("exact_simplex_kernel");
         int out[16];
         RELP_HIP(hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, stream));
         RELP_HIP(hipStreamSynchronize(stream));
@@ -4256,7 +4251,7 @@ void exact_words_test(int device, int limbs, int mode, int count, const unsigned
         case 128: hipLaunchKernelGGL(exact_words_test_kernel<128>, grid, block, 0, 0, mode, d_a, d_b, d_out); break;
         default: throw std::invalid_argument("limbs must be 16, 32, 64 or 128");
     }
-    RELP_HIP(hipGetLastError());
+    check_launch("exact_words_test_kernel");
     RELP_HIP(hipDeviceSynchronize());
     RELP_HIP(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
 }
@@ -4370,7 +4365,7 @@ void exact_finish_entries(int device, int limbs, int count, const unsigned long 
         case 128: hipLaunchKernelGGL(exact_finish_test_kernel<128>, grid, block, 0, 0, lp, count, d_words, shift, flip, d_bits); break;
         default: throw std::invalid_argument("limbs must be 16, 32, 64 or 128");
     }
-    RELP_HIP(hipGetLastError());
+    check_launch("exact_finish_test_kernel");
     RELP_HIP(hipDeviceSynchronize());
     RELP_HIP(hipMemcpy(N_out, d_N, entries * limbs * sizeof(u64), hipMemcpyDeviceToHost));
     RELP_HIP(hipMemcpy(bits_out, d_bits, entries * sizeof(int), hipMemcpyDeviceToHost));

@@ -25,7 +25,8 @@
 #include <vector>
 
 #include "../../include/relp_amd.h"
-#include "solver.hpp"
+#include "launch.hpp"
+#include "rat.hpp"
 
 namespace relp {
 namespace {
@@ -460,7 +461,7 @@ public:
         RELP_HIP(hipMalloc((void**)&source.p, m_ * sizeof(int)));
         RELP_HIP(hipMemcpy(source.p, row_of_column.data(), m_ * sizeof(int), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(bix_permute_rows_kernel, dim3(launch_blocks((long long)m_ * m_)), dim3(128), 0, 0, N_, N2_, m_, W_, source.p);
-        RELP_HIP(hipGetLastError());
+        check_launch("bix_permute_rows_kernel");
         RELP_HIP(hipDeviceSynchronize());
         std::swap(N_, N2_);
         have_column_ = false;
@@ -481,7 +482,7 @@ public:
             RELP_HIP(hipMalloc((void**)&scales.p, m_ * sizeof(i64)));
             RELP_HIP(hipMemcpy(scales.p, row_scale.data(), m_ * sizeof(i64), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(bix_scale_columns_kernel, dim3(launch_blocks((long long)m_ * m_)), dim3(128), 0, 0, N_, m_, W_, scales.p);
-            RELP_HIP(hipGetLastError());
+            check_launch("bix_scale_columns_kernel");
             RELP_HIP(hipDeviceSynchronize());
         }
     }
@@ -494,7 +495,7 @@ public:
         for (;;) {
             upload_column(nnz, rows, scaled);
             hipLaunchKernelGGL(bix_left_kernel, dim3(launch_blocks(m_)), dim3(128), 0, 0, N_, m_, W_, nnz, d_rows_, d_values_, alpha_, 0, m_);
-            RELP_HIP(hipGetLastError());
+            check_launch("bix_left_kernel");
             // alpha~ must fit the width it is multiplied at
             hipLaunchKernelGGL(bix_bits_kernel, dim3(launch_blocks(m_)), dim3(128), 0, 0, alpha_, (long long)m_, W_ + 2, alpha_bits_);
             std::vector<int> bits(m_);
@@ -523,7 +524,7 @@ public:
         const i64 scale = scale_column(nnz, index, num, den, scaled);
         upload_column(nnz, index, scaled);
         hipLaunchKernelGGL(bix_right_kernel, dim3(launch_blocks(m_)), dim3(128), 0, 0, N_, m_, W_, nnz, d_rows_, d_values_, row_out_);
-        RELP_HIP(hipGetLastError());
+        check_launch("bix_right_kernel");
         RELP_HIP(hipMemcpy(numerators_out, row_out_, (size_t)m_ * (W_ + 2) * sizeof(u64), hipMemcpyDeviceToHost));
         denominator(scale, denominator_out);
     }
@@ -549,7 +550,7 @@ public:
         RELP_HIP(hipMemcpy(d_den, denominator_in, vw * sizeof(u64), hipMemcpyHostToDevice));
         hipLaunchKernelGGL(bix_right_words_kernel, dim3(launch_blocks(m_)), dim3(128), 0, 0, N_, m_, W_, nnz, d_index, d_values, vw, d_out, n_out);
         hipLaunchKernelGGL(bix_product_kernel, dim3(1), dim3(1), 0, 0, D_, W_, d_den, vw, d_out + (size_t)m_ * n_out, n_out);
-        RELP_HIP(hipGetLastError());
+        check_launch("bix_product_kernel");
         RELP_HIP(hipMemcpy(numerators_out, d_out, (size_t)m_ * n_out * sizeof(u64), hipMemcpyDeviceToHost));
         RELP_HIP(hipMemcpy(denominator_out, d_out + (size_t)m_ * n_out, (size_t)n_out * sizeof(u64), hipMemcpyDeviceToHost));
         return n_out;
@@ -569,7 +570,7 @@ public:
         const i64 scale = scale_column(nnz, rows, num, den, scaled);
         upload_column(nnz, rows, scaled);
         hipLaunchKernelGGL(bix_left_kernel, dim3(1), dim3(64), 0, 0, N_, m_, W_, nnz, d_rows_, d_values_, row_out_, i, 1);
-        RELP_HIP(hipGetLastError());
+        check_launch("bix_left_kernel");
         RELP_HIP(hipMemcpy(numerator_out, row_out_, (size_t)(W_ + 2) * sizeof(u64), hipMemcpyDeviceToHost));
         denominator(scale, denominator_out);
         bool nonzero = false;
@@ -614,7 +615,7 @@ public:
             hipLaunchKernelGGL(bix_factors_kernel, dim3(launch_blocks(m_)), dim3(128), 0, 0, alpha_, u_, m_, W_, factors_);
             hipLaunchKernelGGL(bix_pivot_kernel, dim3(launch_blocks((long long)m_ * m_)), dim3(128), 0, 0, N_, N2_, m_, W_, p, c1_, factors_, shift_, flip, (i64)alpha_scale_);
             hipLaunchKernelGGL(bix_new_denominator_kernel, dim3(1), dim3(1), 0, 0, alpha_ + (size_t)p * (W_ + 2), W_, flip, D_);
-            RELP_HIP(hipGetLastError());
+            check_launch("bix_new_denominator_kernel");
             RELP_HIP(hipDeviceSynchronize());
             std::swap(N_, N2_);
             have_column_ = false;
@@ -716,7 +717,7 @@ private:
         allocate(2 * from);
         hipLaunchKernelGGL(bix_widen_kernel, dim3(launch_blocks((long long)m_ * m_)), dim3(128), 0, 0, old_N, N_, (long long)m_ * m_, from, W_);
         hipLaunchKernelGGL(bix_widen_kernel, dim3(1), dim3(1), 0, 0, old_D, D_, 1LL, from, W_);
-        RELP_HIP(hipGetLastError());
+        check_launch("bix_widen_kernel");
         RELP_HIP(hipDeviceSynchronize());
         for (u64* p : {old_N, old_N2, old_D, old_alpha, old_row, old_u, old_c1, old_f, old_s}) (void)hipFree(p);
     }
@@ -754,7 +755,7 @@ private:
         upload_column(nnz, column_rows_.data(), column_values_);
         hipLaunchKernelGGL(bix_left_kernel, dim3(launch_blocks(m_)), dim3(128), 0, 0, N_, m_, W_, nnz, d_rows_, d_values_, alpha_, 0, m_);
         hipLaunchKernelGGL(bix_bits_kernel, dim3(launch_blocks(m_)), dim3(128), 0, 0, alpha_, (long long)m_, W_ + 2, alpha_bits_);
-        RELP_HIP(hipGetLastError());
+        check_launch("bix_bits_kernel");
     }
     void download_alpha(std::vector<u64>& out) {
         out.resize((size_t)m_ * (W_ + 2));
@@ -762,7 +763,7 @@ private:
     }
     void denominator(i64 scale, u64* out) {  // D * scale, W + 2 words
         hipLaunchKernelGGL(bix_scaled_copy_kernel, dim3(1), dim3(1), 0, 0, D_, W_, scale, scratch_denominator(), W_ + 2);
-        RELP_HIP(hipGetLastError());
+        check_launch("bix_scaled_copy_kernel");
         RELP_HIP(hipMemcpy(out, scratch_denominator(), (size_t)(W_ + 2) * sizeof(u64), hipMemcpyDeviceToHost));
     }
     u64* scratch_denominator() { return row_out_; }  // (read back before the next use; row results are copied out first)

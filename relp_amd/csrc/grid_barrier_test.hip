@@ -16,7 +16,8 @@
 #include <vector>
 
 #include "grid_barrier.hpp"
-#include "solver.hpp"
+#include "exact.hpp"
+#include "launch.hpp"
 
 namespace relp {
 
@@ -100,7 +101,7 @@ void grid_barrier_test(int device, int grid, int rounds, int reads, int mode, lo
     RELP_HIP(hipMemcpy(d_out, host_out, sizeof(host_out), hipMemcpyHostToDevice));
     void* args[] = {(void*)&d_barrier, (void*)&d_slots, (void*)&rounds, (void*)&reads, (void*)&mode, (void*)&d_out};
     RELP_HIP(hipLaunchCooperativeKernel((const void*)grid_barrier_test_kernel, dim3(grid), dim3(GB_THREADS), args, 0, nullptr));
-    RELP_HIP(hipGetLastError());
+    check_launch("grid_barrier_test_kernel");
     RELP_HIP(hipDeviceSynchronize());
     RELP_HIP(hipMemcpy(host_out, d_out, sizeof(host_out), hipMemcpyDeviceToHost));
     RELP_HIP(hipMemcpy(words.data(), d_barrier, words.size() * sizeof(unsigned), hipMemcpyDeviceToHost));

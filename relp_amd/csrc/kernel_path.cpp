@@ -6,6 +6,8 @@
 #include <sstream>
 #include <stdexcept>
 
+#include "device_columns.hpp"
+
 namespace relp {
 
 KernelPath plan_kernel_path(const relp_options& opt_, const MatrixData& md, const DeviceColumns& cols, const DeviceMatrix& a,

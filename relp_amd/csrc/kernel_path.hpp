@@ -7,10 +7,13 @@
 #include <vector>
 
 #include "../../include/relp_amd.h"
-#include "device_columns.hpp"
 #include "kernel_limits.hpp"
 
 namespace relp {
+
+struct MatrixData;  // (model.hpp; the next two device_columns.hpp: the planner's inputs, which a launcher that reads a plan does not need)
+struct DeviceColumns;
+struct DeviceMatrix;
 
 // How the dense block is stored: the narrowest type that holds every entry exactly (relp_options.dense_storage may ask for a wider
 // one), as tiles for the column-per-lane pricing (*_LANE), rows permuted within 1024-row chunks (I8_PERMUTED) or plain column-major.
@@ -106,19 +109,6 @@ struct KernelPath {
         return launches_per_batch(forced, replayed) + (long long)launches_per_pivot(forced, replayed) * count;
     }
 };
-
-// Implicit upper bounds apply to an LP that has a finite bound (relp_options.implicit_bounds); the device LP then has the
-// constraint rows and the first four column groups only.
-inline bool implicit_bounds_apply(const relp_options& o, const MatrixData& md) { return o.implicit_bounds != 0 && md.nr_variable_bounds() > 0; }
-inline DeviceColumns device_columns(const MatrixData& md, bool bounded) {
-    return bounded ? DeviceColumns(md, md.nr_constraints(), md.col_end[3]) : DeviceColumns(md);
-}
-
-// `Tableau::select_primal_pivot_row` (tableau/mod.rs:287-313): which ratio test runs.  TEXTBOOK asks for the reference's rule; AUTO
-// (the default) takes it where the data are small integers and the kernels of the path implement it, Harris on decimal data.
-inline bool resolves_to_textbook(const relp_options& o, const DeviceMatrix& data, bool kernels_have_it) {
-    return o.ratio_rule == RELP_RATIO_TEXTBOOK || (o.ratio_rule == RELP_RATIO_AUTO && data.small_integer_data() && kernels_have_it);
-}
 
 // Throws std::runtime_error ("LP without rows") or std::invalid_argument (a carry or a ratio rule the LP cannot have) -- before
 // anything is allocated.  `column_names` (may be null) names the column in the message of the network check.

@@ -13,7 +13,6 @@
 // Reference functions each kernel replaces are cited at the kernel; paths relative to
 // /root/reference/src/algorithm/two_phase/.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <cmath>
 #include <cstdlib>
@@ -21,9 +20,9 @@
 #include <utility>
 
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "pivot_step.hpp"
 #include "price_step.hpp"
-#include "solver.hpp"
 #include "wave_ops.hpp"
 
 namespace relp {
@@ -3520,60 +3519,24 @@ __global__ void relative_cost_kernel(DeviceLP lp, double* out) {
 // ---------------------------------------------------------------------------------------------------
 // launch helpers used by solver.hip
 // ---------------------------------------------------------------------------------------------------
-// Measurement hook (bench.py roofline leg): when armed, the NEXT launch of the named hot-loop kernel is bracketed by a
-// start/stop event pair through hipExtLaunchKernelGGL, i.e. its own execution time inside the real pivot sequence.
-struct LaunchTimer {
-    int which = -1;  // 0 price (sparse or dense), 1 fused ftran/ratio, 2 update
-    hipEvent_t start = nullptr, stop = nullptr;
-};
-static thread_local LaunchTimer g_timer;
-void arm_launch_timer(int which, hipEvent_t start, hipEvent_t stop) {
-    g_timer.which = which;
-    g_timer.start = start;
-    g_timer.stop = stop;
-}
-// (kernels of another file: hand the armed event pair over, if it is meant for `which`)
-void take_launch_timer(int which, hipEvent_t* start, hipEvent_t* stop) {
-    *start = *stop = nullptr;
-    if (g_timer.which == which) {
-        g_timer.which = -1;
-        *start = g_timer.start;
-        *stop = g_timer.stop;
-    }
-}
-#define RELP_LAUNCH(WHICH, KERNEL, GRID, BLOCK, LDS, STREAM, ...)                                            \
-    do {                                                                                                     \
-        if (g_timer.which == (WHICH)) {                                                                      \
-            g_timer.which = -1;                                                                              \
-            hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, (std::uint32_t)(LDS), STREAM, g_timer.start, g_timer.stop, 0, __VA_ARGS__); \
-        } else {                                                                                             \
-            hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                               \
-        }                                                                                                    \
-    } while (0)
+thread_local LaunchTimer g_timer;  // (launch.hpp)
 constexpr int PRICE_LPC = 8;  // lanes per sparse column in the pricing kernel
-
-template <int RULE>
-static void launch_price_rule(const DeviceLP& d, const KernelPath& path, PriceKernel kernel, int skip_weights, double tol, hipStream_t s) {
-    const int which = d.n_dense > 0 ? -2 : 0;  // with a dense block the dense kernel is the one that is timed
-    const dim3 grid(path.price_blocks), block(256);
-    const int first = path.sparse_first, last = d.n, cand_offset = 0;
-    switch (kernel) {
-    case PriceKernel::UNIT_PAIRS: RELP_LAUNCH(which, (price_kernel<RULE, false, 2, true>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
-    case PriceKernel::GENERATED: RELP_LAUNCH(which, (price_unit_kernel<RULE>), grid, block, (size_t)d.rho_words * sizeof(unsigned), s, d, skip_weights, tol, first, last, cand_offset); break;
-    case PriceKernel::WIDTH_2: RELP_LAUNCH(which, (price_kernel<RULE, false, 2>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
-    case PriceKernel::LDS: RELP_LAUNCH(which, (price_kernel<RULE, true, PRICE_LPC>), grid, block, path.price_lds, s, d, skip_weights, tol, first, last, cand_offset); break;
-    case PriceKernel::GATHER: RELP_LAUNCH(which, (price_kernel<RULE, false, PRICE_LPC>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
-    }
-}
 
 // sparse (CSC) pricing over the device columns [path.sparse_first, n): `kernel` is path.price_kernel or path.price_kernel_fused
 void launch_price(const DeviceLP& d, const KernelPath& path, PriceKernel kernel, int rule, int skip_weights, double tol, hipStream_t s) {
-    switch (rule) {
-        case RELP_PIVOT_DANTZIG: launch_price_rule<RELP_PIVOT_DANTZIG>(d, path, kernel, skip_weights, tol, s); break;
-        case RELP_PIVOT_FIRST_PROFITABLE: launch_price_rule<RELP_PIVOT_FIRST_PROFITABLE>(d, path, kernel, skip_weights, tol, s); break;
-        case RELP_PIVOT_FIRST_PROFITABLE_MEMORY: launch_price_rule<RELP_PIVOT_FIRST_PROFITABLE_MEMORY>(d, path, kernel, skip_weights, tol, s); break;
-        default: launch_price_rule<RELP_PIVOT_STEEPEST_EDGE>(d, path, kernel, skip_weights, tol, s); break;
-    }
+    const int which = d.n_dense > 0 ? -2 : 0;  // with a dense block the dense kernel is the one that is timed
+    const dim3 grid(path.price_blocks), block(256);
+    const int first = path.sparse_first, last = d.n, cand_offset = 0;
+    with_pivot_rule(rule, [&](auto r) {
+        constexpr int RULE = decltype(r)::value;
+        switch (kernel) {
+        case PriceKernel::UNIT_PAIRS: RELP_LAUNCH(which, (price_kernel<RULE, false, 2, true>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
+        case PriceKernel::GENERATED: RELP_LAUNCH(which, (price_unit_kernel<RULE>), grid, block, (size_t)d.rho_words * sizeof(unsigned), s, d, skip_weights, tol, first, last, cand_offset); break;
+        case PriceKernel::WIDTH_2: RELP_LAUNCH(which, (price_kernel<RULE, false, 2>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
+        case PriceKernel::LDS: RELP_LAUNCH(which, (price_kernel<RULE, true, PRICE_LPC>), grid, block, path.price_lds, s, d, skip_weights, tol, first, last, cand_offset); break;
+        case PriceKernel::GATHER: RELP_LAUNCH(which, (price_kernel<RULE, false, PRICE_LPC>), grid, block, 0, s, d, skip_weights, tol, first, last, cand_offset); break;
+        }
+    });
 }
 
 void launch_price_dense(const DeviceLP& d, const KernelPath& path, int skip_weights, double tol, hipStream_t s) {
@@ -3590,90 +3553,63 @@ void launch_price_dense(const DeviceLP& d, const KernelPath& path, int skip_weig
     case DenseStorage::F64_ROWS: RELP_LAUNCH(0, price_dense_kernel<false>, grid, row_block, lds, s, d, skip_weights, tol, cand_offset); break;
     }
 }
-// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel on the CURRENT device: setting it to the current LP's size would
-// let the last loaded handle decide for every other one.  It is set once per device (PerDeviceOnce, solver.hpp), to what the CU has
-// (160 KB minus the kernel's static LDS).
-static void allow_full_lds(const void* kernel) {
-    hipFuncAttributes attr{};
-    size_t fixed = 0;
-    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) fixed = attr.sharedSizeBytes;
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - fixed)) != hipSuccess) (void)hipGetLastError();
-}
 void configure_dense_lds() {
     static PerDeviceOnce once;
-    once.run([] {
-        allow_full_lds(reinterpret_cast<const void*>(&price_dense_kernel<false>));
-        allow_full_lds(reinterpret_cast<const void*>(&price_dense_kernel<true>));
-        allow_full_lds(reinterpret_cast<const void*>(&price_dense_kernel<false, true>));
-    });
+    allow_full_lds_once(once, &price_dense_kernel<false>, &price_dense_kernel<true>, &price_dense_kernel<false, true>);
 }
 void launch_ftran_partial(const DeviceLP& d, int n_slices, int n_price_blocks, int rule, hipStream_t s) {
     hipLaunchKernelGGL(ftran_partial_kernel, dim3((d.m + 255) / 256, n_slices), dim3(256), 0, s, d, n_slices, n_price_blocks, rule);
 }
 
 void configure_lds() {
-    // opt in to > 64 KB of dynamic LDS (160 KB per CU on gfx950), once per device
     static PerDeviceOnce once;
-    once.run([] {
-        allow_full_lds(reinterpret_cast<const void*>(&price_kernel<RELP_PIVOT_STEEPEST_EDGE, true, PRICE_LPC>));
-        allow_full_lds(reinterpret_cast<const void*>(&price_kernel<RELP_PIVOT_DANTZIG, true, PRICE_LPC>));
-        allow_full_lds(reinterpret_cast<const void*>(&price_kernel<RELP_PIVOT_FIRST_PROFITABLE, true, PRICE_LPC>));
-        allow_full_lds(reinterpret_cast<const void*>(&price_kernel<RELP_PIVOT_FIRST_PROFITABLE_MEMORY, true, PRICE_LPC>));
-    });
+    allow_full_lds_once(once, &price_kernel<RELP_PIVOT_STEEPEST_EDGE, true, PRICE_LPC>, &price_kernel<RELP_PIVOT_DANTZIG, true, PRICE_LPC>,
+                        &price_kernel<RELP_PIVOT_FIRST_PROFITABLE, true, PRICE_LPC>, &price_kernel<RELP_PIVOT_FIRST_PROFITABLE_MEMORY, true, PRICE_LPC>);
 }
 
 // mode 0 runs path.ratio_kernel, modes 1 and 2 path.ratio_kernel_no_change; n_alpha_slices > 0 (alpha given in alpha_in) is read
 // by the register-resident kernel only
-template <int RULE>
-static void launch_ftran_ratio_rule(const DeviceLP& d, const KernelPath& path, double tol_pivot, double harris_delta, int skip_artificial_rows,
-                                    int mode, int n_alpha_slices, hipStream_t s) {
+void launch_ftran_ratio(const DeviceLP& d, const KernelPath& path, int rule, double tol_pivot, double harris_delta, int skip_artificial_rows,
+                        int mode, int n_alpha_slices, hipStream_t s) {
     const RatioKernel kernel = mode == 0 ? path.ratio_kernel : path.ratio_kernel_no_change;
     const int n_price_blocks = path.slots();
     if (n_alpha_slices > 0 && ratio_rows_per_thread(kernel) == 0) throw std::logic_error("launch_ftran_ratio: a preselected alpha needs the register-resident ratio test");
 #define RELP_RATIO_REGISTERS(R) \
     RELP_LAUNCH(1, (ftran_ratio_fast_kernel<RULE, R>), dim3(1), dim3(K2F_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices)
-    switch (kernel) {
-    case RatioKernel::REGISTERS_2: RELP_RATIO_REGISTERS(2); break;
-    case RatioKernel::REGISTERS_4: RELP_RATIO_REGISTERS(4); break;
-    case RatioKernel::REGISTERS_8: RELP_RATIO_REGISTERS(8); break;
-    case RatioKernel::REGISTERS_16: RELP_RATIO_REGISTERS(16); break;
-    case RatioKernel::MULTI_WORKGROUP: {
-        const int blocks = (d.m + K2L_THREADS - 1) / K2L_THREADS;
-        RELP_LAUNCH(1, (k2l_ftran_kernel<RULE>), dim3(blocks), dim3(K2L_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows);
-        hipLaunchKernelGGL(k2l_harris_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks, tol_pivot, skip_artificial_rows);
-        hipLaunchKernelGGL(k2l_apply_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks);
-        break;
-    }
-    case RatioKernel::ONE_WORKGROUP:
-        RELP_LAUNCH(1, (ftran_ratio_kernel<RULE>), dim3(1), dim3(K2_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode);
-        break;
-    }
+    with_steepest_edge_or_dantzig(rule, [&](auto r) {
+        constexpr int RULE = decltype(r)::value;
+        switch (kernel) {
+        case RatioKernel::REGISTERS_2: RELP_RATIO_REGISTERS(2); break;
+        case RatioKernel::REGISTERS_4: RELP_RATIO_REGISTERS(4); break;
+        case RatioKernel::REGISTERS_8: RELP_RATIO_REGISTERS(8); break;
+        case RatioKernel::REGISTERS_16: RELP_RATIO_REGISTERS(16); break;
+        case RatioKernel::MULTI_WORKGROUP: {
+            const int blocks = (d.m + K2L_THREADS - 1) / K2L_THREADS;
+            RELP_LAUNCH(1, (k2l_ftran_kernel<RULE>), dim3(blocks), dim3(K2L_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows);
+            hipLaunchKernelGGL(k2l_harris_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks, tol_pivot, skip_artificial_rows);
+            hipLaunchKernelGGL(k2l_apply_kernel, dim3(blocks), dim3(K2L_THREADS), 0, s, d, blocks);
+            break;
+        }
+        case RatioKernel::ONE_WORKGROUP:
+            RELP_LAUNCH(1, (ftran_ratio_kernel<RULE>), dim3(1), dim3(K2_THREADS), 0, s, d, n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows, mode);
+            break;
+        }
+    });
 #undef RELP_RATIO_REGISTERS
 }
 
-void launch_ftran_ratio(const DeviceLP& d, const KernelPath& path, int rule, double tol_pivot, double harris_delta, int skip_artificial_rows,
-                        int mode, int n_alpha_slices, hipStream_t s) {
-    if (rule == RELP_PIVOT_STEEPEST_EDGE)
-        launch_ftran_ratio_rule<RELP_PIVOT_STEEPEST_EDGE>(d, path, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices, s);
-    else
-        launch_ftran_ratio_rule<RELP_PIVOT_DANTZIG>(d, path, tol_pivot, harris_delta, skip_artificial_rows, mode, n_alpha_slices, s);
-}
-
-template <int RULE>
-static void launch_pivot_fused_rule(const DeviceLP& d, const KernelPath& path, int parity, double tol_pivot, double harris_delta,
-                                    int skip_artificial_rows, hipStream_t s) {
-    const dim3 grid((d.m + KF_NW - 1) / KF_NW + 1);  // the writer, then a workgroup per KF_NW columns of the inverse
-    const int n_price_blocks = path.price_blocks;
-    switch (path.fused_rows) {
-    case 2: RELP_LAUNCH(1, (pivot_fused_kernel<RULE, 2>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows); break;
-    case 4: RELP_LAUNCH(1, (pivot_fused_kernel<RULE, 4>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows); break;
-    default: throw std::logic_error("launch_pivot_fused: the path has no fused pivot");
-    }
-}
 void launch_pivot_fused(const DeviceLP& d, const KernelPath& path, int rule, int parity, double tol_pivot, double harris_delta,
                         int skip_artificial_rows, hipStream_t s) {
-    if (rule == RELP_PIVOT_STEEPEST_EDGE) launch_pivot_fused_rule<RELP_PIVOT_STEEPEST_EDGE>(d, path, parity, tol_pivot, harris_delta, skip_artificial_rows, s);
-    else launch_pivot_fused_rule<RELP_PIVOT_DANTZIG>(d, path, parity, tol_pivot, harris_delta, skip_artificial_rows, s);
+    const dim3 grid((d.m + KF_NW - 1) / KF_NW + 1);  // the writer, then a workgroup per KF_NW columns of the inverse
+    const int n_price_blocks = path.price_blocks;
+    with_steepest_edge_or_dantzig(rule, [&](auto r) {
+        constexpr int RULE = decltype(r)::value;
+        switch (path.fused_rows) {
+        case 2: RELP_LAUNCH(1, (pivot_fused_kernel<RULE, 2>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows); break;
+        case 4: RELP_LAUNCH(1, (pivot_fused_kernel<RULE, 4>), grid, dim3(KF_THREADS), 0, s, d, d.state[parity], d.state[parity ^ 1], n_price_blocks, tol_pivot, harris_delta, skip_artificial_rows); break;
+        default: throw std::logic_error("launch_pivot_fused: the path has no fused pivot");
+        }
+    });
 }
 void launch_begin_batch(const DeviceLP& d, long long add, hipStream_t s) {
     hipLaunchKernelGGL(begin_batch_kernel, dim3(1), dim3(256), 0, s, d, add);
@@ -3762,7 +3698,7 @@ void launch_alpha_reduce(const DeviceLP& d, int n_slices, hipStream_t s) {
 }
 void configure_btran_lds() {
     static PerDeviceOnce once;
-    once.run([] { allow_full_lds(reinterpret_cast<const void*>(&btran_pass_kernel)); });
+    allow_full_lds_once(once, &btran_pass_kernel);
 }
 // deferred product form: fold the new eta into the kept columns, then one read-only pass for rho_p, w and -pi
 void launch_eta_update(const DeviceLP& d, double tol_dual, hipStream_t s) {

@@ -1,7 +1,8 @@
 // Launch helpers that one file defines and another calls: the f64 pipeline of kernels.hip and the forest carry's row of the inverse
 // (network_carry.hip).  Included by the defining file too, so that a changed parameter list is a diagnostic and not a link error.
 #pragma once
-#include "solver.hpp"
+#include "device_lp.hpp"
+#include "kernel_path.hpp"
 
 namespace relp {
 
@@ -10,8 +11,6 @@ void launch_price(const DeviceLP& d, const KernelPath& path, PriceKernel kernel,
 void launch_price_dense(const DeviceLP& d, const KernelPath& path, int skip_weights, double tol, hipStream_t s);
 void configure_dense_lds();
 void launch_ftran_partial(const DeviceLP& d, int n_slices, int n_price_blocks, int rule, hipStream_t s);
-void arm_launch_timer(int which, hipEvent_t start, hipEvent_t stop);
-void take_launch_timer(int which, hipEvent_t* start, hipEvent_t* stop);
 void configure_lds();
 void launch_ftran_ratio(const DeviceLP& d, const KernelPath& path, int rule, double tol_pivot, double harris_delta, int skip_artificial_rows,
                         int mode, int n_alpha_slices, hipStream_t s);

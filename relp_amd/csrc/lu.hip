@@ -22,8 +22,6 @@
 // storage order, reductions have a fixed tree.
 #include "lu.hpp"
 
-#include <hip/hip_ext.h>
-
 #include <algorithm>
 #include <cstdint>
 #include <chrono>
@@ -32,9 +30,12 @@
 #include <string>
 #include <thread>
 
+#include "device_lp.hpp"
+#include "launch.hpp"
+#include "model.hpp"
+#include "options.hpp"
 #include "pivot_step.hpp"
 #include "price_step.hpp"
-#include "solver.hpp"
 #include "wave_ops.hpp"
 
 namespace relp {
@@ -1870,20 +1871,10 @@ __global__ void __launch_bounds__(LU_THREADS) lu_update_kernel(DeviceLU lu, int 
     lu_ft_update_block(lu, sh, t, eta_count, new_diag, lu.spike);
 }
 
-static PerDeviceOnce g_lu_lds_configured;  // (per device: solver.hpp)
-static void allow_full_lds(const void* kernel);
 static void configure_lu_lds() {
-    g_lu_lds_configured.run([] {
-        allow_full_lds(reinterpret_cast<const void*>(&lu_ftran_kernel<false>));
-        allow_full_lds(reinterpret_cast<const void*>(&lu_ftran_kernel<true>));
-        allow_full_lds(reinterpret_cast<const void*>(&lu_btran_kernel<false>));
-        allow_full_lds(reinterpret_cast<const void*>(&lu_btran_kernel<true>));
-        allow_full_lds(reinterpret_cast<const void*>(&lu_update_kernel));
-    });
-}
-static void check_launch(const char* what) {
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) throw DeviceError(std::string(what) + ": " + hipGetErrorString(err));
+    static PerDeviceOnce once;  // (per device: launch.hpp)
+    allow_full_lds_once(once, &lu_ftran_kernel<false>, &lu_ftran_kernel<true>, &lu_btran_kernel<false>, &lu_btran_kernel<true>,
+                        &lu_update_kernel);
 }
 
 void launch_lu_ftran(const DeviceLU& lu, const int* rows, const double* vals, int nnz, double* out, int keep_spike, hipStream_t s) {
@@ -2406,57 +2397,25 @@ __global__ void __launch_bounds__(256) lu_row_scan_kernel(DeviceLP lp, const dou
     }
 }
 
-static PerDeviceOnce g_lu_pivot_configured;
-static void allow_full_lds(const void* kernel) {
-    // dynamic + static LDS may reach the 160 KB of a CU; the attribute belongs to the kernel on the current device, so it is set
-    // once per device to the maximum (not to the current LP's size: the last loaded handle would decide for every other one)
-    hipFuncAttributes attr{};
-    size_t fixed = 0;
-    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) fixed = attr.sharedSizeBytes;
-    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - fixed));
-    if (err != hipSuccess) {
-        (void)hipGetLastError();  // not sticky: the launch itself reports a request that is too large
-    }
-}
 static void configure_lu_pivot_lds() {
-  g_lu_pivot_configured.run([] {
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_STEEPEST_EDGE, false>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_STEEPEST_EDGE, true>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_DANTZIG, false>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_DANTZIG, true>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE, false>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE, true>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE_MEMORY, false>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE_MEMORY, true>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_xb_kernel<false>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_xb_kernel<true>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pi_kernel<false>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_pi_kernel<true>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_gamma_kernel<false>));
-    allow_full_lds(reinterpret_cast<const void*>(&lu_gamma_kernel<true>));
-  });
+    static PerDeviceOnce once;
+    allow_full_lds_once(once, &lu_pivot_kernel<RELP_PIVOT_STEEPEST_EDGE, false>, &lu_pivot_kernel<RELP_PIVOT_STEEPEST_EDGE, true>,
+                        &lu_pivot_kernel<RELP_PIVOT_DANTZIG, false>, &lu_pivot_kernel<RELP_PIVOT_DANTZIG, true>,
+                        &lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE, false>, &lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE, true>,
+                        &lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE_MEMORY, false>, &lu_pivot_kernel<RELP_PIVOT_FIRST_PROFITABLE_MEMORY, true>,
+                        &lu_xb_kernel<false>, &lu_xb_kernel<true>, &lu_pi_kernel<false>, &lu_pi_kernel<true>, &lu_gamma_kernel<false>,
+                        &lu_gamma_kernel<true>);
 }
-template <int RULE>
-static void launch_lu_pivot_rule(const DeviceLP& d, const DeviceLU& lu, int n_price_blocks, double tol_pivot, double harris_delta,
-                                 int skip_art, int mode, int refactor_period, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    auto kernel = lu.inverse_factors ? lu_pivot_kernel<RULE, true> : lu_pivot_kernel<RULE, false>;
-    if (start)
-        hipExtLaunchKernelGGL(kernel, dim3(1), dim3(LU_THREADS), (std::uint32_t)lu_lds_bytes_for(lu), s, start, stop, 0,
-                              d, lu, n_price_blocks, tol_pivot, harris_delta, skip_art, mode, refactor_period);
-    else
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(LU_THREADS), lu_lds_bytes_for(lu), s, d, lu, n_price_blocks, tol_pivot,
-                           harris_delta, skip_art, mode, refactor_period);
-}
-// `capturing`: inside a stream capture hipGetLastError must not be polled per launch (the capture's end reports failures)
+// inside a stream capture hipGetLastError must not be polled per launch (the capture's end reports failures): no check_launch here
 void launch_lu_pivot(const DeviceLP& d, const DeviceLU& lu, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
-                     int skip_art, int mode, int refactor_period, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+                     int skip_art, int mode, int refactor_period, hipStream_t s) {
     configure_lu_pivot_lds();
-    switch (rule) {
-        case RELP_PIVOT_DANTZIG: launch_lu_pivot_rule<RELP_PIVOT_DANTZIG>(d, lu, n_price_blocks, tol_pivot, harris_delta, skip_art, mode, refactor_period, s, start, stop); break;
-        case RELP_PIVOT_FIRST_PROFITABLE: launch_lu_pivot_rule<RELP_PIVOT_FIRST_PROFITABLE>(d, lu, n_price_blocks, tol_pivot, harris_delta, skip_art, mode, refactor_period, s, start, stop); break;
-        case RELP_PIVOT_FIRST_PROFITABLE_MEMORY: launch_lu_pivot_rule<RELP_PIVOT_FIRST_PROFITABLE_MEMORY>(d, lu, n_price_blocks, tol_pivot, harris_delta, skip_art, mode, refactor_period, s, start, stop); break;
-        default: launch_lu_pivot_rule<RELP_PIVOT_STEEPEST_EDGE>(d, lu, n_price_blocks, tol_pivot, harris_delta, skip_art, mode, refactor_period, s, start, stop); break;
-    }
+    with_pivot_rule(rule, [&](auto r) {
+        constexpr int RULE = decltype(r)::value;
+        auto kernel = lu.inverse_factors ? lu_pivot_kernel<RULE, true> : lu_pivot_kernel<RULE, false>;
+        RELP_LAUNCH(1, kernel, dim3(1), dim3(LU_THREADS), lu_lds_bytes_for(lu), s, d, lu, n_price_blocks, tol_pivot, harris_delta, skip_art, mode,
+                    refactor_period);
+    });
 }
 __global__ void lu_clear_refactor_status_kernel(Ctl* ctl) {
     if (ctl->status == ST_REFACTOR) ctl->status = ST_RUNNING;

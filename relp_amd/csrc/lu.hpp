@@ -198,7 +198,7 @@ void launch_lu_update(const DeviceLU& lu, int p, hipStream_t s);
 // the LU carry inside the device-resident loop (solver.hip)
 struct DeviceLP;
 void launch_lu_pivot(const DeviceLP& d, const DeviceLU& lu, int rule, int n_price_blocks, double tol_pivot, double harris_delta,
-                     int skip_art, int mode, int refactor_period, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+                     int skip_art, int mode, int refactor_period, hipStream_t s);
 void launch_lu_xb(const DeviceLP& d, const DeviceLU& lu, hipStream_t s);
 void launch_lu_pi(const DeviceLP& d, const DeviceLU& lu, hipStream_t s);
 void launch_lu_gamma(const DeviceLP& d, const DeviceLU& lu, hipStream_t s);

@@ -19,8 +19,10 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "device_lp.hpp"
+#include "launch.hpp"
 #include "lu.hpp"
-#include "solver.hpp"
+#include "options.hpp"
 #include "wave_ops.hpp"
 
 namespace relp {
@@ -618,10 +620,7 @@ void launch_lu_invert(const LuFactorOut& factors, const LuInverseWork& iw_in, co
     bool in_lds = false;
     const size_t lds = lu_invert_lds_bytes(iw.m, &in_lds);
     static PerDeviceOnce once;
-    once.run([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lu_invert_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lu_invert_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    });
+    allow_full_lds_once(once, &lu_invert_kernel<true>, &lu_invert_kernel<false>);
     if (in_lds) hipLaunchKernelGGL(lu_invert_kernel<true>, dim3(2), dim3(LUT_THREADS), lds, stream, factors, iw, status_in);
     else hipLaunchKernelGGL(lu_invert_kernel<false>, dim3(2), dim3(LUT_THREADS), lds, stream, factors, iw, status_in);
 }

@@ -7,7 +7,8 @@
 #include <stdexcept>
 #include <string>
 
-#include "solver.hpp"
+#include "launch.hpp"
+#include "options.hpp"
 #include "wave_ops.hpp"
 
 namespace relp {
@@ -1031,10 +1032,7 @@ void launch_lu_factor(const LuFactorSource& src, const LuFactorWork& w, const Lu
     ww.cap_l = o.cap_l;
     ww.cap_u = o.cap_u;
     static PerDeviceOnce once;
-    once.run([] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lu_factor_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 148 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lu_factor_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 148 * 1024);
-    });
+    allow_full_lds_once(once, &lu_factor_kernel<1>, &lu_factor_kernel<2>);
     const size_t m8 = ((size_t)w.m * sizeof(int) + 7) & ~size_t(7);
     const size_t level1 = (size_t)w.m * sizeof(double) + 8 * m8, level2 = level1 + 7 * m8 + m8 + 8;
     const size_t budget = (size_t)140 * 1024;

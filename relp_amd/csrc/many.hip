@@ -42,7 +42,9 @@
 #include <vector>
 
 #include "exact_values.hpp"
+#include "launch.hpp"
 #include "many_certify.hpp"
+#include "options.hpp"
 #include "pivot_step.hpp"
 #include "price_step.hpp"
 #include "solver.hpp"
@@ -843,11 +845,7 @@ int32_t relp_many_create_with(const relp_model* const* models, int32_t n_models,
         RELP_HIP(hipEventCreate(&many->ev_stop));
         for (hipEvent_t& e : many->ev_done) RELP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         static PerDeviceOnce once;
-        once.run([] {
-            for (const void* kernel : {reinterpret_cast<const void*>(&many_kernel<true, false>), reinterpret_cast<const void*>(&many_kernel<true, true>)})
-                if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MANY_LDS_BYTES - MANY_STATIC_LDS)) != hipSuccess)
-                    (void)hipGetLastError();
-        });
+        allow_full_lds_once(once, &many_kernel<true, false>, &many_kernel<true, true>);
     } catch (const DeviceError& e) {
         many_set_error(error, error_capacity, e.what());
         many->release();
@@ -905,7 +903,7 @@ int32_t relp_many_solve(relp_many* many, relp_many_result* results, double* kern
                 else if (lds) hipLaunchKernelGGL((many_kernel<true, false>), dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
                 else if (bounded) hipLaunchKernelGGL((many_kernel<false, true>), dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
                 else hipLaunchKernelGGL((many_kernel<false, false>), dim3(blocks), dim3(MANY_THREADS), bytes, s, part);
-                RELP_HIP(hipGetLastError());
+                check_launch("many_kernel");
             }
             if (t > 0) {
                 RELP_HIP(hipEventRecord(many->ev_done[t], s));

@@ -36,6 +36,7 @@
 #include <thread>
 
 #include "certify_parts.hpp"
+#include "launch.hpp"
 #include "many_certify.hpp"
 
 namespace relp {
@@ -504,11 +505,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
         args.slab = memory.alloc<u32>((size_t)slab_words);
         args.flags = upload(flags);  // (zeros)
         static PerDeviceOnce once;
-        once.run([] {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&many_certify_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(MC_LDS_BYTES - MC_STATIC_LDS)) != hipSuccess)
-                (void)hipGetLastError();
-        });
+        allow_full_lds_once(once, &many_certify_kernel<true>);
         hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_done[MC_TIERS] = {};
         struct Events {
             hipEvent_t *a, *b, *c;
@@ -534,7 +531,7 @@ void many_certify_batched(const std::vector<ManyCertifyItem>& items, int device,
                 const size_t bytes = mc_lds_bytes(rows[t], lds);
                 if (lds) hipLaunchKernelGGL((many_certify_kernel<true>), dim3(blocks), dim3(MC_THREADS), bytes, s, part);
                 else hipLaunchKernelGGL((many_certify_kernel<false>), dim3(blocks), dim3(MC_THREADS), bytes, s, part);
-                RELP_HIP(hipGetLastError());
+                check_launch("many_certify_kernel");
             }
             if (t > 0) {
                 RELP_HIP(hipEventRecord(ev_done[t], s));

@@ -10,7 +10,7 @@
 
 namespace relp {
 
-struct ExactWitnesses;  // x, y and the ray of a proved certificate (solver.hpp, certify_parts.hpp)
+struct ExactWitnesses;  // x, y and the ray of a proved certificate (certify.hpp, certify_parts.hpp)
 
 // Why the batched stage did not prove an LP (relp_many_certificate.fallback_reason, include/relp_amd.h)
 enum ManyCertifyReason {

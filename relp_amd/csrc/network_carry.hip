@@ -1,4 +1,4 @@
-// Spanning-forest carry (RELP_CARRY_NETWORK): the basis of a network LP kept as a forest of the rows (solver.hpp: NetTree).
+// Spanning-forest carry (RELP_CARRY_NETWORK): the basis of a network LP kept as a forest of the rows (device_lp.hpp: NetTree).
 //
 // A basic incidence column joins two rows; a basic single-entry column (an artificial, an arc at a removed s or t) is the root
 // arc of its row's tree.  With sign[x] the entry of x's parent arc (as it stands in B: negated when held complemented) at x:

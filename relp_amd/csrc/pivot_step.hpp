@@ -13,7 +13,7 @@
 // variable has one -- and the entering variable may run into its own bound first (a "bound flip", no basis change).  A variable at
 // its upper bound is held in complemented form, so its column enters with the opposite sign.
 #pragma once
-#include "solver.hpp"
+#include "device_lp.hpp"
 #include "wave_ops.hpp"
 
 namespace relp {

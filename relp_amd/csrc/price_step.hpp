@@ -9,6 +9,7 @@
 // "a weight without an entry in the pivot row does not change" where the fetch is skipped -- and take the rules from here.
 // Everything is __forceinline__; RULE and `bounded` fold away where the caller passes a constant.
 #pragma once
+#include "../../include/relp_amd.h"
 #include "pivot_step.hpp"
 
 namespace relp {

@@ -4,6 +4,7 @@
 //   phase_two.rs:22-59             phase-two loop
 //   kind/artificial/partially.rs   virtual artificial columns (index space: artificials first)
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "solver.hpp"
 
 #include <thread>
@@ -818,9 +819,7 @@ void Solver::enqueue_ftran_ratio(int mode) {
         return;
     }
     if (path_.lu_mode) {
-        hipEvent_t start = nullptr, stop = nullptr;
-        take_launch_timer(1, &start, &stop);
-        launch_lu_pivot(d_, lu().device(), opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, path_.refactor_period, stream_, start, stop);
+        launch_lu_pivot(d_, lu().device(), opt_.pivot_rule, slots, opt_.tol_pivot, ratio_delta(), skip_art, mode, path_.refactor_period, stream_);
         return;
     }
     if (path_.ftran_slices > 0) {

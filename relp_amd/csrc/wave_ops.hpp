@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
-#include "solver.hpp"
+#include "kernel_limits.hpp"
 
 namespace relp {
 

@@ -3,10 +3,15 @@
 // the models:
 //   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Irelp_amd/csrc tools/kernel_path_sanitize.cpp
 //       relp_amd/csrc/kernel_path.cpp -Lrelp_amd -lrelp_amd -Wl,-rpath,$PWD/relp_amd -o kernel_path_sanitize && ./kernel_path_sanitize
+#include <cstddef>
 #include <cstdio>
+#include <cstring>
+#include <memory>
 #include <vector>
 
+#include "device_columns.hpp"
 #include "kernel_path.hpp"
+#include "options.hpp"
 
 using namespace relp;
 
@@ -20,7 +25,45 @@ static void plan(const relp_model* model, relp_options o, const char* what) {
     }
 }
 
+// adopt_options (options.hpp) on every struct size a header has had, read from a heap buffer of exactly that size (an over-read is an
+// ASan report), and on what it refuses or clamps.  Returns the number of failed expectations.
+static int check_adopt_options() {
+    int failures = 0;
+    auto expect = [&](bool ok, const char* what) {
+        if (!ok) std::printf("adopt_options: %s\n", what), ++failures;
+    };
+    relp_options defaults, out;
+    relp_options_default(&defaults);
+    expect(adopt_options(nullptr, &out) == RELP_OK && std::memcmp(&out, &defaults, sizeof out) == 0, "a null pointer does not give the defaults");
+    int known = 0;
+    for (int32_t size = 0; size <= (int32_t)sizeof(relp_options) + 8; ++size) {
+        if (!known_options_size(size)) continue;
+        ++known;
+        std::unique_ptr<unsigned char[]> exact(new unsigned char[size]);
+        relp_options_default_sized(reinterpret_cast<relp_options*>(exact.get()), size);
+        relp_options wanted;
+        std::memcpy(&wanted, &defaults, sizeof wanted);  // (padding included: the results are compared as bytes)
+        const int64_t max_pivots = 12345;  // (a field every size has, changed in the caller's struct)
+        std::memcpy(exact.get() + offsetof(relp_options, max_pivots), &max_pivots, sizeof max_pivots);
+        wanted.max_pivots = max_pivots;
+        expect(adopt_options(reinterpret_cast<const relp_options*>(exact.get()), &out) == RELP_OK, "a known size is refused");
+        expect(out.struct_size == (int32_t)sizeof(relp_options) && std::memcmp(&out, &wanted, sizeof out) == 0,
+               "a known size does not give the caller's fields and the defaults behind them");
+    }
+    expect(known == 2, "the sizes relp_options has had are not two");
+    relp_options odd = defaults;
+    odd.struct_size = (int32_t)sizeof(relp_options) - 4;
+    expect(adopt_options(&odd, &out) == RELP_ERR_ARGUMENT, "an unknown size is accepted");
+    relp_options wide = defaults;
+    wide.ftran_slices = 1000, wide.price_lds_max = 1 << 30;
+    expect(adopt_options(&wide, &out) == RELP_OK && out.ftran_slices == 64 && out.price_lds_max == 160 * 1024, "ftran_slices / price_lds_max above their range");
+    wide.ftran_slices = -5, wide.price_lds_max = -1;
+    expect(adopt_options(&wide, &out) == RELP_OK && out.ftran_slices == 0 && out.price_lds_max == 0, "ftran_slices / price_lds_max below their range");
+    return failures;
+}
+
 int main() {
+    if (check_adopt_options() != 0) return 1;
     relp_options o;
     relp_options_default(&o);
     char error[512];
