@@ -2606,7 +2606,8 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
 //     decides the step and stores lp.alpha, out.xB, out.basis, the column positions and the control block; it alone hands the state
 //     on when no pivot is made (status not running, budget used up, no entering column, unbounded); then it returns;
 //   * workgroup b >= 1 owns the columns (b - 1) * KF_NW + wave.  It goes from pass 2 straight to them -- alpha_pq = s_alpha[p], no
-//     broadcast, no step decision -- and writes its column of T_new, w_j, rho_j and -pi_j, nothing else.
+//     broadcast, no step decision -- and writes its column of T_new (write-through: nothing of it stays dirty in an L2 for the kernel
+//     boundary to write back), w_j, rho_j and -pi_j, nothing else.
 //   A kernel ends with its last wave: the bookkeeping (a dependent re-read of the control block by one thread) runs beside the column
 //   updates, not in front of one of them.
 // Workgroups are not synchronised, so nothing a workgroup reads at its start may be written by another one before its end:
@@ -2628,7 +2629,9 @@ __global__ void __launch_bounds__(K2F_THREADS) ftran_ratio_fast_kernel(DeviceLP 
 // pass 2 (one); the writer's broadcast adds one.  No scratch: Ctl is handed on field by field.
 // Measured and dropped: one wave per workgroup with all rows in registers (a wave cannot keep enough loads in
 // flight: 25 us), wave-local decisions out of LDS (16 rows and 32 divisions per lane: 14 us), and ONE launch per pivot with
-// every workgroup pricing all columns (360 KB of conflicting LDS gathers per workgroup: 21 us).
+// every workgroup pricing all columns (360 KB of conflicting LDS gathers per workgroup: 21 us); the own column read from the buffer
+// the batch parity names (equal to t_buf in every launch that pivots) and issued with round trip 1: 33 loads ahead of the first wait
+// as compiled, the loop where it was, and the shortest launch that makes no pivot 1.6 -> 3.8 us (profiles/fused_parity_ab.txt).
 // ---------------------------------------------------------------------------------------------------
 constexpr int KF_THREADS = K2F_THREADS;    // (the k2f_* front half)
 constexpr int KF_NW = KF_THREADS / WAVE;  // waves = columns of the inverse per workgroup
@@ -2824,12 +2827,16 @@ __global__ void __launch_bounds__(KF_THREADS) pivot_fused_kernel(DeviceLP lp, De
 #pragma unroll
     for (int u = 0; u < KF_U; ++u) a_u[u] = s_alpha[lane_again + u * WAVE];
     __builtin_amdgcn_sched_barrier(0);
+    // The column goes out WRITE-THROUGH (a relaxed store at agent scope: global_store_dwordx2 ... sc1; same values, lanes and order).
+    // Plain stores left the 8 m^2 bytes of the new inverse -- 5.4 MB on 25FV47 -- dirty in the L2s at the end of the kernel, and the
+    // write-back at the kernel boundary stood in front of the next pricing launch: about 0.5 us per pivot of the loop, of which the
+    // profiler's serialised kernel average shows 0.4 (profiles/fused_parity_ab.txt).  The next reader is another XCD anyway.
 #pragma unroll
     for (int u = 0; u < KF_U; ++u) {
         const int i = lane_again + u * WAVE;
         const double a = a_u[u];
         w_j += a * o[u];
-        if (i < m) c_new[i] = (i == p) ? r_j : ((a != 0.0) ? o[u] - a * r_j : o[u]);
+        if (i < m) __hip_atomic_store(&c_new[i], (i == p) ? r_j : ((a != 0.0) ? o[u] - a * r_j : o[u]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     w_j = wave_sum(w_j);
     if (lane == LAST) {
