@@ -890,6 +890,34 @@ int32_t relp_get_dual_pivots(const relp_handle* handle, int64_t* dual_pivots);
  * relp_debug_kernel_path; a load that would itself be refused returns its status and message). */
 int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length);
 
+/* ---- dual simplex: start a child LP from its parent's inverse on the device (dual_inherit_kernel, relp_amd/csrc/dual.hip) ---------
+ * In a cut loop or a branching step the parent is solved, rows are appended or a right-hand side is tightened, and the child is
+ * re-solved from the parent's basis.  relp_begin_dual builds the child's inverse from scratch; these two calls write it from the
+ * inverse the parent handle still holds: with the parent's basis in the first m positions and the slack of each of the k new rows
+ * behind it, B_child^-1 = [B^-1 0; -S^-1 C B^-1  S^-1] (C: the new rows on the parent's basic columns, S: the new slacks' own
+ * entries) -- a copy plus k sparse combinations of rows of the parent's inverse; for k = 0 a copy.  `child` has the child LP loaded,
+ * `parent` is another handle on the same device that has solved (or been given a basis for) the parent LP and is only read;
+ * `basis_columns`: the child's m + k provider columns in that order (the parent's relp_get_basis in the child's columns, then the
+ * slacks).  Costs and right-hand sides may differ anywhere: x_B and -pi are recomputed from the child's data, and the
+ * dual-feasibility check of relp_begin_dual still runs.  A forced polish guards the inherited inverse: it measures max |I - B Binv|
+ * against the child's own matrix, corrects what it finds, and rebuilds from scratch by itself from 0.5 on.
+ * Refused before anything is launched, the launch counters of both handles unchanged: RELP_ERR_ARGUMENT for a plan of either handle
+ * that the dual kernels do not take, a parent on another device, and a pair of LPs and bases that are not in that relation
+ * (relp_debug_dual_inherit_refusal; the row or column is named); RELP_ERR_STATE for a parent without a loaded LP, a parent on which
+ * no solve, relp_set_basis or relp_solve_dual has happened, and parent == child.
+ * relp_solve_dual_from is relp_solve_dual with this start.  relp_get_record_json says which start the last of these calls took:
+ * "dual_start": "scratch" (relp_begin_dual) | "inherited" | "scratch_after_inherit" (the guard rebuilt) | "none";
+ * "dual_start_seconds": its wall time, the stream synchronised at its end; "dual_start_gemms": the m x m x m products inside it;
+ * "dual_start_residual": the guard's first reading (null where no guard ran). */
+int32_t relp_begin_dual_from(relp_handle* child, const relp_handle* parent, const int32_t* basis_columns);
+int32_t relp_solve_dual_from(relp_handle* child, const relp_handle* parent, const int32_t* basis_columns, relp_result* result);
+/* Host only: the empty string if `child` with `basis_columns` can inherit from `parent` with `parent_basis` (both bases as
+ * relp_get_basis gives them) under `options`, else the reason: relp_debug_dual_refusal of either model, or the relation above with
+ * the row or column named (the protocol of relp_debug_dual_refusal). */
+int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_model* child, const int32_t* parent_basis,
+                                        const int32_t* basis_columns, const relp_options* options, char* buffer, int32_t capacity,
+                                        int32_t* length);
+
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);
 

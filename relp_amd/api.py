@@ -195,6 +195,8 @@ SYMBOLS = [
     "relp_model_cost_exact", "relp_model_right_hand_side_exact", "relp_model_fixed_cost_exact",
     # dual simplex from a dual-feasible basis (relp_amd/csrc/dual.hip)
     "relp_solve_dual", "relp_begin_dual", "relp_iterate_dual", "relp_get_dual_pivots", "relp_debug_dual_refusal",
+    # ... started from the parent's inverse on the device (dual_inherit_kernel)
+    "relp_begin_dual_from", "relp_solve_dual_from", "relp_debug_dual_inherit_refusal",
 ]
 
 
@@ -505,6 +507,25 @@ class Model:
             raise RelpError(status, buf.value.decode())
         return buf.value.decode()
 
+    def dual_inherit_refusal(self, parent_model, parent_basis, basis, **options):
+        """Why ``Solver(**options).begin_dual_from`` would refuse to start this model with ``basis`` from a handle that holds
+        ``parent_model`` at ``parent_basis``, in words that name the row or column; ``""`` if it takes the pair
+        (``relp_debug_dual_inherit_refusal``).  Covers ``dual_refusal`` of either model's plan.  Host only."""
+        opts = default_options(**options)
+        parent_arr = np.ascontiguousarray(parent_basis, dtype=np.int32)
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        if len(parent_arr) != parent_model.nr_rows or len(arr) != self.nr_rows:
+            raise ValueError("a basis has one column per row: %d for %d rows of the parent, %d for %d rows of this model" % (
+                len(parent_arr), parent_model.nr_rows, len(arr), self.nr_rows))
+        args = (parent_model._h, self._h, _ptr(parent_arr, C.c_int32), _ptr(arr, C.c_int32), C.byref(opts))
+        length = C.c_int32()
+        lib().relp_debug_dual_inherit_refusal(*args, None, 0, C.byref(length))
+        buf = C.create_string_buffer(length.value + 1)
+        status = lib().relp_debug_dual_inherit_refusal(*args, buf, length.value + 1, C.byref(length))
+        if status != OK:
+            raise RelpError(status, buf.value.decode())
+        return buf.value.decode()
+
     def pivot_element_indices(self):
         count = C.c_int32()
         rows = np.zeros(self.nr_rows, dtype=np.int32)
@@ -723,6 +744,23 @@ class Solver:
         """``set_basis`` and the checks of ``solve_dual``, no pivot (``relp_begin_dual``)."""
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_begin_dual(self._h, _ptr(arr, C.c_int32)))
+
+    def begin_dual_from(self, parent, basis):
+        """``begin_dual`` with the inverse written from the one ``parent`` holds (``relp_begin_dual_from``): ``parent`` is another
+        ``Solver`` on the same device whose LP this one extends by rows (or differs from in costs and right-hand sides only), solved or
+        given a basis; ``basis`` is the parent's ``basis()`` in this LP's columns followed by the slack of each new row.  The parent is
+        only read.  ``RelpError`` where a plan, the parent's state or the relation of the two LPs (``Model.dual_inherit_refusal``) is
+        refused, before anything is launched."""
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        self._check(lib().relp_begin_dual_from(self._h, parent._h, _ptr(arr, C.c_int32)))
+
+    def solve_dual_from(self, parent, basis):
+        """``solve_dual`` with the start of ``begin_dual_from``; returns ``Result`` (``relp_solve_dual_from``).  ``record()`` says
+        which start was taken (``"dual_start"``) and what it cost (``"dual_start_seconds"``, ``"dual_start_gemms"``)."""
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        result = Result()
+        self._check(lib().relp_solve_dual_from(self._h, parent._h, _ptr(arr, C.c_int32), C.byref(result)))
+        return result
 
     def iterate_dual(self, count):
         """Up to ``count`` dual pivots: ``(done, reason)``; ``STOP_NO_ENTERING``: no infeasible row is left, ``STOP_UNBOUNDED``: the

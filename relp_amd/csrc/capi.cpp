@@ -6,6 +6,7 @@
 #include <new>
 #include <sstream>
 
+#include "dual_inherit.hpp"
 #include "network.hpp"
 #include "presolve.hpp"
 #include "exact_values.hpp"
@@ -769,7 +770,11 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     out << "{\"name\": \"" << json_escaped(sv.form().name) << "\", \"presolve\": \"" << presolve_states[sv.form().presolve_state & 3] << "\", \"m\": " << md.nr_rows() << ", \"n\": " << md.nr_columns() << ", \"nnz\": " << nnz
         << ", \"device_rows\": " << d.m << ", \"artificials\": " << d.n_art << ", \"result\": \"" << kinds[r.kind >= 0 && r.kind <= 4 ? r.kind : 0]
         << "\", \"carry\": \"" << (h->options.carry == RELP_CARRY_LU ? "lu" : h->options.carry == RELP_CARRY_LU_INVERSE ? "lu_inverse" : sv.network_carry() ? "network" : "explicit") << "\", \"pivots_phase_one\": " << r.pivots_phase_one
-        << ", \"pivots_phase_two\": " << r.pivots_phase_two << ", \"dual_pivots\": " << sv.dual_pivots() << ", \"dual_device_seconds\": " << sv.dual_device_seconds() << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
+        << ", \"pivots_phase_two\": " << r.pivots_phase_two << ", \"dual_pivots\": " << sv.dual_pivots() << ", \"dual_device_seconds\": " << sv.dual_device_seconds() << ", \"dual_start\": \"" << sv.dual_start()
+        << "\", \"dual_start_seconds\": " << sv.dual_start_seconds() << ", \"dual_start_gemms\": " << sv.dual_start_gemms() << ", \"dual_start_residual\": ";
+    if (sv.dual_start_residual() >= 0.0) out << sv.dual_start_residual();
+    else out << "null";
+    out << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
         << "\", \"device_refactor_fallbacks\": " << sv.device_refactor_fallbacks()
         << ", \"async_refactors\": " << sv.async_refactors() << ", \"async_refactors_abandoned\": " << sv.async_refactors_abandoned() << ", \"async_worst_residual\": " << sv.async_worst_residual()
@@ -889,6 +894,20 @@ int32_t relp_begin_dual(relp_handle* h, const int32_t* basis_columns) {
     REQUIRE_LOADED(h);
     if (!basis_columns) return RELP_ERR_ARGUMENT;
     return guarded(h, [&] { h->solver->begin_dual(basis_columns); });
+}
+int32_t relp_begin_dual_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns) {
+    REQUIRE_LOADED(h);
+    if (!parent || !parent->solver || !basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] { h->solver->begin_dual_from(*parent->solver, basis_columns); });
+}
+int32_t relp_solve_dual_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns, relp_result* result) {
+    REQUIRE_LOADED(h);
+    if (!parent || !parent->solver || !basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] {
+        h->solver->last_error.clear();
+        h->solver->solve_dual_from(*parent->solver, basis_columns, result);
+        if (!h->solver->last_error.empty()) h->error = h->solver->last_error;  // (as relp_solve_dual)
+    });
 }
 int32_t relp_iterate_dual(relp_handle* h, int64_t count, int64_t* done, int32_t* stop_reason) {
     REQUIRE_LOADED(h);
@@ -1101,6 +1120,40 @@ int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* opt
         const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
         text = dual_refusal(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
     } catch (const std::invalid_argument& e) {  // (the load itself would be refused: its message)
+        text = e.what();
+        status = RELP_ERR_ARGUMENT;
+    } catch (const std::exception& e) {
+        text = e.what();
+        status = RELP_ERR_STATE;
+    }
+    if (length) *length = (int32_t)text.size();
+    if (buffer && capacity > 0) {
+        const int32_t nbytes = std::min<int32_t>((int32_t)text.size(), capacity - 1);
+        std::memcpy(buffer, text.data(), nbytes);
+        buffer[nbytes] = 0;
+    }
+    return status;
+}
+int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_model* child, const int32_t* parent_basis, const int32_t* basis_columns,
+                                        const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+    relp_options o;
+    if (!parent || !child || !parent_basis || !basis_columns || adopt_options(options, &o) != RELP_OK) return RELP_ERR_ARGUMENT;
+    int32_t status = RELP_OK;
+    std::string text;
+    try {
+        for (const relp_model* model : {parent, child}) {  // the plan of either LP first, as Solver::begin_dual_from asks
+            const MatrixData& md = model->form.data;
+            const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
+            text = dual_refusal(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
+            if (!text.empty()) {
+                text = (model == parent ? "the parent's plan: " : "the child's plan: ") + text;
+                break;
+            }
+        }
+        if (text.empty())
+            text = dual_inherit_refusal(parent->form, child->form, std::vector<int>(parent_basis, parent_basis + parent->form.data.nr_rows()),
+                                        std::vector<int>(basis_columns, basis_columns + child->form.data.nr_rows()));
+    } catch (const std::invalid_argument& e) {  // (a load that would itself be refused: its message)
         text = e.what();
         status = RELP_ERR_ARGUMENT;
     } catch (const std::exception& e) {

@@ -1,4 +1,5 @@
-// Dual simplex from a given dual-feasible basis: the five kernels of one dual pivot (gfx950, wave64) and their launch helpers.
+// Dual simplex from a given dual-feasible basis: the five kernels of one dual pivot (gfx950, wave64), the kernel that starts a child
+// LP from its parent's inverse, and their launch helpers.
 //
 // The primal kernels cannot leave a primal-infeasible basis (step_decision clamps the leaving value at zero), and the rules of
 // pivot_step.hpp are shared with the fused pivot, so the dual loop is a set of kernels of its own over the same device state
@@ -23,6 +24,7 @@ constexpr int DL_U = 8;               // rows per thread in flight together (K2_
 constexpr int DL_COL_CHUNK = 1024;    // entries of the entering column staged per pass
 constexpr int DU_THREADS = 256;       // dual_update_kernel: four waves, a column pair each
 constexpr int DU_CPW = 2;
+constexpr int DI_THREADS = 256;       // dual_inherit_kernel: four waves, a column of the child's inverse each
 
 // ---------------------------------------------------------------------------------------------------
 // 1. The leaving row: key = -x_B[i] among the rows with x_B[i] < -delta, ties to the lowest basic column, then the lowest row.
@@ -307,8 +309,52 @@ __global__ void __launch_bounds__(DU_THREADS) dual_update_kernel(DeviceLP lp) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The start from a parent's inverse (dual_inherit.hpp): the child's basis is the parent's in the first m positions and the slack of
+// each of the k appended rows behind it, so its inverse is [B^-1 0; -S^-1 C B^-1  S^-1].  A wave per column j of the child's inverse.
+//   j <  m: rows 0 .. m-1 are column j of the parent's inverse (lanes over rows, both sides coalesced; the leading dimensions differ
+//           and neither need be even, so 8-byte accesses); then a lane per new row r, in rounds of 64: over the entries of row m + r
+//           in CSR order whose column is basic at a position below m,  -(sum v parent[pos[col], j]) / s_r  with s_r the entry of the
+//           row's own slack (the column at position m + r).  A fixed order, no atomics; a long cut makes its lane's loop long.
+//   j >= m: the unit column scaled by 1 / s_{j-m}.
+// Every entry of the child's first buffer is written: nothing is left from an earlier use of it.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DI_THREADS) dual_inherit_kernel(DeviceLP lp, const double* __restrict__ parent, int m, int parent_ld) {
+    const int m_child = lp.m, ld = lp.ld;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int j = blockIdx.x * (DI_THREADS / WAVE) + threadIdx.x / WAVE;
+    if (j >= m_child) return;
+    double* out = lp.Binv + (size_t)j * ld;
+    if (j < m) {
+        const double* src = parent + (size_t)j * parent_ld;
+        for (int i = lane; i < m; i += WAVE) out[i] = src[i];
+        for (int row = m + lane; row < m_child; row += WAVE) {
+            double sum = 0.0, own = 0.0;
+            const int last = lp.row_start[row + 1];
+            for (int e = lp.row_start[row]; e < last; ++e) {
+                const int p = lp.pos[lp.col_index[e]];
+                const double v = lp.row_value[e];
+                if (p == row) own = v;
+                else if (p >= 0 && p < m) sum += v * src[p];
+            }
+            out[row] = -sum / own;
+        }
+    } else {
+        double own = 0.0;  // (every lane walks the row: the same addresses, one fetch per wave)
+        const int last = lp.row_start[j + 1];
+        for (int e = lp.row_start[j]; e < last; ++e)
+            if (lp.pos[lp.col_index[e]] == j) own = lp.row_value[e];
+        const double diagonal = 1.0 / own;
+        for (int i = lane; i < m_child; i += WAVE) out[i] = i == j ? diagonal : 0.0;
+    }
+}
+
 }  // namespace
 
+void launch_dual_inherit(const DeviceLP& child, const double* parent_inverse, int parent_m, int parent_ld, hipStream_t s) {
+    const int per_block = DI_THREADS / WAVE;
+    hipLaunchKernelGGL(dual_inherit_kernel, dim3((child.m + per_block - 1) / per_block), dim3(DI_THREADS), 0, s, child, parent_inverse, parent_m, parent_ld);
+}
 void launch_dual_leave(const DeviceLP& d, double harris_delta, hipStream_t s) {
     hipLaunchKernelGGL(dual_leave_kernel, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta);
 }

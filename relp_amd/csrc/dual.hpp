@@ -39,4 +39,10 @@ void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivo
 void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, double tol_pivot, hipStream_t s);
 void launch_dual_update(const DeviceLP& d, hipStream_t s);
 
+// The start from a parent's inverse (Solver::begin_dual_from; the relation between the two LPs: dual_inherit.hpp).  `child` has its
+// pos uploaded for the basis [the parent's basis in the first parent_m positions | the slack of each appended row]; `parent_inverse`
+// is the parent's column-major inverse (parent_m x parent_m, leading dimension parent_ld) on the same device.  Writes every entry of
+// the child's first buffer: the parent's columns, the child.m - parent_m border rows, the scaled unit columns of the new slacks.
+void launch_dual_inherit(const DeviceLP& child, const double* parent_inverse, int parent_m, int parent_ld, hipStream_t s);
+
 }  // namespace relp

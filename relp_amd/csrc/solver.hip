@@ -3,6 +3,7 @@
 //   phase_one.rs:123-278           phase-one loop + zero-level pivots
 //   phase_two.rs:22-59             phase-two loop
 //   kind/artificial/partially.rs   virtual artificial columns (index space: artificials first)
+#include "dual_inherit.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
 #include "solver.hpp"
@@ -67,6 +68,7 @@ Solver::~Solver() {
     destroy_graphs();
     if (ev_a_) (void)hipEventDestroy(ev_a_);
     if (ev_b_) (void)hipEventDestroy(ev_b_);
+    if (ev_parent_) (void)hipEventDestroy(ev_parent_);
     if (ev_snapshot_) (void)hipEventDestroy(ev_snapshot_);
     if (ev_refactored_) (void)hipEventDestroy(ev_refactored_);
     if (refactor_stream_) (void)hipStreamDestroy(refactor_stream_);
@@ -86,6 +88,7 @@ void Solver::free_device() {
     net_ = NetTree{};
     dual_ = DualBuffers{};
     dual_ready_ = false;
+    dual_start_ = "none";
 }
 
 void Solver::reset_stats() { stats_ = relp_stats{}; }
@@ -870,6 +873,7 @@ void Solver::polish(bool refresh_vectors, bool force) {
     // m = 65 534 the residual pass and the two refresh passes are 34 GB each
     if (since_polish_ == 0 && !force && !(opt_.switches & RELP_SW_POLISH_ALWAYS)) return;
     const int m = d_.m;
+    polish_rebuilt_ = false;
     // dense pipeline: only the columns of the stored inverse that are not unit vectors take part (the corresponding
     // rows of S are zero and those columns of the polished inverse do not change): both GEMMs shrink by m / touched
     const bool by_rows = path_.track_touched && path_.polish_gemm == PolishGemm::MFMA;  // (the plain-FMA kernels compute every row)
@@ -892,6 +896,7 @@ void Solver::polish(bool refresh_vectors, bool force) {
         }
         if (!(c.residual == c.residual)) throw std::runtime_error("NaN in basis inverse");
         if (it == 0) {
+            polish_first_residual_ = c.residual;
             max_residual_ = std::max(max_residual_, c.residual);
             // the drift seen after this many pivots schedules the next polish: far below the working accuracy -> wait
             // twice as long (up to 16 periods), close to it -> back to the configured period
@@ -903,9 +908,11 @@ void Solver::polish(bool refresh_vectors, bool force) {
         if (c.residual < 1e-12) break;  // nothing to correct: skip the second GEMM
         if (c.residual >= 0.5) {  // drifted too far for the quadratic iteration: rebuild from the basis columns
             invert_from_scratch();
+            polish_rebuilt_ = true;
             break;
         }
         launch_gemm_polish(path_.polish_gemm, d_.Binv, d_.R, d_.Binv2, m, d_.ld, rows, n_rows, stream_);
+        ++polish_gemms_;
         if (by_rows) launch_copy_rows(d_.Binv2, d_.Binv, m, d_.ld, rows, n_rows, stream_);
         else RELP_HIP(hipMemcpyAsync(d_.Binv, d_.Binv2, (size_t)m * d_.ld * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         if (c.residual < 1e-8) break;  // one quadratic step takes it to ~residual^2
@@ -966,6 +973,7 @@ void Solver::invert_from_scratch() {
         RELP_HIP(hipMemsetAsync(&d_.ctl->residual, 0, sizeof(double), stream_));
         launch_residual(d_, d_.Binv, d_.R, stream_);
         launch_gemm_polish(path_.polish_gemm, d_.Binv, d_.R, d_.Binv2, m, d_.ld, nullptr, m, stream_);
+        ++polish_gemms_;
         RELP_HIP(hipMemcpyAsync(d_.Binv, d_.Binv2, (size_t)m * d_.ld * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         Ctl c = read_ctl();
         if (c.residual < 1e-11) break;
@@ -978,6 +986,18 @@ void Solver::invert_from_scratch() {
 
 // `InverseMaintainer::from_basis` (carry/mod.rs:444-478) + `Tableau::new_with_inverse_maintainer`: phase two from a given basis.
 void Solver::set_basis(const int* basis_columns) {
+    place_basis(basis_columns);
+    invert_from_scratch();
+    if (path_.lu_mode) launch_lu_xb(d_, lu().device(), stream_);
+    else if (path_.network) net_refresh(true, false);
+    else launch_xb(d_, stream_);
+    reset_basis_counters();
+    set_phase(2);
+}
+
+// The first part of set_basis: the basis as the device holds it, pos, (implicit bounds: which columns are complemented, the
+// right-hand side and the bounds of the basic variables,) and a fresh control block.  The inverse is the caller's to provide.
+void Solver::place_basis(const int* basis_columns) {
     if (!loaded_) throw std::runtime_error("no LP loaded");
     RELP_HIP(hipSetDevice(opt_.device));
     dual_ready_ = false;
@@ -1065,10 +1085,10 @@ void Solver::set_basis(const int* basis_columns) {
     c.last_selected = -1;
     c.scan_column = std::numeric_limits<int>::max();
     write_ctl(c);
-    invert_from_scratch();
-    if (path_.lu_mode) launch_lu_xb(d_, lu().device(), stream_);
-    else if (path_.network) net_refresh(true, false);
-    else launch_xb(d_, stream_);
+}
+
+// ... and the last: the inverse is that of a basis given from outside, nothing has been counted on it yet.
+void Solver::reset_basis_counters() {
     binv_identity_ = false;
     refactors_ = 0;
     refactor_seconds_ = 0.0;
@@ -1078,7 +1098,6 @@ void Solver::set_basis(const int* basis_columns) {
     since_polish_ = 0;
     polish_scale_ = 1;
     redundant_rows_.clear();
-    set_phase(2);
 }
 
 long long Solver::iterate(long long count, int* stop_reason) {
@@ -1350,17 +1369,77 @@ void Solver::certify(relp_result* result) {
 // ---- dual simplex from a given basis (dual.hip) -------------------------------------------------------
 // The optimal basis of an LP stays dual feasible when rows are appended or a right-hand side is tightened, and is primal infeasible
 // where the change bites: the caller loads the changed LP and passes the old basis, extended by the slack of each new row.
-void Solver::begin_dual(const int* basis_columns) {
+void Solver::check_dual_start(const int* basis_columns) const {
     if (!loaded_) throw std::runtime_error("no LP loaded");
-    RELP_HIP(hipSetDevice(opt_.device));
     const std::string refusal = dual_refusal(path_);
     if (!refusal.empty()) throw std::invalid_argument(refusal);
-    const int m = d_.m, n = d_.n, n_art = d_.n_art;
-    for (int i = 0; i < m; ++i)
+    for (int i = 0; i < d_.m; ++i)
         if (basis_columns[i] < 0)
             throw std::invalid_argument("begin_dual: the basis holds an artificial column (code " + std::to_string(basis_columns[i]) + " on row " + std::to_string(i) +
                                         "): the dual simplex starts from a basis of the LP's own columns");
+}
+
+void Solver::begin_dual(const int* basis_columns) {
+    check_dual_start(basis_columns);
+    RELP_HIP(hipSetDevice(opt_.device));
+    const double t0 = now_seconds();
+    const long long gemms_before = polish_gemms_;
+    dual_start_ = "none";
     set_basis(basis_columns);  // inverse from scratch, x_B, the costs of phase two, -pi; every column of the inverse marked touched
+    dual_start_residual_ = -1.0;  // (no guard: the inverse was iterated to its own stopping rule)
+    finish_dual_start(basis_columns, "scratch", t0, gemms_before);
+}
+
+std::vector<int> Solver::provider_basis() const {
+    std::vector<int> basis(d_.m);
+    RELP_HIP(hipMemcpyAsync(basis.data(), d_.basis, d_.m * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    RELP_HIP(hipStreamSynchronize(stream_));
+    for (int& column : basis) column = cols_.to_provider(column);
+    return basis;
+}
+
+// The child of a cut loop or of a branching step: `parent` holds the inverse of all but k rows of this basis, polished, on the same
+// device (dual_inherit.hpp has the block form).  Everything that can refuse does so before the first launch.
+void Solver::begin_dual_from(const Solver& parent, const int* basis_columns) {
+    if (!loaded_) throw std::runtime_error("no LP loaded");
+    if (&parent == this) throw std::runtime_error("begin_dual_from: the parent is this handle itself (the child is loaded on a handle of its own)");
+    if (!parent.loaded_) throw std::runtime_error("begin_dual_from: the parent handle has no LP loaded");
+    const std::string parent_plan = dual_refusal(parent.path_);
+    if (!parent_plan.empty()) throw std::invalid_argument("begin_dual_from: the parent's plan: " + parent_plan);
+    check_dual_start(basis_columns);
+    if (parent.opt_.device != opt_.device)
+        throw std::invalid_argument("begin_dual_from: the parent is on device " + std::to_string(parent.opt_.device) + ", this handle on device " +
+                                    std::to_string(opt_.device) + ": the inverse is inherited on one device");
+    if (parent.phase_ == 0)
+        throw std::runtime_error("begin_dual_from: the parent has no basis and inverse yet (a solve, set_basis or solve_dual on it comes first)");
+    RELP_HIP(hipSetDevice(opt_.device));
+    const std::string relation = dual_inherit_refusal(parent.form_, form_, parent.provider_basis(), std::vector<int>(basis_columns, basis_columns + d_.m));
+    if (!relation.empty()) throw std::invalid_argument("begin_dual_from: " + relation);
+    const double t0 = now_seconds();
+    const long long gemms_before = polish_gemms_;
+    dual_start_ = "none";
+    place_basis(basis_columns);
+    if (!ev_parent_) RELP_HIP(hipEventCreateWithFlags(&ev_parent_, hipEventDisableTiming));
+    RELP_HIP(hipEventRecord(ev_parent_, parent.stream_));  // whatever the parent still has on its way to its inverse comes first
+    RELP_HIP(hipStreamWaitEvent(stream_, ev_parent_, 0));
+    stats_.launches += 2;
+    launch_dual_inherit(d_, parent.d_.Binv, parent.d_.m, parent.d_.ld, stream_);
+    launch_mark_all_touched(d_, stream_);  // no column of an inherited inverse is known to be a unit vector
+    reset_basis_counters();
+    // The guard: max |I - B Binv| of this basis against this LP's own matrix; below 1e-12 it adds nothing, otherwise one or two
+    // Newton-Schulz steps, from 0.5 on the from-scratch inverse.  It also refreshes x_B (and -pi, which set_phase recomputes with the
+    // costs of phase two in place: the copy below only keeps the polish's own -pi pass off a cost vector nothing has written yet).
+    RELP_HIP(hipMemcpyAsync(d_.cost, d_.cost2, d_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+    polish_first_residual_ = -1.0;
+    polish(true, true);
+    dual_start_residual_ = polish_first_residual_;
+    RELP_HIP(hipStreamSynchronize(stream_));  // the parent's inverse has been read: the caller may use the parent again
+    set_phase(2);
+    finish_dual_start(basis_columns, polish_rebuilt_ ? "scratch_after_inherit" : "inherited", t0, gemms_before);
+}
+
+void Solver::finish_dual_start(const int* basis_columns, const char* how, double t0, long long gemms_before) {
+    const int m = d_.m, n = d_.n, n_art = d_.n_art;
     if (!dual_.alpha_row) {
         dual_.blocks = dual_blocks(n_art, n);
         dual_.alpha_row = device_alloc<double>(n);
@@ -1384,6 +1463,10 @@ void Solver::begin_dual(const int* basis_columns) {
     dual_pivots_ = 0;
     dual_device_seconds_ = 0.0;
     dual_ready_ = true;
+    RELP_HIP(hipStreamSynchronize(stream_));
+    dual_start_ = how;
+    dual_start_seconds_ = now_seconds() - t0;
+    dual_start_gemms_ = polish_gemms_ - gemms_before;
 }
 
 // One batch: the budget, then five launches per pivot (dual.hpp).  The chain is a run of no-ops from the first kernel that stops it.
@@ -1452,14 +1535,18 @@ long long Solver::iterate_dual(long long count, int* stop_reason) {
     return done;
 }
 
-void Solver::solve_dual(const int* basis_columns, relp_result* result) {
+void Solver::solve_dual(const int* basis_columns, relp_result* result) { run_dual(nullptr, basis_columns, result); }
+void Solver::solve_dual_from(const Solver& parent, const int* basis_columns, relp_result* result) { run_dual(&parent, basis_columns, result); }
+
+void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_result* result) {
     if (!loaded_) throw std::runtime_error("no LP loaded");
     RELP_HIP(hipSetDevice(opt_.device));
     const double t0 = now_seconds();
     exact_objective.clear();
     exact_primal.reset();
     exact_witnesses.reset();
-    begin_dual(basis_columns);
+    if (parent) begin_dual_from(*parent, basis_columns);
+    else begin_dual(basis_columns);
     const long long cap = opt_.max_pivots > 0 ? opt_.max_pivots : 200LL * (d_.m + d_.n) + 100000;
     int kind = RELP_RESULT_NONE;
     int reason = 0;

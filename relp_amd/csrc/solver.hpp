@@ -53,7 +53,23 @@ public:
     void begin_dual(const int* basis_columns);
     long long iterate_dual(long long count, int* stop_reason);
     void solve_dual(const int* basis_columns, relp_result* result);
+    // The same from the inverse of `parent`, a handle on the same device whose LP this one extends (dual_inherit.hpp: the parent's
+    // basis in the first positions, the slack of each appended row behind it; costs and right-hand sides may differ).  The refusals
+    // come before anything is launched: std::invalid_argument for a plan the dual kernels do not take (either handle), a parent on
+    // another device and a non-empty dual_inherit_refusal; std::runtime_error for a parent that has no LP, or no basis and inverse
+    // yet, or is this handle.  Then the child's inverse is written from the parent's by one kernel (dual_inherit_kernel) behind an
+    // event on the parent's stream, and a forced polish guards it: its residual pass measures the child's basis against the child's
+    // own matrix, corrects what it finds and rebuilds from scratch by itself from 0.5 on.  The parent is only read.
+    void begin_dual_from(const Solver& parent, const int* basis_columns);
+    void solve_dual_from(const Solver& parent, const int* basis_columns, relp_result* result);
     long long dual_pivots() const { return dual_pivots_; }  // of the last solve_dual / since begin_dual
+    // How the last begin_dual / begin_dual_from got its inverse ("none" before the first): "scratch", "inherited", or
+    // "scratch_after_inherit" where the guard of an inherited inverse rebuilt it; the wall time of that call (the stream synchronised
+    // at its end), the GEMMs of the polish and the from-scratch inverse inside it, and the guard's first residual (-1: no guard ran).
+    const char* dual_start() const { return dual_start_; }
+    double dual_start_seconds() const { return dual_start_seconds_; }
+    long long dual_start_gemms() const { return dual_start_gemms_; }
+    double dual_start_residual() const { return dual_start_residual_; }
     double dual_device_seconds() const { return dual_device_seconds_; }  // ... and the device time of their batches (stream events)
 
     // fine-grained ops (trait parity)
@@ -154,6 +170,21 @@ private:
     long long dual_pivots_ = 0;
     double dual_device_seconds_ = 0.0;
     void launch_dual_pivots(int count);
+    // set_basis in three parts, shared with begin_dual_from: basis, pos and the control block; (the inverse); the handle's counters
+    void place_basis(const int* basis_columns);
+    void reset_basis_counters();
+    void check_dual_start(const int* basis_columns) const;  // the refusals begin_dual and begin_dual_from share: the plan, an artificial
+    // ... and their tail behind set_phase(2): the loop's buffers, the dual-feasibility check that names the column, the counters
+    void finish_dual_start(const int* basis_columns, const char* how, double t0, long long gemms_before);
+    void run_dual(const Solver* parent, const int* basis_columns, relp_result* result);  // solve_dual and solve_dual_from: one loop
+    std::vector<int> provider_basis() const;  // the basis on the device, provider columns by position (plans without implicit bounds)
+    const char* dual_start_ = "none";
+    double dual_start_seconds_ = 0.0, dual_start_residual_ = -1.0;
+    long long dual_start_gemms_ = 0;
+    long long polish_gemms_ = 0;            // launch_gemm_polish calls of this handle (polish, invert_from_scratch)
+    double polish_first_residual_ = -1.0;   // of the last polish that measured one: its first reading ...
+    bool polish_rebuilt_ = false;           // ... and whether it gave up on the quadratic step and inverted from scratch
+    hipEvent_t ev_parent_ = nullptr;        // begin_dual_from: recorded on the parent's stream, waited for on this one
     std::vector<double> net_host_solve(const HostTree& t, bool transposed, const std::vector<double>& v) const;  // B^-1 v or v' B^-1
     CertifyScratch certify_scratch_;
     // spanning-forest carry (network_carry.hip)

@@ -13,7 +13,16 @@ For the cut cases of tests/dual_lps.py at m = 1025 and m = 2049 (the parent solv
 ``--decimal`` divides every matrix value by 10: the Harris rule runs instead of the reference's.
 Every figure is the median of 5 runs after one warm-up, in one process.
 
-    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N]
+``--start`` prints the other table instead, one line per child (4 and 24 cuts, integer and decimal data): how the dual loop starts.
+  solve_dual        wall time of the whole call around a stream synchronise, and how much of it ``begin_dual`` took
+                    (``dual_start_seconds`` of ``record()``)
+  begin_dual        from scratch: ``dual_start_seconds`` and ``dual_start_gemms``
+  begin_dual_from   from the inverse of the parent's handle, which stays open beside the child's: the same two, and the guard's residual
+  solve_dual_from   the whole call with that start
+with the smallest and largest of the 5 runs beside each median.  Run against a library that has no ``relp_begin_dual_from``
+(``RELP_AMD_LIB``), it prints ``solve_dual`` alone.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]]
 """
 import argparse
 import os
@@ -103,12 +112,82 @@ def probe(m, decimal, n_cuts):
     plain.close()
 
 
+def spread_of(run):
+    """Median, minimum and maximum of each column over the 5 runs after the warm-up."""
+    run()
+    samples = [run() for _ in range(RUNS)]
+    return [(statistics.median(column), min(column), max(column)) for column in zip(*samples)]
+
+
+def start_probe(m, decimal, n_cuts, traced=False):
+    """One child of the table of DESIGN.md section 10: how the dual loop starts and what that is of the whole re-solve.  ``traced``:
+    the two begin calls only, every handle with plain launches."""
+    seed, _ = dual_lps.STATE_CASES[m]
+    case = dual_lps.cut_case(m, dual_lps.MIXED, seed, n_cuts, decimal=decimal)
+    options = dict(certify=1, use_graph=0) if traced else dict(certify=1)
+    parent = relp_amd.Solver(**options).load_model(case.parent)
+    assert parent.solve_relaxation().certified
+    child, basis, _ = case.child(parent.basis(), parent.solution_exact())
+    solver = relp_amd.Solver(**options).load_model(child)
+    inherits = hasattr(relp_amd.lib(), "relp_begin_dual_from")  # (a library of before the start from the parent's inverse: solve_dual alone)
+
+    def solve(call):
+        def run():
+            started = time.perf_counter()
+            result = call()
+            wall = 1e3 * (time.perf_counter() - started)
+            assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+            record = solver.record()
+            return wall, 1e3 * record.get("dual_start_seconds", 0.0), solver.dual_pivots()
+        return run
+
+    def begin(call):
+        def run():
+            call()
+            record = solver.record()
+            return 1e3 * record["dual_start_seconds"], record["dual_start_gemms"], record["dual_start_residual"] or 0.0
+        return run
+
+    label = "m = %d + %d cuts, %s" % (m, n_cuts, "decimal" if decimal else "integer")
+    if traced:
+        (scratch_ms, _, _), (scratch_gemms, _, _), _ = spread_of(begin(lambda: solver.begin_dual(basis)))
+        (from_ms, _, _), (from_gemms, _, _), _ = spread_of(begin(lambda: solver.begin_dual_from(parent, basis)))
+        print("%s (traced, plain launches): begin_dual %.2f ms, %d GEMMs | begin_dual_from %.2f ms, %d GEMMs" % (label, scratch_ms, scratch_gemms, from_ms, from_gemms), flush=True)
+        solver.close()
+        parent.close()
+        return
+    (solve_ms, solve_lo, solve_hi), (start_in_solve, _, _), (pivots, _, _) = spread_of(solve(lambda: solver.solve_dual(basis)))
+    text = "%s: solve_dual %.1f ms (%.1f .. %.1f), %d dual pivots" % (label, solve_ms, solve_lo, solve_hi, pivots)
+    if inherits:
+        (scratch_ms, scratch_lo, scratch_hi), (scratch_gemms, _, _), _ = spread_of(begin(lambda: solver.begin_dual(basis)))
+        (from_ms, from_lo, from_hi), (from_gemms, _, _), (residual, _, _) = spread_of(begin(lambda: solver.begin_dual_from(parent, basis)))
+        (warm_ms, warm_lo, warm_hi), _, (warm_pivots, _, _) = spread_of(solve(lambda: solver.solve_dual_from(parent, basis)))
+        # (the two inverses differ in their last bits, so on dual-degenerate data the two walks need not make the same pivots)
+        text += (", of which begin_dual %.1f ms = %.0f %% | begin_dual %.2f ms (%.2f .. %.2f), %d GEMMs | begin_dual_from %.2f ms (%.2f .. %.2f), "
+                 "%d GEMMs, guard's residual %.1e | solve_dual_from (%s) %.1f ms (%.1f .. %.1f), %d dual pivots" % (
+                     start_in_solve, 100.0 * start_in_solve / solve_ms, scratch_ms, scratch_lo, scratch_hi, scratch_gemms, from_ms, from_lo, from_hi,
+                     from_gemms, residual, solver.record()["dual_start"], warm_ms, warm_lo, warm_hi, warm_pivots))
+    print(text, flush=True)
+    solver.close()
+    parent.close()
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
     parser.add_argument("--decimal", action="store_true")
     parser.add_argument("--cuts", type=int, default=0, help="cuts per child (default: those of tests/dual_lps.py)")
+    parser.add_argument("--start", action="store_true", help="only the table of the dual loop's start: 4 and 24 cuts (or --cuts), integer and decimal data")
+    parser.add_argument("--traced", action="store_true",
+                        help="with --start, for a run under rocprofv3 --kernel-trace (which does not survive the replay of a captured graph: "
+                             "tools/profile_r2_maxflow.sh): every handle with plain launches, and begin_dual / begin_dual_from only")
     args = parser.parse_args()
+    if args.start:
+        for m in args.sizes:
+            for n_cuts in ([args.cuts] if args.cuts else [4, 24]):
+                for decimal in ([True] if args.decimal else [False, True]):
+                    start_probe(m, decimal, n_cuts, args.traced)
+        return
     for m in args.sizes:
         probe(m, args.decimal, args.cuts)
 
