@@ -22,7 +22,7 @@ same numbers from the structure of that elimination alone -- the k x k Schur blo
 -- for sparse LPs of thousands of rows (tests/test_gpu_sparse_state.py: 8193 rows, k = 100, well under a second and 22 MB).
 """
 from fractions import Fraction
-from math import lcm
+from math import gcd, lcm
 
 import numpy as np
 
@@ -89,6 +89,86 @@ def fraction_free_inverse(matrix):
         work[k, k:] = row
         previous = pivot
     return work[:, s:], previous
+
+
+_sparse_inverses = {}  # the components that ``sparse_inverse`` has inverted, by content: the bases of one walk share most of theirs
+_SPARSE_INVERSES_KEPT = 1 << 20  # numerators (Python integers) kept at the most: beyond, the oldest results go first
+_sparse_inverse_entries = [0]
+
+
+def sparse_inverse(matrix):
+    """``(N, D)`` with ``matrix^-1 = N / D`` and ``|D| = |det|``, as ``fraction_free_inverse`` returns them (the sign of D may differ, and N
+    with it), for a SPARSE block: Gauss-Jordan on rows held as dicts of integers over one denominator per row (reduced by their gcd after
+    every update), the pivot in the active column with the fewest active rows and there in the shortest row.  An arrow of 259 columns
+    costs its 259^2 results, not 259^3 integer updates.  Results are kept by content."""
+    s = matrix.shape[0]
+    if s == 0:
+        return np.zeros((0, 0), dtype=object), 1
+    filled = [(int(i), int(j), int(matrix[i, j])) for i, j in zip(*np.nonzero(matrix != 0))]
+    key = (s, tuple(filled))
+    if key in _sparse_inverses:
+        return _sparse_inverses[key]
+    left, right, den = [{} for _ in range(s)], [{i: 1} for i in range(s)], [1] * s  # row r = (left[r] | right[r]) / den[r], integers
+    in_column, count = [set() for _ in range(s)], [0] * s  # rows with an entry in the column; how many of them are active
+    for i, j, v in filled:
+        left[i][j] = v
+        in_column[j].add(i)
+        count[j] += 1
+    active, active_columns, row_of, det = set(range(s)), set(range(s)), {}, Fraction(1)
+    for _ in range(s):
+        j = min(active_columns, key=lambda c: (count[c], c))
+        if count[j] == 0:
+            raise ZeroDivisionError("singular basis")
+        i = min((r for r in in_column[j] if r in active), key=lambda r: (len(left[r]), r))
+        pivot = left[i][j]
+        det *= Fraction(pivot, den[i])
+        den[i] = pivot  # the row over its pivot: (integers / den) / (pivot / den)
+        for r in [r for r in in_column[j] if r != i]:
+            factor = left[r][j]  # row r <- row r - (factor / den[r]) (row i / pivot) = (pivot row r - factor row i) / (den[r] pivot)
+            row = {c: v * pivot for c, v in left[r].items()} if pivot != 1 else left[r]
+            for c, v in left[i].items():
+                had = c in row
+                value = row.get(c, 0) - factor * v
+                if value == 0:
+                    if had:
+                        del row[c]
+                        in_column[c].discard(r)
+                        count[c] -= r in active
+                else:
+                    row[c] = value
+                    if not had:
+                        in_column[c].add(r)
+                        count[c] += r in active
+            target = {c: v * pivot for c, v in right[r].items()} if pivot != 1 else right[r]
+            for c, v in right[i].items():
+                value = target.get(c, 0) - factor * v
+                if value == 0:
+                    target.pop(c, None)
+                else:
+                    target[c] = value
+            den[r] *= pivot
+            common = gcd(den[r], *row.values(), *target.values())
+            if common > 1:
+                row, target, den[r] = {c: v // common for c, v in row.items()}, {c: v // common for c, v in target.items()}, den[r] // common
+            left[r], right[r] = row, target
+        active.discard(i)
+        active_columns.discard(j)
+        for c in left[i]:
+            count[c] -= 1
+        row_of[j] = i
+    assert det.denominator == 1
+    numerators = np.zeros((s, s), dtype=object)
+    for j in range(s):
+        for c, v in right[row_of[j]].items():
+            numerators[j, c], rest = divmod(v * det.numerator, den[row_of[j]])
+            assert rest == 0
+    _sparse_inverses[key] = numerators, det.numerator
+    _sparse_inverse_entries[0] += s * s
+    while _sparse_inverse_entries[0] > _SPARSE_INVERSES_KEPT and len(_sparse_inverses) > 1:
+        oldest = next(iter(_sparse_inverses))  # (a dict keeps the order of insertion)
+        _sparse_inverse_entries[0] -= oldest[0] * oldest[0]
+        del _sparse_inverses[oldest]
+    return numerators, det.numerator
 
 
 class BasisState:
@@ -300,6 +380,10 @@ class BasisState:
         return long_double(*zip(*[split_fraction(t) for t in total]))
 
 
+class Component:
+    """One connected component of the Schur block of a ``SparseBasisState`` (``_invert_components``)."""
+
+
 class SparseBasisState(BasisState):
     """The same state for a sparse LP of thousands of rows, held in the structure ``_invert`` finds and never as an (m, m) or (m, n)
     array.  With ``B' = B diag(scale)`` (integer; single-entry columns become unit vectors), ``unit`` the positions of those columns,
@@ -308,10 +392,13 @@ class SparseBasisState(BasisState):
         x = B'^-1 y:   x_other = S^-1 y_rest,                         x_u = y_row(u) - U[u, :] x_other
         z = w' B'^-1:  z_rest = (w_other - w_unit' U) S^-1,           z_row(u) = w_u
 
-    so a row of the inverse has entries in ``rest`` and, for a unit position, at its own row.  Stored: ``S^-1 = block / det`` in Python
-    integers and as ``longdouble``, ``U`` as coordinate lists, the scales, and all n columns in compressed form.  The per-column
-    quantities cost O(k nnz_j + nnz(U)) each.  Index spaces, ``den``, ``x_exact``, ``objective_exact``, ``reduced_cost_exact``,
-    ``alpha_exact`` and ``gamma_exact`` are those of ``BasisState``; ``num`` is read a row at a time (``row_exact``)."""
+    so a row of the inverse has entries in ``rest`` and, for a unit position, at its own row.  ``S`` is inverted per CONNECTED COMPONENT
+    of its row / column graph (``components``: a planted basis of 900 non-unit columns in blocks of at most 258 costs the sum of the
+    blocks' cubes, not 900^3), each ``S_c^-1 = block_c / det_c`` in Python integers; ``det`` is the product of the ``det_c``, and
+    ``den`` and ``row_exact`` are stated over it, so that they are the numbers of ``BasisState``.  Stored besides: ``S^-1`` as
+    ``longdouble``, ``U`` as coordinate lists, the scales, and all n columns in compressed form.  The per-column quantities cost
+    O(k nnz_j + nnz(U)) each.  Index spaces, ``den``, ``x_exact``, ``objective_exact``, ``reduced_cost_exact``, ``alpha_exact`` and
+    ``gamma_exact`` are those of ``BasisState``; ``num`` is read a row at a time (``row_exact``)."""
 
     # ---- B^-1 --------------------------------------------------------------------------------------
     def _invert(self):
@@ -343,7 +430,7 @@ class SparseBasisState(BasisState):
                     schur[rest_at[i], a] = value
                 else:
                     coo.append((int(unit_at[i]), a, value))
-        self.block, self.det = fraction_free_inverse(schur)
+        self._invert_components(schur)
         self.k, self.scale = k, scale
         self.unit, self.unit_row, self.other, self.rest = (np.array(v, dtype=np.int64) for v in (unit, unit_row, other, rest))
         self.rest_at, self.unit_at = rest_at, unit_at
@@ -355,6 +442,9 @@ class SparseBasisState(BasisState):
         self.coo_of_unit = {}  # place in `unit` -> [(place in `other`, integer)]
         for u, a, value in coo:
             self.coo_of_unit.setdefault(u, []).append((a, value))
+        self.coo_of_other = {}  # place in `other` -> [(place in `unit`, integer)]
+        for u, a, value in coo:
+            self.coo_of_other.setdefault(a, []).append((u, value))
         self.place = np.zeros(m, dtype=np.int64)  # position -> its place in `unit` or in `other`
         self.place[self.unit] = np.arange(len(unit))
         self.place[self.other] = np.arange(k)
@@ -367,28 +457,70 @@ class SparseBasisState(BasisState):
             self.factor.append(scale[position].numerator * (-1 if d < 0 else 1))
         self.scale_long = long_double(*zip(*[split_fraction(s) for s in scale]))
         hi, lo = np.zeros((k, k)), np.zeros((k, k))
-        for a in range(k):
-            for i in range(k):
-                hi[a, i], lo[a, i] = split(self.block[a, i], self.det)
+        for c in self.components:
+            for a, row in zip(c.columns, c.block):
+                for i, value in zip(c.rows, row):
+                    hi[a, i], lo[a, i] = split(value, c.det)
         self.block_long = long_double(hi, lo)
         self._csc = None
+
+    def _invert_components(self, schur):
+        """``components``: the connected components of the graph that joins place i of ``rest`` with place a of ``other`` where
+        ``schur[i, a] != 0``, each with ``rows`` (places in ``rest``), ``columns`` (places in ``other``), ``block[a, i]`` and ``det``:
+        ``S_c^-1 = block / det``.  ``component_of[a]``, ``component_at[a]``: the component of place a of ``other`` and a's place in its
+        ``columns``; ``row_component_of[i]``, ``row_component_at[i]``: the same for place i of ``rest``."""
+        k = schur.shape[0]
+        parent = list(range(2 * k))  # places of `rest`, then places of `other`
+
+        def find(v):
+            while parent[v] != v:
+                parent[v] = parent[parent[v]]
+                v = parent[v]
+            return v
+        for i, a in zip(*np.nonzero(schur != 0)):
+            first, second = find(int(i)), find(k + int(a))
+            if first != second:
+                parent[second] = first
+        members = {}
+        for v in range(2 * k):
+            members.setdefault(find(v), ([], []))[v >= k].append(v - k if v >= k else v)
+        self.components = []
+        self.component_of, self.component_at = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64)
+        self.row_component_of, self.row_component_at = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64)
+        self.det = 1
+        for rows, columns in sorted(members.values()):
+            if len(rows) != len(columns):
+                raise ZeroDivisionError("singular basis")
+            component = Component()
+            component.rows, component.columns = np.array(rows, dtype=np.int64), np.array(columns, dtype=np.int64)
+            component.block, component.det = sparse_inverse(schur[np.ix_(rows, columns)])
+            self.component_of[columns], self.component_at[columns] = len(self.components), np.arange(len(columns))
+            self.row_component_of[rows], self.row_component_at[rows] = len(self.components), np.arange(len(rows))
+            self.components.append(component)
+            self.det *= component.det
+        for component in self.components:
+            component.cofactor = self.det // component.det
+
+    def _row_by_components(self, position):
+        """Row ``position`` of ``det B'^-1`` before ``factor``: ``(columns, numerators)``, unsorted, zeros included."""
+        if self.in_other[position]:
+            a = self.place[position]
+            c = self.components[self.component_of[a]]
+            return self.rest[c.rows], c.block[self.component_at[a], :] * c.cofactor
+        u = int(self.place[position])
+        own = (np.array([self.unit_row[u]]), np.array([self.det], dtype=object))
+        spread = {}  # component -> - U[u, columns of the component] block
+        for a, value in self.coo_of_unit.get(u, ()):
+            at = int(self.component_of[a])
+            spread[at] = spread.get(at, 0) - value * self.components[at].block[self.component_at[a], :]
+        parts = [(self.rest[self.components[at].rows], values * self.components[at].cofactor) for at, values in sorted(spread.items())]
+        return np.concatenate([p[0] for p in parts] + [own[0]]), np.concatenate([p[1] for p in parts] + [own[1]])
 
     def row_exact(self, position):
         """Row ``position`` of ``B^-1`` as ``(columns, numerators)`` over ``den[position]``; zeros left out, columns ascending."""
         position = int(position)
-        factor = self.factor[position]
-        if self.in_other[position]:
-            where, values = self.rest, self.block[self.place[position], :] * factor
-        else:
-            u = int(self.place[position])
-            entries = self.coo_of_unit.get(u)
-            if entries is None:
-                return np.array([self.unit_row[u]]), np.array([self.det * factor], dtype=object)
-            spread = np.zeros(self.k, dtype=object)
-            for a, value in entries:
-                spread = spread - value * self.block[a, :]
-            where = np.concatenate([self.rest, [self.unit_row[u]]])
-            values = np.concatenate([spread, np.array([self.det], dtype=object)]) * factor
+        where, values = self._row_by_components(position)
+        values = values * self.factor[position]
         keep = np.flatnonzero(values != 0)
         order = keep[np.argsort(where[keep], kind="stable")]
         return where[order], values[order]
@@ -420,24 +552,29 @@ class SparseBasisState(BasisState):
         """``B^-1 y`` for the sparse ``y`` (Fractions) as ``{position: Fraction}``, zeros left out."""
         common = lcm(*[v.denominator for v in values]) if len(values) else 1
         ints = [int(v * common) for v in values]
-        den = self.det * common
-        product = np.zeros(self.k, dtype=object)  # det S^-1 y_rest
-        top = {}  # place in `unit` -> common y_row(u)
+        products = {}  # component -> common det_c S_c^-1 y_rows
+        top = {}  # place in `unit` -> y_row(u) - U[u, :] x_other
         for i, v in zip(rows, ints):
+            if v == 0:
+                continue
             if self.rest_at[i] >= 0:
-                product = product + v * self.block[:, self.rest_at[i]]
+                at = int(self.row_component_of[self.rest_at[i]])
+                products[at] = products.get(at, 0) + v * self.components[at].block[:, self.row_component_at[self.rest_at[i]]]
             else:
-                top[int(self.unit_at[i])] = v * self.det
-        out = {}
-        for a in np.flatnonzero(product != 0):
-            out[int(self.other[a])] = self.scale[self.other[a]] * Fraction(int(product[a]), den)
-        if len(out):
-            for u, a, value in zip(self.coo_unit.tolist(), self.coo_other.tolist(), self.coo_value):
-                if product[a] != 0:
-                    top[u] = top.get(u, 0) - value * product[a]
+                top[int(self.unit_at[i])] = Fraction(v, common)
+        out, solved = {}, {}  # solved: place in `other` -> x_other before the scale
+        for at, product in products.items():
+            c = self.components[at]
+            for inside in np.flatnonzero(product != 0):
+                a = int(c.columns[inside])
+                solved[a] = Fraction(int(product[inside]), c.det * common)
+                out[int(self.other[a])] = self.scale[self.other[a]] * solved[a]
+        for a, x in solved.items():
+            for u, value in self.coo_of_other.get(a, ()):
+                top[u] = top.get(u, 0) - value * x
         for u, value in top.items():
             if value != 0:
-                out[int(self.unit[u])] = self.scale[self.unit[u]] * Fraction(int(value), den)
+                out[int(self.unit[u])] = self.scale[self.unit[u]] * value
         return out
 
     def _combine(self, weights):
@@ -455,11 +592,15 @@ class SparseBasisState(BasisState):
         for u in by_unit.keys() & self.coo_of_unit.keys():
             for a, value in self.coo_of_unit[u]:
                 reduced[a] -= by_unit[u] * value
-        common = lcm(*[v.denominator for v in reduced]) if self.k else 1
-        product = np.array([int(v * common) for v in reduced], dtype=object).dot(self.block) if self.k else []
-        for i, value in zip(self.rest.tolist(), product):
-            if value != 0:
-                out[i] = Fraction(int(value), self.det * common)
+        for c in self.components:
+            mine = [reduced[a] for a in c.columns]
+            if not any(mine):
+                continue
+            common = lcm(*[v.denominator for v in mine])
+            product = np.array([int(v * common) for v in mine], dtype=object).dot(c.block)
+            for i, value in zip(self.rest[c.rows].tolist(), product):
+                if value != 0:
+                    out[i] = Fraction(int(value), c.det * common)
         return out
 
     def _vectors(self):

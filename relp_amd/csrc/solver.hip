@@ -935,6 +935,8 @@ void Solver::ensure_polish_buffers() {
 
 void Solver::invert_from_scratch() {
     if (path_.lu_mode) {
+        // (set_basis on a handle that never began phase one: the refactorisation kernels write into arrays that lu_identity sizes by bounds)
+        if (path_.device_refactor && !lu().device_prepared()) lu_identity();
         refactor_lu(false);
         return;
     }

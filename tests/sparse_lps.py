@@ -39,6 +39,13 @@ PIVOTS, BATCH = 100, 64  # what every case of tests/test_gpu_sparse_state.py wal
 _cases = {}
 
 
+def btrans(m):
+    """Three vectors with a small non-zero integer in EVERY row: a wrong entry in a row that nothing else reads still shows."""
+    i = np.arange(m)
+    rows = i.astype(np.int32)
+    return [(rows, (1.0 + i % 7)), (rows, -(1.0 + i % 5)), (rows, (1.0 + (3 * i) % 9) * np.where(i % 2, -1.0, 1.0))]
+
+
 def less_lp(m, n, lengths, seed):
     """min c x, A x <= A x0 + r, x >= 0 (docstring of the module)."""
     rng = np.random.RandomState(seed)
@@ -140,9 +147,10 @@ def preconditions(exact, provider, mix):
     return not_unit, chosen, nnz, len(entered)
 
 
-def walk(provider, phase, pivots, textbook=False):
+def walk(provider, phase, pivots, textbook=False, basis=None):
     """``pivots`` steps of the numpy f64 model of the device's loop, never polished; returns the model (``basis_of`` reads its basis).
-    ``textbook``: the reference's ratio test (the exact minimum ratio, ties to the lowest leaving column) in place of the Harris test."""
+    ``textbook``: the reference's ratio test (the exact minimum ratio, ties to the lowest leaving column) in place of the Harris test.
+    ``basis``: where to start (as ``Solver.set_basis`` takes it, no artificial) instead of the slack basis; inverted by numpy."""
     from f64_model import Model, Options
 
     class Textbook(Model):
@@ -158,6 +166,13 @@ def walk(provider, phase, pivots, textbook=False):
     options.max_iters = pivots
     model = (Textbook if textbook else Model)(provider, options)
     assert (model.n_art > 0) == (phase == 1)
+    if basis is not None:
+        assert model.n_art == 0 and min(basis) >= 0
+        model.basis = np.array(basis, dtype=np.int64)
+        model.pos[:] = -1
+        model.pos[model.basis] = np.arange(model.m)
+        model.Binv = np.linalg.inv(model.A[:, model.basis].toarray())
+        model.xB = model.Binv @ model.xB
     model.set_phase(model.cost1 if phase == 1 else model.cost2)
     assert model.run_phase(phase) == "iteration_limit"
     model.price()  # applies the weight update of the last pivot

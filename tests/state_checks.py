@@ -8,6 +8,10 @@ import pytest
 from basis_state import long_double, newton_schulz_polish, polished_tolerance
 
 EVERYTHING = ("inverse", "vertex", "costs", "weights", "alpha", "btran", "selection")
+# The tolerance of an un-polished state per part of ``assert_state``'s ``report``, on the scale the report is in: the absolute term of
+# ``close()`` (inverse, vertex, alpha, btran), relative to max(1, |objective|), to 1 + |cost|, and relative for the weights.
+ABSOLUTE, RELATIVE = 1e-9, 1e-8  # close(): |error| <= ABSOLUTE max(1, max |want|) + RELATIVE |want|
+TOLERANCE = {"inverse": ABSOLUTE, "vertex": ABSOLUTE, "objective": 1e-9, "costs": 1e-9, "weights": 1e-8, "alpha": ABSOLUTE, "btran": ABSOLUTE}
 
 
 def close(got, want):
@@ -15,7 +19,7 @@ def close(got, want):
     want = np.asarray(want, dtype=np.longdouble)
     scale = max(1.0, float(np.abs(want).max()))
     error = np.abs(np.asarray(got, dtype=np.longdouble) - want)
-    return bool((error <= 1e-9 * scale + 1e-8 * np.abs(want)).all())
+    return bool((error <= ABSOLUTE * scale + RELATIVE * np.abs(want)).all())
 
 
 def deviation(got, want):
@@ -59,11 +63,11 @@ def assert_state(solver, exact, parts=EVERYTHING, inverse=None, inverse_rows=Non
         _note(report, "vertex", deviation(solver.b(), long_double(*exact.x_basic())))
         assert close(solver.b(), long_double(*exact.x_basic())), "b"
         _note(report, "objective", abs(solver.objective_function_value() - float(exact.objective_exact)) / max(1.0, abs(float(exact.objective_exact))))
-        assert solver.objective_function_value() == pytest.approx(float(exact.objective_exact), rel=1e-9, abs=1e-10)
+        assert solver.objective_function_value() == pytest.approx(float(exact.objective_exact), rel=TOLERANCE["objective"], abs=1e-10)
     if "costs" in parts:
         got = solver.relative_costs()[checked]
         _note(report, "costs", (np.abs(got - np.asarray(want_cost, dtype=np.float64)) / (1 + np.abs(np.asarray(want_cost, dtype=np.float64)))).max())
-        assert np.allclose(got, np.asarray(want_cost, dtype=np.float64), rtol=1e-9, atol=1e-9), \
+        assert np.allclose(got, np.asarray(want_cost, dtype=np.float64), rtol=TOLERANCE["costs"], atol=TOLERANCE["costs"]), \
             ("relative cost", int(checked[np.argmax(np.abs(got - np.asarray(want_cost, dtype=np.float64)))]))
     want_gamma = exact.gammas(checked_free)
     if "weights" in parts:
@@ -71,7 +75,7 @@ def assert_state(solver, exact, parts=EVERYTHING, inverse=None, inverse_rows=Non
         assert np.isnan(got[exact.is_basic]).all()
         relative = np.abs(np.asarray(got[checked_free], dtype=np.longdouble) / want_gamma - 1)
         _note(report, "weights", relative.max())
-        assert relative.max() <= 1e-8, ("gamma", int(checked_free[np.argmax(relative)]), float(relative.max()))
+        assert relative.max() <= TOLERANCE["weights"], ("gamma", int(checked_free[np.argmax(relative)]), float(relative.max()))
     if "alpha" in parts:
         if alpha_columns is None:
             slack = next((int(j) for j in free if j >= n_dense), n_dense)

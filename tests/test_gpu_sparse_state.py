@@ -67,6 +67,7 @@ from relp_amd.api import SW_K2_SINGLE, SW_NO_TOUCHED
 from basis_state import long_double
 from state_checks import assert_polished, assert_state, device_inverse
 import sparse_lps
+from sparse_lps import btrans
 
 pytestmark = pytest.mark.gpu
 PIVOTS, BATCH = sparse_lps.PIVOTS, sparse_lps.BATCH
@@ -112,13 +113,6 @@ def inverse_rows(exact, not_unit):
     for edge in range(512, m, 512):
         rows |= {edge - 1, edge}
     return sorted(rows)
-
-
-def btrans(m):
-    """Three vectors with a small non-zero integer in EVERY row: a wrong entry in a row that nothing else reads still shows."""
-    i = np.arange(m)
-    rows = i.astype(np.int32)
-    return [(rows, (1.0 + i % 7)), (rows, -(1.0 + i % 5)), (rows, (1.0 + (3 * i) % 9) * np.where(i % 2, -1.0, 1.0))]
 
 
 def walked(family, mix, m, options):
