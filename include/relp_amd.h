@@ -110,6 +110,14 @@ typedef enum relp_lu_refactor {
                                   else, and any refactorisation the kernels give up on, takes the synchronous paths above */
 } relp_lu_refactor;
 
+/* The leaving row of a dual pivot (relp_amd/csrc/dual.hip), among the rows with x_B[i] < -harris_delta; ties go to the lowest basic
+ * column, then the lowest row, under both rules. */
+typedef enum relp_dual_pricing {
+    RELP_DUAL_PRICING_INFEASIBILITY = 0,  /* the largest -x_B[i] (the default) */
+    RELP_DUAL_PRICING_STEEPEST_EDGE = 1   /* the largest x_B[i]^2 / beta_i, beta_i = |e_i' B^-1|^2 the squared norm of row i of the
+                                             inverse, recomputed from the inverse after every dual pivot (relp_get_dual_weights) */
+} relp_dual_pricing;
+
 /* A/B switches of the kernels (`relp_options.switches`; tests and measurements -- all clear = what the library would choose).
  * Round 5: these were environment variables of the same names (RELP_NO_TOUCHED ...); the library no longer reads the environment
  * for anything that changes a kernel or a result, so a caller's options cannot be overruled from outside. */
@@ -201,6 +209,9 @@ typedef struct relp_options {
     int32_t luf_lds_arena;     /* ... cap on the entries of the active sub-matrix held in LDS (test hook: spills) */
     int32_t luf_arena_cap;     /* ... cap on the words of the global arena (test hook: a basis that outgrows it) */
     double carry_weights_min;  /* steepest-edge weights carried from phase one into phase two from this many columns (4e9) */
+    /* ---- appended in round 7: the leaving-row rule of the dual loop ---- */
+    int32_t dual_pricing;      /* relp_dual_pricing; any other value is RELP_ERR_ARGUMENT at relp_create */
+    int32_t reserved_round7;   /* must be 0 (keeps the struct a multiple of 8 bytes without tail padding) */
 } relp_options;
 
 typedef struct relp_result {
@@ -886,6 +897,10 @@ int32_t relp_solve_dual(relp_handle* handle, const int32_t* basis_columns, relp_
 int32_t relp_begin_dual(relp_handle* handle, const int32_t* basis_columns);
 int32_t relp_iterate_dual(relp_handle* handle, int64_t count, int64_t* done, int32_t* stop_reason);
 int32_t relp_get_dual_pivots(const relp_handle* handle, int64_t* dual_pivots);
+/* options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE: the m weights beta_i of the dual loop as the next dual pivot would read them
+ * (by row of the basis).  RELP_ERR_STATE before a relp_begin_dual / relp_solve_dual on the loaded LP, and on a handle whose
+ * dual_pricing is 0 (it keeps no weights).  relp_get_record_json names the rule: "dual_pricing": "infeasibility" | "steepest_edge". */
+int32_t relp_get_dual_weights(relp_handle* handle, double* out /* m */);
 /* Host only: the empty string if the plan of (model, options) takes the dual loop, else the reason (the protocol of
  * relp_debug_kernel_path; a load that would itself be refused returns its status and message). */
 int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length);

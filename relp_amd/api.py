@@ -20,6 +20,7 @@ STOP_NO_ENTERING, STOP_UNBOUNDED, STOP_BUDGET = 1, 2, 3
 CARRY_EXPLICIT, CARRY_LU, CARRY_LU_INVERSE, CARRY_NETWORK = 0, 1, 2, 3
 RATIO_HARRIS, RATIO_TEXTBOOK, RATIO_AUTO = 0, 1, 2
 WITNESS_PRIMAL, WITNESS_DUAL, WITNESS_RAY = 0, 1, 2  # relp_witness
+DUAL_PRICING_INFEASIBILITY, DUAL_PRICING_STEEPEST_EDGE = 0, 1  # relp_dual_pricing
 
 
 class RelpError(RuntimeError):
@@ -40,7 +41,8 @@ class Options(C.Structure):
                 ("switches", C.c_uint32), ("dense_blocks", C.c_int32), ("ftran_slices", C.c_int32), ("price_lds_max", C.c_int32),
                 ("certify_threads", C.c_int32), ("exact_grid", C.c_int32), ("exact_update", C.c_int32), ("luf_dense_tail", C.c_int32),
                 ("luf_slack", C.c_int32), ("luf_lds", C.c_int32), ("luf_lds_arena", C.c_int32), ("luf_arena_cap", C.c_int32),
-                ("carry_weights_min", C.c_double)]
+                ("carry_weights_min", C.c_double),
+                ("dual_pricing", C.c_int32), ("reserved_round7", C.c_int32)]
 
 
 # relp_switch bits of Options.switches (include/relp_amd.h)
@@ -195,6 +197,8 @@ SYMBOLS = [
     "relp_model_cost_exact", "relp_model_right_hand_side_exact", "relp_model_fixed_cost_exact",
     # dual simplex from a dual-feasible basis (relp_amd/csrc/dual.hip)
     "relp_solve_dual", "relp_begin_dual", "relp_iterate_dual", "relp_get_dual_pivots", "relp_debug_dual_refusal",
+    # ... with the steepest-edge rule for the leaving row (Options.dual_pricing)
+    "relp_get_dual_weights",
     # ... started from the parent's inverse on the device (dual_inherit_kernel)
     "relp_begin_dual_from", "relp_solve_dual_from", "relp_debug_dual_inherit_refusal",
 ]
@@ -768,6 +772,14 @@ class Solver:
         done, reason = C.c_int64(), C.c_int32()
         self._check(lib().relp_iterate_dual(self._h, int(count), C.byref(done), C.byref(reason)))
         return done.value, reason.value
+
+    def dual_weights(self):
+        """``dual_pricing=DUAL_PRICING_STEEPEST_EDGE``: the m weights of the leaving-row rule, the squared norms of the rows of the
+        inverse, as the next dual pivot would read them (``relp_get_dual_weights``).  ``RelpError`` (``ERR_STATE``) before a
+        ``begin_dual`` and on a handle with ``dual_pricing=0``."""
+        out = np.empty(self.m, dtype=np.float64)
+        self._check(lib().relp_get_dual_weights(self._h, _ptr(out, C.c_double)))
+        return out
 
     def dual_pivots(self):
         """Dual pivots of the last ``solve_dual`` / since ``begin_dual``."""

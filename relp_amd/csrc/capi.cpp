@@ -78,6 +78,7 @@ static void library_defaults(relp_options* o) {
     o->product_form = 0;
     o->ftran_min_nnz = 0;
     o->lu_refactor = RELP_REFACTOR_AUTO;
+    o->dual_pricing = RELP_DUAL_PRICING_INFEASIBILITY;
     o->struct_size = (int32_t)sizeof(relp_options);  // (the switches and sizes appended in round 5 stay 0: the library's choices)
 }
 
@@ -774,6 +775,7 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
         << "\", \"dual_start_seconds\": " << sv.dual_start_seconds() << ", \"dual_start_gemms\": " << sv.dual_start_gemms() << ", \"dual_start_residual\": ";
     if (sv.dual_start_residual() >= 0.0) out << sv.dual_start_residual();
     else out << "null";
+    out << ", \"dual_pricing\": \"" << (h->options.dual_pricing == RELP_DUAL_PRICING_STEEPEST_EDGE ? "steepest_edge" : "infeasibility") << "\"";
     out << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
         << "\", \"device_refactor_fallbacks\": " << sv.device_refactor_fallbacks()
@@ -923,6 +925,12 @@ int32_t relp_get_dual_pivots(const relp_handle* h, int64_t* dual_pivots) {
     if (!dual_pivots) return RELP_ERR_ARGUMENT;
     *dual_pivots = h->solver->dual_pivots();
     return RELP_OK;
+}
+
+int32_t relp_get_dual_weights(relp_handle* h, double* out) {
+    REQUIRE_LOADED(h);
+    if (!out) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] { h->solver->dual_weights(out); });
 }
 
 int32_t relp_begin_phase_one(relp_handle* h) {

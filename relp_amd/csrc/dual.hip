@@ -1,9 +1,10 @@
-// Dual simplex from a given dual-feasible basis: the five kernels of one dual pivot (gfx950, wave64), the kernel that starts a child
-// LP from its parent's inverse, and their launch helpers.
+// Dual simplex from a given dual-feasible basis: the five kernels of one dual pivot (gfx950, wave64), the two that keep the weights of
+// the steepest-edge leaving rule, the kernel that starts a child LP from its parent's inverse, and their launch helpers.
 //
 // The primal kernels cannot leave a primal-infeasible basis (step_decision clamps the leaving value at zero), and the rules of
 // pivot_step.hpp are shared with the fused pivot, so the dual loop is a set of kernels of its own over the same device state
-// (dual.hpp).  The textbook method: the leaving row is the most infeasible one, the entering column the one whose relative cost
+// (dual.hpp).  The textbook method: the leaving row is the most infeasible one (or, as an option, the one with the largest
+// x_B[i]^2 / |row i of the inverse|^2: dual steepest edge), the entering column the one whose relative cost
 // reaches zero first along row p of the tableau, found by a two-pass ratio test of the same shape as the primal Harris test
 // (pass 1: the largest dual step that keeps every relative cost above -tol_dual; pass 2: the largest |alpha_pj| within it).
 // Candidates go through per-workgroup slots that one workgroup folds, as in the primal loop; no floating-point atomics, every
@@ -25,13 +26,18 @@ constexpr int DL_COL_CHUNK = 1024;    // entries of the entering column staged p
 constexpr int DU_THREADS = 256;       // dual_update_kernel: four waves, a column pair each
 constexpr int DU_CPW = 2;
 constexpr int DI_THREADS = 256;       // dual_inherit_kernel: four waves, a column of the child's inverse each
+constexpr int DW_THREADS = 256;       // dual_weights_kernel: four waves over one tile of 64 rows, a quarter of the slice's columns each
+constexpr int DW_U = 16;              // its columns in flight per lane
 
 // ---------------------------------------------------------------------------------------------------
 // 1. The leaving row: key = -x_B[i] among the rows with x_B[i] < -delta, ties to the lowest basic column, then the lowest row.
 //    Then rho = row p of the inverse (m strided loads of the column-major inverse, as btran_vec_kernel does for a unit vector).
 //    Also the budget check of the chain: the four kernels behind this one only look at the status.
 // ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, double delta) {
+//    STEEPEST (relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE): key = x_B[i]^2 / beta[i] among the same rows, the same ties.
+//    The instantiation of rule 0 never reads `beta`: its instructions are those of the kernel before the second rule existed.
+template <bool STEEPEST>
+__global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, double delta, const double* __restrict__ beta) {
     __shared__ double s_key[DL_THREADS / WAVE];
     __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
     Ctl* ctl = lp.ctl;
@@ -44,18 +50,19 @@ __global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, dou
     double key = 0.0;
     unsigned long long rank = RANK_NONE;
     for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
-        double xbv[DL_U];
+        double xbv[DL_U], betav[DL_U];
         int basv[DL_U];
 #pragma unroll
         for (int u = 0; u < DL_U; ++u) {
             const int i = i0 + u * DL_THREADS;
             xbv[u] = i < m ? lp.xB[i] : 0.0;
             basv[u] = i < m ? lp.basis[i] : 0;
+            if (STEEPEST) betav[u] = i < m ? beta[i] : 1.0;
         }
 #pragma unroll
         for (int u = 0; u < DL_U; ++u) {
             const int i = i0 + u * DL_THREADS;
-            if (i < m && xbv[u] < -delta) keep_better(-xbv[u], leaving_rank(basv[u], i), key, rank);
+            if (i < m && xbv[u] < -delta) keep_better(STEEPEST ? xbv[u] * xbv[u] / betav[u] : -xbv[u], leaving_rank(basv[u], i), key, rank);
         }
     }
     block_argbest<true>(key, rank, s_key, s_rank);  // (the first use of the slots)
@@ -310,6 +317,59 @@ __global__ void __launch_bounds__(DU_THREADS) dual_update_kernel(DeviceLP lp) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The weights of the steepest-edge rule, beta_i = sum_j Binv[i, j]^2, from the column-major inverse in its first buffer.  Workgroup
+// (tile, slice): rows 64 tile .. 64 tile + 63, a lane per row in each of the four waves, so every load of a wave is 64 consecutive
+// doubles of one column (8-byte accesses: ld need not be even, see dual_inherit_kernel); columns [slice per_slice, (slice + 1)
+// per_slice) of the m, a contiguous quarter per wave, DW_U loads in flight, the squares added in column order; then the four quarters
+// in wave order through LDS.  One partial sum per (slice, row) at out[slice m + row]; with one slice `out` is beta itself, otherwise
+// dual_weights_fold_kernel adds the slices in slice order.  Every sum in a fixed order and no atomics: the same bits at every run.
+// `chained`: behind the launches of a pivot, a no-op unless the chain is still running, like them.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DW_THREADS) dual_weights_kernel(DeviceLP lp, double* __restrict__ out, int per_slice, int chained) {
+    __shared__ double s_quarter[DW_THREADS / WAVE][WAVE];
+    if (chained && lp.ctl->status != ST_RUNNING) return;
+    const int m = lp.m, ld = lp.ld;
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const int row = blockIdx.x * WAVE + lane;
+    const int per_wave = (per_slice + DW_THREADS / WAVE - 1) / (DW_THREADS / WAVE);
+    const int slice_end = min(m, ((int)blockIdx.y + 1) * per_slice);
+    const int first = min(slice_end, (int)blockIdx.y * per_slice + wave * per_wave), last = min(slice_end, first + per_wave);
+    double sum = 0.0;
+    if (row < m) {
+        const double* entry = lp.Binv + row;
+        for (int j0 = first; j0 < last; j0 += DW_U) {
+            double v[DW_U];
+#pragma unroll
+            for (int u = 0; u < DW_U; ++u) v[u] = j0 + u < last ? entry[(size_t)(j0 + u) * ld] : 0.0;
+#pragma unroll
+            for (int u = 0; u < DW_U; ++u) sum += v[u] * v[u];  // (a column past the end adds +0: the sum is never negative)
+        }
+    }
+    s_quarter[wave][lane] = sum;
+    __syncthreads();
+    if (wave == 0 && row < m) {
+        double total = s_quarter[0][lane];
+#pragma unroll
+        for (int w = 1; w < DW_THREADS / WAVE; ++w) total += s_quarter[w][lane];
+        out[(size_t)blockIdx.y * m + row] = total;
+    }
+}
+
+__global__ void __launch_bounds__(DW_THREADS) dual_weights_fold_kernel(DeviceLP lp, const double* __restrict__ part, double* __restrict__ beta, int slices, int chained) {
+    if (chained && lp.ctl->status != ST_RUNNING) return;
+    const int m = lp.m;
+    const int row = blockIdx.x * DW_THREADS + threadIdx.x;
+    if (row >= m) return;
+    double v[DUAL_WEIGHT_SLICES_MAX];  // every slice's partial sum in flight together, then added in slice order
+#pragma unroll
+    for (int s = 0; s < DUAL_WEIGHT_SLICES_MAX; ++s) v[s] = s < slices ? part[(size_t)s * m + row] : 0.0;
+    double total = v[0];
+#pragma unroll
+    for (int s = 1; s < DUAL_WEIGHT_SLICES_MAX; ++s) total += v[s];  // (a slice past the last adds +0: the sum is never negative)
+    beta[row] = total;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The start from a parent's inverse (dual_inherit.hpp): the child's basis is the parent's in the first m positions and the slack of
 // each of the k appended rows behind it, so its inverse is [B^-1 0; -S^-1 C B^-1  S^-1].  A wave per column j of the child's inverse.
 //   j <  m: rows 0 .. m-1 are column j of the parent's inverse (lanes over rows, both sides coalesced; the leading dimensions differ
@@ -355,8 +415,16 @@ void launch_dual_inherit(const DeviceLP& child, const double* parent_inverse, in
     const int per_block = DI_THREADS / WAVE;
     hipLaunchKernelGGL(dual_inherit_kernel, dim3((child.m + per_block - 1) / per_block), dim3(DI_THREADS), 0, s, child, parent_inverse, parent_m, parent_ld);
 }
-void launch_dual_leave(const DeviceLP& d, double harris_delta, hipStream_t s) {
-    hipLaunchKernelGGL(dual_leave_kernel, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta);
+void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, hipStream_t s) {
+    if (beta) hipLaunchKernelGGL(dual_leave_kernel<true>, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta, beta);
+    else hipLaunchKernelGGL(dual_leave_kernel<false>, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta, beta);
+}
+int launch_dual_weights(const DeviceLP& d, const DualBuffers& b, bool chained, hipStream_t s) {
+    const int m = d.m, per_slice = (m + b.slices - 1) / b.slices;
+    hipLaunchKernelGGL(dual_weights_kernel, dim3((m + WAVE - 1) / WAVE, b.slices), dim3(DW_THREADS), 0, s, d, b.slices == 1 ? b.beta : b.beta_part, per_slice, chained ? 1 : 0);
+    if (b.slices == 1) return 1;
+    hipLaunchKernelGGL(dual_weights_fold_kernel, dim3((m + DW_THREADS - 1) / DW_THREADS), dim3(DW_THREADS), 0, s, d, b.beta_part, b.beta, b.slices, chained ? 1 : 0);
+    return 2;
 }
 void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, double tol_pivot, double slack, hipStream_t s) {
     static PerDeviceOnce once;  // more than 64 KB of dynamic LDS is an opt-in, per device

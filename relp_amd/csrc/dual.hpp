@@ -19,25 +19,41 @@ struct DualBuffers {
     double* cand_key = nullptr;    // [blocks] pass 2: one candidate per workgroup of dual_choose_kernel ...
     int* cand_j = nullptr;         // ... its column, -1: none
     int blocks = 0;                // workgroups of the two grids over the provider columns [n_art, n)
+    // relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE only (nullptr / 0 otherwise: the loop of rule 0 is what it was)
+    double* beta = nullptr;        // [m] beta_i = |e_i' B^-1|^2, the squared norm of row i of the inverse
+    double* beta_part = nullptr;   // [slices][m] dual_weights_kernel: the sum over one slice of columns, per row
+    int slices = 0;                // column slices of its grid (dual_weight_slices)
 };
 
 constexpr int DUAL_COLUMNS_PER_BLOCK = 256;  // dual_row_kernel, dual_choose_kernel: one lane per column
 inline int dual_blocks(int n_art, int n) { return (n - n_art + DUAL_COLUMNS_PER_BLOCK - 1) / DUAL_COLUMNS_PER_BLOCK; }
 
+// Column slices of dual_weights_kernel: at least 64 columns each (16 per wave of its workgroups), 16 at most -- at m = 2049 the grid is
+// 33 row tiles x 16 slices, two workgroups per compute unit; one slice up to m = 127.
+constexpr int DUAL_WEIGHT_SLICES_MAX = 16;
+inline int dual_weight_slices(int m) { return m / 64 < 1 ? 1 : m / 64 > DUAL_WEIGHT_SLICES_MAX ? DUAL_WEIGHT_SLICES_MAX : m / 64; }
+
 // One dual pivot is these five launches in this order.  Each returns at once unless Ctl::status == ST_RUNNING; dual_leave_kernel
 // also stops the chain when the budget of the batch is used up (ST_BUDGET), so a batch that finishes early is a run of no-ops.
-//   leave:   the leaving row p (largest infeasibility among x_B[i] < -harris_delta; ties: lowest basic column, lowest row), rho = row p
-//            of the inverse; none: ST_NO_ENTERING, the basis is primal feasible
+//   leave:   the leaving row p (largest infeasibility among x_B[i] < -harris_delta, or largest x_B[i]^2 / beta_i under the steepest-edge
+//            rule; ties: lowest basic column, lowest row), rho = row p of the inverse; none: ST_NO_ENTERING, the basis is primal feasible
 //   row:     alpha_pj, d_j and pass 1 of the ratio test over the non-basic provider columns (`lds`: rho and -pi staged in LDS)
 //   choose:  theta_max, pass 2 (largest |alpha_pj| within theta_max, key 1 under the textbook rule; ties: lowest column)
 //   pivot:   the entering column q (none: ST_UNBOUNDED, the LP is infeasible), FTRAN, x_B, basis, pos, control block; ST_REFACTOR
 //            with nothing written where the FTRAN value of the pivot is not below -tol_pivot as the row's value was
 //   update:  the inverse and -pi
-void launch_dual_leave(const DeviceLP& d, double harris_delta, hipStream_t s);
+void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, hipStream_t s);  // beta == nullptr: rule 0
 void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, double tol_pivot, double slack, hipStream_t s);
 void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivot, bool textbook, hipStream_t s);
 void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, double tol_pivot, hipStream_t s);
 void launch_dual_update(const DeviceLP& d, hipStream_t s);
+
+// The steepest-edge rule of the leaving row (b.beta allocated): launch_dual_leave takes `beta` = b.beta and keys a row by
+// x_B[i]^2 / beta_i; after launch_dual_update the weights are computed again from the new inverse, which they equal by construction
+// (no recurrence, nothing to drift).  Returns the number of launches: 1 with one slice (the partial sums are the weights), else 2
+// (dual_weights_kernel, then the fold of the partial sums in slice order).  `chained`: behind a pivot's launches, a no-op unless
+// Ctl::status == ST_RUNNING like them; false from the host (the starts, after a polish), where the status says nothing about the inverse.
+int launch_dual_weights(const DeviceLP& d, const DualBuffers& b, bool chained, hipStream_t s);
 
 // The start from a parent's inverse (Solver::begin_dual_from; the relation between the two LPs: dual_inherit.hpp).  `child` has its
 // pos uploaded for the basis [the parent's basis in the first parent_m positions | the slack of each appended row]; `parent_inverse`

@@ -874,6 +874,7 @@ void Solver::polish(bool refresh_vectors, bool force) {
     if (since_polish_ == 0 && !force && !(opt_.switches & RELP_SW_POLISH_ALWAYS)) return;
     const int m = d_.m;
     polish_rebuilt_ = false;
+    dual_weights_current_ = false;  // (the inverse may be rewritten below)
     // dense pipeline: only the columns of the stored inverse that are not unit vectors take part (the corresponding
     // rows of S are zero and those columns of the polished inverse do not change): both GEMMs shrink by m / touched
     const bool by_rows = path_.track_touched && path_.polish_gemm == PolishGemm::MFMA;  // (the plain-FMA kernels compute every row)
@@ -1134,6 +1135,7 @@ long long Solver::iterate(long long count, int* stop_reason) {
         pivots_[phase_ - 1] += made;
         if (made > 0) binv_identity_ = false;  // (the phase hand-over must not take the weights of the identity basis)
         if (made > 0) last_pivot_dual_ = false;
+        if (made > 0) dual_weights_current_ = false;
         if (after.status == ST_NO_ENTERING || after.status == ST_UNBOUNDED) { reason = after.status; break; }
         if (after.status == ST_REFACTOR) {  // LU carry: should_refactor (or an unstable update) -- BasisInverse::invert
             // (the new factors may be on their way on the other stream: wait for them, replay, go on; else factorise now)
@@ -1450,6 +1452,11 @@ void Solver::finish_dual_start(const int* basis_columns, const char* how, double
         dual_.cand_key = device_alloc<double>(dual_.blocks);
         dual_.cand_j = device_alloc<int>(dual_.blocks);
     }
+    if (steepest_dual() && !dual_.beta) {  // (rule 0 allocates nothing more than it did)
+        dual_.slices = dual_weight_slices(m);
+        dual_.beta = device_alloc<double>(m);
+        if (dual_.slices > 1) dual_.beta_part = device_alloc<double>((size_t)dual_.slices * m);
+    }
     const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
     dual_lds_ = 2 * (size_t)m * sizeof(double) <= lds_max;
     std::vector<double> cbar(n);
@@ -1465,23 +1472,46 @@ void Solver::finish_dual_start(const int* basis_columns, const char* how, double
     dual_pivots_ = 0;
     dual_device_seconds_ = 0.0;
     dual_ready_ = true;
+    dual_weights_current_ = false;
+    refresh_dual_weights();  // (behind either start: the inverse is final here)
     RELP_HIP(hipStreamSynchronize(stream_));
     dual_start_ = how;
     dual_start_seconds_ = now_seconds() - t0;
     dual_start_gemms_ = polish_gemms_ - gemms_before;
 }
 
-// One batch: the budget, then five launches per pivot (dual.hpp).  The chain is a run of no-ops from the first kernel that stops it.
+// The weights of the steepest-edge leaving rule from the inverse as it stands (a no-op under rule 0, before a start, and while they are
+// current): at the end of either start, and in front of the first batch of dual pivots after anything but a dual pivot has written
+// the inverse -- a polish (inside iterate_dual, the forced ones of run_dual, refactor) or primal pivots.
+void Solver::refresh_dual_weights() {
+    if (!steepest_dual() || !dual_ready_ || dual_weights_current_) return;
+    stats_.launches += launch_dual_weights(d_, dual_, false, stream_);
+    dual_weights_current_ = true;
+}
+
+void Solver::dual_weights(double* out) {
+    if (!loaded_) throw std::runtime_error("no LP loaded");
+    if (!steepest_dual()) throw std::runtime_error("dual_weights: the handle's dual_pricing is 0 (largest infeasibility keeps no weights)");
+    if (!dual_ready_) throw std::runtime_error("dual_weights: no dual loop started (begin_dual comes first)");
+    RELP_HIP(hipSetDevice(opt_.device));
+    refresh_dual_weights();
+    RELP_HIP(hipMemcpyAsync(out, dual_.beta, d_.m * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    RELP_HIP(hipStreamSynchronize(stream_));
+}
+
+// One batch: the budget, then five launches per pivot (dual.hpp), and behind them the one or two of the weights under the steepest-edge
+// rule.  The chain is a run of no-ops from the first kernel that stops it.
 void Solver::launch_dual_pivots(int count) {
     stats_.launches += 1 + 5LL * count;
     launch_budget(d_, count, stream_);
     const bool textbook = path_.ratio_textbook;
     for (int it = 0; it < count; ++it) {
-        launch_dual_leave(d_, opt_.harris_delta, stream_);
+        launch_dual_leave(d_, opt_.harris_delta, dual_.beta, stream_);
         launch_dual_row(d_, dual_, dual_lds_, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, stream_);
         launch_dual_choose(d_, dual_, opt_.tol_pivot, textbook, stream_);
         launch_dual_pivot(d_, dual_, opt_.tol_pivot, stream_);
         launch_dual_update(d_, stream_);
+        if (dual_.beta) stats_.launches += launch_dual_weights(d_, dual_, true, stream_);
     }
 }
 
@@ -1501,6 +1531,7 @@ long long Solver::iterate_dual(long long count, int* stop_reason) {
     while (done < count) {
         const long long room = opt_.polish_period > 0 ? (long long)opt_.polish_period * polish_scale_ - since_polish_ : count;
         if (room <= 0) { polish(true); continue; }
+        refresh_dual_weights();  // (after a polish here, in the ST_REFACTOR path below or in run_dual, or primal pivots since the last batch)
         const int batch = (int)std::min<long long>({count - done, room, (long long)full_batch});
         RELP_HIP(hipEventRecord(ev_a_, stream_));  // the device time of the batch, for relp_get_record_json ("dual_device_seconds")
         launch_dual_pivots(batch);
@@ -1953,6 +1984,7 @@ void Solver::bring_into_basis(int column, int row) {
     since_polish_ += 1;
     binv_identity_ = false;
     last_pivot_dual_ = false;
+    dual_weights_current_ = false;
     if (c.status == ST_REFACTOR) refactor_lu(true);  // LU carry: `should_refactor` was true for this pivot
 }
 // `BasisInverse::should_refactor` + `invert` (lower_upper/mod.rs:78-92, 249-252) on demand: the Newton-Schulz polish of the

@@ -63,6 +63,9 @@ public:
     void begin_dual_from(const Solver& parent, const int* basis_columns);
     void solve_dual_from(const Solver& parent, const int* basis_columns, relp_result* result);
     long long dual_pivots() const { return dual_pivots_; }  // of the last solve_dual / since begin_dual
+    // relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE: the m weights the next dual pivot would read (the squared row norms
+    // of the inverse).  std::runtime_error under rule 0 and before a begin_dual.
+    void dual_weights(double* out);
     // How the last begin_dual / begin_dual_from got its inverse ("none" before the first): "scratch", "inherited", or
     // "scratch_after_inherit" where the guard of an inherited inverse rebuilt it; the wall time of that call (the stream synchronised
     // at its end), the GEMMs of the polish and the from-scratch inverse inside it, and the guard's first residual (-1: no guard ran).
@@ -170,6 +173,9 @@ private:
     long long dual_pivots_ = 0;
     double dual_device_seconds_ = 0.0;
     void launch_dual_pivots(int count);
+    bool steepest_dual() const { return opt_.dual_pricing == RELP_DUAL_PRICING_STEEPEST_EDGE; }
+    void refresh_dual_weights();
+    bool dual_weights_current_ = false;  // DualBuffers::beta holds the row norms of the inverse as it stands
     // set_basis in three parts, shared with begin_dual_from: basis, pos and the control block; (the inverse); the handle's counters
     void place_basis(const int* basis_columns);
     void reset_basis_counters();

@@ -22,7 +22,12 @@ Every figure is the median of 5 runs after one warm-up, in one process.
 with the smallest and largest of the 5 runs beside each median.  Run against a library that has no ``relp_begin_dual_from``
 (``RELP_AMD_LIB``), it prints ``solve_dual`` alone.
 
-    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]]
+``--pricing 0 1`` prints the third table, one line per child (the same eight) and leaving-row rule (``Options.dual_pricing``: 0 largest
+infeasibility, 1 steepest edge), both rules in the one run: the dual pivots of ``solve_dual``, the device time of one of them
+(``dual_device_seconds`` over the pivots: the batches between two events, the weight pass of rule 1 included), and the wall time of
+``solve_dual`` and of ``solve_dual_from`` around a stream synchronise.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1]
 """
 import argparse
 import os
@@ -172,6 +177,39 @@ def start_probe(m, decimal, n_cuts, traced=False):
     parent.close()
 
 
+def pricing_probe(m, decimal, n_cuts, rules):
+    """One child of the pricing table of DESIGN.md section 10, a line per rule."""
+    seed, _ = dual_lps.STATE_CASES[m]
+    case = dual_lps.cut_case(m, dual_lps.MIXED, seed, n_cuts, decimal=decimal)
+    parent = relp_amd.Solver(certify=1).load_model(case.parent)
+    assert parent.solve_relaxation().certified
+    child, basis, _ = case.child(parent.basis(), parent.solution_exact())
+    objectives = set()
+    for rule in rules:
+        solver = relp_amd.Solver(certify=1, dual_pricing=rule).load_model(child)
+
+        def solve(call):
+            def run():
+                started = time.perf_counter()
+                result = call()
+                wall = 1e3 * (time.perf_counter() - started)
+                assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+                objectives.add(solver.objective_exact())
+                pivots = solver.dual_pivots()
+                return wall, pivots, 1e6 * solver.record()["dual_device_seconds"] / max(1, pivots), result.pivots_phase_two
+            return run
+
+        (wall, lo, hi), (pivots, _, _), (device_us, _, _), (clean_up, _, _) = spread_of(solve(lambda: solver.solve_dual(basis)))
+        (from_wall, from_lo, from_hi), (from_pivots, _, _), (from_us, _, _), _ = spread_of(solve(lambda: solver.solve_dual_from(parent, basis)))
+        print("m = %d + %d cuts, %s, %s: %d dual + %d primal pivots, %.1f us of device time per dual pivot | solve_dual %.1f ms (%.1f .. %.1f) | "
+              "solve_dual_from %.1f ms (%.1f .. %.1f), %d dual pivots, %.1f us each" % (
+                  m, n_cuts, "decimal" if decimal else "integer", "steepest edge" if rule else "largest infeasibility", pivots, clean_up, device_us,
+                  wall, lo, hi, from_wall, from_lo, from_hi, from_pivots, from_us), flush=True)
+        solver.close()
+    assert len(objectives) == 1, objectives  # every run, under either rule, ends at the same exact optimum
+    parent.close()
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
@@ -181,7 +219,15 @@ def main():
     parser.add_argument("--traced", action="store_true",
                         help="with --start, for a run under rocprofv3 --kernel-trace (which does not survive the replay of a captured graph: "
                              "tools/profile_r2_maxflow.sh): every handle with plain launches, and begin_dual / begin_dual_from only")
+    parser.add_argument("--pricing", type=int, nargs="+", choices=[0, 1], default=None,
+                        help="only the table of the leaving-row rule: the children of --start under each of the rules given")
     args = parser.parse_args()
+    if args.pricing is not None:
+        for m in args.sizes:
+            for n_cuts in ([args.cuts] if args.cuts else [4, 24]):
+                for decimal in ([True] if args.decimal else [False, True]):
+                    pricing_probe(m, decimal, n_cuts, args.pricing)
+        return
     if args.start:
         for m in args.sizes:
             for n_cuts in ([args.cuts] if args.cuts else [4, 24]):
