@@ -933,6 +933,30 @@ int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_mod
                                         const int32_t* basis_columns, const relp_options* options, char* buffer, int32_t capacity,
                                         int32_t* length);
 
+/* ---- dual simplex on implicit upper bounds: re-solve a branched child (the BOUNDED kernels of relp_amd/csrc/dual.hip) ---------------
+ * A branch is a changed variable bound.  With options.implicit_bounds = 1 the bounds are no rows of the device LP, so the child of a
+ * branching step has the parent's constraint rows and the dual loop's cost per pivot stays that of the constraint rows.  These two
+ * calls are relp_begin_dual / relp_solve_dual for such a plan, and for every plan those two take (there they run the same kernels):
+ * relp_debug_dual_bounded_refusal is relp_debug_dual_refusal of the plan without its bounds, the 8192 rows counted on the constraint
+ * rows.  `basis_columns`: a basis of the formulation, one column per row of the model with the bound rows included, as relp_get_basis
+ * returns it in both modes: the parent's basis plus the slack of every row the child's formulation gained (a new bound is such a row).
+ * RELP_ERR_ARGUMENT before anything is launched for a refused plan and for an artificial column in any of those rows; after the
+ * inverse has been built for a basis that is not dual feasible: the signed relative cost sgn_j (c_j - pi . a_j) of a non-basic column
+ * (sgn_j = -1 where it sits at its upper bound) is below -tol_dual; the column is named, a fixed variable (both bounds equal) is
+ * never priced.  A basic variable above its upper bound is no error: like one below zero it is a row the loop repairs.
+ * One dual pivot: the leaving row has the largest violation max(-x_i, x_i - u_i) (options.dual_pricing = 1: its square over the row
+ * norm of the inverse); the entering column is found by the ratio test of relp_solve_dual on the signed row; the leaving variable
+ * stops at the bound it violated, and one that the branch fixed does not enter again.  There is no bound-flipping ratio test: an
+ * entering variable that overshoots its own bound is a violated row for a later pivot.
+ * relp_iterate_dual, relp_get_dual_pivots, relp_get_dual_weights and the record keys are shared with relp_begin_dual;
+ * relp_get_record_json adds "dual_bounded": true where the last start ran the loop on implicit bounds.  A finite optimum is
+ * certified as a cold solve with implicit bounds is; RELP_RESULT_INFEASIBLE comes back with certified = 0 and the relp_last_error of
+ * relp_solve_dual.  relp_begin_dual, relp_solve_dual, relp_begin_dual_from and relp_solve_dual_from keep refusing a plan with
+ * implicit bounds (the inherited inverse would need the parent's complemented basic columns). */
+int32_t relp_solve_dual_bounded(relp_handle* handle, const int32_t* basis_columns, relp_result* result);
+int32_t relp_begin_dual_bounded(relp_handle* handle, const int32_t* basis_columns);
+int32_t relp_debug_dual_bounded_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length);
+
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);
 

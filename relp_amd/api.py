@@ -201,6 +201,8 @@ SYMBOLS = [
     "relp_get_dual_weights",
     # ... started from the parent's inverse on the device (dual_inherit_kernel)
     "relp_begin_dual_from", "relp_solve_dual_from", "relp_debug_dual_inherit_refusal",
+    # ... on implicit upper bounds: the child of a branching step (the BOUNDED kernels of dual.hip)
+    "relp_begin_dual_bounded", "relp_solve_dual_bounded", "relp_debug_dual_bounded_refusal",
 ]
 
 
@@ -511,6 +513,19 @@ class Model:
             raise RelpError(status, buf.value.decode())
         return buf.value.decode()
 
+    def dual_bounded_refusal(self, **options):
+        """Why ``Solver(**options).solve_dual_bounded`` would refuse this model's plan, in words; ``""`` if it takes it
+        (``relp_debug_dual_bounded_refusal``): ``dual_refusal`` of the plan without its implicit bounds, the row limit counted on the
+        constraint rows.  Host only."""
+        opts = default_options(**options)
+        length = C.c_int32()
+        lib().relp_debug_dual_bounded_refusal(self._h, C.byref(opts), None, 0, C.byref(length))
+        buf = C.create_string_buffer(length.value + 1)
+        status = lib().relp_debug_dual_bounded_refusal(self._h, C.byref(opts), buf, length.value + 1, C.byref(length))
+        if status != OK:
+            raise RelpError(status, buf.value.decode())
+        return buf.value.decode()
+
     def dual_inherit_refusal(self, parent_model, parent_basis, basis, **options):
         """Why ``Solver(**options).begin_dual_from`` would refuse to start this model with ``basis`` from a handle that holds
         ``parent_model`` at ``parent_basis``, in words that name the row or column; ``""`` if it takes the pair
@@ -764,6 +779,22 @@ class Solver:
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_from(self._h, parent._h, _ptr(arr, C.c_int32), C.byref(result)))
+        return result
+
+    def begin_dual_bounded(self, basis):
+        """``begin_dual`` for a plan with implicit upper bounds (``implicit_bounds=1``), and for every plan ``begin_dual`` takes
+        (``relp_begin_dual_bounded``).  ``basis``: a basis of the formulation, one column per row of the model with the bound rows
+        included, as ``basis()`` returns it: the parent's plus the slack of every row the child's formulation gained.  A basic variable
+        above its upper bound is what the loop repairs.  ``iterate_dual``, ``dual_pivots`` and ``dual_weights`` are shared."""
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        self._check(lib().relp_begin_dual_bounded(self._h, _ptr(arr, C.c_int32)))
+
+    def solve_dual_bounded(self, basis):
+        """``solve_dual`` with the start of ``begin_dual_bounded``: the re-solve of a branched child from its parent's basis; returns
+        ``Result`` (``relp_solve_dual_bounded``).  ``record()["dual_bounded"]`` says whether the loop ran on implicit bounds."""
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        result = Result()
+        self._check(lib().relp_solve_dual_bounded(self._h, _ptr(arr, C.c_int32), C.byref(result)))
         return result
 
     def iterate_dual(self, count):

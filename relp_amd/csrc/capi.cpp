@@ -775,6 +775,7 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
         << "\", \"dual_start_seconds\": " << sv.dual_start_seconds() << ", \"dual_start_gemms\": " << sv.dual_start_gemms() << ", \"dual_start_residual\": ";
     if (sv.dual_start_residual() >= 0.0) out << sv.dual_start_residual();
     else out << "null";
+    out << ", \"dual_bounded\": " << (sv.dual_bounded() ? "true" : "false");
     out << ", \"dual_pricing\": \"" << (h->options.dual_pricing == RELP_DUAL_PRICING_STEEPEST_EDGE ? "steepest_edge" : "infeasibility") << "\"";
     out << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
@@ -896,6 +897,20 @@ int32_t relp_begin_dual(relp_handle* h, const int32_t* basis_columns) {
     REQUIRE_LOADED(h);
     if (!basis_columns) return RELP_ERR_ARGUMENT;
     return guarded(h, [&] { h->solver->begin_dual(basis_columns); });
+}
+int32_t relp_solve_dual_bounded(relp_handle* h, const int32_t* basis_columns, relp_result* result) {
+    REQUIRE_LOADED(h);
+    if (!basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] {
+        h->solver->last_error.clear();
+        h->solver->solve_dual_bounded(basis_columns, result);
+        if (!h->solver->last_error.empty()) h->error = h->solver->last_error;  // (as relp_solve_dual)
+    });
+}
+int32_t relp_begin_dual_bounded(relp_handle* h, const int32_t* basis_columns) {
+    REQUIRE_LOADED(h);
+    if (!basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] { h->solver->begin_dual_bounded(basis_columns); });
 }
 int32_t relp_begin_dual_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns) {
     REQUIRE_LOADED(h);
@@ -1118,7 +1133,8 @@ int32_t relp_debug_kernel_path(const relp_model* model, const relp_options* opti
     }
     return status;
 }
-int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+// relp_debug_dual_refusal and relp_debug_dual_bounded_refusal: the plan of the load, then `refusal` of it
+static int32_t debug_plan_refusal(std::string (*refusal)(const KernelPath&), const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
     relp_options o;
     if (!model || adopt_options(options, &o) != RELP_OK) return RELP_ERR_ARGUMENT;
     int32_t status = RELP_OK;
@@ -1126,7 +1142,7 @@ int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* opt
     try {
         const MatrixData& md = model->form.data;
         const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
-        text = dual_refusal(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
+        text = refusal(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
     } catch (const std::invalid_argument& e) {  // (the load itself would be refused: its message)
         text = e.what();
         status = RELP_ERR_ARGUMENT;
@@ -1141,6 +1157,12 @@ int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* opt
         buffer[nbytes] = 0;
     }
     return status;
+}
+int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+    return debug_plan_refusal(dual_refusal, model, options, buffer, capacity, length);
+}
+int32_t relp_debug_dual_bounded_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+    return debug_plan_refusal(dual_bounded_refusal, model, options, buffer, capacity, length);
 }
 int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_model* child, const int32_t* parent_basis, const int32_t* basis_columns,
                                         const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {

@@ -9,6 +9,11 @@
 // (pass 1: the largest dual step that keeps every relative cost above -tol_dual; pass 2: the largest |alpha_pj| within it).
 // Candidates go through per-workgroup slots that one workgroup folds, as in the primal loop; no floating-point atomics, every
 // reduction in a fixed order.
+//
+// Implicit upper bounds (DeviceLP::ub, the state the bounded primal kernels keep): the leave, row and pivot kernels have a BOUNDED
+// instantiation each that states the same method on the held representation -- every column held as x_j or as u_j - x_j, a basic
+// variable infeasible below 0 or above xub[i] -- and dual_choose_kernel and dual_update_kernel serve both, since they only see the
+// signed row (abar_j, d_j) and the signed column alpha_q.  The instantiations without bounds are the kernels as they were.
 #include <hip/hip_runtime.h>
 
 #include "launch.hpp"
@@ -29,6 +34,10 @@ constexpr int DI_THREADS = 256;       // dual_inherit_kernel: four waves, a colu
 constexpr int DW_THREADS = 256;       // dual_weights_kernel: four waves over one tile of 64 rows, a quarter of the slice's columns each
 constexpr int DW_U = 16;              // its columns in flight per lane
 
+// Implicit upper bounds: the side of a basic variable with the value x and the upper bound `up` (+inf: none).  +1: it is (or would be)
+// infeasible below 0 and has to rise; -1: above `up` and has to fall.  The three BOUNDED kernels form it from x_B[p] and xub[p].
+__device__ __forceinline__ double dual_side(double x, double up) { return x - up > -x ? -1.0 : 1.0; }
+
 // ---------------------------------------------------------------------------------------------------
 // 1. The leaving row: key = -x_B[i] among the rows with x_B[i] < -delta, ties to the lowest basic column, then the lowest row.
 //    Then rho = row p of the inverse (m strided loads of the column-major inverse, as btran_vec_kernel does for a unit vector).
@@ -36,7 +45,10 @@ constexpr int DW_U = 16;              // its columns in flight per lane
 // ---------------------------------------------------------------------------------------------------
 //    STEEPEST (relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE): key = x_B[i]^2 / beta[i] among the same rows, the same ties.
 //    The instantiation of rule 0 never reads `beta`: its instructions are those of the kernel before the second rule existed.
-template <bool STEEPEST>
+//    BOUNDED: the violation of row i is v_i = max(-x_B[i], x_B[i] - xub[i]) (xub = +inf: no upper side), the rows with v_i > delta are
+//    eligible, key v_i or v_i^2 / beta[i].  The side of the leaving row is not stored: dual_side of (x_B[p], xub[p]), which no kernel
+//    writes between this one and dual_pivot_kernel.
+template <bool STEEPEST, bool BOUNDED>
 __global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, double delta, const double* __restrict__ beta) {
     __shared__ double s_key[DL_THREADS / WAVE];
     __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
@@ -50,7 +62,7 @@ __global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, dou
     double key = 0.0;
     unsigned long long rank = RANK_NONE;
     for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
-        double xbv[DL_U], betav[DL_U];
+        double xbv[DL_U], betav[DL_U], upv[DL_U];
         int basv[DL_U];
 #pragma unroll
         for (int u = 0; u < DL_U; ++u) {
@@ -58,11 +70,17 @@ __global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, dou
             xbv[u] = i < m ? lp.xB[i] : 0.0;
             basv[u] = i < m ? lp.basis[i] : 0;
             if (STEEPEST) betav[u] = i < m ? beta[i] : 1.0;
+            if (BOUNDED) upv[u] = i < m ? lp.xub[i] : INFINITY;
         }
 #pragma unroll
         for (int u = 0; u < DL_U; ++u) {
             const int i = i0 + u * DL_THREADS;
-            if (i < m && xbv[u] < -delta) keep_better(STEEPEST ? xbv[u] * xbv[u] / betav[u] : -xbv[u], leaving_rank(basv[u], i), key, rank);
+            if constexpr (BOUNDED) {
+                const double v = fmax(-xbv[u], xbv[u] - upv[u]);
+                if (i < m && v > delta) keep_better(STEEPEST ? v * v / betav[u] : v, leaving_rank(basv[u], i), key, rank);
+            } else {
+                if (i < m && xbv[u] < -delta) keep_better(STEEPEST ? xbv[u] * xbv[u] / betav[u] : -xbv[u], leaving_rank(basv[u], i), key, rank);
+            }
         }
     }
     block_argbest<true>(key, rank, s_key, s_rank);  // (the first use of the slots)
@@ -135,6 +153,57 @@ __global__ void __launch_bounds__(DUAL_COLUMNS_PER_BLOCK) dual_row_kernel(Device
     if (threadIdx.x == 0) b.part_theta[blockIdx.x] = theta;
 }
 
+// The same on implicit upper bounds, a kernel of its own (as a second template parameter it changed the order of two instructions of
+// the kernel above): over the columns with pos -1 or -2 (a fixed column, pos -3, is never priced), in the held form and towards the
+// side s of the leaving row: abar_j = s sgn_j (rho . a_j), d_j = sgn_j (c_j + sum v (-pi)[r]) -- the same sums in the same order, one
+// lane per column, multiplied by +-1 after them.  flipped[j] is loaded beside pos[j]; the side comes from two uniform loads behind
+// Ctl::p that are on their way while rho and -pi are staged.
+template <bool LDS>
+__global__ void __launch_bounds__(DUAL_COLUMNS_PER_BLOCK) dual_row_bounded_kernel(DeviceLP lp, DualBuffers b, double tol_pivot, double slack) {
+    extern __shared__ __attribute__((aligned(16))) double s_vectors[];
+    __shared__ __attribute__((aligned(16))) double s_red[DUAL_COLUMNS_PER_BLOCK / WAVE + 2];
+    if (lp.ctl->status != ST_RUNNING) return;
+    const int m = lp.m;
+    const int p = lp.ctl->p;
+    const double side = dual_side(lp.xB[p], lp.xub[p]);
+    const double* rho = lp.rho;
+    const double* minus_pi = lp.minus_pi;
+    if (LDS) {
+        for (int i = threadIdx.x; i < m; i += DUAL_COLUMNS_PER_BLOCK) {
+            s_vectors[i] = lp.rho[i];
+            s_vectors[m + i] = lp.minus_pi[i];
+        }
+        __syncthreads();
+        rho = s_vectors;
+        minus_pi = s_vectors + m;
+    }
+    const int j = lp.n_art + blockIdx.x * DUAL_COLUMNS_PER_BLOCK + threadIdx.x;
+    double theta = INFINITY;
+    if (j < lp.n) {
+        double a = 0.0, dj = 0.0;
+        const int position = lp.pos[j];
+        const int complemented = lp.flipped[j];
+        if (position == -1 || position == -2) {
+            dj = lp.cost[j];
+            const int first = lp.col_start[j], last = lp.col_start[j + 1];
+            for (int e = first; e < last; ++e) {
+                const int r = lp.row_index[e];
+                const double v = lp.value[e];
+                dj += v * minus_pi[r];
+                a += v * rho[r];
+            }
+            const double sgn = complemented ? -1.0 : 1.0;
+            dj *= sgn;
+            a *= sgn * side;
+            if (a < -tol_pivot) theta = (fmax(dj, 0.0) + slack) / fabs(a);
+        }
+        b.alpha_row[j] = a;
+        b.d[j] = dj;
+    }
+    theta = block_reduce<1>(theta, s_red);
+    if (threadIdx.x == 0) b.part_theta[blockIdx.x] = theta;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // 3. theta_max = the minimum of the partial minima (every workgroup folds them itself, in the same order), then pass 2: among the
 //    eligible columns with max(d_j, 0) / |alpha_pj| <= theta_max the largest |alpha_pj| (key 1 under the textbook rule), ties to the
@@ -174,12 +243,17 @@ __global__ void __launch_bounds__(DUAL_COLUMNS_PER_BLOCK) dual_choose_kernel(Dev
 //    then the step theta = x_B[p] / alpha_q[p] -- the FTRAN value of the pivot, used
 //    below and by the update of the inverse alike --, x_B, basis, pos and the control block.
 // ---------------------------------------------------------------------------------------------------
+//    BOUNDED: alpha_q = Binv (sgn_q a_q); the pivot is usable when s alpha_q[p] < -tol_pivot; theta = (x_B[p] - bound) / alpha_q[p] with
+//    bound = 0 or xub[p] by the side s.  A column that leaves at its upper bound is held complemented from then on (rhs moves over
+//    its entries as in ftran_ratio_kernel; exchange_columns of pivot_step.hpp); one of width 0 gets pos -3 and never enters again.
+//    The entering value may exceed ub[q]: that is an infeasible row for a later pivot (no bound-flipping ratio test).
+template <bool BOUNDED>
 __global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, DualBuffers b, double tol_pivot) {
     __shared__ double s_key[DL_THREADS / WAVE];
     __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
     __shared__ int s_rows[DL_COL_CHUNK];
     __shared__ double s_vals[DL_COL_CHUNK];
-    __shared__ double s_pivot[2];  // alpha_q[p], x_B[p]
+    __shared__ double s_pivot[BOUNDED ? 3 : 2];  // alpha_q[p], x_B[p], (xub[p])
     Ctl* ctl = lp.ctl;
     if (ctl->status != ST_RUNNING) return;
     const int m = lp.m, ld = lp.ld;
@@ -203,6 +277,11 @@ __global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, Dua
     const int q = (int)rank;
     const int ca = lp.col_start[q], cb = lp.col_start[q + 1];
     const bool single = (cb - ca) <= DL_COL_CHUNK;
+    double sgn_q = 1.0, ub_q = INFINITY;
+    if constexpr (BOUNDED) {
+        sgn_q = lp.flipped[q] ? -1.0 : 1.0;
+        ub_q = lp.ub[q];
+    }
     if (!single)
         for (int i = threadIdx.x; i < m; i += DL_THREADS) lp.alpha[i] = 0.0;
     for (int c0 = ca; c0 < cb; c0 += DL_COL_CHUNK) {
@@ -232,15 +311,76 @@ __global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, Dua
 #pragma unroll
             for (int u = 0; u < DL_U; ++u) {
                 const int i = i0 + u * DL_THREADS;
-                if (i < m) lp.alpha[i] = acc[u];  // (read again below by the thread that wrote it)
+                if constexpr (BOUNDED) {
+                    // (the sign of the held column goes on after the last chunk's sum, not per chunk)
+                    if (i < m) lp.alpha[i] = c0 + DL_COL_CHUNK >= cb ? acc[u] * sgn_q : acc[u];
+                } else {
+                    if (i < m) lp.alpha[i] = acc[u];  // (read again below by the thread that wrote it)
+                }
             }
         }
     }
     if ((p % DL_THREADS) == (int)threadIdx.x) {  // the thread that owns row p
         s_pivot[0] = lp.alpha[p];
         s_pivot[1] = lp.xB[p];
+        if constexpr (BOUNDED) s_pivot[2] = lp.xub[p];
+    }
+    // BOUNDED: what thread 0 rewrites at the end -- basis[p], flipped[leaving] -- is read by every thread here, in front of this barrier
+    int leaving = 0, leaving_flipped = 0, leaving_first = 0, leaving_last = 0;
+    if constexpr (BOUNDED) {
+        leaving = lp.basis[p];
+        leaving_flipped = lp.flipped[leaving];
+        leaving_first = lp.col_start[leaving];
+        leaving_last = lp.col_start[leaving + 1];
     }
     __syncthreads();
+    if constexpr (BOUNDED) {
+        const double alpha_pq = s_pivot[0], x_p = s_pivot[1], up_p = s_pivot[2];
+        const double side = dual_side(x_p, up_p);
+        if (!(side * alpha_pq < -tol_pivot)) {  // (as below: nothing has been written)
+            if (threadIdx.x == 0) {
+                ctl->status = ST_REFACTOR;
+                ctl->pending = 0;
+            }
+            return;
+        }
+        const bool leaves_at_upper = side < 0.0;
+        const double theta = (leaves_at_upper ? x_p - up_p : x_p) / alpha_pq;
+        for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
+            double av[DL_U], xbv[DL_U];
+#pragma unroll
+            for (int u = 0; u < DL_U; ++u) {
+                const int i = i0 + u * DL_THREADS;
+                av[u] = i < m ? lp.alpha[i] : 0.0;
+                xbv[u] = i < m ? lp.xB[i] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < DL_U; ++u) {
+                const int i = i0 + u * DL_THREADS;
+                if (i < m) lp.xB[i] = i == p ? theta : xbv[u] - theta * av[u];
+            }
+        }
+        if (leaves_at_upper) {  // the leaving variable stops at its upper bound: held in complemented form from now on
+            const double sgn_l = leaving_flipped ? -1.0 : 1.0;
+            for (int e = leaving_first + (int)threadIdx.x; e < leaving_last; e += DL_THREADS) lp.rhs[lp.row_index[e]] -= up_p * sgn_l * lp.value[e];
+        }
+        if (threadIdx.x == 0) {
+            const double d_q = b.d[q];
+            lp.basis[p] = q;
+            const int fl = exchange_columns(lp.pos, lp.flipped, lp.xub, true, q, p, leaving, leaving_flipped, leaves_at_upper, ub_q);
+            if (leaves_at_upper) ctl->flip_cost += (fl ? 1.0 : -1.0) * up_p * lp.cost[leaving];
+            if (lp.ub[leaving] == 0.0) lp.pos[leaving] = -3;  // both bounds are the same point: never priced again
+            ctl->q = q;
+            ctl->leaving = leaving;
+            ctl->alpha_pq = alpha_pq;
+            ctl->cbar_q = d_q;
+            ctl->xp = theta;
+            ctl->minus_obj = ctl->minus_obj - d_q * theta;
+            ctl->iters = ctl->iters + 1;
+            ctl->pending = 0;
+        }
+        return;
+    }
     const double alpha_pq = s_pivot[0];
     // The column was chosen on rho_p . a_q < -tol_pivot; the FTRAN value is the same number through the other side of the inverse.
     // Where the two disagree -- the FTRAN value is no usable pivot of that sign -- the inverse has drifted: x_B, the basis and the inverse
@@ -415,9 +555,9 @@ void launch_dual_inherit(const DeviceLP& child, const double* parent_inverse, in
     const int per_block = DI_THREADS / WAVE;
     hipLaunchKernelGGL(dual_inherit_kernel, dim3((child.m + per_block - 1) / per_block), dim3(DI_THREADS), 0, s, child, parent_inverse, parent_m, parent_ld);
 }
-void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, hipStream_t s) {
-    if (beta) hipLaunchKernelGGL(dual_leave_kernel<true>, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta, beta);
-    else hipLaunchKernelGGL(dual_leave_kernel<false>, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta, beta);
+void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, bool bounded, hipStream_t s) {
+    auto kernel = beta ? (bounded ? dual_leave_kernel<true, true> : dual_leave_kernel<true, false>) : (bounded ? dual_leave_kernel<false, true> : dual_leave_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta, beta);
 }
 int launch_dual_weights(const DeviceLP& d, const DualBuffers& b, bool chained, hipStream_t s) {
     const int m = d.m, per_slice = (m + b.slices - 1) / b.slices;
@@ -426,17 +566,19 @@ int launch_dual_weights(const DeviceLP& d, const DualBuffers& b, bool chained, h
     hipLaunchKernelGGL(dual_weights_fold_kernel, dim3((m + DW_THREADS - 1) / DW_THREADS), dim3(DW_THREADS), 0, s, d, b.beta_part, b.beta, b.slices, chained ? 1 : 0);
     return 2;
 }
-void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, double tol_pivot, double slack, hipStream_t s) {
-    static PerDeviceOnce once;  // more than 64 KB of dynamic LDS is an opt-in, per device
-    allow_full_lds_once(once, &dual_row_kernel<true>);
-    if (lds) hipLaunchKernelGGL(dual_row_kernel<true>, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 2 * (size_t)d.m * sizeof(double), s, d, b, tol_pivot, slack);
-    else hipLaunchKernelGGL(dual_row_kernel<false>, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 0, s, d, b, tol_pivot, slack);
+void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, bool bounded, double tol_pivot, double slack, hipStream_t s) {
+    static PerDeviceOnce once, once_bounded;  // more than 64 KB of dynamic LDS is an opt-in, per device and kernel
+    if (bounded) allow_full_lds_once(once_bounded, &dual_row_bounded_kernel<true>);
+    else allow_full_lds_once(once, &dual_row_kernel<true>);
+    auto kernel = lds ? (bounded ? dual_row_bounded_kernel<true> : dual_row_kernel<true>) : (bounded ? dual_row_bounded_kernel<false> : dual_row_kernel<false>);
+    hipLaunchKernelGGL(kernel, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), lds ? 2 * (size_t)d.m * sizeof(double) : 0, s, d, b, tol_pivot, slack);
 }
 void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivot, bool textbook, hipStream_t s) {
     hipLaunchKernelGGL(dual_choose_kernel, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 0, s, d, b, tol_pivot, textbook ? 1 : 0);
 }
-void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, double tol_pivot, hipStream_t s) {
-    hipLaunchKernelGGL(dual_pivot_kernel, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
+void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, bool bounded, double tol_pivot, hipStream_t s) {
+    if (bounded) hipLaunchKernelGGL(dual_pivot_kernel<true>, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
+    else hipLaunchKernelGGL(dual_pivot_kernel<false>, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
 }
 void launch_dual_update(const DeviceLP& d, hipStream_t s) {
     const int waves = (d.m + DU_CPW - 1) / DU_CPW, per_block = DU_THREADS / WAVE;

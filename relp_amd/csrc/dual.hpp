@@ -42,10 +42,15 @@ inline int dual_weight_slices(int m) { return m / 64 < 1 ? 1 : m / 64 > DUAL_WEI
 //   pivot:   the entering column q (none: ST_UNBOUNDED, the LP is infeasible), FTRAN, x_B, basis, pos, control block; ST_REFACTOR
 //            with nothing written where the FTRAN value of the pivot is not below -tol_pivot as the row's value was
 //   update:  the inverse and -pi
-void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, hipStream_t s);  // beta == nullptr: rule 0
-void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, double tol_pivot, double slack, hipStream_t s);
+// `bounded` (KernelPath::bounded, the loop of Solver::begin_dual_bounded): the instantiations that know implicit upper bounds, over the
+// state the bounded primal kernels keep (DeviceLP::ub, xub, flipped, rhs; pos -2 / -3).  A row is infeasible below 0 or above xub[i]
+// (the side s = +1 / -1); the row of the tableau is taken in the held form and towards that side, abar_j = s sgn_j rho . a_j and
+// d_j = sgn_j (c_j - pi . a_j), so that choose and update are the same kernels; the pivot checks s alpha_q[p] < -tol_pivot, steps to
+// the violated bound, and complements a column that leaves at its upper bound.  false: the kernels as they were.
+void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, bool bounded, hipStream_t s);  // beta == nullptr: rule 0
+void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, bool bounded, double tol_pivot, double slack, hipStream_t s);
 void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivot, bool textbook, hipStream_t s);
-void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, double tol_pivot, hipStream_t s);
+void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, bool bounded, double tol_pivot, hipStream_t s);
 void launch_dual_update(const DeviceLP& d, hipStream_t s);
 
 // The steepest-edge rule of the leaving row (b.beta allocated): launch_dual_leave takes `beta` = b.beta and keys a row by

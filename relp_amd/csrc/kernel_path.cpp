@@ -226,6 +226,12 @@ std::string dual_refusal(const KernelPath& p) {
     return std::string();
 }
 
+std::string dual_bounded_refusal(const KernelPath& p) {
+    KernelPath without_bounds = p;
+    without_bounds.bounded = false;
+    return dual_refusal(without_bounds);
+}
+
 std::string kernel_path_json(const KernelPath& p) {
     static const char* storage[] = {"NONE", "I8_LANE", "F32_LANE", "F64_LANE", "I8_PERMUTED", "F32_ROWS", "F64_ROWS"};
     static const char* price[] = {"UNIT_PAIRS", "GENERATED", "WIDTH_2", "LDS", "GATHER"};

@@ -120,6 +120,9 @@ KernelPath plan_kernel_path(const relp_options& o, const MatrixData& md, const D
 // they take the explicit carry without the dense pipeline, up to the row count of the single-workgroup kernels.
 constexpr int DUAL_MAX_ROWS = 8192;
 std::string dual_refusal(const KernelPath& p);
+// ... and the loop that knows implicit upper bounds (Solver::begin_dual_bounded): dual_refusal of the plan with `bounded` cleared.  It
+// takes every plan the loop above takes, with bounds or without; p.m counts the constraint rows only.
+std::string dual_bounded_refusal(const KernelPath& p);
 
 // The plan as one JSON object (relp_debug_kernel_path); slack_of_row by its length only.
 std::string kernel_path_json(const KernelPath& p);

@@ -88,6 +88,7 @@ void Solver::free_device() {
     net_ = NetTree{};
     dual_ = DualBuffers{};
     dual_ready_ = false;
+    dual_bounded_ = false;
     dual_start_ = "none";
 }
 
@@ -1373,18 +1374,24 @@ void Solver::certify(relp_result* result) {
 // ---- dual simplex from a given basis (dual.hip) -------------------------------------------------------
 // The optimal basis of an LP stays dual feasible when rows are appended or a right-hand side is tightened, and is primal infeasible
 // where the change bites: the caller loads the changed LP and passes the old basis, extended by the slack of each new row.
-void Solver::check_dual_start(const int* basis_columns) const {
+void Solver::check_dual_start(const int* basis_columns, bool bounded_entry) const {
     if (!loaded_) throw std::runtime_error("no LP loaded");
-    const std::string refusal = dual_refusal(path_);
+    const std::string refusal = bounded_entry ? dual_bounded_refusal(path_) : dual_refusal(path_);
     if (!refusal.empty()) throw std::invalid_argument(refusal);
-    for (int i = 0; i < d_.m; ++i)
+    const int rows = path_.bounded ? form_.data.nr_rows() : d_.m;  // (implicit bounds: a basis of the formulation, bound rows included)
+    for (int i = 0; i < rows; ++i)
         if (basis_columns[i] < 0)
             throw std::invalid_argument("begin_dual: the basis holds an artificial column (code " + std::to_string(basis_columns[i]) + " on row " + std::to_string(i) +
                                         "): the dual simplex starts from a basis of the LP's own columns");
 }
 
-void Solver::begin_dual(const int* basis_columns) {
-    check_dual_start(basis_columns);
+void Solver::begin_dual(const int* basis_columns) { start_dual_from_scratch(basis_columns, false); }
+// Implicit upper bounds: the same start -- place_basis reduces the formulation's basis to the constraint rows, complements the columns
+// at their upper bound and moves them over to the right-hand side -- and the loop of the BOUNDED kernels behind it (launch_dual_pivots).
+void Solver::begin_dual_bounded(const int* basis_columns) { start_dual_from_scratch(basis_columns, true); }
+
+void Solver::start_dual_from_scratch(const int* basis_columns, bool bounded_entry) {
+    check_dual_start(basis_columns, bounded_entry);
     RELP_HIP(hipSetDevice(opt_.device));
     const double t0 = now_seconds();
     const long long gemms_before = polish_gemms_;
@@ -1461,7 +1468,14 @@ void Solver::finish_dual_start(const int* basis_columns, const char* how, double
     dual_lds_ = 2 * (size_t)m * sizeof(double) <= lds_max;
     std::vector<double> cbar(n);
     relative_costs(cbar.data());
-    for (int i = 0; i < m; ++i) cbar[cols_.to_device(basis_columns[i])] = 0.0;  // (a basic column's is zero up to rounding)
+    if (path_.bounded) {  // the signed costs of the held form; a fixed column (pos -3) is never priced, a basic one is zero up to rounding
+        std::vector<int> pos(n);
+        RELP_HIP(hipMemcpyAsync(pos.data(), d_.pos, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        RELP_HIP(hipStreamSynchronize(stream_));
+        for (int j = n_art; j < n; ++j) cbar[j] = pos[j] == -1 ? cbar[j] : pos[j] == -2 ? -cbar[j] : 0.0;
+    } else {
+        for (int i = 0; i < m; ++i) cbar[cols_.to_device(basis_columns[i])] = 0.0;  // (a basic column's is zero up to rounding)
+    }
     for (int j = n_art; j < n; ++j)
         if (cbar[j] < -opt_.tol_dual) {
             char value[32];
@@ -1472,6 +1486,7 @@ void Solver::finish_dual_start(const int* basis_columns, const char* how, double
     dual_pivots_ = 0;
     dual_device_seconds_ = 0.0;
     dual_ready_ = true;
+    dual_bounded_ = path_.bounded;
     dual_weights_current_ = false;
     refresh_dual_weights();  // (behind either start: the inverse is final here)
     RELP_HIP(hipStreamSynchronize(stream_));
@@ -1506,10 +1521,10 @@ void Solver::launch_dual_pivots(int count) {
     launch_budget(d_, count, stream_);
     const bool textbook = path_.ratio_textbook;
     for (int it = 0; it < count; ++it) {
-        launch_dual_leave(d_, opt_.harris_delta, dual_.beta, stream_);
-        launch_dual_row(d_, dual_, dual_lds_, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, stream_);
+        launch_dual_leave(d_, opt_.harris_delta, dual_.beta, path_.bounded, stream_);
+        launch_dual_row(d_, dual_, dual_lds_, path_.bounded, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, stream_);
         launch_dual_choose(d_, dual_, opt_.tol_pivot, textbook, stream_);
-        launch_dual_pivot(d_, dual_, opt_.tol_pivot, stream_);
+        launch_dual_pivot(d_, dual_, path_.bounded, opt_.tol_pivot, stream_);
         launch_dual_update(d_, stream_);
         if (dual_.beta) stats_.launches += launch_dual_weights(d_, dual_, true, stream_);
     }
@@ -1570,8 +1585,9 @@ long long Solver::iterate_dual(long long count, int* stop_reason) {
 
 void Solver::solve_dual(const int* basis_columns, relp_result* result) { run_dual(nullptr, basis_columns, result); }
 void Solver::solve_dual_from(const Solver& parent, const int* basis_columns, relp_result* result) { run_dual(&parent, basis_columns, result); }
+void Solver::solve_dual_bounded(const int* basis_columns, relp_result* result) { run_dual(nullptr, basis_columns, result, true); }
 
-void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_result* result) {
+void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_result* result, bool bounded_entry) {
     if (!loaded_) throw std::runtime_error("no LP loaded");
     RELP_HIP(hipSetDevice(opt_.device));
     const double t0 = now_seconds();
@@ -1579,7 +1595,7 @@ void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_resul
     exact_primal.reset();
     exact_witnesses.reset();
     if (parent) begin_dual_from(*parent, basis_columns);
-    else begin_dual(basis_columns);
+    else start_dual_from_scratch(basis_columns, bounded_entry);
     const long long cap = opt_.max_pivots > 0 ? opt_.max_pivots : 200LL * (d_.m + d_.n) + 100000;
     int kind = RELP_RESULT_NONE;
     int reason = 0;

@@ -62,6 +62,13 @@ public:
     // own matrix, corrects what it finds and rebuilds from scratch by itself from 0.5 on.  The parent is only read.
     void begin_dual_from(const Solver& parent, const int* basis_columns);
     void solve_dual_from(const Solver& parent, const int* basis_columns, relp_result* result);
+    // The same loop on a plan with implicit upper bounds (the BOUNDED instantiations of dual.hip), and on every plan begin_dual takes
+    // (then with the kernels begin_dual runs): dual_bounded_refusal.  `basis_columns` is a basis of the reference's formulation, one
+    // column per row of MatrixData with the bound rows included, as get_basis returns it; a basic variable above its upper bound is what
+    // the loop repairs, not an error.  begin_dual, solve_dual and the _from pair keep refusing a bounded plan.
+    void begin_dual_bounded(const int* basis_columns);
+    void solve_dual_bounded(const int* basis_columns, relp_result* result);
+    bool dual_bounded() const { return dual_bounded_; }  // the last start ran the loop with implicit upper bounds
     long long dual_pivots() const { return dual_pivots_; }  // of the last solve_dual / since begin_dual
     // relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE: the m weights the next dual pivot would read (the squared row norms
     // of the inverse).  std::runtime_error under rule 0 and before a begin_dual.
@@ -179,10 +186,14 @@ private:
     // set_basis in three parts, shared with begin_dual_from: basis, pos and the control block; (the inverse); the handle's counters
     void place_basis(const int* basis_columns);
     void reset_basis_counters();
-    void check_dual_start(const int* basis_columns) const;  // the refusals begin_dual and begin_dual_from share: the plan, an artificial
+    // the refusals every start shares: the plan (`bounded_entry`: dual_bounded_refusal instead of dual_refusal), an artificial in any row
+    // of the basis as it is given (a bounded plan: every row of the formulation)
+    void check_dual_start(const int* basis_columns, bool bounded_entry = false) const;
+    void start_dual_from_scratch(const int* basis_columns, bool bounded_entry);  // begin_dual and begin_dual_bounded
+    bool dual_bounded_ = false;
     // ... and their tail behind set_phase(2): the loop's buffers, the dual-feasibility check that names the column, the counters
     void finish_dual_start(const int* basis_columns, const char* how, double t0, long long gemms_before);
-    void run_dual(const Solver* parent, const int* basis_columns, relp_result* result);  // solve_dual and solve_dual_from: one loop
+    void run_dual(const Solver* parent, const int* basis_columns, relp_result* result, bool bounded_entry = false);  // every solve_dual*: one loop
     std::vector<int> provider_basis() const;  // the basis on the device, provider columns by position (plans without implicit bounds)
     const char* dual_start_ = "none";
     double dual_start_seconds_ = 0.0, dual_start_residual_ = -1.0;

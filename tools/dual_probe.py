@@ -27,7 +27,13 @@ infeasibility, 1 steepest edge), both rules in the one run: the dual pivots of `
 (``dual_device_seconds`` over the pivots: the batches between two events, the weight pass of rule 1 included), and the wall time of
 ``solve_dual`` and of ``solve_dual_from`` around a stream synchronise.
 
-    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1]
+``--bounded``: the child of a branching step on an LP with a bound on every structural variable (tests/dual_bounded_lps.py, 24 cuts and
+8 tightened bounds unless ``--cuts`` says otherwise), re-solved both ways from the same basis of the formulation: ``solve_dual`` with
+the bounds as rows (``implicit_bounds=0``) and ``solve_dual_bounded`` on implicit bounds (``implicit_bounds=1``).  Per way: the rows of
+the device LP, the dual pivots, the wall time of the call and the device time per dual pivot; where the row limit of the dual loop
+refuses the explicit formulation, the refusal.  Both end at the same exact objective.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded]
 """
 import argparse
 import os
@@ -210,6 +216,41 @@ def pricing_probe(m, decimal, n_cuts, rules):
     parent.close()
 
 
+def bounded_probe(m, decimal, n_cuts, n_tight=8):
+    """One child of the bounded table of DESIGN.md section 10, a line per formulation."""
+    import dual_bounded_lps
+    case = dual_bounded_lps.BoundedCase(m, 1000 + m, n_cuts, n_tight, decimal=decimal, every=1)
+    parent = relp_amd.Solver(certify=1, implicit_bounds=1).load_model(case.parent.model)
+    assert parent.solve_relaxation().certified
+    child, basis, _, branches = case.child(parent.basis(), parent.solution_exact())
+    parent.close()
+    label = "m = %d + %d cuts, %d tightened bounds, %s" % (m, n_cuts, len(branches), "decimal" if decimal else "integer")
+    objectives = set()
+    for implicit, entry in ((0, "solve_dual"), (1, "solve_dual_bounded")):
+        refusal = child.model.dual_bounded_refusal(implicit_bounds=implicit)
+        rows = child.model.kernel_path(implicit_bounds=implicit)["m"]
+        if refusal:
+            print("%s | %s, implicit_bounds = %d: %d rows, refused: %s" % (label, entry, implicit, rows, refusal), flush=True)
+            continue
+        solver = relp_amd.Solver(certify=1, implicit_bounds=implicit).load_model(child.model)
+
+        def run():
+            started = time.perf_counter()
+            result = getattr(solver, entry)(basis)
+            wall = 1e3 * (time.perf_counter() - started)
+            assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+            objectives.add(solver.objective_exact())
+            pivots = solver.dual_pivots()
+            return wall, pivots, 1e6 * solver.record()["dual_device_seconds"] / max(1, pivots), result.pivots_phase_two, 1e3 * solver.record()["dual_start_seconds"]
+
+        (wall, lo, hi), (pivots, _, _), (device_us, us_lo, us_hi), (clean_up, _, _), (start_ms, _, _) = spread_of(run)
+        print("%s | %s, implicit_bounds = %d: %d rows, %d dual + %d primal pivots, %.1f ms (%.1f .. %.1f) of which the start %.1f ms, "
+              "%.1f us (%.1f .. %.1f) of device time per dual pivot" % (label, entry, implicit, rows, pivots, clean_up, wall, lo, hi, start_ms, device_us, us_lo, us_hi),
+              flush=True)
+        solver.close()
+    assert len(objectives) <= 1, objectives  # both formulations end at the same exact optimum
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
@@ -221,7 +262,14 @@ def main():
                              "tools/profile_r2_maxflow.sh): every handle with plain launches, and begin_dual / begin_dual_from only")
     parser.add_argument("--pricing", type=int, nargs="+", choices=[0, 1], default=None,
                         help="only the table of the leaving-row rule: the children of --start under each of the rules given")
+    parser.add_argument("--bounded", action="store_true",
+                        help="only the table of the loop on implicit upper bounds: a bound on every structural variable, both formulations")
     args = parser.parse_args()
+    if args.bounded:
+        for m in args.sizes:
+            for decimal in ([True] if args.decimal else [False, True]):
+                bounded_probe(m, decimal, args.cuts or 24)
+        return
     if args.pricing is not None:
         for m in args.sizes:
             for n_cuts in ([args.cuts] if args.cuts else [4, 24]):
