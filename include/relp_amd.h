@@ -946,8 +946,8 @@ int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_mod
  * never priced.  A basic variable above its upper bound is no error: like one below zero it is a row the loop repairs.
  * One dual pivot: the leaving row has the largest violation max(-x_i, x_i - u_i) (options.dual_pricing = 1: its square over the row
  * norm of the inverse); the entering column is found by the ratio test of relp_solve_dual on the signed row; the leaving variable
- * stops at the bound it violated, and one that the branch fixed does not enter again.  There is no bound-flipping ratio test: an
- * entering variable that overshoots its own bound is a violated row for a later pivot.
+ * stops at the bound it violated, and one that the branch fixed does not enter again.  An entering variable that overshoots its own
+ * bound is a violated row for a later pivot; the bound-flipping ("long-step") ratio test is an option, relp_set_dual_long_step below.
  * relp_iterate_dual, relp_get_dual_pivots, relp_get_dual_weights and the record keys are shared with relp_begin_dual;
  * relp_get_record_json adds "dual_bounded": true where the last start ran the loop on implicit bounds.  A finite optimum is
  * certified as a cold solve with implicit bounds is; RELP_RESULT_INFEASIBLE comes back with certified = 0 and the relp_last_error of
@@ -956,6 +956,20 @@ int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_mod
 int32_t relp_solve_dual_bounded(relp_handle* handle, const int32_t* basis_columns, relp_result* result);
 int32_t relp_begin_dual_bounded(relp_handle* handle, const int32_t* basis_columns);
 int32_t relp_debug_dual_bounded_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length);
+
+/* The long-step (bound-flipping) ratio test of that loop, a switch on the handle (relp_options has no field for it): `on` = 1 or 0,
+ * off on a new handle; any other value is RELP_ERR_ARGUMENT, a null handle answers as relp_begin_dual does.  It holds until changed
+ * and is read by relp_begin_dual_bounded / relp_solve_dual_bounded.  With it on, the candidates of the ratio test are walked in the
+ * order of their ratios, and a candidate with a finite upper bound whose ratio the dual step can pass -- the leaving row stays violated
+ * by more than options.harris_delta with the column at its other bound -- goes to that bound instead of entering (at most 32 per
+ * pivot); the entering column is the one the ratio test of the loop chooses among the rest, by the same rule (textbook or Harris) and
+ * ties.  One more launch per dual pivot, and no further basis change.  With it off every launch and result is what it was.  On a plan
+ * without implicit bounds the switch changes nothing; while it is on, relp_begin_dual, relp_solve_dual, relp_begin_dual_from and
+ * relp_solve_dual_from return RELP_ERR_ARGUMENT (their loop has no boxed column to flip).
+ * relp_get_record_json: "dual_long_step" (the last start ran the loop with it), "dual_flips" (columns sent to their other bound over
+ * the dual pivots since that start) and "dual_long_step_skipped" (pivots whose boxed candidates, more than 2048, did not fit the
+ * kernel: the plain rule there). */
+int32_t relp_set_dual_long_step(relp_handle* handle, int32_t on);
 
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);

@@ -203,6 +203,8 @@ SYMBOLS = [
     "relp_begin_dual_from", "relp_solve_dual_from", "relp_debug_dual_inherit_refusal",
     # ... on implicit upper bounds: the child of a branching step (the BOUNDED kernels of dual.hip)
     "relp_begin_dual_bounded", "relp_solve_dual_bounded", "relp_debug_dual_bounded_refusal",
+    # ... with the long-step (bound-flipping) ratio test (dual_long_step_kernel)
+    "relp_set_dual_long_step",
 ]
 
 
@@ -789,9 +791,19 @@ class Solver:
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_begin_dual_bounded(self._h, _ptr(arr, C.c_int32)))
 
-    def solve_dual_bounded(self, basis):
+    def set_dual_long_step(self, on):
+        """The long-step (bound-flipping) ratio test of the loop on implicit bounds, on or off (``relp_set_dual_long_step``; off on
+        a new handle).  It holds until changed; ``begin_dual_bounded`` / ``solve_dual_bounded`` read it, and while it is on the plain
+        ``begin_dual`` / ``solve_dual`` entry points raise ``RelpError``.  ``record()``: ``"dual_long_step"``, ``"dual_flips"``,
+        ``"dual_long_step_skipped"``."""
+        self._check(lib().relp_set_dual_long_step(self._h, int(on)))
+
+    def solve_dual_bounded(self, basis, long_step=None):
         """``solve_dual`` with the start of ``begin_dual_bounded``: the re-solve of a branched child from its parent's basis; returns
-        ``Result`` (``relp_solve_dual_bounded``).  ``record()["dual_bounded"]`` says whether the loop ran on implicit bounds."""
+        ``Result`` (``relp_solve_dual_bounded``).  ``record()["dual_bounded"]`` says whether the loop ran on implicit bounds.
+        ``long_step``: ``set_dual_long_step`` first; ``None`` keeps the handle's setting."""
+        if long_step is not None:
+            self.set_dual_long_step(long_step)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_bounded(self._h, _ptr(arr, C.c_int32), C.byref(result)))

@@ -776,6 +776,8 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     if (sv.dual_start_residual() >= 0.0) out << sv.dual_start_residual();
     else out << "null";
     out << ", \"dual_bounded\": " << (sv.dual_bounded() ? "true" : "false");
+    out << ", \"dual_long_step\": " << (sv.dual_long_step() ? "true" : "false") << ", \"dual_flips\": " << sv.dual_flips()
+        << ", \"dual_long_step_skipped\": " << sv.dual_long_step_skipped();
     out << ", \"dual_pricing\": \"" << (h->options.dual_pricing == RELP_DUAL_PRICING_STEEPEST_EDGE ? "steepest_edge" : "infeasibility") << "\"";
     out << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
@@ -911,6 +913,15 @@ int32_t relp_begin_dual_bounded(relp_handle* h, const int32_t* basis_columns) {
     REQUIRE_LOADED(h);
     if (!basis_columns) return RELP_ERR_ARGUMENT;
     return guarded(h, [&] { h->solver->begin_dual_bounded(basis_columns); });
+}
+int32_t relp_set_dual_long_step(relp_handle* h, int32_t on) {
+    if (!h || !h->solver) return RELP_ERR_ARGUMENT;
+    if (on != 0 && on != 1) {
+        h->error = "relp_set_dual_long_step: the switch is 0 or 1, not " + std::to_string(on);
+        return RELP_ERR_ARGUMENT;
+    }
+    h->solver->set_dual_long_step(on == 1);
+    return RELP_OK;
 }
 int32_t relp_begin_dual_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns) {
     REQUIRE_LOADED(h);

@@ -205,6 +205,119 @@ __global__ void __launch_bounds__(DUAL_COLUMNS_PER_BLOCK) dual_row_bounded_kerne
 }
 
 // ---------------------------------------------------------------------------------------------------
+// 2b. The long-step (bound-flipping) ratio test, an option of the loop on implicit bounds: one workgroup between the row kernel (either
+//    variant) and dual_choose_kernel.  Along the dual ray of row p the slope of the dual objective is the violation delta = v_p; it
+//    drops by ub_j |abar_j| at the ratio of every boxed candidate j, because that column can go to its other bound instead of
+//    entering.  The candidates (abar_j < -tol_pivot) in the order (max(d_j, 0) / |abar_j|, j): the walk passes a candidate while the
+//    slope behind it stays above harris_delta -- row p is then still a row dual_leave_kernel would call violated, on the same side --
+//    and ends at one without a bound, at the last candidate of all, at the first that would take the slope to harris_delta or below,
+//    and after DUAL_MAX_FLIPS passed ones (every prefix of the order that keeps the slope positive is a legal flip set).
+//    The boxed candidates are compacted into LDS (ratio, ub_j |abar_j|, j; the slots in no fixed order, which no result depends on:
+//    every choice below is a minimum under the total order (ratio, j)), the candidates without a bound only give their smallest
+//    (ratio, j).  Then one round per passed candidate: the workgroup's arg-min over the unmarked slots, the tests above, the mark.
+//    F is short (1 to 3 columns on the test family), so peeling beats a sort.  Out: flip_count[0] = |F|, flip_j in walk order,
+//    alpha_row[j] = 0 on F ("not eligible" to dual_choose_kernel and to the pass below) and part_theta rewritten -- slot 0 = pass 1
+//    over the candidates outside F, the other slots +inf --, so that dual_choose_kernel and the pivot kernel choose the entering
+//    column outside F by their own rule.  Nothing of DeviceLP is written: the flips are applied by dual_pivot_kernel<true, true>
+//    behind its guard.  More boxed candidates than slots: F is empty for this pivot (the plain rule) and flip_count[1] = 1 says so.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DL_THREADS) dual_long_step_kernel(DeviceLP lp, DualBuffers b, double tol_pivot, double slack, double harris_delta) {
+    __shared__ double s_key[DL_THREADS / WAVE];
+    __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
+    __shared__ double s_red[DL_THREADS / WAVE + 2];
+    __shared__ double s_ratio[DUAL_LONG_STEP_SLOTS];
+    __shared__ double s_drop[DUAL_LONG_STEP_SLOTS];  // ub_j |abar_j|: what the slope loses when j is passed
+    __shared__ int s_col[DUAL_LONG_STEP_SLOTS];      // j, -1 once passed
+    __shared__ int s_count[2];                       // boxed candidates, candidates without a bound
+    if (lp.ctl->status != ST_RUNNING) return;
+    const int p = lp.ctl->p;
+    const double x_p = lp.xB[p], up_p = lp.xub[p];
+    if (threadIdx.x < 2) s_count[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        b.flip_count[0] = 0;
+        b.flip_count[1] = 0;
+    }
+    __syncthreads();
+    double free_key = 0.0;  // the first candidate without a bound: the largest -ratio, ties to the lowest column
+    unsigned long long free_rank = RANK_NONE;
+    for (int j0 = lp.n_art + threadIdx.x; j0 < lp.n; j0 += DL_U * DL_THREADS) {
+        double av[DL_U], dv[DL_U], widthv[DL_U];  // DL_U columns per thread in flight together: one round trip up to 8192 columns
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int j = j0 + u * DL_THREADS;
+            av[u] = j < lp.n ? b.alpha_row[j] : 0.0;
+            dv[u] = j < lp.n ? b.d[j] : 0.0;
+            widthv[u] = j < lp.n ? lp.ub[j] : INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int j = j0 + u * DL_THREADS;
+            if (!(av[u] < -tol_pivot)) continue;  // (a column past the end has alpha 0)
+            const double mag = fabs(av[u]), ratio = fmax(dv[u], 0.0) / mag;
+            if (widthv[u] < INFINITY) {
+                const int slot = atomicAdd(&s_count[0], 1);  // (an integer counter in LDS; the slot order is free, see above)
+                if (slot < DUAL_LONG_STEP_SLOTS) {
+                    s_ratio[slot] = ratio;
+                    s_drop[slot] = widthv[u] * mag;
+                    s_col[slot] = j;
+                }
+            } else {
+                atomicAdd(&s_count[1], 1);
+                keep_better(-ratio, (unsigned long long)(unsigned)j, free_key, free_rank);
+            }
+        }
+    }
+    block_argbest<true>(free_key, free_rank, s_key, s_rank);  // (the slots' first use; its barrier also publishes s_count and the slots)
+    const int boxed = s_count[0], candidates = boxed + s_count[1];
+    if (boxed == 0) return;
+    if (boxed > DUAL_LONG_STEP_SLOTS) {
+        if (threadIdx.x == 0) b.flip_count[1] = 1;
+        return;
+    }
+    double slope = fmax(-x_p, x_p - up_p);
+    int passed = 0;
+    while (passed < DUAL_MAX_FLIPS && passed + 1 < candidates) {  // (the last candidate of all is never passed: it enters)
+        double key = 0.0;
+        unsigned long long rank = RANK_NONE;
+        for (int e = threadIdx.x; e < boxed; e += DL_THREADS) {
+            const int j = s_col[e];
+            if (j >= 0) keep_better(-s_ratio[e], ((unsigned long long)(unsigned)j << 32) | (unsigned)e, key, rank);
+        }
+        block_argbest(key, rank, s_key, s_rank);
+        if (rank == RANK_NONE) break;
+        const int j = (int)(rank >> 32), e = (int)(rank & 0xffffffffu);
+        if (free_rank != RANK_NONE && (free_key > key || (free_key == key && (int)free_rank < j))) break;  // a candidate without a bound comes first
+        const double behind = slope - s_drop[e];
+        if (!(behind > harris_delta)) break;
+        if (threadIdx.x == 0) {  // (every thread scanned s_col in front of block_argbest's barriers)
+            s_col[e] = -1;
+            b.flip_j[passed] = j;
+            b.alpha_row[j] = 0.0;
+        }
+        slope = behind;
+        passed += 1;
+        __syncthreads();  // the mark, and alpha_row[j] = 0, for every thread
+    }
+    if (passed == 0) return;
+    double theta = INFINITY;
+    for (int j0 = lp.n_art + threadIdx.x; j0 < lp.n; j0 += DL_U * DL_THREADS) {
+        double av[DL_U], dv[DL_U];
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u) {
+            const int j = j0 + u * DL_THREADS;
+            av[u] = j < lp.n ? b.alpha_row[j] : 0.0;
+            dv[u] = j < lp.n ? b.d[j] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < DL_U; ++u)
+            if (av[u] < -tol_pivot) theta = fmin(theta, (fmax(dv[u], 0.0) + slack) / fabs(av[u]));
+    }
+    theta = block_reduce<1>(theta, s_red);
+    for (int k = threadIdx.x; k < b.blocks; k += DL_THREADS) b.part_theta[k] = k == 0 ? theta : INFINITY;
+    if (threadIdx.x == 0) b.flip_count[0] = passed;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // 3. theta_max = the minimum of the partial minima (every workgroup folds them itself, in the same order), then pass 2: among the
 //    eligible columns with max(d_j, 0) / |alpha_pj| <= theta_max the largest |alpha_pj| (key 1 under the textbook rule), ties to the
 //    lowest column.  One candidate per workgroup.
@@ -246,14 +359,23 @@ __global__ void __launch_bounds__(DUAL_COLUMNS_PER_BLOCK) dual_choose_kernel(Dev
 //    BOUNDED: alpha_q = Binv (sgn_q a_q); the pivot is usable when s alpha_q[p] < -tol_pivot; theta = (x_B[p] - bound) / alpha_q[p] with
 //    bound = 0 or xub[p] by the side s.  A column that leaves at its upper bound is held complemented from then on (rhs moves over
 //    its entries as in ftran_ratio_kernel; exchange_columns of pivot_step.hpp); one of width 0 gets pos -3 and never enters again.
-//    The entering value may exceed ub[q]: that is an infeasible row for a later pivot (no bound-flipping ratio test).
-template <bool BOUNDED>
+//    The entering value may exceed ub[q]: that is an infeasible row for a later pivot.
+//    LONG (BOUNDED only; the long-step ratio test, behind dual_long_step_kernel): the columns of the flip set F go to their other bound
+//    in the same launch, behind the same guard.  In front of the barrier, where nothing but scratch is written: w = Binv Delta with
+//    Delta = sum over F of ub_j sgn_j a_j, one column after the other in flip order through the staging of the entering column, into
+//    DualBuffers::flip_w.  Behind the guard: theta = (x_B[p] - w[p] - bound) / alpha_q[p], x_B = (x_B - w) - theta alpha_q in the one
+//    pass, rhs -= Delta column by column, the complement marks of F, flip_cost, the objective and the two totals.  With F empty
+//    every value is the one the instantiation without LONG computes (x - 0 is x).
+template <bool BOUNDED, bool LONG = false>
 __global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, DualBuffers b, double tol_pivot) {
+    static_assert(BOUNDED || !LONG, "the long step flips boxed columns: implicit bounds only");
     __shared__ double s_key[DL_THREADS / WAVE];
     __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
     __shared__ int s_rows[DL_COL_CHUNK];
     __shared__ double s_vals[DL_COL_CHUNK];
-    __shared__ double s_pivot[BOUNDED ? 3 : 2];  // alpha_q[p], x_B[p], (xub[p])
+    __shared__ double s_pivot[BOUNDED ? (LONG ? 4 : 3) : 2];  // alpha_q[p], x_B[p], (xub[p]), (w[p])
+    __shared__ int s_flip_j[LONG ? DUAL_MAX_FLIPS : 1];          // LONG: the flip set and ub_j sgn_j of each, read here in front of
+    __shared__ double s_flip_scale[LONG ? DUAL_MAX_FLIPS : 1];   // the barrier: flipped[j] is rewritten at the end
     Ctl* ctl = lp.ctl;
     if (ctl->status != ST_RUNNING) return;
     const int m = lp.m, ld = lp.ld;
@@ -320,10 +442,60 @@ __global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, Dua
             }
         }
     }
+    int flips = 0;
+    if constexpr (LONG) {
+        flips = min(b.flip_count[0], DUAL_MAX_FLIPS);
+        if (flips > 0) {
+            if ((int)threadIdx.x < flips) {
+                const int j = b.flip_j[threadIdx.x];
+                s_flip_j[threadIdx.x] = j;
+                s_flip_scale[threadIdx.x] = lp.ub[j] * (lp.flipped[j] ? -1.0 : 1.0);
+            }
+            for (int i = threadIdx.x; i < m; i += DL_THREADS) b.flip_w[i] = 0.0;  // (read again below by the thread that wrote it)
+            __syncthreads();
+            for (int f = 0; f < flips; ++f) {
+                const int j = s_flip_j[f];
+                const double scale = s_flip_scale[f];
+                const int fa = lp.col_start[j], fb = lp.col_start[j + 1];
+                for (int c0 = fa; c0 < fb; c0 += DL_COL_CHUNK) {
+                    const int cnt = min(DL_COL_CHUNK, fb - c0);
+                    __syncthreads();
+                    for (int e = threadIdx.x; e < cnt; e += DL_THREADS) {
+                        s_rows[e] = lp.row_index[c0 + e];
+                        s_vals[e] = lp.value[c0 + e] * scale;
+                    }
+                    __syncthreads();
+                    for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
+                        double acc[DL_U];
+#pragma unroll
+                        for (int u = 0; u < DL_U; ++u) {
+                            const int i = i0 + u * DL_THREADS;
+                            acc[u] = i < m ? b.flip_w[i] : 0.0;
+                        }
+                        for (int e = 0; e < cnt; ++e) {
+                            const size_t off = (size_t)s_rows[e] * ld;
+                            const double v = s_vals[e];
+#pragma unroll
+                            for (int u = 0; u < DL_U; ++u) {
+                                const int i = i0 + u * DL_THREADS;
+                                if (i < m) acc[u] += lp.Binv[off + i] * v;
+                            }
+                        }
+#pragma unroll
+                        for (int u = 0; u < DL_U; ++u) {
+                            const int i = i0 + u * DL_THREADS;
+                            if (i < m) b.flip_w[i] = acc[u];
+                        }
+                    }
+                }
+            }
+        }
+    }
     if ((p % DL_THREADS) == (int)threadIdx.x) {  // the thread that owns row p
         s_pivot[0] = lp.alpha[p];
         s_pivot[1] = lp.xB[p];
         if constexpr (BOUNDED) s_pivot[2] = lp.xub[p];
+        if constexpr (LONG) s_pivot[3] = flips > 0 ? b.flip_w[p] : 0.0;
     }
     // BOUNDED: what thread 0 rewrites at the end -- basis[p], flipped[leaving] -- is read by every thread here, in front of this barrier
     int leaving = 0, leaving_flipped = 0, leaving_first = 0, leaving_last = 0;
@@ -345,19 +517,42 @@ __global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, Dua
             return;
         }
         const bool leaves_at_upper = side < 0.0;
-        const double theta = (leaves_at_upper ? x_p - up_p : x_p) / alpha_pq;
+        double theta = (leaves_at_upper ? x_p - up_p : x_p) / alpha_pq;
+        if constexpr (LONG) theta = ((leaves_at_upper ? x_p - up_p : x_p) - s_pivot[3]) / alpha_pq;  // (row p after the flips: still violated, on the same side)
         for (int i0 = threadIdx.x; i0 < m; i0 += DL_U * DL_THREADS) {
-            double av[DL_U], xbv[DL_U];
+            double av[DL_U], xbv[DL_U], wv[DL_U];
 #pragma unroll
             for (int u = 0; u < DL_U; ++u) {
                 const int i = i0 + u * DL_THREADS;
                 av[u] = i < m ? lp.alpha[i] : 0.0;
                 xbv[u] = i < m ? lp.xB[i] : 0.0;
+                if constexpr (LONG) wv[u] = (flips > 0 && i < m) ? b.flip_w[i] : 0.0;
             }
 #pragma unroll
             for (int u = 0; u < DL_U; ++u) {
                 const int i = i0 + u * DL_THREADS;
-                if (i < m) lp.xB[i] = i == p ? theta : xbv[u] - theta * av[u];
+                if constexpr (LONG) {
+                    if (i < m) lp.xB[i] = i == p ? theta : (xbv[u] - wv[u]) - theta * av[u];
+                } else {
+                    if (i < m) lp.xB[i] = i == p ? theta : xbv[u] - theta * av[u];
+                }
+            }
+        }
+        if constexpr (LONG) {
+            // rhs -= Delta, a column of F after the other (two of them may share a row), each as a column that leaves at its upper
+            // bound moves it below; then the marks, one thread per column of F (no column of F is q or the leaving one)
+            for (int f = 0; f < flips; ++f) {
+                const int j = s_flip_j[f];
+                const double scale = s_flip_scale[f];
+                const int fb = lp.col_start[j + 1];
+                for (int e = lp.col_start[j] + (int)threadIdx.x; e < fb; e += DL_THREADS) lp.rhs[lp.row_index[e]] -= scale * lp.value[e];
+                __syncthreads();
+            }
+            if ((int)threadIdx.x < flips) {
+                const int j = s_flip_j[threadIdx.x];
+                const int now_flipped = s_flip_scale[threadIdx.x] < 0.0 ? 0 : 1;
+                lp.flipped[j] = now_flipped;
+                lp.pos[j] = now_flipped ? -2 : -1;
             }
         }
         if (leaves_at_upper) {  // the leaving variable stops at its upper bound: held in complemented form from now on
@@ -365,6 +560,21 @@ __global__ void __launch_bounds__(DL_THREADS) dual_pivot_kernel(DeviceLP lp, Dua
             for (int e = leaving_first + (int)threadIdx.x; e < leaving_last; e += DL_THREADS) lp.rhs[lp.row_index[e]] -= up_p * sgn_l * lp.value[e];
         }
         if (threadIdx.x == 0) {
+            if constexpr (LONG) {  // the objective moves by sum d_j ub_j over F, d_j as priced at this pivot; flip_cost as in ctl_bound_flip
+                double moved = 0.0, shift = 0.0;
+                for (int f = 0; f < flips; ++f) {
+                    const int j = s_flip_j[f];
+                    const double scale = s_flip_scale[f];
+                    moved += b.d[j] * fabs(scale);
+                    shift += scale * lp.cost[j];  // (+ub_j c_j for a column that is complemented now, - for one that is not any more)
+                }
+                if (flips > 0) {
+                    ctl->minus_obj = ctl->minus_obj - moved;
+                    ctl->flip_cost += shift;
+                }
+                b.flip_count[2] += flips;
+                b.flip_count[3] += b.flip_count[1];
+            }
             const double d_q = b.d[q];
             lp.basis[p] = q;
             const int fl = exchange_columns(lp.pos, lp.flipped, lp.xub, true, q, p, leaving, leaving_flipped, leaves_at_upper, ub_q);
@@ -576,8 +786,12 @@ void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, bool bou
 void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivot, bool textbook, hipStream_t s) {
     hipLaunchKernelGGL(dual_choose_kernel, dim3(b.blocks), dim3(DUAL_COLUMNS_PER_BLOCK), 0, s, d, b, tol_pivot, textbook ? 1 : 0);
 }
-void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, bool bounded, double tol_pivot, hipStream_t s) {
-    if (bounded) hipLaunchKernelGGL(dual_pivot_kernel<true>, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
+void launch_dual_long_step(const DeviceLP& d, const DualBuffers& b, double tol_pivot, double slack, double harris_delta, hipStream_t s) {
+    hipLaunchKernelGGL(dual_long_step_kernel, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot, slack, harris_delta);
+}
+void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, bool bounded, bool long_step, double tol_pivot, hipStream_t s) {
+    if (bounded && long_step) hipLaunchKernelGGL((dual_pivot_kernel<true, true>), dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
+    else if (bounded) hipLaunchKernelGGL(dual_pivot_kernel<true>, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
     else hipLaunchKernelGGL(dual_pivot_kernel<false>, dim3(1), dim3(DL_THREADS), 0, s, d, b, tol_pivot);
 }
 void launch_dual_update(const DeviceLP& d, hipStream_t s) {

@@ -23,9 +23,15 @@ struct DualBuffers {
     double* beta = nullptr;        // [m] beta_i = |e_i' B^-1|^2, the squared norm of row i of the inverse
     double* beta_part = nullptr;   // [slices][m] dual_weights_kernel: the sum over one slice of columns, per row
     int slices = 0;                // column slices of its grid (dual_weight_slices)
+    // The long-step ratio test only (Solver::set_dual_long_step on a plan with implicit bounds; nullptr otherwise)
+    int* flip_count = nullptr;     // [4] of this pivot: |F|, 1 where the kernel fell back to F = {}; since the start: flips applied, fall-backs
+    int* flip_j = nullptr;         // [DUAL_MAX_FLIPS] the columns of F in the order of the walk
+    double* flip_w = nullptr;      // [m] scratch of the pivot kernel: Binv Delta, Delta = sum over F of ub_j sgn_j a_j
 };
 
 constexpr int DUAL_COLUMNS_PER_BLOCK = 256;  // dual_row_kernel, dual_choose_kernel: one lane per column
+constexpr int DUAL_MAX_FLIPS = 32;           // long step: columns passed in one pivot at most (stopping early is always valid)
+constexpr int DUAL_LONG_STEP_SLOTS = 2048;   // dual_long_step_kernel: boxed candidates of one pivot it holds in LDS (40 KB)
 inline int dual_blocks(int n_art, int n) { return (n - n_art + DUAL_COLUMNS_PER_BLOCK - 1) / DUAL_COLUMNS_PER_BLOCK; }
 
 // Column slices of dual_weights_kernel: at least 64 columns each (16 per wave of its workgroups), 16 at most -- at m = 2049 the grid is
@@ -50,8 +56,14 @@ inline int dual_weight_slices(int m) { return m / 64 < 1 ? 1 : m / 64 > DUAL_WEI
 void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, bool bounded, hipStream_t s);  // beta == nullptr: rule 0
 void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, bool bounded, double tol_pivot, double slack, hipStream_t s);
 void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivot, bool textbook, hipStream_t s);
-void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, bool bounded, double tol_pivot, hipStream_t s);
+void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, bool bounded, bool long_step, double tol_pivot, hipStream_t s);
 void launch_dual_update(const DeviceLP& d, hipStream_t s);
+
+// The long-step (bound-flipping) ratio test of the bounded loop, a sixth launch between row and choose (b.flip_count allocated, and
+// launch_dual_pivot with `long_step`): the boxed candidates whose ratios the dual step may pass while row p stays violated by more than
+// harris_delta go to their other bound instead of entering (DualBuffers::flip_j), choose and pivot find the entering column among the
+// rest, and the pivot kernel applies the flips behind its ST_REFACTOR guard.  `slack` as launch_dual_row's.
+void launch_dual_long_step(const DeviceLP& d, const DualBuffers& b, double tol_pivot, double slack, double harris_delta, hipStream_t s);
 
 // The steepest-edge rule of the leaving row (b.beta allocated): launch_dual_leave takes `beta` = b.beta and keys a row by
 // x_B[i]^2 / beta_i; after launch_dual_update the weights are computed again from the new inverse, which they equal by construction

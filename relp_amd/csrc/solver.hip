@@ -82,6 +82,7 @@ void Solver::free_device() {
     device_memory_.free_all();
     pinned_memory_.free_all();
     h_ctl_ = h_ctl_out_ = nullptr;
+    h_flip_totals_ = nullptr;
     h_rb_basis_ = h_rb_flipped_ = h_rb_pos_ = nullptr;
     h_rb_xb_ = h_rb_ub_ = nullptr;
     d_ = DeviceLP{};
@@ -89,6 +90,8 @@ void Solver::free_device() {
     dual_ = DualBuffers{};
     dual_ready_ = false;
     dual_bounded_ = false;
+    dual_long_active_ = false;
+    dual_flips_ = dual_long_skipped_ = 0;
     dual_start_ = "none";
 }
 
@@ -1378,6 +1381,9 @@ void Solver::check_dual_start(const int* basis_columns, bool bounded_entry) cons
     if (!loaded_) throw std::runtime_error("no LP loaded");
     const std::string refusal = bounded_entry ? dual_bounded_refusal(path_) : dual_refusal(path_);
     if (!refusal.empty()) throw std::invalid_argument(refusal);
+    if (!bounded_entry && dual_long_step_)
+        throw std::invalid_argument("begin_dual: the long-step ratio test is switched on (relp_set_dual_long_step), and only the loop on implicit upper bounds has it: "
+                                    "relp_begin_dual_bounded / relp_solve_dual_bounded take this call, or switch it off");
     const int rows = path_.bounded ? form_.data.nr_rows() : d_.m;  // (implicit bounds: a basis of the formulation, bound rows included)
     for (int i = 0; i < rows; ++i)
         if (basis_columns[i] < 0)
@@ -1464,6 +1470,15 @@ void Solver::finish_dual_start(const int* basis_columns, const char* how, double
         dual_.beta = device_alloc<double>(m);
         if (dual_.slices > 1) dual_.beta_part = device_alloc<double>((size_t)dual_.slices * m);
     }
+    dual_long_active_ = dual_long_step_ && path_.bounded;
+    if (dual_long_active_ && !dual_.flip_count) {  // (with the switch off nothing more is allocated than was)
+        dual_.flip_count = device_alloc<int>(4);
+        dual_.flip_j = device_alloc<int>(DUAL_MAX_FLIPS);
+        dual_.flip_w = device_alloc<double>(m);
+        h_flip_totals_ = pinned_memory_.alloc<int>(2);
+    }
+    if (dual_long_active_) RELP_HIP(hipMemsetAsync(dual_.flip_count, 0, 4 * sizeof(int), stream_));
+    dual_flips_ = dual_long_skipped_ = 0;
     const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
     dual_lds_ = 2 * (size_t)m * sizeof(double) <= lds_max;
     std::vector<double> cbar(n);
@@ -1514,17 +1529,18 @@ void Solver::dual_weights(double* out) {
     RELP_HIP(hipStreamSynchronize(stream_));
 }
 
-// One batch: the budget, then five launches per pivot (dual.hpp), and behind them the one or two of the weights under the steepest-edge
-// rule.  The chain is a run of no-ops from the first kernel that stops it.
+// One batch: the budget, then five launches per pivot (dual.hpp) -- six with the long-step ratio test --, and behind them the one or two
+// of the weights under the steepest-edge rule.  The chain is a run of no-ops from the first kernel that stops it.
 void Solver::launch_dual_pivots(int count) {
-    stats_.launches += 1 + 5LL * count;
+    stats_.launches += 1 + (dual_long_active_ ? 6LL : 5LL) * count;
     launch_budget(d_, count, stream_);
     const bool textbook = path_.ratio_textbook;
     for (int it = 0; it < count; ++it) {
         launch_dual_leave(d_, opt_.harris_delta, dual_.beta, path_.bounded, stream_);
         launch_dual_row(d_, dual_, dual_lds_, path_.bounded, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, stream_);
+        if (dual_long_active_) launch_dual_long_step(d_, dual_, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, opt_.harris_delta, stream_);
         launch_dual_choose(d_, dual_, opt_.tol_pivot, textbook, stream_);
-        launch_dual_pivot(d_, dual_, path_.bounded, opt_.tol_pivot, stream_);
+        launch_dual_pivot(d_, dual_, path_.bounded, dual_long_active_, opt_.tol_pivot, stream_);
         launch_dual_update(d_, stream_);
         if (dual_.beta) stats_.launches += launch_dual_weights(d_, dual_, true, stream_);
     }
@@ -1552,6 +1568,12 @@ long long Solver::iterate_dual(long long count, int* stop_reason) {
         launch_dual_pivots(batch);
         RELP_HIP(hipEventRecord(ev_b_, stream_));
         Ctl after = read_ctl();
+        if (dual_long_active_) {  // the two totals since the start (dual_pivot_kernel adds to them behind its guard)
+            RELP_HIP(hipMemcpyAsync(h_flip_totals_, dual_.flip_count + 2, 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));  // (pinned, as the control block's mirror)
+            RELP_HIP(hipStreamSynchronize(stream_));
+            dual_flips_ = h_flip_totals_[0];
+            dual_long_skipped_ = h_flip_totals_[1];
+        }
         float batch_ms = 0.0f;
         RELP_HIP(hipEventElapsedTime(&batch_ms, ev_a_, ev_b_));
         dual_device_seconds_ += 1e-3 * batch_ms;

@@ -69,6 +69,13 @@ public:
     void begin_dual_bounded(const int* basis_columns);
     void solve_dual_bounded(const int* basis_columns, relp_result* result);
     bool dual_bounded() const { return dual_bounded_; }  // the last start ran the loop with implicit upper bounds
+    // The long-step (bound-flipping) ratio test of that loop (dual.hpp: launch_dual_long_step), off by default.  The switch holds until
+    // changed and is read by begin_dual_bounded / solve_dual_bounded; while it is on, begin_dual, solve_dual and the _from pair refuse
+    // (std::invalid_argument).  On a bounded-entry plan without bounds there is no boxed column and it changes nothing.
+    void set_dual_long_step(bool on) { dual_long_step_ = on; }
+    bool dual_long_step() const { return dual_long_active_; }  // the last start ran the loop with it
+    long long dual_flips() const { return dual_flips_; }  // columns it sent to their other bound, over the dual pivots since that start
+    long long dual_long_step_skipped() const { return dual_long_skipped_; }  // pivots at which it held too many candidates and made none
     long long dual_pivots() const { return dual_pivots_; }  // of the last solve_dual / since begin_dual
     // relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE: the m weights the next dual pivot would read (the squared row norms
     // of the inverse).  std::runtime_error under rule 0 and before a begin_dual.
@@ -191,6 +198,10 @@ private:
     void check_dual_start(const int* basis_columns, bool bounded_entry = false) const;
     void start_dual_from_scratch(const int* basis_columns, bool bounded_entry);  // begin_dual and begin_dual_bounded
     bool dual_bounded_ = false;
+    bool dual_long_step_ = false;    // the switch
+    bool dual_long_active_ = false;  // ... as the last start read it, on a plan with implicit bounds
+    long long dual_flips_ = 0, dual_long_skipped_ = 0;
+    int* h_flip_totals_ = nullptr;   // pinned: DualBuffers::flip_count[2..3] after a batch
     // ... and their tail behind set_phase(2): the loop's buffers, the dual-feasibility check that names the column, the counters
     void finish_dual_start(const int* basis_columns, const char* how, double t0, long long gemms_before);
     void run_dual(const Solver* parent, const int* basis_columns, relp_result* result, bool bounded_entry = false);  // every solve_dual*: one loop

@@ -33,7 +33,13 @@ the bounds as rows (``implicit_bounds=0``) and ``solve_dual_bounded`` on implici
 the device LP, the dual pivots, the wall time of the call and the device time per dual pivot; where the row limit of the dual loop
 refuses the explicit formulation, the refusal.  Both end at the same exact objective.
 
-    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded]
+``--bounded --long-step``: the same child on implicit bounds under both ratio tests from the same basis, the plain one and the
+long-step (bound-flipping) one (``Solver.set_dual_long_step``), a line per rule: dual pivots, flips, the whole certified call and the
+device time per dual pivot.  ``--every N`` puts a bound on every N-th structural variable (1 unless given; 2 is the family of the
+tests), ``--tight N`` tightens N bounds (8 unless given): with few bounds the walks of the two rules coincide and the difference of
+the two device times is what a pivot with the switch on and no flip costs.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded [--long-step]]
 """
 import argparse
 import os
@@ -251,6 +257,37 @@ def bounded_probe(m, decimal, n_cuts, n_tight=8):
     assert len(objectives) <= 1, objectives  # both formulations end at the same exact optimum
 
 
+def long_step_probe(m, decimal, n_cuts, n_tight, every):
+    """One child of the long-step table of DESIGN.md section 10, a line per ratio test."""
+    import dual_bounded_lps
+    case = dual_bounded_lps.BoundedCase(m, 1000 + m, n_cuts, n_tight, decimal=decimal, every=every)
+    parent = relp_amd.Solver(certify=1, implicit_bounds=1).load_model(case.parent.model)
+    assert parent.solve_relaxation().certified
+    child, basis, _, branches = case.child(parent.basis(), parent.solution_exact())
+    parent.close()
+    label = "m = %d + %d cuts, %d tightened bounds, a bound on every %d. variable, %s" % (m, n_cuts, len(branches), every, "decimal" if decimal else "integer")
+    objectives = set()
+    for long_step in (False, True):
+        solver = relp_amd.Solver(certify=1, implicit_bounds=1).load_model(child.model)
+        solver.set_dual_long_step(long_step)
+
+        def run():
+            started = time.perf_counter()
+            result = solver.solve_dual_bounded(basis)
+            wall = 1e3 * (time.perf_counter() - started)
+            assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+            objectives.add(solver.objective_exact())
+            record, pivots = solver.record(), solver.dual_pivots()
+            assert record["dual_long_step"] is long_step
+            return wall, pivots, 1e6 * record["dual_device_seconds"] / max(1, pivots), result.pivots_phase_two, record["dual_flips"], record["dual_long_step_skipped"]
+
+        (wall, lo, hi), (pivots, _, _), (device_us, us_lo, us_hi), (clean_up, _, _), (flips, _, _), (skipped, _, _) = spread_of(run)
+        print("%s | %s: %d dual + %d primal pivots, %d flips (%d pivots fell back), %.1f ms (%.1f .. %.1f), %.1f us (%.1f .. %.1f) of device time per dual pivot" % (
+            label, "long step" if long_step else "plain rule", pivots, clean_up, flips, skipped, wall, lo, hi, device_us, us_lo, us_hi), flush=True)
+        solver.close()
+    assert len(objectives) == 1, objectives  # both rules end at the same exact optimum
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
@@ -264,7 +301,15 @@ def main():
                         help="only the table of the leaving-row rule: the children of --start under each of the rules given")
     parser.add_argument("--bounded", action="store_true",
                         help="only the table of the loop on implicit upper bounds: a bound on every structural variable, both formulations")
+    parser.add_argument("--long-step", action="store_true", help="with --bounded: implicit bounds under the plain and the long-step ratio test")
+    parser.add_argument("--every", type=int, default=1, help="with --long-step: a bound on every N-th structural variable")
+    parser.add_argument("--tight", type=int, default=8, help="with --long-step: tightened bounds per child")
     args = parser.parse_args()
+    if args.bounded and args.long_step:
+        for m in args.sizes:
+            for decimal in ([True] if args.decimal else [False, True]):
+                long_step_probe(m, decimal, args.cuts or 24, args.tight, args.every)
+        return
     if args.bounded:
         for m in args.sizes:
             for decimal in ([True] if args.decimal else [False, True]):
