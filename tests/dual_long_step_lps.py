@@ -9,6 +9,12 @@ candidate that would take the slope to 0 or below end it, and that candidate ent
 first: complemented, ``rhs -= ub_j sgn_j a_j``, ``x_B -= Binv Delta``; row p is then violated by exactly the remaining slope, on the
 same side, which ``step`` asserts.
 
+Three keywords restate limits of the kernels and default to "none", which is the rule above: ``slope_floor`` (a candidate is passed
+while ``slope - ub_j |abar_j| > slope_floor`` and a row counts as violated above it: the kernels' ``harris_delta``), ``slots`` (more
+boxed candidates than this in one row: F is empty at that pivot and ``skipped`` counts it) and ``max_flips``.  ``walks`` records per
+pivot what the walk saw.  ``HarrisLongStepBoundedDualReference`` chooses the entering column outside F by the two-pass rule.  The
+planted rows of tests/dual_planted_rows.py use all of these; the random family below uses none.
+
 The family is that of tests/dual_bounded_lps.py with a bound on every structural variable (``every=1``): the more columns are boxed,
 the more often a ratio can be passed.
 """
@@ -36,17 +42,25 @@ class LongStepBoundedDualReference(BoundedDualReference):
     as in the base class, and for the column the smaller of the lead of q over the next candidate and of its lead over the last
     passed candidate's ratio."""
 
-    def __init__(self, form, basis, max_flips=DUAL_MAX_FLIPS):
+    def __init__(self, form, basis, max_flips=DUAL_MAX_FLIPS, slope_floor=0, slots=None):
         super().__init__(form, basis)
         self.max_flips = max_flips
+        self.slope_floor = Fraction(slope_floor)  # the walk passes a candidate while ``behind > slope_floor`` (the kernel: harris_delta)
+        self.slots = slots  # more boxed candidates than this in one row: no flip at that pivot, ``skipped`` counts it (None: no limit)
+        self.skipped = 0
         self.flips, self.slope_margins = [], []
+        self.walks = []  # per pivot: what the walk saw (tests/dual_planted_rows.py reads it)
+
+    def entering(self, candidates, k):
+        """The index of the entering candidate among ``candidates[k:]``, the sorted ones outside F: the textbook rule takes the first."""
+        return k
 
     def step(self):
         m, form = self.m, self.form
         rows = []
         for i in range(m):
             v, side = self.violation(i)
-            if v > 0:
+            if v > self.slope_floor:  # (dual_leave_kernel: a row is violated above harris_delta; the default 0 is the base class's rule)
                 rows.append((self.key(i, v), -self.basis[i], -i, v, side))
         if not rows:
             return relp_amd.STOP_NO_ENTERING
@@ -69,19 +83,28 @@ class LongStepBoundedDualReference(BoundedDualReference):
             return relp_amd.STOP_UNBOUNDED
         candidates.sort()
         # the walk
-        slope, passed, slope_margin = delta, [], 1.0
+        boxed = sum(1 for _, j, _ in candidates if self.ub[j] is not None)
+        overflow = self.slots is not None and boxed > self.slots
+        self.skipped += int(overflow)
+        max_flips = 0 if overflow else self.max_flips
+        slope, passed, slope_margin, stopped_behind = delta, [], 1.0, None
         while True:
             _, j, magnitude = candidates[len(passed)]
-            if self.ub[j] is None or len(passed) == len(candidates) - 1 or len(passed) >= self.max_flips:
+            if self.ub[j] is None or len(passed) == len(candidates) - 1 or len(passed) >= max_flips:
                 break
             behind = slope - self.ub[j] * magnitude
             slope_margin = min(slope_margin, float(abs(behind) / delta))
-            if behind <= 0:
+            if behind <= self.slope_floor:
+                stopped_behind = behind
                 break
             passed.append(j)
             slope = behind
         k = len(passed)
-        ratio_q, q, _ = candidates[k]
+        entered = self.entering(candidates, k)
+        self.walks.append({"p": p, "side": side, "delta": delta, "candidates": list(candidates), "boxed": boxed, "overflow": overflow,
+                           "passed": list(passed), "forms": [self.flipped[j] for j in passed], "slope": slope, "stopped_behind": stopped_behind,
+                           "entered": entered, "costs": d})
+        ratio_q, q, _ = candidates[entered]
         leads = []
         if k + 1 < len(candidates):
             following = candidates[k + 1][0]
@@ -133,6 +156,27 @@ class LongStepBoundedDualReference(BoundedDualReference):
 
     def total_flips(self):
         return sum(len(passed) for passed in self.flips)
+
+
+class HarrisLongStepBoundedDualReference(LongStepBoundedDualReference):
+    """... with the two-pass rule of ``dual_row_bounded_kernel``, the rewrite of ``dual_long_step_kernel`` and ``dual_choose_kernel`` with
+    ``textbook == 0`` for the entering column: the walk is the same (it orders by ``max(d_j, 0) / |abar_j|``); over the candidates
+    outside F with ``abar_j < -tol_pivot``, ``theta_max = min (max(d_j, 0) + tol_dual) / |abar_j|``, and q has the largest
+    ``|abar_j|`` among those with ``max(d_j, 0) / |abar_j| <= theta_max``, ties to the lowest column.  ``tol_dual`` / ``tol_pivot``: the
+    exact values of the handle's doubles.  ``theta_margins``: per pivot the smallest ``|ratio_j - theta_max| / theta_max`` -- the one
+    comparison in which the device rounds ``d_j + tol_dual`` and the reference does not."""
+
+    def __init__(self, form, basis, tol_dual, tol_pivot, **options):
+        super().__init__(form, basis, **options)
+        self.tol_dual, self.tol_pivot = Fraction(tol_dual), Fraction(tol_pivot)
+        self.theta_margins = []
+
+    def entering(self, candidates, k):
+        rest = [(index, ratio, j, magnitude) for index, (ratio, j, magnitude) in enumerate(candidates) if index >= k and magnitude > self.tol_pivot]
+        theta_max = min((ratio * magnitude + self.tol_dual) / magnitude for _, ratio, _, magnitude in rest)
+        self.theta_margins.append(min(float(abs(ratio - theta_max) / theta_max) for _, ratio, _, _ in rest))
+        within = [(-magnitude, j, index) for index, ratio, j, magnitude in rest if ratio <= theta_max]
+        return min(within)[2]
 
 
 class SteepestLongStepBoundedDualReference(LongStepBoundedDualReference):
