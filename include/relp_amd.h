@@ -952,10 +952,40 @@ int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_mod
  * relp_get_record_json adds "dual_bounded": true where the last start ran the loop on implicit bounds.  A finite optimum is
  * certified as a cold solve with implicit bounds is; RELP_RESULT_INFEASIBLE comes back with certified = 0 and the relp_last_error of
  * relp_solve_dual.  relp_begin_dual, relp_solve_dual, relp_begin_dual_from and relp_solve_dual_from keep refusing a plan with
- * implicit bounds (the inherited inverse would need the parent's complemented basic columns). */
+ * implicit bounds; the inherited start of such a plan is relp_begin_dual_bounded_from below. */
 int32_t relp_solve_dual_bounded(relp_handle* handle, const int32_t* basis_columns, relp_result* result);
 int32_t relp_begin_dual_bounded(relp_handle* handle, const int32_t* basis_columns);
 int32_t relp_debug_dual_bounded_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length);
+
+/* ---- ... started from the parent's inverse (dual_inherit_mapped_kernel, relp_amd/csrc/dual.hip) -------------------------------------
+ * relp_begin_dual_from for two LPs held on implicit bounds.  The child of a pure branch has the parent's constraint rows, so its basis
+ * matrix is the parent's up to the order of the positions and a sign per column: a column that one handle holds complemented
+ * (x_j = u_j - x'_j) and the other does not.  `parent` holds its basis wherever its own pivots left it; `basis_columns` is the child's
+ * basis of the formulation as relp_begin_dual_bounded takes it (the parent's relp_get_basis in the child's columns, plus the slack of
+ * every row the child's formulation gained).  The relation is decided on the two bases reduced to the constraint rows: the child has
+ * k >= 0 more constraint rows than the parent's m, its first m are the parent's in order; neither reduced basis holds an artificial;
+ * every basic column of the child is either the same column as a basic column of the parent -- structural j, or the slack or surplus
+ * of constraint row i, whatever its number -- with exactly the parent's entries on those m rows, or a column with one entry, in a new
+ * row, one per new row.  Bounds, costs and right-hand sides may differ anywhere.  Position i of the child then holds what the parent
+ * holds at a position src[i], and row i of the child's inverse is +-(row src[i] of the parent's); the k rows of the new slacks are
+ * sparse combinations of those, as in relp_begin_dual_from.  The same guard follows, and the dual-feasibility check of
+ * relp_begin_dual_bounded on the signed costs.  The long-step switch is read as relp_begin_dual_bounded reads it.
+ * Refused before anything is launched, the launch counters of both handles unchanged: RELP_ERR_ARGUMENT where
+ * relp_debug_dual_bounded_refusal names the plan of either handle, where a handle holds the bounds of its LP as rows
+ * (options.implicit_bounds = 0 on an LP with a bound), for a parent on another device and for a pair outside the relation
+ * (relp_debug_dual_bounded_inherit_refusal; the row or column is named); RELP_ERR_STATE for a parent without a loaded LP, a parent
+ * without basis and inverse, and parent == child.  The parent is only read.
+ * relp_solve_dual_bounded_from is relp_solve_dual_bounded with this start.  relp_get_record_json: "dual_start" and its companions as
+ * after relp_begin_dual_from, "dual_bounded" as after relp_begin_dual_bounded, and "dual_inherit_complemented" / "dual_inherit_moved":
+ * the inherited positions whose column the two handles hold with opposite signs, and those with src[i] != i (both 0 after any other
+ * start). */
+int32_t relp_begin_dual_bounded_from(relp_handle* child, const relp_handle* parent, const int32_t* basis_columns);
+int32_t relp_solve_dual_bounded_from(relp_handle* child, const relp_handle* parent, const int32_t* basis_columns, relp_result* result);
+/* Host only, the protocol and the arguments of relp_debug_dual_inherit_refusal, both bases as bases of the formulation: the empty
+ * string, or relp_debug_dual_bounded_refusal of either model, or the relation above with the row or column named. */
+int32_t relp_debug_dual_bounded_inherit_refusal(const relp_model* parent, const relp_model* child, const int32_t* parent_basis,
+                                                const int32_t* basis_columns, const relp_options* options, char* buffer, int32_t capacity,
+                                                int32_t* length);
 
 /* The long-step (bound-flipping) ratio test of that loop, a switch on the handle (relp_options has no field for it): `on` = 1 or 0,
  * off on a new handle; any other value is RELP_ERR_ARGUMENT, a null handle answers as relp_begin_dual does.  It holds until changed

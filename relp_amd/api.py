@@ -205,6 +205,8 @@ SYMBOLS = [
     "relp_begin_dual_bounded", "relp_solve_dual_bounded", "relp_debug_dual_bounded_refusal",
     # ... with the long-step (bound-flipping) ratio test (dual_long_step_kernel)
     "relp_set_dual_long_step",
+    # ... started from the parent's inverse between two LPs held on implicit bounds (dual_inherit_mapped_kernel)
+    "relp_begin_dual_bounded_from", "relp_solve_dual_bounded_from", "relp_debug_dual_bounded_inherit_refusal",
 ]
 
 
@@ -547,6 +549,26 @@ class Model:
             raise RelpError(status, buf.value.decode())
         return buf.value.decode()
 
+    def dual_bounded_inherit_refusal(self, parent_model, parent_basis, basis, **options):
+        """Why ``Solver(**options).begin_dual_bounded_from`` would refuse to start this model with ``basis`` from a handle that holds
+        ``parent_model`` at ``parent_basis`` -- both bases of the formulation, bound rows included --, in words that name the row or
+        column; ``""`` if it takes the pair (``relp_debug_dual_bounded_inherit_refusal``).  Covers ``dual_bounded_refusal`` of either
+        model's plan.  Host only."""
+        opts = default_options(**options)
+        parent_arr = np.ascontiguousarray(parent_basis, dtype=np.int32)
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        if len(parent_arr) != parent_model.nr_rows or len(arr) != self.nr_rows:
+            raise ValueError("a basis has one column per row: %d for %d rows of the parent, %d for %d rows of this model" % (
+                len(parent_arr), parent_model.nr_rows, len(arr), self.nr_rows))
+        args = (parent_model._h, self._h, _ptr(parent_arr, C.c_int32), _ptr(arr, C.c_int32), C.byref(opts))
+        length = C.c_int32()
+        lib().relp_debug_dual_bounded_inherit_refusal(*args, None, 0, C.byref(length))
+        buf = C.create_string_buffer(length.value + 1)
+        status = lib().relp_debug_dual_bounded_inherit_refusal(*args, buf, length.value + 1, C.byref(length))
+        if status != OK:
+            raise RelpError(status, buf.value.decode())
+        return buf.value.decode()
+
     def pivot_element_indices(self):
         count = C.c_int32()
         rows = np.zeros(self.nr_rows, dtype=np.int32)
@@ -807,6 +829,26 @@ class Solver:
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_bounded(self._h, _ptr(arr, C.c_int32), C.byref(result)))
+        return result
+
+    def begin_dual_bounded_from(self, parent, basis):
+        """``begin_dual_bounded`` with the inverse written from the one ``parent`` holds (``relp_begin_dual_bounded_from``): ``parent``
+        is another ``Solver`` on the same device, on implicit bounds too, whose LP this one differs from in bounds, costs and
+        right-hand sides and extends by constraint rows; ``basis`` is the parent's ``basis()`` in this LP's columns plus the slack of
+        every row the formulation gained.  The parent may hold its basis at any positions and any of its columns complemented; it is
+        only read.  ``RelpError`` where a plan, the parent's state or the relation (``Model.dual_bounded_inherit_refusal``) is refused,
+        before anything is launched.  ``record()``: ``"dual_start"``, ``"dual_inherit_complemented"``, ``"dual_inherit_moved"``."""
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        self._check(lib().relp_begin_dual_bounded_from(self._h, parent._h, _ptr(arr, C.c_int32)))
+
+    def solve_dual_bounded_from(self, parent, basis, long_step=None):
+        """``solve_dual_bounded`` with the start of ``begin_dual_bounded_from``; returns ``Result``
+        (``relp_solve_dual_bounded_from``).  ``long_step`` as ``solve_dual_bounded`` takes it."""
+        if long_step is not None:
+            self.set_dual_long_step(long_step)
+        arr = np.ascontiguousarray(basis, dtype=np.int32)
+        result = Result()
+        self._check(lib().relp_solve_dual_bounded_from(self._h, parent._h, _ptr(arr, C.c_int32), C.byref(result)))
         return result
 
     def iterate_dual(self, count):

@@ -776,6 +776,7 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     if (sv.dual_start_residual() >= 0.0) out << sv.dual_start_residual();
     else out << "null";
     out << ", \"dual_bounded\": " << (sv.dual_bounded() ? "true" : "false");
+    out << ", \"dual_inherit_complemented\": " << sv.dual_inherit_complemented() << ", \"dual_inherit_moved\": " << sv.dual_inherit_moved();
     out << ", \"dual_long_step\": " << (sv.dual_long_step() ? "true" : "false") << ", \"dual_flips\": " << sv.dual_flips()
         << ", \"dual_long_step_skipped\": " << sv.dual_long_step_skipped();
     out << ", \"dual_pricing\": \"" << (h->options.dual_pricing == RELP_DUAL_PRICING_STEEPEST_EDGE ? "steepest_edge" : "infeasibility") << "\"";
@@ -934,6 +935,20 @@ int32_t relp_solve_dual_from(relp_handle* h, const relp_handle* parent, const in
     return guarded(h, [&] {
         h->solver->last_error.clear();
         h->solver->solve_dual_from(*parent->solver, basis_columns, result);
+        if (!h->solver->last_error.empty()) h->error = h->solver->last_error;  // (as relp_solve_dual)
+    });
+}
+int32_t relp_begin_dual_bounded_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns) {
+    REQUIRE_LOADED(h);
+    if (!parent || !parent->solver || !basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] { h->solver->begin_dual_bounded_from(*parent->solver, basis_columns); });
+}
+int32_t relp_solve_dual_bounded_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns, relp_result* result) {
+    REQUIRE_LOADED(h);
+    if (!parent || !parent->solver || !basis_columns) return RELP_ERR_ARGUMENT;
+    return guarded(h, [&] {
+        h->solver->last_error.clear();
+        h->solver->solve_dual_bounded_from(*parent->solver, basis_columns, result);
         if (!h->solver->last_error.empty()) h->error = h->solver->last_error;  // (as relp_solve_dual)
     });
 }
@@ -1175,25 +1190,28 @@ int32_t relp_debug_dual_refusal(const relp_model* model, const relp_options* opt
 int32_t relp_debug_dual_bounded_refusal(const relp_model* model, const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
     return debug_plan_refusal(dual_bounded_refusal, model, options, buffer, capacity, length);
 }
-int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_model* child, const int32_t* parent_basis, const int32_t* basis_columns,
-                                        const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+// relp_debug_dual_inherit_refusal and relp_debug_dual_bounded_inherit_refusal: the plan of either LP first, as the start asks, then the relation
+static int32_t debug_inherit_refusal(bool bounded, const relp_model* parent, const relp_model* child, const int32_t* parent_basis, const int32_t* basis_columns,
+                                     const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
     relp_options o;
     if (!parent || !child || !parent_basis || !basis_columns || adopt_options(options, &o) != RELP_OK) return RELP_ERR_ARGUMENT;
     int32_t status = RELP_OK;
     std::string text;
     try {
-        for (const relp_model* model : {parent, child}) {  // the plan of either LP first, as Solver::begin_dual_from asks
+        for (const relp_model* model : {parent, child}) {
             const MatrixData& md = model->form.data;
             const DeviceColumns cols = device_columns(md, implicit_bounds_apply(o, md));
-            text = dual_refusal(plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names));
+            const KernelPath plan = plan_kernel_path(o, md, cols, DeviceMatrix(cols, md), &model->form.column_names);
+            text = bounded ? dual_bounded_refusal(plan) : dual_refusal(plan);
+            if (text.empty() && bounded && !plan.bounded && md.nr_variable_bounds() > 0)
+                text = "its upper bounds are rows of the device LP (implicit_bounds = 0): the relation is one of LPs held on implicit bounds";
             if (!text.empty()) {
                 text = (model == parent ? "the parent's plan: " : "the child's plan: ") + text;
                 break;
             }
         }
-        if (text.empty())
-            text = dual_inherit_refusal(parent->form, child->form, std::vector<int>(parent_basis, parent_basis + parent->form.data.nr_rows()),
-                                        std::vector<int>(basis_columns, basis_columns + child->form.data.nr_rows()));
+        const std::vector<int> from(parent_basis, parent_basis + parent->form.data.nr_rows()), to(basis_columns, basis_columns + child->form.data.nr_rows());
+        if (text.empty()) text = bounded ? dual_bounded_inherit_refusal(parent->form, child->form, from, to) : dual_inherit_refusal(parent->form, child->form, from, to);
     } catch (const std::invalid_argument& e) {  // (a load that would itself be refused: its message)
         text = e.what();
         status = RELP_ERR_ARGUMENT;
@@ -1208,6 +1226,14 @@ int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_mod
         buffer[nbytes] = 0;
     }
     return status;
+}
+int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_model* child, const int32_t* parent_basis, const int32_t* basis_columns,
+                                        const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+    return debug_inherit_refusal(false, parent, child, parent_basis, basis_columns, options, buffer, capacity, length);
+}
+int32_t relp_debug_dual_bounded_inherit_refusal(const relp_model* parent, const relp_model* child, const int32_t* parent_basis, const int32_t* basis_columns,
+                                                const relp_options* options, char* buffer, int32_t capacity, int32_t* length) {
+    return debug_inherit_refusal(true, parent, child, parent_basis, basis_columns, options, buffer, capacity, length);
 }
 int32_t relp_debug_stamps(relp_handle* h, uint64_t* out64) {
     REQUIRE_LOADED(h);

@@ -759,8 +759,66 @@ __global__ void __launch_bounds__(DI_THREADS) dual_inherit_kernel(DeviceLP lp, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The same start between two LPs held on implicit upper bounds (dual_bounded_inherit_refusal, dual_inherit.hpp): the child's basic
+// columns are the parent's and the slack of each appended row, but at other positions and some of them complemented on one side only,
+// so the identity map of dual_inherit_kernel becomes (src, sg): position i of the child holds what the parent holds at position
+// src[i] >= 0, with the sign sg[i] = sgn_parent * sgn_child between the two held forms, or the slack of new row m + rho where
+// src[i] = -1 - rho.  Row i of the child's inverse is sg[i] times row src[i] of the parent's, the row of a new slack is the border
+// row -(sum v sgn_col inv_child[pos[col], j]) / s_r over the entries of its row in CSR order whose column is basic at an inherited
+// position (sgn_col from the child's `flipped`, +1 after place_basis, and s_r the signed entry of the slack itself).  A wave per column
+// j of the child's inverse, lanes over positions; the gather through src stays inside column j of the parent (8-byte accesses: neither
+// leading dimension need be even).  A fixed order, no atomics; every entry of the child's first buffer is written.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DI_THREADS) dual_inherit_mapped_kernel(DeviceLP lp, const double* __restrict__ parent, int m, int parent_ld,
+                                                                         const int* __restrict__ src, const int* __restrict__ sg) {
+    const int m_child = lp.m, ld = lp.ld;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int j = blockIdx.x * (DI_THREADS / WAVE) + threadIdx.x / WAVE;
+    if (j >= m_child) return;
+    double* out = lp.Binv + (size_t)j * ld;
+    if (j < m) {
+        const double* column = parent + (size_t)j * parent_ld;
+        for (int i = lane; i < m_child; i += WAVE) {
+            const int from = src[i];
+            if (from >= 0) {
+                out[i] = (double)sg[i] * column[from];
+                continue;
+            }
+            const int row = m - 1 - from;  // the slack of new row m + rho sits here
+            double sum = 0.0, own = 0.0;
+            const int last = lp.row_start[row + 1];
+            for (int e = lp.row_start[row]; e < last; ++e) {
+                const int c = lp.col_index[e];
+                const int p = lp.pos[c];
+                if (p < 0) continue;
+                const double v = lp.flipped && lp.flipped[c] ? -lp.row_value[e] : lp.row_value[e];
+                if (p == i) own = v;
+                else if (src[p] >= 0) sum += v * ((double)sg[p] * column[src[p]]);  // (what the lane of position p writes, bit for bit)
+            }
+            out[i] = -sum / own;
+        }
+    } else {
+        const int rho = j - m;
+        double own = 0.0;  // (every lane walks the row: the same addresses, one fetch per wave)
+        const int last = lp.row_start[j + 1];
+        for (int e = lp.row_start[j]; e < last; ++e) {
+            const int c = lp.col_index[e];
+            const int p = lp.pos[c];
+            if (p >= 0 && src[p] == -1 - rho) own = lp.flipped && lp.flipped[c] ? -lp.row_value[e] : lp.row_value[e];
+        }
+        const double diagonal = 1.0 / own;
+        for (int i = lane; i < m_child; i += WAVE) out[i] = src[i] == -1 - rho ? diagonal : 0.0;
+    }
+}
+
 }  // namespace
 
+void launch_dual_inherit_mapped(const DeviceLP& child, const double* parent_inverse, int parent_m, int parent_ld, const int* src, const int* sg, hipStream_t s) {
+    const int per_block = DI_THREADS / WAVE;
+    hipLaunchKernelGGL(dual_inherit_mapped_kernel, dim3((child.m + per_block - 1) / per_block), dim3(DI_THREADS), 0, s, child, parent_inverse, parent_m, parent_ld,
+                       src, sg);
+}
 void launch_dual_inherit(const DeviceLP& child, const double* parent_inverse, int parent_m, int parent_ld, hipStream_t s) {
     const int per_block = DI_THREADS / WAVE;
     hipLaunchKernelGGL(dual_inherit_kernel, dim3((child.m + per_block - 1) / per_block), dim3(DI_THREADS), 0, s, child, parent_inverse, parent_m, parent_ld);

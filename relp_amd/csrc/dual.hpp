@@ -78,4 +78,11 @@ int launch_dual_weights(const DeviceLP& d, const DualBuffers& b, bool chained, h
 // the child's first buffer: the parent's columns, the child.m - parent_m border rows, the scaled unit columns of the new slacks.
 void launch_dual_inherit(const DeviceLP& child, const double* parent_inverse, int parent_m, int parent_ld, hipStream_t s);
 
+// The same between two LPs held on implicit upper bounds (Solver::begin_dual_bounded_from; dual_bounded_inherit_refusal): `src` and
+// `sg` are device arrays of child.m ints.  src[i] in [0, parent_m): the child's position i holds the column the parent holds at that
+// position, sg[i] = +-1 the product of the signs the two held forms give it; src[i] = -1 - rho, rho in [0, child.m - parent_m), each
+// once: the slack of new row parent_m + rho (sg[i] is not read).  `child` has pos and flipped uploaded for its basis.  Writes every
+// entry of the child's first buffer; reads the parent's inverse only (the caller checks the ranges: the kernel trusts them).
+void launch_dual_inherit_mapped(const DeviceLP& child, const double* parent_inverse, int parent_m, int parent_ld, const int* src, const int* sg, hipStream_t s);
+
 }  // namespace relp

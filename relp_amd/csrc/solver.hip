@@ -93,6 +93,8 @@ void Solver::free_device() {
     dual_long_active_ = false;
     dual_flips_ = dual_long_skipped_ = 0;
     dual_start_ = "none";
+    d_inherit_map_ = nullptr;
+    dual_inherit_complemented_ = dual_inherit_moved_ = 0;
 }
 
 void Solver::reset_stats() { stats_ = relp_stats{}; }
@@ -1021,48 +1023,12 @@ void Solver::place_basis(const int* basis_columns) {
     } else {
         // Implicit bounds: `basis_columns` is a basis of the reference's formulation (one column per row of MatrixData).  A
         // bounded variable whose bound slack is NOT basic sits at its bound: non-basic and complemented on the device; with
-        // the slack basic it is basic here exactly when it is basic there.
+        // the slack basic it is basic here exactly when it is basic there (reduce_bounded_basis, dual_inherit.hpp: the relation of
+        // begin_dual_bounded_from reads the same reduction).
         const MatrixData& md = form_.data;
-        const int rows_full = md.nr_rows(), cols_full = md.nr_columns(), n_dev = md.col_end[3];
-        std::vector<int> row_of(cols_full, -1);
-        std::vector<int> artificial_row_of(d_.n_art, -1);
-        for (int i = 0; i < rows_full; ++i) {
-            const int c = basis_columns[i];
-            if (c >= 0) {
-                if (c >= cols_full || row_of[c] >= 0) throw std::invalid_argument("bad basis");
-                row_of[c] = i;
-            } else {
-                const int k = cols_.to_device(c);  // (an artificial's device column is its number)
-                if (k >= d_.n_art || artificial_row_of[k] >= 0) throw std::invalid_argument("bad basis");
-                artificial_row_of[k] = i;
-            }
-        }
-        std::vector<int> flipped(n, 0);
-        auto bound_pair = [&](int variable, int slack) {
-            if (row_of[slack] < 0) {
-                if (row_of[variable] < 0) throw std::invalid_argument("bad basis: neither a bounded variable nor its bound slack is basic");
-                flipped[d_.n_art + variable] = 1;  // at its upper bound
-                row_of[variable] = -2;             // not basic on the device
-            }
-        };
-        for (int k2 = 0; k2 < (int)md.bound_to_variable.size(); ++k2) bound_pair(md.bound_to_variable[k2], md.col_end[3] + k2);
-        for (int k2 = 0; k2 < md.nr_range; ++k2) bound_pair(md.col_end[0] + k2, md.col_end[4] + k2);
-        std::vector<int> device_basic;  // device column, preferred row
-        std::vector<int> wanted_row;
-        for (int k = 0; k < d_.n_art; ++k)
-            if (artificial_row_of[k] >= 0) { device_basic.push_back(k); wanted_row.push_back(artificial_row_of[k]); }
-        for (int c = 0; c < n_dev; ++c)
-            if (row_of[c] >= 0) { device_basic.push_back(d_.n_art + c); wanted_row.push_back(row_of[c]); }
-        if ((int)device_basic.size() != m) throw std::invalid_argument("bad basis: it does not reduce to a basis of the constraint rows");
-        std::fill(basis.begin(), basis.end(), -1);
-        std::vector<int> homeless;
-        for (size_t t = 0; t < device_basic.size(); ++t) {
-            if (wanted_row[t] < m && basis[wanted_row[t]] < 0) basis[wanted_row[t]] = device_basic[t];
-            else homeless.push_back(device_basic[t]);
-        }
-        size_t next = 0;
-        for (int i = 0; i < m; ++i)
-            if (basis[i] < 0) basis[i] = homeless[next++];
+        ReducedBasis reduced = reduce_bounded_basis(md, d_.n_art, basis_columns);
+        basis = std::move(reduced.basis);
+        std::vector<int> flipped = std::move(reduced.flipped);
         for (int j = 0; j < n; ++j) {
             if (zero_width_[j]) flipped[j] = 0;  // both bounds are the same point
             pos[j] = zero_width_[j] ? -3 : (flipped[j] ? -2 : -1);
@@ -1402,6 +1368,7 @@ void Solver::start_dual_from_scratch(const int* basis_columns, bool bounded_entr
     const double t0 = now_seconds();
     const long long gemms_before = polish_gemms_;
     dual_start_ = "none";
+    dual_inherit_complemented_ = dual_inherit_moved_ = 0;
     set_basis(basis_columns);  // inverse from scratch, x_B, the costs of phase two, -pi; every column of the inverse marked touched
     dual_start_residual_ = -1.0;  // (no guard: the inverse was iterated to its own stopping rule)
     finish_dual_start(basis_columns, "scratch", t0, gemms_before);
@@ -1435,6 +1402,7 @@ void Solver::begin_dual_from(const Solver& parent, const int* basis_columns) {
     const double t0 = now_seconds();
     const long long gemms_before = polish_gemms_;
     dual_start_ = "none";
+    dual_inherit_complemented_ = dual_inherit_moved_ = 0;
     place_basis(basis_columns);
     if (!ev_parent_) RELP_HIP(hipEventCreateWithFlags(&ev_parent_, hipEventDisableTiming));
     RELP_HIP(hipEventRecord(ev_parent_, parent.stream_));  // whatever the parent still has on its way to its inverse comes first
@@ -1453,6 +1421,92 @@ void Solver::begin_dual_from(const Solver& parent, const int* basis_columns) {
     RELP_HIP(hipStreamSynchronize(stream_));  // the parent's inverse has been read: the caller may use the parent again
     set_phase(2);
     finish_dual_start(basis_columns, polish_rebuilt_ ? "scratch_after_inherit" : "inherited", t0, gemms_before);
+}
+
+void Solver::held_state(std::vector<int>* basis, std::vector<int>* pos, std::vector<int>* flipped) const {
+    basis->resize(d_.m);
+    pos->resize(d_.n);
+    flipped->assign(d_.n, 0);
+    RELP_HIP(hipMemcpyAsync(basis->data(), d_.basis, d_.m * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    RELP_HIP(hipMemcpyAsync(pos->data(), d_.pos, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    if (path_.bounded) RELP_HIP(hipMemcpyAsync(flipped->data(), d_.flipped, d_.n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    RELP_HIP(hipStreamSynchronize(stream_));
+}
+
+// begin_dual_from between two LPs held on implicit upper bounds, step by step.  The child of a branching step keeps its parent's
+// constraint rows, so its basis matrix is the parent's up to the order of the positions and the sign of the columns one side holds
+// complemented: the relation (dual_bounded_inherit_refusal) names the parent's column behind every position, the parent's device state
+// its position and sign there.  Everything that can refuse does so before the first launch.
+void Solver::begin_dual_bounded_from(const Solver& parent, const int* basis_columns) {
+    if (!loaded_) throw std::runtime_error("no LP loaded");
+    if (&parent == this) throw std::runtime_error("begin_dual_bounded_from: the parent is this handle itself (the child is loaded on a handle of its own)");
+    if (!parent.loaded_) throw std::runtime_error("begin_dual_bounded_from: the parent handle has no LP loaded");
+    const std::string parent_plan = dual_bounded_refusal(parent.path_);
+    if (!parent_plan.empty()) throw std::invalid_argument("begin_dual_bounded_from: the parent's plan: " + parent_plan);
+    check_dual_start(basis_columns, true);
+    for (const Solver* handle : {&parent, (const Solver*)this})
+        if (!handle->path_.bounded && handle->form_.data.nr_variable_bounds() > 0)
+            throw std::invalid_argument(std::string("begin_dual_bounded_from: ") + (handle == this ? "this handle" : "the parent") +
+                                        " holds its upper bounds as rows of the device LP (implicit_bounds = 0): the relation is one of LPs held on implicit bounds");
+    if (parent.opt_.device != opt_.device)
+        throw std::invalid_argument("begin_dual_bounded_from: the parent is on device " + std::to_string(parent.opt_.device) + ", this handle on device " +
+                                    std::to_string(opt_.device) + ": the inverse is inherited on one device");
+    if (parent.phase_ == 0)
+        throw std::runtime_error("begin_dual_bounded_from: the parent has no basis and inverse yet (a solve, set_basis or solve_dual_bounded on it comes first)");
+    RELP_HIP(hipSetDevice(opt_.device));
+    // the parent's basis of its formulation and where it holds each column, off its device state (copies: nothing is launched)
+    std::vector<int> parent_basis, parent_pos, parent_flipped;
+    parent.held_state(&parent_basis, &parent_pos, &parent_flipped);
+    const std::vector<int> parent_formulation = parent.path_.bounded ? parent.explicit_basis(parent_basis, parent_pos) : parent.cols_.to_provider(parent_basis);
+    std::vector<int> source;
+    const std::string relation = dual_bounded_inherit_refusal(parent.form_, form_, parent_formulation,
+                                                              std::vector<int>(basis_columns, basis_columns + form_.data.nr_rows()), &source);
+    if (!relation.empty()) throw std::invalid_argument("begin_dual_bounded_from: " + relation);
+    const int m = d_.m, m_parent = parent.d_.m;
+    std::vector<int> map(2 * (size_t)m, 1);  // src | sg
+    std::vector<int> parent_column(m, -1);
+    for (int i = 0; i < m; ++i) {
+        map[i] = source[i];
+        if (source[i] < 0) continue;
+        parent_column[i] = parent.cols_.to_device(source[i]);
+        map[i] = parent_pos[parent_column[i]];
+        if (map[i] < 0 || map[i] >= m_parent)
+            throw std::runtime_error("begin_dual_bounded_from: column " + std::to_string(source[i]) + " of the parent is not basic on its device");
+    }
+    const double t0 = now_seconds();
+    const long long gemms_before = polish_gemms_;
+    dual_start_ = "none";
+    dual_inherit_complemented_ = dual_inherit_moved_ = 0;
+    place_basis(basis_columns);
+    // the signs: the parent's as its walk left them; this handle's as place_basis has just written them (+1 on every basic column)
+    std::vector<int> basis, pos, flipped;
+    held_state(&basis, &pos, &flipped);
+    long long complemented = 0, moved = 0;
+    for (int i = 0; i < m; ++i) {
+        if (map[i] < 0) continue;
+        map[m + i] = (parent_flipped[parent_column[i]] ? -1 : 1) * (flipped[basis[i]] ? -1 : 1);
+        complemented += map[m + i] < 0;
+        moved += map[i] != i;
+    }
+    if (!d_inherit_map_) d_inherit_map_ = device_alloc<int>(2 * (size_t)m);
+    upload_vec(d_inherit_map_, map, stream_);
+    if (!ev_parent_) RELP_HIP(hipEventCreateWithFlags(&ev_parent_, hipEventDisableTiming));
+    RELP_HIP(hipEventRecord(ev_parent_, parent.stream_));  // whatever the parent still has on its way to its inverse comes first
+    RELP_HIP(hipStreamWaitEvent(stream_, ev_parent_, 0));
+    stats_.launches += 2;
+    launch_dual_inherit_mapped(d_, parent.d_.Binv, m_parent, parent.d_.ld, d_inherit_map_, d_inherit_map_ + m, stream_);
+    launch_mark_all_touched(d_, stream_);  // no column of an inherited inverse is known to be a unit vector
+    reset_basis_counters();
+    // the guard of begin_dual_from, with its threshold
+    RELP_HIP(hipMemcpyAsync(d_.cost, d_.cost2, d_.n * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+    polish_first_residual_ = -1.0;
+    polish(true, true);
+    dual_start_residual_ = polish_first_residual_;
+    RELP_HIP(hipStreamSynchronize(stream_));  // the parent's inverse and the map have been read: the caller may use the parent again
+    set_phase(2);
+    finish_dual_start(basis_columns, polish_rebuilt_ ? "scratch_after_inherit" : "inherited", t0, gemms_before);
+    dual_inherit_complemented_ = complemented;
+    dual_inherit_moved_ = moved;
 }
 
 void Solver::finish_dual_start(const int* basis_columns, const char* how, double t0, long long gemms_before) {
@@ -1608,6 +1662,7 @@ long long Solver::iterate_dual(long long count, int* stop_reason) {
 void Solver::solve_dual(const int* basis_columns, relp_result* result) { run_dual(nullptr, basis_columns, result); }
 void Solver::solve_dual_from(const Solver& parent, const int* basis_columns, relp_result* result) { run_dual(&parent, basis_columns, result); }
 void Solver::solve_dual_bounded(const int* basis_columns, relp_result* result) { run_dual(nullptr, basis_columns, result, true); }
+void Solver::solve_dual_bounded_from(const Solver& parent, const int* basis_columns, relp_result* result) { run_dual(&parent, basis_columns, result, true); }
 
 void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_result* result, bool bounded_entry) {
     if (!loaded_) throw std::runtime_error("no LP loaded");
@@ -1616,7 +1671,8 @@ void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_resul
     exact_objective.clear();
     exact_primal.reset();
     exact_witnesses.reset();
-    if (parent) begin_dual_from(*parent, basis_columns);
+    if (parent && bounded_entry) begin_dual_bounded_from(*parent, basis_columns);
+    else if (parent) begin_dual_from(*parent, basis_columns);
     else start_dual_from_scratch(basis_columns, bounded_entry);
     const long long cap = opt_.max_pivots > 0 ? opt_.max_pivots : 200LL * (d_.m + d_.n) + 100000;
     int kind = RELP_RESULT_NONE;

@@ -69,6 +69,18 @@ public:
     void begin_dual_bounded(const int* basis_columns);
     void solve_dual_bounded(const int* basis_columns, relp_result* result);
     bool dual_bounded() const { return dual_bounded_; }  // the last start ran the loop with implicit upper bounds
+    // begin_dual_bounded with the inverse written from the one `parent` holds, as begin_dual_from does it for plans without implicit
+    // bounds: the relation is dual_bounded_inherit_refusal over the two formulations' bases (the parent's read off its device state),
+    // the kernel dual_inherit_mapped_kernel, which takes the positions and the complemented columns of either side as they are.  The
+    // refusals come before anything is launched, with the classes of begin_dual_from: std::invalid_argument for dual_bounded_refusal of
+    // either plan, a plan that holds its bounds as rows (implicit_bounds = 0 on an LP with a bound), a parent on another device and a
+    // non-empty relation; std::runtime_error for a parent without LP, without basis and inverse, or this handle.  The same guard.
+    void begin_dual_bounded_from(const Solver& parent, const int* basis_columns);
+    void solve_dual_bounded_from(const Solver& parent, const int* basis_columns, relp_result* result);
+    // Of the last start (0 after any other than begin_dual_bounded_from): inherited positions whose column the two handles hold with
+    // opposite signs, and inherited positions that are not the parent's.
+    long long dual_inherit_complemented() const { return dual_inherit_complemented_; }
+    long long dual_inherit_moved() const { return dual_inherit_moved_; }
     // The long-step (bound-flipping) ratio test of that loop (dual.hpp: launch_dual_long_step), off by default.  The switch holds until
     // changed and is read by begin_dual_bounded / solve_dual_bounded; while it is on, begin_dual, solve_dual and the _from pair refuse
     // (std::invalid_argument).  On a bounded-entry plan without bounds there is no boxed column and it changes nothing.
@@ -213,6 +225,10 @@ private:
     double polish_first_residual_ = -1.0;   // of the last polish that measured one: its first reading ...
     bool polish_rebuilt_ = false;           // ... and whether it gave up on the quadratic step and inverted from scratch
     hipEvent_t ev_parent_ = nullptr;        // begin_dual_from: recorded on the parent's stream, waited for on this one
+    int* d_inherit_map_ = nullptr;          // begin_dual_bounded_from: [2 m] src | sg of dual_inherit_mapped_kernel, allocated by its first call
+    long long dual_inherit_complemented_ = 0, dual_inherit_moved_ = 0;
+    // the basis, pos and (a bounded plan: else zeros) flipped of the device state, read behind the handle's stream
+    void held_state(std::vector<int>* basis, std::vector<int>* pos, std::vector<int>* flipped) const;
     std::vector<double> net_host_solve(const HostTree& t, bool transposed, const std::vector<double>& v) const;  // B^-1 v or v' B^-1
     CertifyScratch certify_scratch_;
     // spanning-forest carry (network_carry.hip)

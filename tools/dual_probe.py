@@ -39,7 +39,16 @@ device time per dual pivot.  ``--every N`` puts a bound on every N-th structural
 tests), ``--tight N`` tightens N bounds (8 unless given): with few bounds the walks of the two rules coincide and the difference of
 the two device times is what a pivot with the switch on and no flip costs.
 
-    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded [--long-step]]
+``--bounded --start``: how the loop on implicit bounds starts, the columns of ``--start`` for the children of ``--bounded`` and, at each
+size, for a pure branch (no cut, 8 tightened bounds: the child has the parent's rows).  The parent's handle stays open beside the
+child's, solved cold on the device, so it holds its basis at its own positions and some basic columns complemented.
+  begin_dual_bounded        from scratch: ``dual_start_seconds`` and ``dual_start_gemms``
+  begin_dual_bounded_from   from the parent's inverse: the same two, the guard's residual, and how many inherited positions were
+                            complemented on one side only / not the parent's (``dual_inherit_complemented``, ``dual_inherit_moved``)
+  solve_dual_bounded, solve_dual_bounded_from   the whole certified call, and how much of it the start took
+``--traced`` as with ``--start``: the two begin calls only, plain launches, for a run under rocprofv3 --kernel-trace.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded [--long-step | --start [--traced]]]
 """
 import argparse
 import os
@@ -257,6 +266,55 @@ def bounded_probe(m, decimal, n_cuts, n_tight=8):
     assert len(objectives) <= 1, objectives  # both formulations end at the same exact optimum
 
 
+def bounded_start_probe(m, decimal, n_cuts, n_tight=8, traced=False):
+    """One child of the table "the inherited start on implicit bounds" of DESIGN.md section 10.  ``n_cuts = 0``: a pure branch."""
+    import dual_bounded_lps
+    case = dual_bounded_lps.BoundedCase(m, 1000 + m, n_cuts, n_tight, decimal=decimal, every=1)
+    options = dict(certify=1, implicit_bounds=1, use_graph=0) if traced else dict(certify=1, implicit_bounds=1)
+    parent = relp_amd.Solver(**options).load_model(case.parent.model)
+    assert parent.solve_relaxation().certified
+    child, basis, _, branches = case.child(parent.basis(), parent.solution_exact())
+    assert child.m == m + n_cuts
+    solver = relp_amd.Solver(**options).load_model(child.model)
+    label = "m = %d + %d cuts, %d tightened bounds, %s" % (m, n_cuts, len(branches), "decimal" if decimal else "integer")
+    objectives = set()
+
+    def solve(call):
+        def run():
+            started = time.perf_counter()
+            result = call()
+            wall = 1e3 * (time.perf_counter() - started)
+            assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+            objectives.add(solver.objective_exact())
+            return wall, 1e3 * solver.record()["dual_start_seconds"], solver.dual_pivots()
+        return run
+
+    def begin(call):
+        def run():
+            call()
+            record = solver.record()
+            return (1e3 * record["dual_start_seconds"], record["dual_start_gemms"], record["dual_start_residual"] or 0.0,
+                    record["dual_inherit_complemented"], record["dual_inherit_moved"])
+        return run
+
+    (scratch_ms, scratch_lo, scratch_hi), (scratch_gemms, _, _), _, _, _ = spread_of(begin(lambda: solver.begin_dual_bounded(basis)))
+    (from_ms, from_lo, from_hi), (from_gemms, _, _), (residual, _, _), (complemented, _, _), (moved, _, _) = spread_of(
+        begin(lambda: solver.begin_dual_bounded_from(parent, basis)))
+    how = solver.record()["dual_start"]
+    text = "%s | begin_dual_bounded %.2f ms (%.2f .. %.2f), %d GEMMs | begin_dual_bounded_from (%s) %.2f ms (%.2f .. %.2f), %d GEMMs, guard's residual %.1e, %d complemented, %d moved" % (
+        label, scratch_ms, scratch_lo, scratch_hi, scratch_gemms, how, from_ms, from_lo, from_hi, from_gemms, residual, complemented, moved)
+    if not traced:
+        (cold_ms, cold_lo, cold_hi), (cold_start, _, _), (cold_pivots, _, _) = spread_of(solve(lambda: solver.solve_dual_bounded(basis)))
+        (warm_ms, warm_lo, warm_hi), (warm_start, _, _), (warm_pivots, _, _) = spread_of(solve(lambda: solver.solve_dual_bounded_from(parent, basis)))
+        text += (" | solve_dual_bounded %.1f ms (%.1f .. %.1f), of which the start %.1f ms = %.0f %%, %d dual pivots | solve_dual_bounded_from %.1f ms (%.1f .. %.1f), "
+                 "of which the start %.2f ms = %.1f %%, %d dual pivots" % (cold_ms, cold_lo, cold_hi, cold_start, 100.0 * cold_start / cold_ms, cold_pivots,
+                                                                       warm_ms, warm_lo, warm_hi, warm_start, 100.0 * warm_start / warm_ms, warm_pivots))
+        assert len(objectives) == 1, objectives  # either start ends at the same exact optimum
+    print(text, flush=True)
+    solver.close()
+    parent.close()
+
+
 def long_step_probe(m, decimal, n_cuts, n_tight, every):
     """One child of the long-step table of DESIGN.md section 10, a line per ratio test."""
     import dual_bounded_lps
@@ -293,7 +351,8 @@ def main():
     parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
     parser.add_argument("--decimal", action="store_true")
     parser.add_argument("--cuts", type=int, default=0, help="cuts per child (default: those of tests/dual_lps.py)")
-    parser.add_argument("--start", action="store_true", help="only the table of the dual loop's start: 4 and 24 cuts (or --cuts), integer and decimal data")
+    parser.add_argument("--start", action="store_true", help="only the table of the dual loop's start: 4 and 24 cuts (or --cuts), integer and decimal data; "
+                        "with --bounded: the starts on implicit bounds, 24 cuts (or --cuts) and a pure branch")
     parser.add_argument("--traced", action="store_true",
                         help="with --start, for a run under rocprofv3 --kernel-trace (which does not survive the replay of a captured graph: "
                              "tools/profile_r2_maxflow.sh): every handle with plain launches, and begin_dual / begin_dual_from only")
@@ -309,6 +368,12 @@ def main():
         for m in args.sizes:
             for decimal in ([True] if args.decimal else [False, True]):
                 long_step_probe(m, decimal, args.cuts or 24, args.tight, args.every)
+        return
+    if args.bounded and args.start:
+        for m in args.sizes:
+            for n_cuts in ([args.cuts] if args.cuts else [24, 0]):
+                for decimal in ([True] if args.decimal else [False, True]):
+                    bounded_start_probe(m, decimal, n_cuts, args.tight, args.traced)
         return
     if args.bounded:
         for m in args.sizes:
