@@ -951,7 +951,7 @@ int32_t relp_debug_dual_inherit_refusal(const relp_model* parent, const relp_mod
  * relp_iterate_dual, relp_get_dual_pivots, relp_get_dual_weights and the record keys are shared with relp_begin_dual;
  * relp_get_record_json adds "dual_bounded": true where the last start ran the loop on implicit bounds.  A finite optimum is
  * certified as a cold solve with implicit bounds is; RELP_RESULT_INFEASIBLE comes back with certified = 0 and the relp_last_error of
- * relp_solve_dual.  relp_begin_dual, relp_solve_dual, relp_begin_dual_from and relp_solve_dual_from keep refusing a plan with
+ * relp_solve_dual (relp_set_dual_farkas below: proved instead).  relp_begin_dual, relp_solve_dual, relp_begin_dual_from and relp_solve_dual_from keep refusing a plan with
  * implicit bounds; the inherited start of such a plan is relp_begin_dual_bounded_from below. */
 int32_t relp_solve_dual_bounded(relp_handle* handle, const int32_t* basis_columns, relp_result* result);
 int32_t relp_begin_dual_bounded(relp_handle* handle, const int32_t* basis_columns);
@@ -1000,6 +1000,26 @@ int32_t relp_debug_dual_bounded_inherit_refusal(const relp_model* parent, const 
  * the dual pivots since that start) and "dual_long_step_skipped" (pivots whose boxed candidates, more than 2048, did not fit the
  * kernel: the plain rule there). */
 int32_t relp_set_dual_long_step(relp_handle* handle, int32_t on);
+
+/* The exact proof of an INFEASIBLE child, a switch on the handle like the one above: `on` = 1 or 0, off on a new handle; any other
+ * value is RELP_ERR_ARGUMENT, a null handle answers as relp_set_dual_long_step does.  It holds until changed and is read by
+ * relp_solve_dual, relp_solve_dual_from, relp_solve_dual_bounded and relp_solve_dual_bounded_from; it takes effect only with
+ * options.certify != 0 and where the loop ends dual unbounded (RELP_RESULT_INFEASIBLE).  With it off, or with options.certify = 0,
+ * that verdict comes back with certified = 0 and the relp_last_error it always had, and every launch, result and record key is what
+ * it was.  With it on, row p of the exact inverse of the final basis -- p: the row at which the loop found the dual unbounded; one
+ * transposed p-adic lifting with a unit right-hand side on the kernels of the optimum's certificate -- is checked as a Farkas vector
+ * in exact integers: y = -rho_p, y'a_j <= 0 for every provider column and y'b > 0.  On a handle with options.implicit_bounds = 1 the
+ * basis spans the constraint rows only, and either sign of rho_p is extended over the bound rows in closed form: with r_j = y'a_j
+ * over the constraint rows, the bound row of column j gets -max(0, r_j), a column without a bound must have r_j <= 0, and
+ * y'b = y_c'b_c - sum_j max(0, r_j) u_j must be positive.
+ * Proved: result.certified = 1 with certify_seconds filled, relp_get_objective_exact returns y'b, and
+ * relp_get_witness_exact(RELP_WITNESS_DUAL) returns y by row of the loaded model's standard form (bound rows included), indexed as
+ * the Farkas vector of a cold INFEASIBLE solve; RELP_WITNESS_PRIMAL and RELP_WITNESS_RAY are not defined for this result.  Not proved:
+ * certified = 0 and relp_last_error names the exact inequality that failed (the provider column that prices positive, or "y'b is
+ * not positive"); no exact repair pivots follow.  One more launch (the leaving-row kernel names the row again) precedes the proof.
+ * relp_get_record_json: "dual_farkas" (the switch as the last start read it) and "dual_farkas_row" (the row p the last proof used,
+ * -1 where there was none).  relp_begin_dual / relp_iterate_dual and relp_many do not read the switch. */
+int32_t relp_set_dual_farkas(relp_handle* handle, int32_t on);
 
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);

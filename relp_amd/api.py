@@ -207,6 +207,8 @@ SYMBOLS = [
     "relp_set_dual_long_step",
     # ... started from the parent's inverse between two LPs held on implicit bounds (dual_inherit_mapped_kernel)
     "relp_begin_dual_bounded_from", "relp_solve_dual_bounded_from", "relp_debug_dual_bounded_inherit_refusal",
+    # ... with the exact Farkas proof of an INFEASIBLE child (certify.hip: certify_dual_farkas)
+    "relp_set_dual_farkas",
 ]
 
 
@@ -774,10 +776,22 @@ class Solver:
         self._check(lib().relp_set_basis(self._h, _ptr(arr, C.c_int32)))
 
     # ---- dual simplex from a dual-feasible basis ----------------------------------------------------
-    def solve_dual(self, basis):
+    def set_dual_farkas(self, on):
+        """The exact proof of an INFEASIBLE child, on or off (``relp_set_dual_farkas``; off on a new handle).  It holds until changed;
+        ``solve_dual``, ``solve_dual_from``, ``solve_dual_bounded`` and ``solve_dual_bounded_from`` read it, and it takes effect with
+        ``certify=1`` where the loop ends dual unbounded: the ``Result`` is then ``certified`` with the Farkas vector as
+        ``witness_exact(WITNESS_DUAL)`` (by row of the standard form, bound rows included; ``relp_amd.witness.check_infeasible`` takes
+        it) and ``y'b`` as ``objective_exact()``, or uncertified with the exact inequality that failed in the handle's last error.
+        Off, that verdict comes back uncertified as it always did.  ``record()``: ``"dual_farkas"``, ``"dual_farkas_row"``."""
+        self._check(lib().relp_set_dual_farkas(self._h, int(on)))
+
+    def solve_dual(self, basis, farkas=None):
         """Re-solve the loaded LP from ``basis`` (as ``set_basis`` takes it: the optimal basis of the LP before rows were appended
         or a right-hand side tightened, extended by the slack of each new row) by dual pivots; returns ``Result``
-        (``relp_solve_dual``).  ``RelpError`` where the plan, or the basis, is refused."""
+        (``relp_solve_dual``).  ``RelpError`` where the plan, or the basis, is refused.  ``farkas``: ``set_dual_farkas`` first; ``None``
+        keeps the handle's setting."""
+        if farkas is not None:
+            self.set_dual_farkas(farkas)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual(self._h, _ptr(arr, C.c_int32), C.byref(result)))
@@ -797,9 +811,12 @@ class Solver:
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_begin_dual_from(self._h, parent._h, _ptr(arr, C.c_int32)))
 
-    def solve_dual_from(self, parent, basis):
+    def solve_dual_from(self, parent, basis, farkas=None):
         """``solve_dual`` with the start of ``begin_dual_from``; returns ``Result`` (``relp_solve_dual_from``).  ``record()`` says
-        which start was taken (``"dual_start"``) and what it cost (``"dual_start_seconds"``, ``"dual_start_gemms"``)."""
+        which start was taken (``"dual_start"``) and what it cost (``"dual_start_seconds"``, ``"dual_start_gemms"``).  ``farkas`` as
+        ``solve_dual`` takes it."""
+        if farkas is not None:
+            self.set_dual_farkas(farkas)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_from(self._h, parent._h, _ptr(arr, C.c_int32), C.byref(result)))
@@ -820,12 +837,14 @@ class Solver:
         ``"dual_long_step_skipped"``."""
         self._check(lib().relp_set_dual_long_step(self._h, int(on)))
 
-    def solve_dual_bounded(self, basis, long_step=None):
+    def solve_dual_bounded(self, basis, long_step=None, farkas=None):
         """``solve_dual`` with the start of ``begin_dual_bounded``: the re-solve of a branched child from its parent's basis; returns
         ``Result`` (``relp_solve_dual_bounded``).  ``record()["dual_bounded"]`` says whether the loop ran on implicit bounds.
-        ``long_step``: ``set_dual_long_step`` first; ``None`` keeps the handle's setting."""
+        ``long_step``: ``set_dual_long_step`` first; ``None`` keeps the handle's setting.  ``farkas``: ``set_dual_farkas`` likewise."""
         if long_step is not None:
             self.set_dual_long_step(long_step)
+        if farkas is not None:
+            self.set_dual_farkas(farkas)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_bounded(self._h, _ptr(arr, C.c_int32), C.byref(result)))
@@ -841,11 +860,13 @@ class Solver:
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_begin_dual_bounded_from(self._h, parent._h, _ptr(arr, C.c_int32)))
 
-    def solve_dual_bounded_from(self, parent, basis, long_step=None):
+    def solve_dual_bounded_from(self, parent, basis, long_step=None, farkas=None):
         """``solve_dual_bounded`` with the start of ``begin_dual_bounded_from``; returns ``Result``
-        (``relp_solve_dual_bounded_from``).  ``long_step`` as ``solve_dual_bounded`` takes it."""
+        (``relp_solve_dual_bounded_from``).  ``long_step`` and ``farkas`` as ``solve_dual_bounded`` takes them."""
         if long_step is not None:
             self.set_dual_long_step(long_step)
+        if farkas is not None:
+            self.set_dual_farkas(farkas)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_bounded_from(self._h, parent._h, _ptr(arr, C.c_int32), C.byref(result)))

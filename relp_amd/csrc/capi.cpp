@@ -779,6 +779,7 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     out << ", \"dual_inherit_complemented\": " << sv.dual_inherit_complemented() << ", \"dual_inherit_moved\": " << sv.dual_inherit_moved();
     out << ", \"dual_long_step\": " << (sv.dual_long_step() ? "true" : "false") << ", \"dual_flips\": " << sv.dual_flips()
         << ", \"dual_long_step_skipped\": " << sv.dual_long_step_skipped();
+    out << ", \"dual_farkas\": " << (sv.dual_farkas() ? "true" : "false") << ", \"dual_farkas_row\": " << sv.dual_farkas_row();
     out << ", \"dual_pricing\": \"" << (h->options.dual_pricing == RELP_DUAL_PRICING_STEEPEST_EDGE ? "steepest_edge" : "infeasibility") << "\"";
     out << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
@@ -922,6 +923,15 @@ int32_t relp_set_dual_long_step(relp_handle* h, int32_t on) {
         return RELP_ERR_ARGUMENT;
     }
     h->solver->set_dual_long_step(on == 1);
+    return RELP_OK;
+}
+int32_t relp_set_dual_farkas(relp_handle* h, int32_t on) {
+    if (!h || !h->solver) return RELP_ERR_ARGUMENT;
+    if (on != 0 && on != 1) {
+        h->error = "relp_set_dual_farkas: the switch is 0 or 1, not " + std::to_string(on);
+        return RELP_ERR_ARGUMENT;
+    }
+    h->solver->set_dual_farkas(on == 1);
     return RELP_OK;
 }
 int32_t relp_begin_dual_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns) {

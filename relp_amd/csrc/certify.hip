@@ -980,11 +980,11 @@ bool certify_fits(i128 v) { return v < ((i128)1 << 62) && v > -((i128)1 << 62); 
 }  // namespace
 
 bool certify_integer_basis(const CertifyStatic& statics, const MatrixData& md, const std::vector<int>& basis, int mode, IntegerBasis* out,
-                           std::vector<i64>* cost_out, std::vector<char>* in_basis_out, std::string* message) {
+                           std::vector<i64>* cost_out, std::vector<char>* in_basis_out, std::string* message, int rows) {
     const std::vector<SparseColumn>& columns = statics.columns;
     const std::vector<i128>& row_mult = statics.row_mult;
     const DeviceColumns& cols = statics.cols;
-    const int m = md.nr_rows();
+    const int m = rows < 0 ? md.nr_rows() : rows;
     const int n_p = md.nr_columns();
     IntegerBasis& B = *out;
     B = IntegerBasis();
@@ -999,6 +999,7 @@ bool certify_integer_basis(const CertifyStatic& statics, const MatrixData& md, c
         if (c >= 0) {
             in_basis[c] = 1;
             for (size_t e = 0; e < columns[c].nnz(); ++e) {
+                if (columns[c].index[e] >= m) continue;  // (`rows`: the bound-row entry of a bounded column)
                 i128 v = certify_scaled(columns[c].value[e], row_mult[columns[c].index[e]]);
                 if (!certify_fits(v)) { *message = "scaled coefficient does not fit 62 bits"; return false; }
                 B.row_index.push_back(columns[c].index[e]);
@@ -1129,6 +1130,130 @@ bool certify_unbounded_ray(const std::vector<int>& basis, const ExactVector& alp
     return true;
 }
 
+namespace {
+// C = B^-1 mod p on the device, for the first trial prime modulo which the integer basis is regular: both orientations of B uploaded,
+// the sparse LU of B mod p from the host, then all m columns of the inverse by one kernel.  The buffers belong to `buf`.  False when B is
+// singular modulo every trial prime.
+struct ModularInverse {
+    u32 p = 0;
+    u32 *C = nullptr, *CT = nullptr;                          // row-major C and its transpose
+    int *col_start = nullptr, *row_index = nullptr;           // B by columns ...
+    i64* value = nullptr;
+    int *row_start = nullptr, *col_index = nullptr;           // ... and by rows
+    i64* row_value = nullptr;
+};
+bool modular_inverse(const IntegerBasis& B, DeviceBuffers& buf, hipStream_t stream, bool timeline, const std::function<void(const char*)>& stamp,
+                     ModularInverse* out) {
+    const int m = B.m;
+    const size_t nnz = B.row_index.size();
+    const auto& primes = CERTIFY_PRIMES;
+    u32* dC = buf.alloc<u32>((size_t)m * m);
+    u32* dCT = buf.alloc<u32>((size_t)m * m);
+    u32* dX = buf.alloc<u32>((size_t)m * m);
+    // both orientations of the integer basis: packed in the pinned arena, one copy, one device block
+    PackedUpload basis_upload;
+    const size_t o_col_start = basis_upload.add(B.col_start), o_row_index = basis_upload.add(B.row_index), o_value = basis_upload.add(B.value);
+    const size_t o_row_start = basis_upload.add(B.row_start), o_col_index = basis_upload.add(B.col_index), o_row_value = basis_upload.add(B.row_value);
+    char* d_basis = basis_upload.send(buf, stream);
+    int* d_col_start = reinterpret_cast<int*>(d_basis + o_col_start);
+    int* d_row_index = reinterpret_cast<int*>(d_basis + o_row_index);
+    i64* d_value = reinterpret_cast<i64*>(d_basis + o_value);
+    int* d_row_start = reinterpret_cast<int*>(d_basis + o_row_start);
+    int* d_col_index = reinterpret_cast<int*>(d_basis + o_col_index);
+    i64* d_row_value = reinterpret_cast<i64*>(d_basis + o_row_value);
+    stamp("device buffers allocated, uploads enqueued");
+    u32 p = 0;
+    for (u32 candidate : primes) {
+        // sparse LU of B mod p on the host (Markowitz order; any non-zero pivot is exact in Z_p): a few 10^4 operations
+        std::vector<u32> value_mod(nnz);
+        for (size_t e = 0; e < nnz; ++e) {
+            i64 v = B.value[e] % (i64)candidate;
+            if (v < 0) v += candidate;
+            value_mod[e] = (u32)v;
+        }
+        LuOptions lo;
+        lo.threshold = 0.0;
+        const LuModOps ops{candidate};
+        const double t_lu = wall_now();
+        const HostLUT<u32> f = lu_factor_t<LuModOps>(m, B.col_start.data(), B.row_index.data(), value_mod.data(), lo, ops);
+        if (timeline) fprintf(stderr, "[certify]   modular LU on the host %.2f ms (L %zu, U %zu entries)\n", (wall_now() - t_lu) * 1e3, f.l_col.size(), f.u_col.size());
+        if (f.singular) continue;  // singular modulo this prime (or singular): try the next one
+        std::vector<u32> dinv(m);
+        for (int i = 0; i < m; ++i) dinv[i] = ops.inverse(f.diag[i]);
+        const size_t nl = f.l_col.size(), nu = f.u_col.size();
+        HostLUT<u32> fs = f;
+        lu_schedules(fs);
+        const int levels_l = (int)fs.lev_start[0].size() - 1, levels_u = (int)fs.lev_start[1].size() - 1;
+        const size_t level_lds = ((size_t)2 * (m + 1) + 2 * nl + 2 * nu + m + (levels_l + 1) + m + (levels_u + 1) + m + m + (size_t)4 * m) * sizeof(u32);
+        const bool by_levels = level_lds <= 150 * 1024 && !thread_tuning().has(RELP_SW_CERTIFY_NO_LEVELS);
+        // the factors, and the level schedules of the kernel that walks them by levels: packed in the pinned arena, one copy
+        PackedUpload factor_upload;
+        const size_t o_rowpos = factor_upload.add(f.rowpos), o_colpos = factor_upload.add(f.colpos), o_ls = factor_upload.add(f.l_start),
+                     o_us = factor_upload.add(f.u_start), o_lc = factor_upload.add(f.l_col), o_uc = factor_upload.add(f.u_col),
+                     o_lv = factor_upload.add(f.l_val), o_uv = factor_upload.add(f.u_val), o_dinv = factor_upload.add(dinv);
+        size_t o_levl = 0, o_rowl = 0, o_levu = 0, o_rowu = 0;
+        if (by_levels) {
+            o_levl = factor_upload.add(fs.lev_start[0]), o_rowl = factor_upload.add(fs.lev_row[0]);
+            o_levu = factor_upload.add(fs.lev_start[1]), o_rowu = factor_upload.add(fs.lev_row[1]);
+        }
+        char* d_factors = factor_upload.send(buf, stream);
+        int* d_rowpos = reinterpret_cast<int*>(d_factors + o_rowpos);
+        int* d_colpos = reinterpret_cast<int*>(d_factors + o_colpos);
+        int* d_ls = reinterpret_cast<int*>(d_factors + o_ls);
+        int* d_us = reinterpret_cast<int*>(d_factors + o_us);
+        int* d_lc = reinterpret_cast<int*>(d_factors + o_lc);
+        int* d_uc = reinterpret_cast<int*>(d_factors + o_uc);
+        u32* d_lv = reinterpret_cast<u32*>(d_factors + o_lv);
+        u32* d_uv = reinterpret_cast<u32*>(d_factors + o_uv);
+        u32* d_dinv = reinterpret_cast<u32*>(d_factors + o_dinv);
+        if (by_levels) {
+            // one wave per column, level by level (modular_inverse_levels_kernel)
+            int* d_levl = reinterpret_cast<int*>(d_factors + o_levl);
+            int* d_rowl = reinterpret_cast<int*>(d_factors + o_rowl);
+            int* d_levu = reinterpret_cast<int*>(d_factors + o_levu);
+            int* d_rowu = reinterpret_cast<int*>(d_factors + o_rowu);
+            static PerDeviceOnce configured_levels;  // (certificates run from the worker threads of a batch, possibly on several devices)
+            allow_full_lds_once(configured_levels, &modular_inverse_levels_kernel);
+            ModularFactors mf{d_rowpos, d_colpos, d_ls, d_lc, d_lv, d_us, d_uc, d_uv, d_dinv, d_levl, d_rowl, levels_l, d_levu, d_rowu, levels_u};
+            hipLaunchKernelGGL(modular_inverse_levels_kernel, dim3((m + 3) / 4), dim3(256), level_lds, stream, m, candidate, mf, dCT);
+            hipLaunchKernelGGL(transpose_u32_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(256), 0, stream, m, dCT, dC);
+        } else {
+            // columns per workgroup: as many (a power of two, at most 32) as fit the LDS next to each other -- beside the
+            // factors themselves when those fit too
+            const size_t factor_bytes = ((size_t)2 * (m + 1) + 2 * nl + 2 * nu + m) * sizeof(u32);
+            const size_t lds_cap = 150 * 1024;
+            int columns = 32;
+            bool staged = factor_bytes + (size_t)8 * m * sizeof(u32) <= lds_cap;  // at least 8 columns beside the factors
+            const size_t room = staged ? lds_cap - factor_bytes : lds_cap;
+            while (columns > 1 && (size_t)columns * m * sizeof(u32) > room) columns /= 2;
+            const bool in_lds = (size_t)columns * m * sizeof(u32) <= room;
+            if (!in_lds) staged = false;
+            static PerDeviceOnce configured;
+            allow_full_lds_once(configured, &modular_inverse_kernel);
+            if (!in_lds) columns = 64;
+            const size_t lds = in_lds ? (size_t)columns * m * sizeof(u32) + (staged ? factor_bytes : 0) : 0;
+            hipLaunchKernelGGL(modular_inverse_kernel, dim3((m + columns - 1) / columns), dim3(staged ? 256 : columns), lds, stream, m, candidate,
+                               d_rowpos, d_colpos, d_ls, d_lc, d_lv, d_us, d_uc, d_uv, d_dinv, dX, dC, dCT, in_lds ? 1 : 0, columns, staged ? 1 : 0);
+        }
+        const double t_sync = wall_now();
+        RELP_HIP(hipStreamSynchronize(stream));
+        if (timeline) fprintf(stderr, "[certify]   waited %.2f ms for the uploads and the inverse kernel\n", (wall_now() - t_sync) * 1e3);
+        p = candidate;
+        break;
+    }
+    out->p = p;
+    out->C = dC;
+    out->CT = dCT;
+    out->col_start = d_col_start;
+    out->row_index = d_row_index;
+    out->value = d_value;
+    out->row_start = d_row_start;
+    out->col_index = d_col_index;
+    out->row_value = d_row_value;
+    return p != 0;
+}
+}  // namespace
+
 void certify_basis(const StandardForm& form, const std::vector<int>& basis_columns, int device, hipStream_t stream,
                    std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
                    std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch,
@@ -1190,7 +1315,6 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
     auto scaled = [&](const Rat& v, i128 mult) { return mul_checked(v.n, mult / v.d); };
     std::vector<int> basis = basis_columns;  // repaired in place by exact pivots when a check fails
     const int max_repairs = 200;
-    const auto& primes = CERTIFY_PRIMES;
 
     for (int round = 0; round <= max_repairs; ++round) {
         // ---- integer basis (CSC + CSR) ------------------------------------------------------------------
@@ -1198,7 +1322,6 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         std::vector<i64> cost_basis;
         std::vector<char> in_basis;
         if (!certify_integer_basis(*statics, md, basis, mode, &B, &cost_basis, &in_basis, message)) return;
-        const size_t nnz = B.row_index.size();
 
         g_times.setup += wall_now() - t_begin - g_times.setup - g_times.inverse - g_times.device_digits - g_times.host_assemble - g_times.checks;
         const double t_inverse = wall_now();
@@ -1207,101 +1330,12 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         DeviceBuffers buf;
         buf.scratch = scratch;
         buf.guard = &scratch_guard;
-        u32* dC = buf.alloc<u32>((size_t)m * m);
-        u32* dCT = buf.alloc<u32>((size_t)m * m);
-        u32* dX = buf.alloc<u32>((size_t)m * m);
-        // both orientations of the integer basis: packed in the pinned arena, one copy, one device block
-        PackedUpload basis_upload;
-        const size_t o_col_start = basis_upload.add(B.col_start), o_row_index = basis_upload.add(B.row_index), o_value = basis_upload.add(B.value);
-        const size_t o_row_start = basis_upload.add(B.row_start), o_col_index = basis_upload.add(B.col_index), o_row_value = basis_upload.add(B.row_value);
-        char* d_basis = basis_upload.send(buf, stream);
-        int* d_col_start = reinterpret_cast<int*>(d_basis + o_col_start);
-        int* d_row_index = reinterpret_cast<int*>(d_basis + o_row_index);
-        i64* d_value = reinterpret_cast<i64*>(d_basis + o_value);
-        int* d_row_start = reinterpret_cast<int*>(d_basis + o_row_start);
-        int* d_col_index = reinterpret_cast<int*>(d_basis + o_col_index);
-        i64* d_row_value = reinterpret_cast<i64*>(d_basis + o_row_value);
-        stamp("device buffers allocated, uploads enqueued");
-        u32 p = 0;
-        for (u32 candidate : primes) {
-            // sparse LU of B mod p on the host (Markowitz order; any non-zero pivot is exact in Z_p): a few 10^4 operations
-            std::vector<u32> value_mod(nnz);
-            for (size_t e = 0; e < nnz; ++e) {
-                i64 v = B.value[e] % (i64)candidate;
-                if (v < 0) v += candidate;
-                value_mod[e] = (u32)v;
-            }
-            LuOptions lo;
-            lo.threshold = 0.0;
-            const LuModOps ops{candidate};
-            const double t_lu = wall_now();
-            const HostLUT<u32> f = lu_factor_t<LuModOps>(m, B.col_start.data(), B.row_index.data(), value_mod.data(), lo, ops);
-            if (timeline) fprintf(stderr, "[certify]   modular LU on the host %.2f ms (L %zu, U %zu entries)\n", (wall_now() - t_lu) * 1e3, f.l_col.size(), f.u_col.size());
-            if (f.singular) continue;  // singular modulo this prime (or singular): try the next one
-            std::vector<u32> dinv(m);
-            for (int i = 0; i < m; ++i) dinv[i] = ops.inverse(f.diag[i]);
-            const size_t nl = f.l_col.size(), nu = f.u_col.size();
-            HostLUT<u32> fs = f;
-            lu_schedules(fs);
-            const int levels_l = (int)fs.lev_start[0].size() - 1, levels_u = (int)fs.lev_start[1].size() - 1;
-            const size_t level_lds = ((size_t)2 * (m + 1) + 2 * nl + 2 * nu + m + (levels_l + 1) + m + (levels_u + 1) + m + m + (size_t)4 * m) * sizeof(u32);
-            const bool by_levels = level_lds <= 150 * 1024 && !thread_tuning().has(RELP_SW_CERTIFY_NO_LEVELS);
-            // the factors, and the level schedules of the kernel that walks them by levels: packed in the pinned arena, one copy
-            PackedUpload factor_upload;
-            const size_t o_rowpos = factor_upload.add(f.rowpos), o_colpos = factor_upload.add(f.colpos), o_ls = factor_upload.add(f.l_start),
-                         o_us = factor_upload.add(f.u_start), o_lc = factor_upload.add(f.l_col), o_uc = factor_upload.add(f.u_col),
-                         o_lv = factor_upload.add(f.l_val), o_uv = factor_upload.add(f.u_val), o_dinv = factor_upload.add(dinv);
-            size_t o_levl = 0, o_rowl = 0, o_levu = 0, o_rowu = 0;
-            if (by_levels) {
-                o_levl = factor_upload.add(fs.lev_start[0]), o_rowl = factor_upload.add(fs.lev_row[0]);
-                o_levu = factor_upload.add(fs.lev_start[1]), o_rowu = factor_upload.add(fs.lev_row[1]);
-            }
-            char* d_factors = factor_upload.send(buf, stream);
-            int* d_rowpos = reinterpret_cast<int*>(d_factors + o_rowpos);
-            int* d_colpos = reinterpret_cast<int*>(d_factors + o_colpos);
-            int* d_ls = reinterpret_cast<int*>(d_factors + o_ls);
-            int* d_us = reinterpret_cast<int*>(d_factors + o_us);
-            int* d_lc = reinterpret_cast<int*>(d_factors + o_lc);
-            int* d_uc = reinterpret_cast<int*>(d_factors + o_uc);
-            u32* d_lv = reinterpret_cast<u32*>(d_factors + o_lv);
-            u32* d_uv = reinterpret_cast<u32*>(d_factors + o_uv);
-            u32* d_dinv = reinterpret_cast<u32*>(d_factors + o_dinv);
-            if (by_levels) {
-                // one wave per column, level by level (modular_inverse_levels_kernel)
-                int* d_levl = reinterpret_cast<int*>(d_factors + o_levl);
-                int* d_rowl = reinterpret_cast<int*>(d_factors + o_rowl);
-                int* d_levu = reinterpret_cast<int*>(d_factors + o_levu);
-                int* d_rowu = reinterpret_cast<int*>(d_factors + o_rowu);
-                static PerDeviceOnce configured_levels;  // (certificates run from the worker threads of a batch, possibly on several devices)
-                allow_full_lds_once(configured_levels, &modular_inverse_levels_kernel);
-                ModularFactors mf{d_rowpos, d_colpos, d_ls, d_lc, d_lv, d_us, d_uc, d_uv, d_dinv, d_levl, d_rowl, levels_l, d_levu, d_rowu, levels_u};
-                hipLaunchKernelGGL(modular_inverse_levels_kernel, dim3((m + 3) / 4), dim3(256), level_lds, stream, m, candidate, mf, dCT);
-                hipLaunchKernelGGL(transpose_u32_kernel, dim3((m + 31) / 32, (m + 31) / 32), dim3(256), 0, stream, m, dCT, dC);
-            } else {
-                // columns per workgroup: as many (a power of two, at most 32) as fit the LDS next to each other -- beside the
-                // factors themselves when those fit too
-                const size_t factor_bytes = ((size_t)2 * (m + 1) + 2 * nl + 2 * nu + m) * sizeof(u32);
-                const size_t lds_cap = 150 * 1024;
-                int columns = 32;
-                bool staged = factor_bytes + (size_t)8 * m * sizeof(u32) <= lds_cap;  // at least 8 columns beside the factors
-                const size_t room = staged ? lds_cap - factor_bytes : lds_cap;
-                while (columns > 1 && (size_t)columns * m * sizeof(u32) > room) columns /= 2;
-                const bool in_lds = (size_t)columns * m * sizeof(u32) <= room;
-                if (!in_lds) staged = false;
-                static PerDeviceOnce configured;
-                allow_full_lds_once(configured, &modular_inverse_kernel);
-                if (!in_lds) columns = 64;
-                const size_t lds = in_lds ? (size_t)columns * m * sizeof(u32) + (staged ? factor_bytes : 0) : 0;
-                hipLaunchKernelGGL(modular_inverse_kernel, dim3((m + columns - 1) / columns), dim3(staged ? 256 : columns), lds, stream, m, candidate,
-                                   d_rowpos, d_colpos, d_ls, d_lc, d_lv, d_us, d_uc, d_uv, d_dinv, dX, dC, dCT, in_lds ? 1 : 0, columns, staged ? 1 : 0);
-            }
-            const double t_sync = wall_now();
-            RELP_HIP(hipStreamSynchronize(stream));
-            if (timeline) fprintf(stderr, "[certify]   waited %.2f ms for the uploads and the inverse kernel\n", (wall_now() - t_sync) * 1e3);
-            p = candidate;
-            break;
-        }
-        if (p == 0) { *message = "basis singular modulo every trial prime (singular basis?)"; return; }
+        ModularInverse inverse;
+        if (!modular_inverse(B, buf, stream, timeline, stamp, &inverse)) { *message = "basis singular modulo every trial prime (singular basis?)"; return; }
+        const u32 p = inverse.p;
+        u32 *dC = inverse.C, *dCT = inverse.CT;
+        int *d_col_start = inverse.col_start, *d_row_index = inverse.row_index, *d_row_start = inverse.row_start, *d_col_index = inverse.col_index;
+        i64 *d_value = inverse.value, *d_row_value = inverse.row_value;
         // (The number of p-adic digits is found by doubling: Cramer's bound through |det B| of the row-scaled integer matrix
         //  over-estimates it three-fold on 25FV47, and the cost of the reconstruction grows with the square of it.)
         g_times.inverse += wall_now() - t_inverse;
@@ -1527,6 +1561,141 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_colum
         }
     }
     *message = "exact repair did not converge";
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the INFEASIBLE verdict of the dual simplex
+// ---------------------------------------------------------------------------------------------------
+// The dual loop stops dual unbounded at a row p of its basis: x_B[p] is infeasible and no column of row p of the tableau has the sign
+// a pivot needs.  Row p of the inverse, rho_p = e_p' B^-1, is then a Farkas vector up to its sign: rho_p a_j is the tableau's entry
+// and rho_p b = x_B[p].  One transposed lifting (diag(r) B)' y^ = e_p gives it exactly, rho_p = r . y^ with the row multipliers r; the
+// products with the columns and with b are host integers over the one denominator of y^.  No primal lifting, no cost scaling.
+//   plain:   the basis spans every row of the standard form; y = -rho_p, y a_j <= 0 for every provider column, y b = -x_B[p] > 0.
+//   bounded: the basis spans the constraint rows.  For y_c = -rho_p or +rho_p and r_j = y_c a_j over the constraint rows, a column
+//            with a bound row br(j) gets y_br(j) = -max(0, r_j) there -- the largest multiplier that keeps y a_j <= 0 and
+//            y (bound slack) <= 0 --, a column without one must have r_j <= 0, and y b = y_c b_c - sum_j max(0, r_j) u_j > 0.
+void certify_dual_farkas(const StandardForm& form, const std::vector<int>& basis, int row, bool bounded, int first_sign, int device,
+                         hipStream_t stream, std::string* objective, bool* certified, std::string* message, CertifyScratch* scratch,
+                         std::shared_ptr<const ExactWitnesses>* witnesses) {
+    std::mutex scratch_guard;
+    if (witnesses) witnesses->reset();
+    objective->clear();
+    *certified = false;
+    message->clear();
+    RELP_HIP(hipSetDevice(device));
+    const MatrixData& md = form.data;
+    const int m = bounded ? md.nr_constraints() : md.nr_rows();
+    const int priced_columns = bounded ? md.col_end[3] : md.nr_columns();  // (bounded: the bound slacks are priced by the closed form)
+    g_times = CertifyTimes{};
+    const bool timeline = diagnostic("RELP_TIME_CERTIFY");
+    const double t_begin = wall_now();
+    auto stamp = [&](const char* what) {
+        if (timeline) fprintf(stderr, "[certify farkas]   +%.2f ms %s\n", (wall_now() - t_begin) * 1e3, what);
+    };
+    std::shared_ptr<const CertifyStatic> statics = scratch ? std::static_pointer_cast<const CertifyStatic>(scratch->statics) : nullptr;
+    if (!statics) {
+        statics = certify_static(form, message);
+        if (!statics) return;
+        if (scratch) scratch->statics = statics;
+    }
+    if ((int)basis.size() != m || row < 0 || row >= m) {
+        *message = "dual Farkas: no row of the basis to prove the verdict with (row " + std::to_string(row) + " of " + std::to_string(m) + ")";
+        return;
+    }
+    for (int k = 0; k < m; ++k)
+        if (basis[k] < 0 || basis[k] >= priced_columns) {
+            *message = "dual Farkas: row " + std::to_string(k) + " of the basis holds the code " + std::to_string(basis[k]) + ", not a column the dual loop prices";
+            return;
+        }
+    const std::vector<SparseColumn>& columns = statics->columns;
+    const std::vector<i128>& row_mult = statics->row_mult;
+
+    // ---- integer basis over the rows the device basis spans, C = B^-1 mod p, one transposed lifting of e_p ------------------------
+    IntegerBasis B;
+    std::vector<i64> no_costs;
+    std::vector<char> in_basis;
+    if (!certify_integer_basis(*statics, md, basis, 1, &B, &no_costs, &in_basis, message, bounded ? m : -1)) return;
+    stamp("integer basis built");
+    DeviceBuffers buf;
+    buf.scratch = scratch;
+    buf.guard = &scratch_guard;
+    ModularInverse inverse;
+    if (!modular_inverse(B, buf, stream, timeline, stamp, &inverse)) {
+        *message = "basis singular modulo every trial prime (singular basis?)";
+        return;
+    }
+    stamp("inverse mod p ready");
+    std::vector<i64> unit(m, 0);
+    unit[row] = 1;
+    ExactVector rho;  // rho_p[i] = row_mult[i] numer[i] / denom
+    g_times.solves++;
+    if (!dixon_solve(B, unit, 1, inverse.p, inverse.CT, buf, inverse.col_start, inverse.row_index, inverse.value, stream, &rho, message, g_times, 32)) return;
+    stamp("row of the inverse lifted");
+    if (rho.denom.sign() < 0) {
+        rho.denom = -rho.denom;
+        for (BigInt& v : rho.numer) v = -v;
+    }
+
+    // ---- exact products: R_j = denom * rho_p a_j over the rows of the basis, and XB = denom * rhs_den * rho_p b ---------------------
+    std::vector<BigInt> priced(priced_columns);
+    WorkerPool::get().run(priced_columns, [&](int j) {
+        BigInt acc(0);
+        for (size_t e = 0; e < columns[j].nnz(); ++e) {
+            const int i = columns[j].index[e];
+            if (i < m) acc = acc + big_from_i128(certify_scaled(columns[j].value[e], row_mult[i])) * rho.numer[i];
+        }
+        priced[j] = acc;
+    });
+    BigInt xb(0);
+    for (int i = 0; i < m; ++i) xb = xb + statics->rhs_big[i] * rho.numer[i];
+    stamp("columns priced");
+
+    // ---- the candidates: y_c = sign * rho_p ---------------------------------------------------------------------------------------
+    std::string reasons;
+    const int signs[2] = {first_sign < 0 ? -1 : 1, first_sign < 0 ? 1 : -1};
+    for (int c = 0; c < (bounded ? 2 : 1); ++c) {
+        const int sign = bounded ? signs[c] : -1;
+        std::string reason;
+        BigInt value = sign < 0 ? -xb : xb;  // over denom * rhs_den
+        std::vector<BigInt> bound_rows(md.nr_rows() - m);  // the multipliers of the bound rows, over denom
+        for (int j = 0; j < priced_columns && reason.empty(); ++j) {
+            const int sgn = sign < 0 ? -priced[j].sign() : priced[j].sign();
+            if (sgn <= 0) continue;
+            const int br = bounded ? md.bound_row_index(j) : -1;
+            if (br < 0) {
+                reason = "provider column " + std::to_string(j) + " prices positive";
+                break;
+            }
+            const BigInt r = sign < 0 ? -priced[j] : priced[j];
+            bound_rows[br - m] = -r;
+            value = value - r * (statics->rhs_big[br] / big_from_i128(row_mult[br]));  // u_j = rhs_big / (row_mult * rhs_den), exactly
+        }
+        if (reason.empty() && value.sign() <= 0) reason = "y'b is not positive";
+        if (!reason.empty()) {
+            if (bounded) reasons += std::string(reasons.empty() ? "" : "; ") + (sign < 0 ? "-rho_p: " : "+rho_p: ") + reason;
+            else reasons = reason;
+            continue;
+        }
+        *objective = reduced_text(value, rho.denom * statics->rhs_den);
+        *certified = true;
+        if (witnesses) {
+            auto kept = std::make_shared<ExactWitnesses>();
+            kept->mode = 1;
+            kept->basis = basis;
+            kept->y.denom = rho.denom;
+            kept->y.numer.resize(md.nr_rows());
+            for (int i = 0; i < m; ++i) {
+                const BigInt v = rho.numer[i] * big_from_i128(row_mult[i]);
+                kept->y.numer[i] = sign < 0 ? -v : v;
+            }
+            for (int i = m; i < md.nr_rows(); ++i) kept->y.numer[i] = std::move(bound_rows[i - m]);  // (in the caller's terms already)
+            kept->finished = true;  // nothing is left to fold in: the row multipliers are in, a Farkas vector has no cost multiplier
+            *witnesses = kept;
+        }
+        stamp("proved");
+        return;
+    }
+    *message = "dual Farkas: row " + std::to_string(row) + " of the inverse does not prove the verdict in exact arithmetic: " + reasons;
 }
 
 }  // namespace relp

@@ -57,5 +57,14 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_provi
                    std::string* objective, bool* certified, long long* repair_pivots, std::string* message, int mode, int entering,
                    std::shared_ptr<const ExactPrimal>* primal, CertifyScratch* scratch,
                    std::shared_ptr<const ExactWitnesses>* witnesses = nullptr);
+// The exact proof of the INFEASIBLE verdict the dual simplex stops with (certify.hip): `basis` is the basis as the device holds it, in
+// provider columns by row -- every row of the standard form, or with `bounded` (an LP held on implicit upper bounds) the constraint
+// rows only --, `row` the row p at which the loop found the dual unbounded.  One transposed lifting gives row p of the inverse exactly;
+// the Farkas vector is its negative, or on a bounded handle either sign of it extended over the bound rows in closed form
+// (`first_sign`: -1 tries -rho_p first, +1 the other one; both are tried).  *certified with *objective = y'b > 0 and the witnesses of an
+// INFEASIBLE certificate (mode 1: y by row of the standard form), or *message names the exact inequality that failed.  No repair pivots.
+void certify_dual_farkas(const StandardForm& form, const std::vector<int>& basis_provider_columns, int row, bool bounded, int first_sign,
+                         int device, hipStream_t stream, std::string* objective, bool* certified, std::string* message,
+                         CertifyScratch* scratch, std::shared_ptr<const ExactWitnesses>* witnesses);
 
 }  // namespace relp

@@ -85,9 +85,10 @@ std::shared_ptr<const CertifyStatic> certify_static(const StandardForm& form, st
 
 // The basis in integers: B (CSC and CSR), the scaled basic costs (`mode` 1: the phase-one costs) and the membership flags of the
 // provider columns.  An artificial column -1-k is the unit column of its row scaled by the row multiplier.  False with `message`
-// set when an entry does not fit 62 bits.
+// set when an entry does not fit 62 bits.  `rows` >= 0: the first `rows` rows of the LP only, with a basis of that many columns (the
+// constraint rows of an LP held on implicit bounds: a bounded column loses its entry on its bound row).
 bool certify_integer_basis(const CertifyStatic& statics, const MatrixData& md, const std::vector<int>& basis, int mode, IntegerBasis* B,
-                           std::vector<long long>* cost_basis, std::vector<char>* in_basis, std::string* message);
+                           std::vector<long long>* cost_basis, std::vector<char>* in_basis, std::string* message, int rows = -1);
 
 // From the first digits.size() p-adic digits of the solution of A z = rhs (transpose 0: A = B, 1: A = B'): the numerators over one
 // common denominator (one rational reconstruction of a random integer combination of the unknowns, then one per entry that

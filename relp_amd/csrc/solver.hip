@@ -1533,6 +1533,8 @@ void Solver::finish_dual_start(const int* basis_columns, const char* how, double
     }
     if (dual_long_active_) RELP_HIP(hipMemsetAsync(dual_.flip_count, 0, 4 * sizeof(int), stream_));
     dual_flips_ = dual_long_skipped_ = 0;
+    dual_farkas_active_ = dual_farkas_;
+    dual_farkas_row_ = -1;
     const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
     dual_lds_ = 2 * (size_t)m * sizeof(double) <= lds_max;
     std::vector<double> cbar(n);
@@ -1698,8 +1700,57 @@ void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_resul
     }
     const bool dual_unbounded = kind == RELP_RESULT_INFEASIBLE;
     collect_result(kind, t0, !dual_unbounded, [](const char*) {}, result);
-    if (dual_unbounded)  // (reported with certified = 0 whatever the options ask for)
+    if (dual_unbounded && dual_farkas_active_ && opt_.certify) certify_dual_infeasible(result);
+    else if (dual_unbounded)  // (without relp_set_dual_farkas: reported with certified = 0 whatever the options ask for)
         last_error ="the dual simplex does not certify infeasibility yet (the Farkas vector is the row of the inverse at which the dual is unbounded)";
+}
+
+// dual_pivot_kernel clears Ctl::p where it stops the loop, and nothing has written x_B, the basis or the weights since: the leaving-row
+// kernel, alone and under a status that lets it run, names the row again.  The control block is put back as the loop left it.
+int Solver::dual_stopped_row() {
+    const Ctl stopped = read_ctl();
+    if (stopped.status != ST_UNBOUNDED) return -1;
+    Ctl running = stopped;
+    running.status = ST_RUNNING;
+    write_ctl(running);
+    stats_.launches += 1;
+    launch_dual_leave(d_, opt_.harris_delta, dual_.beta, path_.bounded, stream_);
+    const Ctl named = read_ctl();
+    write_ctl(stopped);
+    return named.status == ST_RUNNING && named.p >= 0 && named.p < d_.m ? named.p : -1;
+}
+
+// The INFEASIBLE verdict of the dual loop, proved: row p of the exact inverse is the Farkas vector (certify.hpp: certify_dual_farkas).
+// The basis is the one the device holds -- on implicit bounds its constraint rows, uncomplemented: the closed form over the bound rows
+// does not ask where a column sits --, and the f64 state only says which sign of the row to try first.
+void Solver::certify_dual_infeasible(relp_result* result) {
+    const double t0 = now_seconds();
+    bool ok = false;
+    std::string message;
+    const int p = dual_stopped_row();
+    if (p < 0) {
+        message = "dual Farkas: the loop does not stand at a dual unbounded row";
+    } else {
+        std::vector<int> basis(d_.m);
+        for (int i = 0; i < d_.m; ++i) basis[i] = cols_.to_provider(h_rb_basis_[i]);  // (collect_result's read-back)
+        int first_sign = -1;
+        if (path_.bounded) {
+            const int column = h_rb_basis_[p];
+            const bool below = !(h_rb_xb_[p] - h_rb_ub_[column] > -h_rb_xb_[p]);  // (dual_side of dual.hip)
+            first_sign = below != (h_rb_flipped_[column] != 0) ? -1 : 1;
+        }
+        try {
+            certify_dual_farkas(form_, basis, p, path_.bounded, first_sign, opt_.device, stream_, &exact_objective, &ok, &message, &certify_scratch_, &exact_witnesses);
+        } catch (const RatOverflow& e) {  // (as certify())
+            ok = false;
+            message = std::string("exact certificate: ") + e.what();
+        }
+        dual_farkas_row_ = p;
+    }
+    last_result.certified = ok ? 1 : 0;
+    last_result.certify_seconds = now_seconds() - t0;
+    if (result) *result = last_result;
+    if (!ok) last_error = message;
 }
 
 // ---- LU carry ---------------------------------------------------------------------------------------

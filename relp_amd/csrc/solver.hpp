@@ -88,6 +88,13 @@ public:
     bool dual_long_step() const { return dual_long_active_; }  // the last start ran the loop with it
     long long dual_flips() const { return dual_flips_; }  // columns it sent to their other bound, over the dual pivots since that start
     long long dual_long_step_skipped() const { return dual_long_skipped_; }  // pivots at which it held too many candidates and made none
+    // The exact proof of an INFEASIBLE verdict of solve_dual / solve_dual_from / solve_dual_bounded / solve_dual_bounded_from
+    // (certify.hpp: certify_dual_farkas), off by default.  The switch holds until changed, is read by every start and takes effect where
+    // relp_options.certify is set and the loop ends dual unbounded: the result is then certified with the Farkas vector as its dual
+    // witness and y'b as its exact objective, or uncertified with the exact inequality that failed in last_error.
+    void set_dual_farkas(bool on) { dual_farkas_ = on; }
+    bool dual_farkas() const { return dual_farkas_active_; }  // the switch as the last start read it
+    int dual_farkas_row() const { return dual_farkas_row_; }  // the row of the basis the last proof used, -1 where there was none
     long long dual_pivots() const { return dual_pivots_; }  // of the last solve_dual / since begin_dual
     // relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE: the m weights the next dual pivot would read (the squared row norms
     // of the inverse).  std::runtime_error under rule 0 and before a begin_dual.
@@ -214,6 +221,11 @@ private:
     bool dual_long_active_ = false;  // ... as the last start read it, on a plan with implicit bounds
     long long dual_flips_ = 0, dual_long_skipped_ = 0;
     int* h_flip_totals_ = nullptr;   // pinned: DualBuffers::flip_count[2..3] after a batch
+    bool dual_farkas_ = false;         // the switch
+    bool dual_farkas_active_ = false;  // ... as the last start read it
+    int dual_farkas_row_ = -1;
+    int dual_stopped_row();                            // the row at which the loop stands dual unbounded (one launch of the leaving-row kernel)
+    void certify_dual_infeasible(relp_result* result);  // behind collect_result, which has read the basis and x_B back
     // ... and their tail behind set_phase(2): the loop's buffers, the dual-feasibility check that names the column, the counters
     void finish_dual_start(const int* basis_columns, const char* how, double t0, long long gemms_before);
     void run_dual(const Solver* parent, const int* basis_columns, relp_result* result, bool bounded_entry = false);  // every solve_dual*: one loop

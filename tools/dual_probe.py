@@ -48,7 +48,17 @@ child's, solved cold on the device, so it holds its basis at its own positions a
   solve_dual_bounded, solve_dual_bounded_from   the whole certified call, and how much of it the start took
 ``--traced`` as with ``--start``: the two begin calls only, plain launches, for a run under rocprofv3 --kernel-trace.
 
-    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded [--long-step | --start [--traced]]]
+``--farkas``: an INFEASIBLE child at each size, without bounds (``dual_lps.infeasible_child``: two contradicting rows over two variables
+that are positive at the parent's vertex) and on implicit bounds (a bound on every variable; the branch fixes two of them at 0 and a row
+asks for their sum to be at least 1, as ``dual_bounded_lps.infeasible_child`` builds it), a line per way to the verdict:
+  dual        ``solve_dual`` / ``solve_dual_bounded`` with ``farkas=True``, certified: the whole call, its start, the dual pivots and
+              ``certify_seconds`` (one launch of the leaving-row kernel, one modular inverse, one transposed lifting, the exact products)
+  inherited   the same through ``solve_dual_from`` / ``solve_dual_bounded_from``, the parent's handle open beside the child's
+  cold        ``solve_relaxation`` of the child on a fresh handle: ms, pivots and whether the verdict came back certified (on implicit
+              bounds it does not: ``collect_result`` certifies finite optima only there)
+Run against a library without ``relp_set_dual_farkas`` (``RELP_AMD_LIB``), it prints the cold lines alone.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded [--long-step | --start [--traced]]] [--farkas]
 """
 import argparse
 import os
@@ -346,6 +356,66 @@ def long_step_probe(m, decimal, n_cuts, n_tight, every):
     assert len(objectives) == 1, objectives  # both rules end at the same exact optimum
 
 
+def farkas_probe(m, bounded):
+    """One child of the table "the INFEASIBLE verdict, proved" of DESIGN.md section 10, a line per way to the verdict."""
+    from fractions import Fraction
+    proves = hasattr(relp_amd.lib(), "relp_set_dual_farkas")  # (a library of before the proof: the cold solve alone)
+    if bounded:
+        import dual_bounded_lps
+        case = dual_bounded_lps.BoundedCase(m, 1000 + m, 0, 0, every=1)
+        form = case.parent
+        options = dict(certify=1, implicit_bounds=1)
+        parent = relp_amd.Solver(**options).load_model(form.model)
+        assert parent.solve_relaxation().certified
+        vertex = {int(j): v for j, v in parent.solution_exact().items() if j < form.ns}
+        j, k = [v for v in sorted(vertex) if vertex[v] > 0 and form.upper[v] is not None][:2]
+        columns, upper = [list(column) for column in form.columns], list(form.upper)
+        for variable in (j, k):
+            columns[variable].append((form.m, Fraction(1)))
+            upper[variable] = 0
+        child_form = dual_bounded_lps.Formulation(columns, list(form.b) + [1], form.cost, upper, n_greater=1)
+        child, basis = child_form.model, dual_bounded_lps.extended_basis(form, child_form, parent.basis())
+        entries = ("solve_dual_bounded", "solve_dual_bounded_from")
+    else:
+        seed, _ = dual_lps.STATE_CASES[m]
+        case = dual_lps.cut_case(m, dual_lps.MIXED, seed, 0)
+        options = dict(certify=1)
+        parent = relp_amd.Solver(**options).load_model(case.parent)
+        assert parent.solve_relaxation().certified
+        child, basis = dual_lps.infeasible_child(case, parent.basis(), parent.solution_exact())
+        entries = ("solve_dual", "solve_dual_from")
+    label = "m = %d, %s, infeasible child of %d rows on the device" % (m, "implicit bounds" if bounded else "no bounds", child.kernel_path(**options)["m"])
+    solver = relp_amd.Solver(**options).load_model(child)
+    values = set()
+
+    def dual(call):
+        def run():
+            started = time.perf_counter()
+            result = call()
+            wall = 1e3 * (time.perf_counter() - started)
+            assert result.kind == relp_amd.INFEASIBLE and result.certified, relp_amd.lib().relp_last_error(solver._h).decode()
+            values.add(solver.objective_exact())
+            return wall, 1e3 * solver.record()["dual_start_seconds"], solver.dual_pivots(), 1e3 * result.certify_seconds
+        return run
+
+    def cold():
+        result = solver.solve_relaxation()
+        assert result.kind == relp_amd.INFEASIBLE
+        return 1e3 * (result.solve_seconds + result.certify_seconds), result.pivots_phase_one + result.pivots_phase_two, 1e3 * result.certify_seconds, result.certified
+
+    if proves:
+        for entry, call in ((entries[0], lambda: getattr(solver, entries[0])(basis, farkas=True)),
+                            (entries[1], lambda: getattr(solver, entries[1])(parent, basis, farkas=True))):
+            (wall, lo, hi), (start_ms, _, _), (pivots, _, _), (certify_ms, certify_lo, certify_hi) = spread_of(dual(call))
+            print("%s | %s (%s): %.1f ms (%.1f .. %.1f), of which the start %.2f ms, %d dual pivots, the proof %.2f ms (%.2f .. %.2f), y'b = %s" % (
+                label, entry, solver.record()["dual_start"], wall, lo, hi, start_ms, pivots, certify_ms, certify_lo, certify_hi, sorted(values)), flush=True)
+    (cold_ms, cold_lo, cold_hi), (cold_pivots, _, _), (cold_certify, _, _), (certified, _, _) = spread_of(cold)
+    print("%s | cold solve_relaxation: %.1f ms (%.1f .. %.1f), %d pivots, certificate %.2f ms, %s" % (
+        label, cold_ms, cold_lo, cold_hi, cold_pivots, cold_certify, "certified" if certified else "NOT certified"), flush=True)
+    solver.close()
+    parent.close()
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
@@ -363,7 +433,13 @@ def main():
     parser.add_argument("--long-step", action="store_true", help="with --bounded: implicit bounds under the plain and the long-step ratio test")
     parser.add_argument("--every", type=int, default=1, help="with --long-step: a bound on every N-th structural variable")
     parser.add_argument("--tight", type=int, default=8, help="with --long-step: tightened bounds per child")
+    parser.add_argument("--farkas", action="store_true", help="only the table of the proved INFEASIBLE verdict: an infeasible child without bounds and on implicit bounds")
     args = parser.parse_args()
+    if args.farkas:
+        for m in args.sizes:
+            for bounded in (False, True):
+                farkas_probe(m, bounded)
+        return
     if args.bounded and args.long_step:
         for m in args.sizes:
             for decimal in ([True] if args.decimal else [False, True]):
