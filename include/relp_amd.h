@@ -38,7 +38,8 @@ typedef enum relp_result_kind {
     RELP_RESULT_FINITE_OPTIMUM = 1,
     RELP_RESULT_INFEASIBLE = 2,
     RELP_RESULT_UNBOUNDED = 3,
-    RELP_RESULT_ITERATION_LIMIT = 4
+    RELP_RESULT_ITERATION_LIMIT = 4,
+    RELP_RESULT_CUTOFF = 5      /* relp_set_dual_cutoff only: the dual loop stopped at a basis whose objective has reached the cutoff */
 } relp_result_kind;
 
 /* strategy/pivot_rule.rs:86-305: the four `PivotRule` implementations. */
@@ -891,7 +892,8 @@ int32_t relp_many_get_solution_exact(const relp_many* many, int32_t model, int32
  * relp_last_error saying so: the dual loop does not prove infeasibility yet.  A pivot element that is unusable even after a
  * polish of the inverse (an ill-conditioned basis) ends the call with RELP_ERR_STATE.
  * relp_begin_dual / relp_iterate_dual: the same loop in steps.  Stop reasons: 1 no infeasible row is left (the basis is primal
- * feasible), 2 the dual is unbounded (the LP is infeasible), 3 `count` pivots were made.  relp_get_last_pivot reports phase 3 after a
+ * feasible), 2 the dual is unbounded (the LP is infeasible), 3 `count` pivots were made, 6 (under relp_set_dual_cutoff only) the
+ * objective of the basis has reached the cutoff.  relp_get_last_pivot reports phase 3 after a
  * dual pivot.  The steepest-edge weights are not maintained by the dual loop: relp_begin_phase_two recomputes them. */
 int32_t relp_solve_dual(relp_handle* handle, const int32_t* basis_columns, relp_result* result);
 int32_t relp_begin_dual(relp_handle* handle, const int32_t* basis_columns);
@@ -1020,6 +1022,35 @@ int32_t relp_set_dual_long_step(relp_handle* handle, int32_t on);
  * relp_get_record_json: "dual_farkas" (the switch as the last start read it) and "dual_farkas_row" (the row p the last proof used,
  * -1 where there was none).  relp_begin_dual / relp_iterate_dual and relp_many do not read the switch. */
 int32_t relp_set_dual_farkas(relp_handle* handle, int32_t on);
+
+/* An objective cutoff for the dual loop, a switch on the handle like the two above: `on` = 1 or 0, off on a new handle; any other value
+ * is RELP_ERR_ARGUMENT, and so is a NaN `cutoff`; a null handle answers as relp_set_dual_farkas does.  +-inf are ordinary values: +inf
+ * never stops the loop and only asks for the proof at the iteration limit, -inf stops it at the start basis.  `cutoff` is in the units
+ * of relp_result.objective: the minimised standard-form objective with the fixed cost included.  The switch holds until changed and is
+ * read by every start of the dual loop, relp_begin_dual, relp_begin_dual_from, relp_begin_dual_bounded and relp_begin_dual_bounded_from
+ * included.  With it off every launch, result, message and record key is what it was.
+ * Every basis of the dual loop is dual feasible, so its objective is a lower bound of the LP.  With the switch on, the kernel that
+ * chooses the leaving row first compares the objective of the basis it stands on with the cutoff, before the iteration budget and
+ * before anything is scanned, and stops the loop where objective >= cutoff: relp_iterate_dual reports stop reason 6, the four
+ * relp_solve_dual* calls RELP_RESULT_CUTOFF, without the primal clean-up.  A start basis already at the cutoff makes 0 pivots; a basis
+ * that is optimal and at the cutoff reports the cutoff, not the optimum.  result.objective is then the f64 objective of that basis
+ * instead of NaN -- for RELP_RESULT_CUTOFF, and for a RELP_RESULT_ITERATION_LIMIT where the dual loop itself ran out of
+ * options.max_pivots (strong branching: relp_set_dual_cutoff(handle, 1, +inf) and a small max_pivots).
+ * With options.certify != 0 both results are proved by the dual half of the optimum's certificate: one transposed p-adic lifting of
+ * B'y = c_B on its kernels, then d_j = c_j - y'a_j >= 0 for every provider column in exact integers and z = y'b + fixed cost.  On a
+ * handle with options.implicit_bounds = 1 the basis spans the constraint rows: the bound row of column j gets min(0, d_j), a column
+ * without a bound must have d_j >= 0, and z = y_c'b_c + sum_j min(0, d_j) u_j + fixed cost.  A RELP_RESULT_CUTOFF also needs z >= cutoff,
+ * the double compared as the exact rational it is; at the iteration limit z is certified whatever its size.
+ * Proved: result.certified = 1 with certify_seconds filled, relp_get_objective_exact returns z, and
+ * relp_get_witness_exact(RELP_WITNESS_DUAL) returns y by row of the loaded model's standard form (bound rows included);
+ * RELP_WITNESS_PRIMAL and RELP_WITNESS_RAY are RELP_ERR_STATE.  Not proved: certified = 0 and relp_last_error names the provider
+ * column that prices negative (under the Harris ratio test a relative cost may be negative by less than tol_dual, and a column without
+ * a bound cannot absorb that), or gives the exact bound and the cutoff it falls short of, or repeats the refusal of the optimum's
+ * certificate; no exact repair pivots follow and the loop is not resumed.
+ * relp_get_record_json: "dual_cutoff" (the value as the last start read it, "inf" / "-inf" as strings, null with the switch off),
+ * "dual_cutoff_stopped" (the loop since that start stopped at the cutoff), "dual_bound_proved"; "result" may be "cutoff".
+ * relp_many does not read the switch; relp_iterate_dual stops at the cutoff but has no result to certify. */
+int32_t relp_set_dual_cutoff(relp_handle* handle, int32_t on, double cutoff);
 
 /* Version / build info ("relp_amd <ver> gfx950"). */
 const char* relp_version(void);

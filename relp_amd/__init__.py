@@ -5,9 +5,9 @@ The package holds the HIP kernels + C ABI (``csrc/``, built into ``librelp_amd.s
 """
 from .api import (  # noqa: F401
     Model, Solver, Batch, Many, ManyResult, ManyConfig, ManyCertificate, Options, Result, RelpError, default_options, lib, LIB_PATH, SYMBOLS,
-    FINITE_OPTIMUM, INFEASIBLE, UNBOUNDED, ITERATION_LIMIT,
+    FINITE_OPTIMUM, INFEASIBLE, UNBOUNDED, ITERATION_LIMIT, CUTOFF,
     STEEPEST_EDGE, DANTZIG, FIRST_PROFITABLE, FIRST_PROFITABLE_MEMORY,
-    STOP_NO_ENTERING, STOP_UNBOUNDED, STOP_BUDGET,
+    STOP_NO_ENTERING, STOP_UNBOUNDED, STOP_BUDGET, STOP_CUTOFF,
     WITNESS_PRIMAL, WITNESS_DUAL, WITNESS_RAY,
 )
-from .witness import WitnessError, check_optimum, check_infeasible, check_unbounded  # noqa: F401
+from .witness import WitnessError, check_optimum, check_infeasible, check_unbounded, check_dual_bound  # noqa: F401

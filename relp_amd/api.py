@@ -15,8 +15,10 @@ LIB_PATH = os.environ.get("RELP_AMD_LIB", os.path.join(_HERE, "librelp_amd.so"))
 
 OK, ERR_ARGUMENT, ERR_PARSE, ERR_DEVICE, ERR_OVERFLOW, ERR_STATE, ERR_NUMERICAL = range(7)
 FINITE_OPTIMUM, INFEASIBLE, UNBOUNDED, ITERATION_LIMIT = 1, 2, 3, 4
+CUTOFF = 5  # only under Solver.set_dual_cutoff: the dual loop stopped at a basis whose objective has reached the cutoff
 STEEPEST_EDGE, DANTZIG, FIRST_PROFITABLE, FIRST_PROFITABLE_MEMORY = 0, 1, 2, 3
 STOP_NO_ENTERING, STOP_UNBOUNDED, STOP_BUDGET = 1, 2, 3
+STOP_CUTOFF = 6  # iterate_dual under Solver.set_dual_cutoff
 CARRY_EXPLICIT, CARRY_LU, CARRY_LU_INVERSE, CARRY_NETWORK = 0, 1, 2, 3
 RATIO_HARRIS, RATIO_TEXTBOOK, RATIO_AUTO = 0, 1, 2
 WITNESS_PRIMAL, WITNESS_DUAL, WITNESS_RAY = 0, 1, 2  # relp_witness
@@ -209,6 +211,8 @@ SYMBOLS = [
     "relp_begin_dual_bounded_from", "relp_solve_dual_bounded_from", "relp_debug_dual_bounded_inherit_refusal",
     # ... with the exact Farkas proof of an INFEASIBLE child (certify.hip: certify_dual_farkas)
     "relp_set_dual_farkas",
+    # ... with an objective cutoff and the exact proof of the bound it stopped at (certify.hip: certify_dual_bound)
+    "relp_set_dual_cutoff",
 ]
 
 
@@ -226,6 +230,8 @@ def lib():
         _lib.relp_many_last_error.argtypes = [C.c_void_p]
         _lib.relp_many_certify.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ManyCertificate), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.relp_many_get_certificate_digits.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        if hasattr(_lib, "relp_set_dual_cutoff"):  # (a double by value; a library of before the cutoff, RELP_AMD_LIB, has no such symbol)
+            _lib.relp_set_dual_cutoff.argtypes = [C.c_void_p, C.c_int32, C.c_double]
     return _lib
 
 
@@ -785,13 +791,30 @@ class Solver:
         Off, that verdict comes back uncertified as it always did.  ``record()``: ``"dual_farkas"``, ``"dual_farkas_row"``."""
         self._check(lib().relp_set_dual_farkas(self._h, int(on)))
 
-    def solve_dual(self, basis, farkas=None):
+    def set_dual_cutoff(self, cutoff):
+        """An objective cutoff for the dual loop (``relp_set_dual_cutoff``; off on a new handle): a float in the units of
+        ``Result.objective`` (the fixed cost included), or ``None`` to turn it off.  It holds until changed and every start of the dual
+        loop reads it.  The loop stops at the first basis whose objective has reached the cutoff: ``iterate_dual`` reports
+        ``STOP_CUTOFF``, the four ``solve_dual*`` methods a ``Result`` of kind ``CUTOFF`` with the objective of that basis.  With
+        ``certify=1`` that result, and an ``ITERATION_LIMIT`` of the dual loop itself (``float("inf")`` and a small ``max_pivots``: strong
+        branching), is ``certified`` as a lower bound of the LP: ``objective_exact()`` is the bound, ``witness_exact(WITNESS_DUAL)`` the
+        dual vector by row of the standard form, bound rows included (``relp_amd.witness.check_dual_bound`` takes both), or the handle's
+        last error names the provider column that prices negative.  ``record()``: ``"dual_cutoff"``, ``"dual_cutoff_stopped"``,
+        ``"dual_bound_proved"``."""
+        if cutoff is None:
+            self._check(lib().relp_set_dual_cutoff(self._h, 0, 0.0))
+        else:
+            self._check(lib().relp_set_dual_cutoff(self._h, 1, float(cutoff)))
+
+    def solve_dual(self, basis, farkas=None, cutoff=None):
         """Re-solve the loaded LP from ``basis`` (as ``set_basis`` takes it: the optimal basis of the LP before rows were appended
         or a right-hand side tightened, extended by the slack of each new row) by dual pivots; returns ``Result``
         (``relp_solve_dual``).  ``RelpError`` where the plan, or the basis, is refused.  ``farkas``: ``set_dual_farkas`` first; ``None``
-        keeps the handle's setting."""
+        keeps the handle's setting.  ``cutoff``: ``set_dual_cutoff`` first, likewise (so ``None`` does not turn a cutoff off)."""
         if farkas is not None:
             self.set_dual_farkas(farkas)
+        if cutoff is not None:
+            self.set_dual_cutoff(cutoff)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual(self._h, _ptr(arr, C.c_int32), C.byref(result)))
@@ -811,12 +834,14 @@ class Solver:
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_begin_dual_from(self._h, parent._h, _ptr(arr, C.c_int32)))
 
-    def solve_dual_from(self, parent, basis, farkas=None):
+    def solve_dual_from(self, parent, basis, farkas=None, cutoff=None):
         """``solve_dual`` with the start of ``begin_dual_from``; returns ``Result`` (``relp_solve_dual_from``).  ``record()`` says
-        which start was taken (``"dual_start"``) and what it cost (``"dual_start_seconds"``, ``"dual_start_gemms"``).  ``farkas`` as
-        ``solve_dual`` takes it."""
+        which start was taken (``"dual_start"``) and what it cost (``"dual_start_seconds"``, ``"dual_start_gemms"``).  ``farkas`` and
+        ``cutoff`` as ``solve_dual`` takes them."""
         if farkas is not None:
             self.set_dual_farkas(farkas)
+        if cutoff is not None:
+            self.set_dual_cutoff(cutoff)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_from(self._h, parent._h, _ptr(arr, C.c_int32), C.byref(result)))
@@ -837,14 +862,17 @@ class Solver:
         ``"dual_long_step_skipped"``."""
         self._check(lib().relp_set_dual_long_step(self._h, int(on)))
 
-    def solve_dual_bounded(self, basis, long_step=None, farkas=None):
+    def solve_dual_bounded(self, basis, cutoff=None, long_step=None, farkas=None):
         """``solve_dual`` with the start of ``begin_dual_bounded``: the re-solve of a branched child from its parent's basis; returns
         ``Result`` (``relp_solve_dual_bounded``).  ``record()["dual_bounded"]`` says whether the loop ran on implicit bounds.
-        ``long_step``: ``set_dual_long_step`` first; ``None`` keeps the handle's setting.  ``farkas``: ``set_dual_farkas`` likewise."""
+        ``long_step``: ``set_dual_long_step`` first; ``None`` keeps the handle's setting.  ``farkas``: ``set_dual_farkas`` likewise,
+        ``cutoff``: ``set_dual_cutoff`` (pass the three by keyword: ``long_step`` and ``farkas`` stay the last two parameters)."""
         if long_step is not None:
             self.set_dual_long_step(long_step)
         if farkas is not None:
             self.set_dual_farkas(farkas)
+        if cutoff is not None:
+            self.set_dual_cutoff(cutoff)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_bounded(self._h, _ptr(arr, C.c_int32), C.byref(result)))
@@ -860,13 +888,15 @@ class Solver:
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         self._check(lib().relp_begin_dual_bounded_from(self._h, parent._h, _ptr(arr, C.c_int32)))
 
-    def solve_dual_bounded_from(self, parent, basis, long_step=None, farkas=None):
+    def solve_dual_bounded_from(self, parent, basis, cutoff=None, long_step=None, farkas=None):
         """``solve_dual_bounded`` with the start of ``begin_dual_bounded_from``; returns ``Result``
-        (``relp_solve_dual_bounded_from``).  ``long_step`` and ``farkas`` as ``solve_dual_bounded`` takes them."""
+        (``relp_solve_dual_bounded_from``).  ``long_step``, ``farkas`` and ``cutoff`` as ``solve_dual_bounded`` takes them."""
         if long_step is not None:
             self.set_dual_long_step(long_step)
         if farkas is not None:
             self.set_dual_farkas(farkas)
+        if cutoff is not None:
+            self.set_dual_cutoff(cutoff)
         arr = np.ascontiguousarray(basis, dtype=np.int32)
         result = Result()
         self._check(lib().relp_solve_dual_bounded_from(self._h, parent._h, _ptr(arr, C.c_int32), C.byref(result)))
@@ -874,7 +904,8 @@ class Solver:
 
     def iterate_dual(self, count):
         """Up to ``count`` dual pivots: ``(done, reason)``; ``STOP_NO_ENTERING``: no infeasible row is left, ``STOP_UNBOUNDED``: the
-        dual is unbounded (the LP is infeasible), ``STOP_BUDGET``."""
+        dual is unbounded (the LP is infeasible), ``STOP_BUDGET``, and under ``set_dual_cutoff`` ``STOP_CUTOFF``: the objective of the
+        basis has reached the cutoff."""
         done, reason = C.c_int64(), C.c_int32()
         self._check(lib().relp_iterate_dual(self._h, int(count), C.byref(done), C.byref(reason)))
         return done.value, reason.value

@@ -1,4 +1,5 @@
 // extern "C" boundary (include/relp_amd.h).  Plain pointers and sizes only; exceptions are mapped to status codes.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -697,7 +698,10 @@ int32_t relp_get_witness_exact(const relp_handle* h, int32_t which, int32_t capa
     };
     if (!sv.last_result.certified || (!sv.exact_witnesses && !sv.exact_primal))
         return refuse("no exact witness: the last result is not certified (set options.certify and solve)");
-    const std::string refusal = witness_refusal(sv.last_result.kind, which);
+    const bool dual_bound = sv.exact_witnesses && exact_witness_mode(*sv.exact_witnesses) == 3;  // (relp_set_dual_cutoff: y alone)
+    if (dual_bound && which != RELP_WITNESS_DUAL)
+        return refuse(std::string("a certified lower bound of the dual simplex has no ") + (which == RELP_WITNESS_PRIMAL ? "RELP_WITNESS_PRIMAL" : "RELP_WITNESS_RAY"));
+    const std::string refusal = dual_bound ? std::string() : witness_refusal(sv.last_result.kind, which);
     if (!refusal.empty()) return refuse(refusal);
     if (!sv.exact_witnesses && which != RELP_WITNESS_PRIMAL)
         return refuse("RELP_CARRY_NETWORK proves its optimum from the forest: it keeps the exact primal solution only, no dual solution and no ray");
@@ -764,12 +768,12 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     long long nnz = 0;
     for (int j = 0; j < md.nr_columns(); ++j) nnz += (long long)md.column(j).nnz();
     const long long pivots = r.pivots_phase_one + r.pivots_phase_two;
-    static const char* kinds[] = {"none", "finite_optimum", "infeasible", "unbounded", "iteration_limit"};
+    static const char* kinds[] = {"none", "finite_optimum", "infeasible", "unbounded", "iteration_limit", "cutoff"};
     std::ostringstream out;
     out.precision(17);
     static const char* presolve_states[] = {"off", "applied", "applied without the implied bounds beyond 126 bits", "dropped (did not fit the host model)"};
     out << "{\"name\": \"" << json_escaped(sv.form().name) << "\", \"presolve\": \"" << presolve_states[sv.form().presolve_state & 3] << "\", \"m\": " << md.nr_rows() << ", \"n\": " << md.nr_columns() << ", \"nnz\": " << nnz
-        << ", \"device_rows\": " << d.m << ", \"artificials\": " << d.n_art << ", \"result\": \"" << kinds[r.kind >= 0 && r.kind <= 4 ? r.kind : 0]
+        << ", \"device_rows\": " << d.m << ", \"artificials\": " << d.n_art << ", \"result\": \"" << kinds[r.kind >= 0 && r.kind <= 5 ? r.kind : 0]
         << "\", \"carry\": \"" << (h->options.carry == RELP_CARRY_LU ? "lu" : h->options.carry == RELP_CARRY_LU_INVERSE ? "lu_inverse" : sv.network_carry() ? "network" : "explicit") << "\", \"pivots_phase_one\": " << r.pivots_phase_one
         << ", \"pivots_phase_two\": " << r.pivots_phase_two << ", \"dual_pivots\": " << sv.dual_pivots() << ", \"dual_device_seconds\": " << sv.dual_device_seconds() << ", \"dual_start\": \"" << sv.dual_start()
         << "\", \"dual_start_seconds\": " << sv.dual_start_seconds() << ", \"dual_start_gemms\": " << sv.dual_start_gemms() << ", \"dual_start_residual\": ";
@@ -780,6 +784,11 @@ int32_t relp_get_record_json(const relp_handle* h, char* buffer, int32_t capacit
     out << ", \"dual_long_step\": " << (sv.dual_long_step() ? "true" : "false") << ", \"dual_flips\": " << sv.dual_flips()
         << ", \"dual_long_step_skipped\": " << sv.dual_long_step_skipped();
     out << ", \"dual_farkas\": " << (sv.dual_farkas() ? "true" : "false") << ", \"dual_farkas_row\": " << sv.dual_farkas_row();
+    out << ", \"dual_cutoff\": ";
+    if (!sv.dual_cutoff_active()) out << "null";
+    else if (std::isinf(sv.dual_cutoff())) out << (sv.dual_cutoff() > 0 ? "\"inf\"" : "\"-inf\"");  // (JSON has no infinite number)
+    else out << sv.dual_cutoff();
+    out << ", \"dual_cutoff_stopped\": " << (sv.dual_cutoff_stopped() ? "true" : "false") << ", \"dual_bound_proved\": " << (sv.dual_bound_proved() ? "true" : "false");
     out << ", \"dual_pricing\": \"" << (h->options.dual_pricing == RELP_DUAL_PRICING_STEEPEST_EDGE ? "steepest_edge" : "infeasibility") << "\"";
     out << ", \"polishes\": " << r.polishes << ", \"refactors\": " << r.refactors
         << ", \"refactor_seconds\": " << r.refactor_seconds << ", \"ratio_rule\": \"" << (sv.ratio_textbook() ? "textbook" : "harris") << "\"" << ", \"lu_refactor\": \"" << (sv.refactors_asynchronously() ? "device, beside the pivots" : sv.refactors_on_device() ? "device" : "host")
@@ -932,6 +941,19 @@ int32_t relp_set_dual_farkas(relp_handle* h, int32_t on) {
         return RELP_ERR_ARGUMENT;
     }
     h->solver->set_dual_farkas(on == 1);
+    return RELP_OK;
+}
+int32_t relp_set_dual_cutoff(relp_handle* h, int32_t on, double cutoff) {
+    if (!h || !h->solver) return RELP_ERR_ARGUMENT;
+    if (on != 0 && on != 1) {
+        h->error = "relp_set_dual_cutoff: the switch is 0 or 1, not " + std::to_string(on);
+        return RELP_ERR_ARGUMENT;
+    }
+    if (std::isnan(cutoff)) {
+        h->error = "relp_set_dual_cutoff: the cutoff is NaN";
+        return RELP_ERR_ARGUMENT;
+    }
+    h->solver->set_dual_cutoff(on == 1, cutoff);
     return RELP_OK;
 }
 int32_t relp_begin_dual_from(relp_handle* h, const relp_handle* parent, const int32_t* basis_columns) {

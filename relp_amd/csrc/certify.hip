@@ -1698,4 +1698,162 @@ void certify_dual_farkas(const StandardForm& form, const std::vector<int>& basis
     *message = "dual Farkas: row " + std::to_string(row) + " of the inverse does not prove the verdict in exact arithmetic: " + reasons;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// the lower bound of a basis the dual simplex stopped on
+// ---------------------------------------------------------------------------------------------------
+// Every basis of the dual loop is dual feasible in f64, so y = c_B B^-1 prices every column non-negative and y'b is a lower bound of the
+// LP.  The dual half of the optimum's certificate proves it: one transposed lifting (diag(r) B)' y^ = mu c_B with the row multipliers r
+// and the cost multiplier mu, y_i = r_i y^_i / mu, then d_j = c_j - y'a_j in host integers over the one denominator mu Dy.
+//   plain:   the basis spans every row of the standard form; every d_j >= 0, z = y'b + fixed cost.
+//   bounded: the basis spans the constraint rows.  A column with a bound row br(j) gets y_br(j) = min(0, d_j) there -- the largest
+//            multiplier that keeps the column and its bound slack priced non-negative --, a column without one (a row slack) must have
+//            d_j >= 0, and z = y_c'b_c + sum_j min(0, d_j) u_j + fixed cost: the closed form of certify_dual_farkas with c in it, which
+//            does not ask which columns the handle holds complemented.
+namespace {
+// the double `v` (finite) as the exact rational numer / 2^shift
+void exact_double(double v, BigInt* numer, int* shift) {
+    int exponent = 0;
+    const double mantissa = std::frexp(v, &exponent);  // v = mantissa 2^exponent, |mantissa| in [0.5, 1) or 0
+    *numer = BigInt((i64)std::ldexp(mantissa, 53));
+    *shift = 53 - exponent;
+}
+BigInt power_of_two(int k) {
+    BigInt out(1);
+    const BigInt step = big_from_i128((i128)1 << 60);
+    for (; k >= 60; k -= 60) out = out * step;
+    return out * big_from_i128((i128)1 << k);
+}
+}  // namespace
+
+void certify_dual_bound(const StandardForm& form, const std::vector<int>& basis, bool bounded, bool at_cutoff, double cutoff, int device,
+                        hipStream_t stream, std::string* objective, bool* certified, std::string* message, CertifyScratch* scratch,
+                        std::shared_ptr<const ExactWitnesses>* witnesses) {
+    std::mutex scratch_guard;
+    if (witnesses) witnesses->reset();
+    objective->clear();
+    *certified = false;
+    message->clear();
+    RELP_HIP(hipSetDevice(device));
+    const MatrixData& md = form.data;
+    const int m = bounded ? md.nr_constraints() : md.nr_rows();
+    const int priced_columns = bounded ? md.col_end[3] : md.nr_columns();  // (bounded: the bound slacks are priced by the closed form)
+    g_times = CertifyTimes{};
+    const bool timeline = diagnostic("RELP_TIME_CERTIFY");
+    const double t_begin = wall_now();
+    auto stamp = [&](const char* what) {
+        if (timeline) fprintf(stderr, "[certify bound]   +%.2f ms %s\n", (wall_now() - t_begin) * 1e3, what);
+    };
+    std::shared_ptr<const CertifyStatic> statics = scratch ? std::static_pointer_cast<const CertifyStatic>(scratch->statics) : nullptr;
+    if (!statics) {
+        statics = certify_static(form, message);
+        if (!statics) return;
+        if (scratch) scratch->statics = statics;
+    }
+    if (statics->cost_mult == 0) {
+        *message = "cost scaling overflows 128 bits";
+        return;
+    }
+    if ((int)basis.size() != m) {
+        *message = "dual bound: the basis has " + std::to_string(basis.size()) + " columns for " + std::to_string(m) + " rows";
+        return;
+    }
+    for (int k = 0; k < m; ++k)
+        if (basis[k] < 0 || basis[k] >= priced_columns) {
+            *message = "dual bound: row " + std::to_string(k) + " of the basis holds the code " + std::to_string(basis[k]) + ", not a column the dual loop prices";
+            return;
+        }
+    const std::vector<SparseColumn>& columns = statics->columns;
+    const std::vector<i128>& row_mult = statics->row_mult;
+
+    // ---- integer basis over the rows the device basis spans, C = B^-1 mod p, one transposed lifting of the scaled c_B ---------------
+    IntegerBasis B;
+    std::vector<i64> cost_basis;
+    std::vector<char> in_basis;
+    if (!certify_integer_basis(*statics, md, basis, 0, &B, &cost_basis, &in_basis, message, bounded ? m : -1)) return;
+    stamp("integer basis built");
+    DeviceBuffers buf;
+    buf.scratch = scratch;
+    buf.guard = &scratch_guard;
+    ModularInverse inverse;
+    if (!modular_inverse(B, buf, stream, timeline, stamp, &inverse)) {
+        *message = "basis singular modulo every trial prime (singular basis?)";
+        return;
+    }
+    stamp("inverse mod p ready");
+    ExactVector y;  // y_i = row_mult[i] numer[i] / (cost_mult denom)
+    g_times.solves++;
+    if (!dixon_solve(B, cost_basis, 1, inverse.p, inverse.CT, buf, inverse.col_start, inverse.row_index, inverse.value, stream, &y, message, g_times, 32)) return;
+    RELP_HIP(hipStreamSynchronize(stream));  // (c_B = 0 returns with its upload still on the way: the buffers go back to the handle below)
+    stamp("dual solution lifted");
+    if (y.denom.sign() < 0) {
+        y.denom = -y.denom;
+        for (BigInt& v : y.numer) v = -v;
+    }
+
+    // ---- exact relative costs D_j = cost_mult denom (c_j - y'a_j) over the rows of the basis; a basic column's is zero -----------------
+    std::vector<BigInt> priced(priced_columns);
+    WorkerPool::get().run(priced_columns, [&](int j) {
+        if (in_basis[j]) return;
+        BigInt acc = big_from_i128(certify_scaled(md.cost_value(j), statics->cost_mult)) * y.denom;
+        for (size_t e = 0; e < columns[j].nnz(); ++e) {
+            const int i = columns[j].index[e];
+            if (i < m) acc = acc - big_from_i128(certify_scaled(columns[j].value[e], row_mult[i])) * y.numer[i];
+        }
+        priced[j] = acc;
+    });
+    stamp("columns priced");
+
+    // ---- the signs, the multipliers of the bound rows and the value over cost_mult denom rhs_den -------------------------------------
+    BigInt value(0);
+    for (int i = 0; i < m; ++i) value = value + statics->rhs_big[i] * y.numer[i];
+    std::vector<BigInt> bound_rows(md.nr_rows() - m);  // over cost_mult denom
+    for (int j = 0; j < priced_columns; ++j) {
+        if (priced[j].sign() >= 0) continue;
+        const int br = bounded ? md.bound_row_index(j) : -1;
+        if (br < 0) {
+            *message = "dual bound: the basis is not dual feasible in exact arithmetic: provider column " + std::to_string(j) + " prices negative";
+            return;
+        }
+        bound_rows[br - m] = priced[j];
+        value = value + priced[j] * (statics->rhs_big[br] / big_from_i128(row_mult[br]));  // u_j = rhs_big / (row_mult * rhs_den), exactly
+    }
+    const BigInt y_den = y.denom * big_from_i128(statics->cost_mult);
+    BigInt z_den = y_den * statics->rhs_den;
+    const Rat& fixed = form.fixed_cost;
+    const BigInt z_num = value * big_from_i128(fixed.d) + big_from_i128(fixed.n) * z_den;
+    z_den = z_den * big_from_i128(fixed.d);
+    *objective = reduced_text(z_num, z_den);
+    if (at_cutoff) {  // the f64 objective passed the cutoff: does the exact bound?  The cutoff as the exact rational the double is.
+        bool reached = cutoff < 0.0 && std::isinf(cutoff);
+        if (std::isfinite(cutoff)) {
+            BigInt c_num;
+            int shift = 0;
+            exact_double(cutoff, &c_num, &shift);
+            const BigInt lhs = shift > 0 ? z_num * power_of_two(shift) : z_num;
+            const BigInt rhs = (shift < 0 ? c_num * power_of_two(-shift) : c_num) * z_den;
+            reached = cmp(lhs, rhs) >= 0;
+        }
+        if (!reached) {
+            char text[40];
+            snprintf(text, sizeof(text), "%.17g", cutoff);
+            *message = "dual bound: the exact bound " + *objective + " of the basis is below the cutoff " + text + " its f64 objective reached";
+            objective->clear();
+            return;
+        }
+    }
+    *certified = true;
+    if (witnesses) {
+        auto kept = std::make_shared<ExactWitnesses>();
+        kept->mode = 3;
+        kept->basis = basis;
+        kept->y.denom = y_den;
+        kept->y.numer.resize(md.nr_rows());
+        for (int i = 0; i < m; ++i) kept->y.numer[i] = y.numer[i] * big_from_i128(row_mult[i]);
+        for (int i = m; i < md.nr_rows(); ++i) kept->y.numer[i] = std::move(bound_rows[i - m]);
+        kept->finished = true;  // nothing is left to fold in: the row and cost multipliers are in
+        *witnesses = kept;
+    }
+    stamp("proved");
+}
+
 }  // namespace relp

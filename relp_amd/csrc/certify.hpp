@@ -66,5 +66,16 @@ void certify_basis(const StandardForm& form, const std::vector<int>& basis_provi
 void certify_dual_farkas(const StandardForm& form, const std::vector<int>& basis_provider_columns, int row, bool bounded, int first_sign,
                          int device, hipStream_t stream, std::string* objective, bool* certified, std::string* message,
                          CertifyScratch* scratch, std::shared_ptr<const ExactWitnesses>* witnesses);
+// The exact lower bound of a basis the dual simplex stopped on, at its objective cutoff or at its iteration limit (certify.hip): `basis`
+// and `bounded` as certify_dual_farkas takes them.  One transposed lifting of B'y = c_B, then d_j = c_j - y'a_j for every provider column
+// in exact integers: every d_j >= 0, or on a bounded handle min(0, d_j) on the bound row of a column that has one and d_j >= 0 for the
+// rest.  *objective = z = y'b + fixed cost (bounded: y_c'b_c + sum_j min(0, d_j) u_j + fixed cost).  `at_cutoff`: certified only if also
+// z >= cutoff, the double taken as the exact rational it is (-inf: always; the result of a loop that stopped at the cutoff); otherwise z
+// is certified whatever its size.  *certified with the witnesses of mode 3 (y by row of the standard form, bound rows included, and
+// nothing else), or *message names the provider column that prices negative, the two numbers, or the refusal of the optimum's
+// certificate ("cost scaling overflows 128 bits").  No repair pivots.
+void certify_dual_bound(const StandardForm& form, const std::vector<int>& basis_provider_columns, bool bounded, bool at_cutoff, double cutoff,
+                        int device, hipStream_t stream, std::string* objective, bool* certified, std::string* message,
+                        CertifyScratch* scratch, std::shared_ptr<const ExactWitnesses>* witnesses);
 
 }  // namespace relp

@@ -55,7 +55,8 @@ struct ExactVector {           // numer[i] / denom
 // folded into y by the first exact_witness_values (under `finish_guard`: accessors may come from several threads), and x is
 // shared with the kept exact primal solution where there is one, not copied.
 struct ExactWitnesses {
-    int mode = 0;               // as certify_basis: 0 FINITE_OPTIMUM, 1 INFEASIBLE, 2 UNBOUNDED
+    int mode = 0;               // as certify_basis: 0 FINITE_OPTIMUM, 1 INFEASIBLE, 2 UNBOUNDED; 3: a lower bound of the dual simplex
+                                // (certify_dual_bound: y alone, finished, no x and no ray)
     std::vector<int> basis;     // the basis that was finally proved: provider column per row (-1-k: artificial k)
     int entering = -1;          // mode 2: the provider column q of the ray
     ExactVector x;              // x_B[k] = x.numer[k] / x.denom ...

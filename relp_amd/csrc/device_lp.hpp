@@ -53,8 +53,9 @@ __device__ __forceinline__ void ctl_copy(Ctl& dst, const Ctl& src) {
 }
 #endif
 
-enum : int { ST_RUNNING = 0, ST_NO_ENTERING = 1, ST_UNBOUNDED = 2, ST_BUDGET = 3, ST_REFACTOR = 4, ST_REFACTOR_FAILED = 5 };  // 4: LU carry, refactorise now;
+enum : int { ST_RUNNING = 0, ST_NO_ENTERING = 1, ST_UNBOUNDED = 2, ST_BUDGET = 3, ST_REFACTOR = 4, ST_REFACTOR_FAILED = 5, ST_CUTOFF = 6 };  // 4: LU carry, refactorise now;
 // 5: the refactorisation kernels gave up (a capacity, a row too long for the eliminating wave): the pivots behind them are no-ops, the host factorises
+// 6: the dual loop under an objective cutoff (dual_leave_kernel<.., .., true>): the objective of its basis has reached the cutoff
 
 struct DeviceLP {
     int m = 0, n = 0, n_art = 0, ld = 0;

@@ -48,12 +48,25 @@ __device__ __forceinline__ double dual_side(double x, double up) { return x - up
 //    BOUNDED: the violation of row i is v_i = max(-x_B[i], x_B[i] - xub[i]) (xub = +inf: no upper side), the rows with v_i > delta are
 //    eligible, key v_i or v_i^2 / beta[i].  The side of the leaving row is not stored: dual_side of (x_B[p], xub[p]), which no kernel
 //    writes between this one and dual_pivot_kernel.
-template <bool STEEPEST, bool BOUNDED>
-__global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, double delta, const double* __restrict__ beta) {
+//    CUTOFF (Solver::set_dual_cutoff): in front of the budget check, so before anything is scanned, the objective of the basis the chain
+//    stands on -- dual feasible, so a lower bound of the LP -- against `cutoff_carry`, the caller's cutoff less the fixed cost: reached,
+//    the chain stops with ST_CUTOFF and Ctl::p is left alone.  Uniform: every thread reads the same control block.  The instantiations
+//    without it never read `cutoff_carry`: their instructions are those of the kernel before the cutoff existed.
+template <bool STEEPEST, bool BOUNDED, bool CUTOFF>
+__global__ void __launch_bounds__(DL_THREADS) dual_leave_kernel(DeviceLP lp, double delta, const double* __restrict__ beta, double cutoff_carry) {
     __shared__ double s_key[DL_THREADS / WAVE];
     __shared__ unsigned long long s_rank[DL_THREADS / WAVE];
     Ctl* ctl = lp.ctl;
     if (ctl->status != ST_RUNNING) return;
+    if constexpr (CUTOFF) {
+        if (-ctl->minus_obj >= cutoff_carry) {
+            if (threadIdx.x == 0) {
+                ctl->status = ST_CUTOFF;
+                ctl->pending = 0;
+            }
+            return;
+        }
+    }
     if (ctl->iters >= ctl->budget) {
         if (threadIdx.x == 0) ctl_budget(*ctl);
         return;
@@ -823,9 +836,12 @@ void launch_dual_inherit(const DeviceLP& child, const double* parent_inverse, in
     const int per_block = DI_THREADS / WAVE;
     hipLaunchKernelGGL(dual_inherit_kernel, dim3((child.m + per_block - 1) / per_block), dim3(DI_THREADS), 0, s, child, parent_inverse, parent_m, parent_ld);
 }
-void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, bool bounded, hipStream_t s) {
-    auto kernel = beta ? (bounded ? dual_leave_kernel<true, true> : dual_leave_kernel<true, false>) : (bounded ? dual_leave_kernel<false, true> : dual_leave_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta, beta);
+void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, bool bounded, bool cutoff, double cutoff_carry, hipStream_t s) {
+    auto kernel = cutoff ? (beta ? (bounded ? dual_leave_kernel<true, true, true> : dual_leave_kernel<true, false, true>)
+                                 : (bounded ? dual_leave_kernel<false, true, true> : dual_leave_kernel<false, false, true>))
+                         : (beta ? (bounded ? dual_leave_kernel<true, true, false> : dual_leave_kernel<true, false, false>)
+                                 : (bounded ? dual_leave_kernel<false, true, false> : dual_leave_kernel<false, false, false>));
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(DL_THREADS), 0, s, d, harris_delta, beta, cutoff_carry);
 }
 int launch_dual_weights(const DeviceLP& d, const DualBuffers& b, bool chained, hipStream_t s) {
     const int m = d.m, per_slice = (m + b.slices - 1) / b.slices;

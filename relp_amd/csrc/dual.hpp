@@ -42,7 +42,8 @@ inline int dual_weight_slices(int m) { return m / 64 < 1 ? 1 : m / 64 > DUAL_WEI
 // One dual pivot is these five launches in this order.  Each returns at once unless Ctl::status == ST_RUNNING; dual_leave_kernel
 // also stops the chain when the budget of the batch is used up (ST_BUDGET), so a batch that finishes early is a run of no-ops.
 //   leave:   the leaving row p (largest infeasibility among x_B[i] < -harris_delta, or largest x_B[i]^2 / beta_i under the steepest-edge
-//            rule; ties: lowest basic column, lowest row), rho = row p of the inverse; none: ST_NO_ENTERING, the basis is primal feasible
+//            rule; ties: lowest basic column, lowest row), rho = row p of the inverse; none: ST_NO_ENTERING, the basis is primal feasible;
+//            with an objective cutoff, first of all: ST_CUTOFF where the objective of this basis has reached it
 //   row:     alpha_pj, d_j and pass 1 of the ratio test over the non-basic provider columns (`lds`: rho and -pi staged in LDS)
 //   choose:  theta_max, pass 2 (largest |alpha_pj| within theta_max, key 1 under the textbook rule; ties: lowest column)
 //   pivot:   the entering column q (none: ST_UNBOUNDED, the LP is infeasible), FTRAN, x_B, basis, pos, control block; ST_REFACTOR
@@ -53,7 +54,11 @@ inline int dual_weight_slices(int m) { return m / 64 < 1 ? 1 : m / 64 > DUAL_WEI
 // (the side s = +1 / -1); the row of the tableau is taken in the held form and towards that side, abar_j = s sgn_j rho . a_j and
 // d_j = sgn_j (c_j - pi . a_j), so that choose and update are the same kernels; the pivot checks s alpha_q[p] < -tol_pivot, steps to
 // the violated bound, and complements a column that leaves at its upper bound.  false: the kernels as they were.
-void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, bool bounded, hipStream_t s);  // beta == nullptr: rule 0
+// `cutoff` (Solver::set_dual_cutoff): the instantiations of the leave kernel that first compare the objective of the basis they stand on,
+// -Ctl::minus_obj, with `cutoff_carry` (the cutoff less the fixed cost) and stop the chain with ST_CUTOFF where it is reached, in front
+// of the budget check and with nothing scanned or written but the status.  false: the kernels as they were; `cutoff_carry` is not read.
+void launch_dual_leave(const DeviceLP& d, double harris_delta, const double* beta, bool bounded, bool cutoff, double cutoff_carry,
+                       hipStream_t s);  // beta == nullptr: rule 0
 void launch_dual_row(const DeviceLP& d, const DualBuffers& b, bool lds, bool bounded, double tol_pivot, double slack, hipStream_t s);
 void launch_dual_choose(const DeviceLP& d, const DualBuffers& b, double tol_pivot, bool textbook, hipStream_t s);
 void launch_dual_pivot(const DeviceLP& d, const DualBuffers& b, bool bounded, bool long_step, double tol_pivot, hipStream_t s);

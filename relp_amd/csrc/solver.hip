@@ -92,6 +92,7 @@ void Solver::free_device() {
     dual_bounded_ = false;
     dual_long_active_ = false;
     dual_flips_ = dual_long_skipped_ = 0;
+    dual_cutoff_active_ = dual_cutoff_stopped_ = dual_bound_proved_ = false;
     dual_start_ = "none";
     d_inherit_map_ = nullptr;
     dual_inherit_complemented_ = dual_inherit_moved_ = 0;
@@ -1535,6 +1536,10 @@ void Solver::finish_dual_start(const int* basis_columns, const char* how, double
     dual_flips_ = dual_long_skipped_ = 0;
     dual_farkas_active_ = dual_farkas_;
     dual_farkas_row_ = -1;
+    dual_cutoff_active_ = dual_cutoff_on_;
+    dual_cutoff_read_ = dual_cutoff_;
+    dual_cutoff_carry_ = dual_cutoff_ - form_.fixed_cost.to_double();  // (Ctl::minus_obj does not hold the fixed cost: collect_result adds it)
+    dual_cutoff_stopped_ = dual_bound_proved_ = false;
     const size_t lds_max = opt_.price_lds_max > 0 ? (size_t)opt_.price_lds_max : (size_t)96 * 1024;
     dual_lds_ = 2 * (size_t)m * sizeof(double) <= lds_max;
     std::vector<double> cbar(n);
@@ -1592,7 +1597,7 @@ void Solver::launch_dual_pivots(int count) {
     launch_budget(d_, count, stream_);
     const bool textbook = path_.ratio_textbook;
     for (int it = 0; it < count; ++it) {
-        launch_dual_leave(d_, opt_.harris_delta, dual_.beta, path_.bounded, stream_);
+        launch_dual_leave(d_, opt_.harris_delta, dual_.beta, path_.bounded, dual_cutoff_active_, dual_cutoff_carry_, stream_);
         launch_dual_row(d_, dual_, dual_lds_, path_.bounded, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, stream_);
         if (dual_long_active_) launch_dual_long_step(d_, dual_, opt_.tol_pivot, textbook ? 0.0 : opt_.tol_dual, opt_.harris_delta, stream_);
         launch_dual_choose(d_, dual_, opt_.tol_pivot, textbook, stream_);
@@ -1643,6 +1648,11 @@ long long Solver::iterate_dual(long long count, int* stop_reason) {
             last_pivot_dual_ = true;
         }
         if (after.status == ST_NO_ENTERING || after.status == ST_UNBOUNDED) { reason = after.status; break; }
+        if (after.status == ST_CUTOFF) {  // (only under set_dual_cutoff: the objective of this basis has reached the cutoff)
+            dual_cutoff_stopped_ = true;
+            reason = ST_CUTOFF;
+            break;
+        }
         if (after.status == ST_REFACTOR) {
             // dual_pivot_kernel found the FTRAN value of its pivot unusable where the row's value was usable: the inverse has drifted.
             // Nothing of that pivot was written.  A forced polish, and the loop asks again; twice in a row at one basis is an error.
@@ -1686,7 +1696,10 @@ void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_resul
         if (iterate_dual(cap - dual_pivots_, &reason) == 0) break;
     }
     if (reason == ST_UNBOUNDED) kind = RELP_RESULT_INFEASIBLE;
+    else if (reason == ST_CUTOFF) kind = RELP_RESULT_CUTOFF;  // (no primal clean-up: the basis is not primal feasible, and need not be)
     else if (reason != ST_NO_ENTERING) kind = RELP_RESULT_ITERATION_LIMIT;
+    // under set_dual_cutoff the basis the dual loop itself stopped on has an objective worth reporting: a lower bound of the LP
+    const bool dual_bound = dual_cutoff_active_ && (kind == RELP_RESULT_CUTOFF || kind == RELP_RESULT_ITERATION_LIMIT);
     if (kind == RELP_RESULT_NONE) {
         // the primal loop from the primal-feasible basis: the weights recomputed, the control block reset (minus_obj kept); it
         // removes relative costs that drifted below -tol_dual and normally makes no pivot
@@ -1700,6 +1713,11 @@ void Solver::run_dual(const Solver* parent, const int* basis_columns, relp_resul
     }
     const bool dual_unbounded = kind == RELP_RESULT_INFEASIBLE;
     collect_result(kind, t0, !dual_unbounded, [](const char*) {}, result);
+    if (dual_bound) {
+        last_result.objective = -read_ctl().minus_obj + form_.fixed_cost.to_double();
+        if (result) *result = last_result;
+        if (opt_.certify) certify_dual_lower_bound(result);
+    }
     if (dual_unbounded && dual_farkas_active_ && opt_.certify) certify_dual_infeasible(result);
     else if (dual_unbounded)  // (without relp_set_dual_farkas: reported with certified = 0 whatever the options ask for)
         last_error ="the dual simplex does not certify infeasibility yet (the Farkas vector is the row of the inverse at which the dual is unbounded)";
@@ -1714,7 +1732,7 @@ int Solver::dual_stopped_row() {
     running.status = ST_RUNNING;
     write_ctl(running);
     stats_.launches += 1;
-    launch_dual_leave(d_, opt_.harris_delta, dual_.beta, path_.bounded, stream_);
+    launch_dual_leave(d_, opt_.harris_delta, dual_.beta, path_.bounded, false, 0.0, stream_);  // (never the cutoff's: it would stop in front of the row)
     const Ctl named = read_ctl();
     write_ctl(stopped);
     return named.status == ST_RUNNING && named.p >= 0 && named.p < d_.m ? named.p : -1;
@@ -1747,6 +1765,30 @@ void Solver::certify_dual_infeasible(relp_result* result) {
         }
         dual_farkas_row_ = p;
     }
+    last_result.certified = ok ? 1 : 0;
+    last_result.certify_seconds = now_seconds() - t0;
+    if (result) *result = last_result;
+    if (!ok) last_error = message;
+}
+
+// The lower bound of a child the dual loop left at the cutoff or at its iteration limit, proved: every basis of that loop is dual feasible
+// in f64, and one transposed lifting of B'y = c_B says whether this one is in exact arithmetic (certify.hpp: certify_dual_bound).  The
+// basis is the one the device holds, as certify_dual_infeasible takes it; nothing is launched on the pivot state.
+void Solver::certify_dual_lower_bound(relp_result* result) {
+    const double t0 = now_seconds();
+    bool ok = false;
+    std::string message;
+    std::vector<int> basis(d_.m);
+    for (int i = 0; i < d_.m; ++i) basis[i] = cols_.to_provider(h_rb_basis_[i]);  // (collect_result's read-back)
+    const bool at_cutoff = last_result.kind == RELP_RESULT_CUTOFF;
+    try {
+        certify_dual_bound(form_, basis, path_.bounded, at_cutoff, dual_cutoff_read_, opt_.device, stream_, &exact_objective, &ok, &message, &certify_scratch_,
+                           &exact_witnesses);
+    } catch (const RatOverflow& e) {  // (as certify())
+        ok = false;
+        message = std::string("exact certificate: ") + e.what();
+    }
+    dual_bound_proved_ = ok;
     last_result.certified = ok ? 1 : 0;
     last_result.certify_seconds = now_seconds() - t0;
     if (result) *result = last_result;

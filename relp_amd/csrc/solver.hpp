@@ -95,6 +95,16 @@ public:
     void set_dual_farkas(bool on) { dual_farkas_ = on; }
     bool dual_farkas() const { return dual_farkas_active_; }  // the switch as the last start read it
     int dual_farkas_row() const { return dual_farkas_row_; }  // the row of the basis the last proof used, -1 where there was none
+    // An objective cutoff for the dual loop, off by default, in the units of relp_result.objective (the fixed cost included).  The switch
+    // holds until changed and is read by every start, the stepwise ones included.  On, the leave kernel stops the chain with ST_CUTOFF at
+    // the first basis whose objective has reached the cutoff (iterate_dual: stop reason 6; run_dual: RELP_RESULT_CUTOFF), and a
+    // solve_dual* that ends there, or at the iteration limit of the dual loop, reports the f64 objective of that basis and -- with
+    // relp_options.certify set -- proves it as a lower bound of the LP (certify.hpp: certify_dual_bound).
+    void set_dual_cutoff(bool on, double cutoff) { dual_cutoff_on_ = on; dual_cutoff_ = cutoff; }
+    bool dual_cutoff_active() const { return dual_cutoff_active_; }  // the switch as the last start read it ...
+    double dual_cutoff() const { return dual_cutoff_read_; }         // ... and its value
+    bool dual_cutoff_stopped() const { return dual_cutoff_stopped_; }  // the loop since that start has stopped at the cutoff
+    bool dual_bound_proved() const { return dual_bound_proved_; }      // the last solve_dual* ended with a proved lower bound
     long long dual_pivots() const { return dual_pivots_; }  // of the last solve_dual / since begin_dual
     // relp_options.dual_pricing = RELP_DUAL_PRICING_STEEPEST_EDGE: the m weights the next dual pivot would read (the squared row norms
     // of the inverse).  std::runtime_error under rule 0 and before a begin_dual.
@@ -226,6 +236,12 @@ private:
     int dual_farkas_row_ = -1;
     int dual_stopped_row();                            // the row at which the loop stands dual unbounded (one launch of the leaving-row kernel)
     void certify_dual_infeasible(relp_result* result);  // behind collect_result, which has read the basis and x_B back
+    bool dual_cutoff_on_ = false;      // the switch and its value
+    double dual_cutoff_ = 0.0;
+    bool dual_cutoff_active_ = false;  // ... as the last start read them; the kernel gets dual_cutoff_read_ less the fixed cost
+    double dual_cutoff_read_ = 0.0, dual_cutoff_carry_ = 0.0;
+    bool dual_cutoff_stopped_ = false, dual_bound_proved_ = false;
+    void certify_dual_lower_bound(relp_result* result);  // behind collect_result, like the one above: the bound of the basis the loop stopped on
     // ... and their tail behind set_phase(2): the loop's buffers, the dual-feasibility check that names the column, the counters
     void finish_dual_start(const int* basis_columns, const char* how, double t0, long long gemms_before);
     void run_dual(const Solver* parent, const int* basis_columns, relp_result* result, bool bounded_entry = false);  // every solve_dual*: one loop

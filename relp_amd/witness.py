@@ -105,6 +105,22 @@ def check_infeasible(model, y, value):
         raise WitnessError("y'b > 0", None, str(yb))
 
 
+def check_dual_bound(model, y, value):
+    """Weak duality without a primal point: y is dual feasible over EVERY provider column and y'b + fixed cost = ``value``, so no
+    feasible x costs less than ``value`` (c'x >= y'A x = y'b).  The witness of a ``CUTOFF`` result of the dual simplex, and of its
+    ``ITERATION_LIMIT`` under ``Solver.set_dual_cutoff``."""
+    form = _Form(model)
+    value = Fraction(value)
+    ys = form.vector(y, form.m, "y", "row")
+    for j in range(form.n):
+        reduced = form.cost[j] - form.priced(ys, j)
+        if reduced < 0:
+            raise WitnessError("c_j - y'a_j >= 0", ("column", j), str(reduced))
+    dual = form.dot_b(ys) + form.fixed
+    if dual != value:
+        raise WitnessError("y'b + fixed cost = value", None, "%s != %s" % (dual, value))
+
+
 def check_unbounded(model, x, ray):
     """x is feasible and d = ``ray`` has d >= 0, A d = 0 and c'd < 0: x + t d is feasible for every t >= 0 and its cost falls
     without bound."""

@@ -58,7 +58,17 @@ asks for their sum to be at least 1, as ``dual_bounded_lps.infeasible_child`` bu
               bounds it does not: ``collect_result`` certifies finite optima only there)
 Run against a library without ``relp_set_dual_farkas`` (``RELP_AMD_LIB``), it prints the cold lines alone.
 
-    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded [--long-step | --start [--traced]]] [--farkas]
+``--cutoff``: the child of the first table (24 cuts) and, with a bound on every structural variable, the child of ``--bounded`` (24 cuts,
+8 tightened bounds), integer and decimal data, each re-solved twice from the same basis in the same run, a line per way:
+  full       ``solve_dual`` / ``solve_dual_bounded`` to the certified optimum, the switch off: the whole call, the dual pivots,
+             ``certify_seconds`` and the device time per dual pivot
+  cutoff     the same call under ``cutoff=`` halfway between the parent's optimum and the child's (both from the runs without it): the
+             whole call, the dual pivots, ``certify_seconds`` (the proof of the bound: one modular inverse, one transposed lifting, the
+             exact products) and in how many of the 5 runs the proof failed (decimal data: under the Harris rule a relative cost may be
+             negative by less than ``tol_dual``, and a column without a bound cannot absorb that)
+Run against a library without ``relp_set_dual_cutoff`` (``RELP_AMD_LIB``), it prints the full lines alone.
+
+    python tools/dual_probe.py [--sizes 1025 2049] [--decimal] [--cuts N] [--start [--traced]] [--pricing 0 1] [--bounded [--long-step | --start [--traced]]] [--farkas] [--cutoff]
 """
 import argparse
 import os
@@ -416,6 +426,72 @@ def farkas_probe(m, bounded):
     parent.close()
 
 
+def cutoff_probe(m, decimal, bounded, n_cuts):
+    """One child of the table "an objective cutoff" of DESIGN.md section 10, a line per way."""
+    from fractions import Fraction
+    stops = hasattr(relp_amd.lib(), "relp_set_dual_cutoff")  # (a library of before the cutoff: the full re-solve alone)
+    if bounded:
+        import dual_bounded_lps
+        case = dual_bounded_lps.BoundedCase(m, 1000 + m, n_cuts, 8, decimal=decimal, every=1)
+        options = dict(certify=1, implicit_bounds=1)
+        parent = relp_amd.Solver(**options).load_model(case.parent.model)
+        assert parent.solve_relaxation().certified
+        form, basis, _, _ = case.child(parent.basis(), parent.solution_exact())
+        child, entry = form.model, "solve_dual_bounded"
+    else:
+        seed, _ = dual_lps.STATE_CASES[m]
+        case = dual_lps.cut_case(m, dual_lps.MIXED, seed, n_cuts, decimal=decimal)
+        options = dict(certify=1)
+        parent = relp_amd.Solver(**options).load_model(case.parent)
+        assert parent.solve_relaxation().certified
+        child, basis, _ = case.child(parent.basis(), parent.solution_exact())
+        entry = "solve_dual"
+    parent_optimum = Fraction(parent.objective_exact())
+    parent.close()
+    label = "m = %d + %d cuts, %s, %s" % (m, n_cuts, "implicit bounds" if bounded else "no bounds", "decimal" if decimal else "integer")
+    solver = relp_amd.Solver(**options).load_model(child)
+    optima = set()
+
+    def full():
+        started = time.perf_counter()
+        result = getattr(solver, entry)(basis)
+        wall = 1e3 * (time.perf_counter() - started)
+        assert result.kind == relp_amd.FINITE_OPTIMUM and result.certified
+        optima.add(solver.objective_exact())
+        pivots = solver.dual_pivots()
+        return wall, pivots, 1e3 * result.certify_seconds, 1e6 * solver.record()["dual_device_seconds"] / max(1, pivots)
+
+    (wall, lo, hi), (pivots, _, _), (certify_ms, certify_lo, certify_hi), (device_us, us_lo, us_hi) = spread_of(full)
+    assert len(optima) == 1, optima
+    child_optimum = Fraction(optima.pop())
+    print("%s | full %s: %.1f ms (%.1f .. %.1f), %d dual pivots, the certificate %.2f ms (%.2f .. %.2f), %.1f us (%.1f .. %.1f) of device time per dual pivot" % (
+        label, entry, wall, lo, hi, pivots, certify_ms, certify_lo, certify_hi, device_us, us_lo, us_hi), flush=True)
+    if stops:
+        cutoff = float((parent_optimum + child_optimum) / 2)
+        reasons = set()
+
+        def stopped():
+            started = time.perf_counter()
+            result = getattr(solver, entry)(basis, cutoff=cutoff)
+            wall = 1e3 * (time.perf_counter() - started)
+            assert result.kind == relp_amd.CUTOFF and result.objective >= cutoff
+            if result.certified:
+                assert Fraction(cutoff) <= Fraction(solver.objective_exact()) <= child_optimum
+            else:
+                reasons.add(relp_amd.lib().relp_last_error(solver._h).decode())
+            return wall, solver.dual_pivots(), 1e3 * result.certify_seconds, 0 if result.certified else 1
+
+        stopped()  # warm-up
+        samples = [stopped() for _ in range(RUNS)]
+        (wall, lo, hi), (pivots, _, _), (certify_ms, certify_lo, certify_hi), _ = [(statistics.median(c), min(c), max(c)) for c in zip(*samples)]
+        failed = sum(sample[3] for sample in samples)
+        print("%s | %s under cutoff %.17g (parent %.6f, child %.6f): %.1f ms (%.1f .. %.1f), %d dual pivots, the proof %.2f ms (%.2f .. %.2f), failed in %d of %d runs%s" % (
+            label, entry, cutoff, float(parent_optimum), float(child_optimum), wall, lo, hi, pivots, certify_ms, certify_lo, certify_hi, failed, RUNS,
+            ": " + "; ".join(sorted(reasons)) if reasons else ""), flush=True)
+        solver.set_dual_cutoff(None)
+    solver.close()
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     parser.add_argument("--sizes", type=int, nargs="*", default=[1025, 2049])
@@ -434,7 +510,15 @@ def main():
     parser.add_argument("--every", type=int, default=1, help="with --long-step: a bound on every N-th structural variable")
     parser.add_argument("--tight", type=int, default=8, help="with --long-step: tightened bounds per child")
     parser.add_argument("--farkas", action="store_true", help="only the table of the proved INFEASIBLE verdict: an infeasible child without bounds and on implicit bounds")
+    parser.add_argument("--cutoff", action="store_true", help="only the table of the objective cutoff: the child re-solved to its optimum and under a "
+                        "cutoff halfway to it, without bounds and on implicit bounds, integer and decimal data")
     args = parser.parse_args()
+    if args.cutoff:
+        for m in args.sizes:
+            for bounded in (False, True):
+                for decimal in ([True] if args.decimal else [False, True]):
+                    cutoff_probe(m, decimal, bounded, args.cuts or 24)
+        return
     if args.farkas:
         for m in args.sizes:
             for bounded in (False, True):
